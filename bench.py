@@ -14,14 +14,22 @@ ends -- inside the timed region -- with ONE RCCL all_gather of every rank's resu
 gathers once per run as well: exps/stage3_root2/test.py + lib/utils/comm.py:47-87).
 Inputs are resident in HBM before the timed region.
 
+A plain run sets up, warms up, times the --steps steps and prints one JSON line (metric, value, unit, higher_is_better,
+dtype, ms_per_step = milliseconds per timed step).  --full adds everything else the benchmark measures or checks, each
+at its own cost: the CPU reference pass (cpu_baseline, config.e2e_parity), the same steps with one launch per step
+(value_launch_frames_0), per-launch HIP events, clocks and the roofline block, host-time breakdowns and the check that
+the timed steps reproduce each other's records.  --dump-outputs DIR writes the records of the LAST timed step as .npy
+files (see dump_records) so that two builds can be compared output for output; the inputs are seeded, identical from run
+to run.
+
 Arithmetic (--precision): "x3" (default) = fp16 hi/lo pairs with three MFMAs per K step: the mode whose results meet
-the reference's fp32 path end to end (3D joints within 1e-3 m, same peaks and limbs: `config.e2e_parity`, computed in
-this very run against the CPU reference on the same images); "f16" = fp16 storage, ~2x faster, ~0.3 cm mean joint error.
+the reference's fp32 path end to end (3D joints within 1e-3 m, same peaks and limbs: `config.e2e_parity`, computed with
+--full against the CPU reference on the same images); "f16" = fp16 storage, ~2x faster, ~0.3 cm mean joint error.
 
 Workload: recipe weights with calibrated heads (benchkit/workload.py: ~24 peaks per key-point channel, ~22 skeletons
 per frame, root depth ~3 m), so the association of the NETWORK's own output is real work; in addition every step
 associates + lifts a resident batch of synthetic scenes whose person count rotates over K in {0, 2, 8, 20}
-(SURVEY.md 8d config 3), timed per K with HIP events on the post-processing stream.
+(SURVEY.md 8d config 3); --full times them per K with HIP events on the post-processing stream.
 """
 import argparse
 import gc
@@ -55,6 +63,88 @@ def records_from(pred_2d, pred_3d, root_z, counts, tag):
         out.append({"pred_2d": pred_2d[i, :P].tolist(), "pred_3d": pred_3d[i, :P].tolist(),
                     "root_d": root_z[i, :P].tolist(), "image_path": f"{tag}/{i}", "gt_3d": [], "gt_2d": []})
     return out
+
+
+DUMP_CAP_BYTES = 64 << 20          # --dump-outputs writes at most this much
+
+
+def _save_npy(dirname, arrays):
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
+
+
+def dump_records(dirname, recs_per_rank, B, j, K):
+    """--dump-outputs of the full path: the records (what a caller of the pipeline receives) of the LAST timed step, i.e. of batch
+    j and synthetic scene set K on every rank.  A frame's record is the last one with its image_path (the last step ran that batch
+    last).  Written per result set, frames in order r0/f0, r0/f1, ..., persons concatenated:
+        persons [frames]            persons found per frame (0: the frame has no record)
+        pred_2d [persons, 15, 4]    float32      pred_3d [persons, 15, 4]  float64      root_d [persons]  float64
+    and the same four with the prefix synth_ for the synthetic scenes associated in that step.  Beyond DUMP_CAP_BYTES, a fixed
+    seeded sample of the frames (in order) is written, with `frames` naming which."""
+    sets = {}
+    for prefix, fmt in (("", "r{r}/b{j}/f{i}"), ("synth_", "synthK{K}/r{r}/b{j}/f{i}")):
+        frames = []
+        for r, recs in enumerate(recs_per_rank):
+            by_path = {rec["image_path"]: rec for rec in recs}
+            frames += [by_path.get(fmt.format(r=r, j=j, K=K, i=i)) for i in range(B)]
+        sets[prefix] = frames
+    n = len(sets[""])
+    size = [sum(16 + (0 if rec is None else np.asarray(rec["pred_2d"]).size * 12 + np.asarray(rec["root_d"]).size * 8)
+                for rec in (frames[i] for frames in sets.values())) for i in range(n)]     # counts f64, 2D f32 + 3D f64, roots f64
+    keep = np.arange(n)
+    if sum(size) > DUMP_CAP_BYTES - (1 << 20):                                                  # (1 MiB: headers, frame list)
+        order = np.random.default_rng(0).permutation(n)
+        total = np.cumsum([size[i] for i in order])
+        keep = np.sort(order[:int(np.searchsorted(total, DUMP_CAP_BYTES - (1 << 20), side="right"))])
+    out = {}
+    for prefix, frames in sets.items():
+        sel = [frames[k] for k in keep]
+        out[prefix + "persons"] = np.array([0 if rec is None else len(rec["root_d"]) for rec in sel], np.float64)
+        have = [rec for rec in sel if rec is not None]
+        out[prefix + "pred_2d"] = np.concatenate([np.asarray(rec["pred_2d"], np.float32).reshape(-1, 15, 4) for rec in have] or [np.zeros((0, 15, 4), np.float32)])
+        out[prefix + "pred_3d"] = np.concatenate([np.asarray(rec["pred_3d"], np.float64).reshape(-1, 15, 4) for rec in have] or [np.zeros((0, 15, 4))])
+        out[prefix + "root_d"] = np.concatenate([np.asarray(rec["root_d"], np.float64).reshape(-1) for rec in have] or [np.zeros(0)])
+    if len(keep) < n:
+        out["frames"] = keep.astype(np.float64)
+    _save_npy(dirname, out)
+
+
+def dump_maps(dirname, maps):
+    """--dump-outputs of --forward-only: the maps of the last forward (float32), whole while they fit DUMP_CAP_BYTES, else the same
+    seeded sample of flat indices of each map (+ <name>_index: which)."""
+    per = DUMP_CAP_BYTES // (12 * len(maps))                  # elements per map when sampled (f32 value + f64 index)
+    total = sum(t.numel() * 4 for t in maps.values())
+    out = {}
+    for name, t in maps.items():
+        a = t.detach().float().cpu().numpy().reshape(-1)
+        if total > DUMP_CAP_BYTES and a.size > per:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, per, replace=False))
+            out[name], out[name + "_index"] = a[idx], idx.astype(np.float64)
+        else:
+            out[name] = a.reshape(tuple(t.shape))
+    _save_npy(dirname, out)
+
+
+def headline(args, world, B, dt, pipe, NB, n_rec, n_ranks):
+    """The result line of the full path as a plain run prints it (--full adds to its config and a roofline block): frames/s over the
+    timed region (dt: its wall time, the MAX over ranks), ms_per_step, and the configuration they were measured in."""
+    fpl = pipe.frames_per_launch
+    return {
+        "metric": "frames/sec at 3x512x832 (SMAP backbone + depth-aware association + 3D lifting)",
+        "value": B * world * args.steps / dt, "unit": "frames/sec", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True, "scaling": "weak",
+        "vs_baseline": None, "dtype": "f16x3" if args.precision == "x3" else "f16", "data": "synthetic",
+        "config": {"workload": f"batch={B} x 3x512x832 per GPU, full SMAP + depth-aware PAF association "
+                               f"+ lifting{' + RefineNet (configs[4])' if args.refine else ''}{' + flip-TTA' if args.flip else ''} "
+                               f"(BASELINE configs[2]; configs[3] when n_gpus=8)",
+                   "frames_per_step": B * world, "records_in_run": n_rec, "resident_batches_in_rotation": NB,
+                   "pipeline": f"post-processing of batch k overlaps later backbones; {args.depth} backbone(s) in flight; "
+                               f"{fpl} frames per backbone launch"
+                               + (f" (= {fpl // B} consecutive steps' batches coalesced; --launch-frames 0: one launch "
+                                  f"per step)" if fpl > B else "")
+                               + "; one end-of-run gather of the records",
+                   "frames_per_launch": fpl, "ranks_in_gather": n_ranks, "full": bool(args.full)}}
 
 
 def usable_cpus(cap=64):
@@ -171,6 +261,9 @@ def forward_only(args, dev, rank, world, B):
         t = torch.tensor([dt], dtype=torch.float64, device=getattr(args, "cdev", dev))
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+    if rank == 0 and args.dump_outputs:
+        hms, det_d, root_d = eng.views(out)
+        dump_maps(args.dump_outputs, {"hms": hms, "det_d": det_d, "root_d": root_d})
     if rank == 0:
         ev = e0.elapsed_time(e1) * 1e-3
         achieved = ALG_GFLOP_PER_FRAME * B * args.steps / ev / 1e3
@@ -305,19 +398,22 @@ def pin_host_threads(local, world):
 
 
 def spawn_or_check_world(args):
-    """--gpus N is the contract, WORLD_SIZE is what a launcher set.  `python bench.py --gpus 8` without a launcher re-executes
-    itself under torch.distributed.run (one process per GPU, rendezvous on 127.0.0.1); a launcher whose world size
-    disagrees with --gpus is an error -- a line that says n_gpus: 1 for a --gpus 8 request would be worse than no line."""
+    """--gpus N is the contract, WORLD_SIZE is what a launcher set.  `python bench.py --gpus 8` without a launcher runs
+    itself under torch.distributed.run as a child process (one process per GPU, rendezvous on 127.0.0.1) and exits with
+    its status; a launcher whose world size disagrees with --gpus is an error -- a line that says n_gpus: 1 for a --gpus 8
+    request would be worse than no line."""
     world = os.environ.get("WORLD_SIZE")
     if world is None and args.gpus > 1:
         import socket
+        import subprocess
         with socket.socket() as sk:
             sk.bind(("127.0.0.1", 0))
             port = sk.getsockname()[1]
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}",
                "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
-        print("bench.py: --gpus %d without a launcher: re-executing as %s" % (args.gpus, " ".join(cmd)), file=sys.stderr, flush=True)
-        os.execv(sys.executable, cmd)
+        print("bench.py: --gpus %d without a launcher: running %s" % (args.gpus, " ".join(cmd)), file=sys.stderr, flush=True)
+        rc = subprocess.call(cmd)
+        sys.exit(rc if rc >= 0 else 128 - rc)          # a child killed by signal s: 128 + s, as a shell reports it
     if int(world or 1) != args.gpus:
         raise SystemExit(f"bench.py: --gpus {args.gpus} but WORLD_SIZE={world or 1}: launch with --nproc-per-node {args.gpus} "
                          f"(or drop the launcher: bench.py spawns its own ranks)")
@@ -334,7 +430,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--batch", type=int, default=8, help="frames per GPU per step")
     ap.add_argument("--no-cpu-baseline", action="store_true",
-                    help="skip the CPU reference pass (no cpu_baseline, no config.e2e_parity): kernel experiments only")
+                    help="with --full: skip the CPU reference pass (no cpu_baseline, no config.e2e_parity); a plain run never makes it")
     ap.add_argument("--rotate", type=int, default=4,
                     help="distinct resident 8-frame batches the timed steps rotate over (1 = the same frames every step, as rounds 1-5 ran)")
     ap.add_argument("--launch-frames", type=int, default=16,
@@ -360,6 +456,11 @@ def main():
     ap.add_argument("--dry-run", action="store_true",
                     help="no GPU: the same control flow (pipeline protocol, end-of-run gather, MAX over ranks, one JSON line on "
                          "rank 0) with a stand-in pipeline and the gloo backend -- what the multi-rank CPU test runs")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: CPU reference pass (cpu_baseline, e2e_parity), the one-launch-per-step "
+                         "rerun, per-launch events, clocks, roofline, host-time breakdowns, the timed-steps reproduction check")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32/float64)")
     args = ap.parse_args()
     spawn_or_check_world(args)
     if args.dry_run:
@@ -423,10 +524,10 @@ def main():
     imgs = img_batches[0]
     cams = np.tile(np.asarray(PEOPLE_CAM, np.float64), (B, 1))
 
-    # ---- end-to-end parity of THIS configuration (outside the timed region; rank 0, N = 1 reports it).  The CPU child
+    # ---- end-to-end parity of THIS configuration (--full; outside the timed region; rank 0, N = 1 reports it).  The CPU child
     #      computes the reference path while the GPU side is being set up.
     parity_out, cpu_ref, hip_frames = None, None, None
-    want_ref = rank == 0 and world == 1 and not args.no_cpu_baseline
+    want_ref = args.full and rank == 0 and world == 1 and not args.no_cpu_baseline
     if want_ref:
         import concurrent.futures as cf
         nref = min(B, 8)
@@ -452,6 +553,7 @@ def main():
 
     host = {"submit": 0.0}
     step_no = [0]
+    last_step = {}                   # batch and scene set of the last timed step (--dump-outputs)
 
     def step(timed):
         # backbone(k) on one stream; association+lift+D2H of batch k on another; records of earlier batches on the host
@@ -459,11 +561,13 @@ def main():
         j = (step_no[0] - first) % NB
         step_no[0] += 1
         t0 = time.perf_counter()
-        recs = pipe.submit(img_batches[j], cams, batch_tags[j], extra=[(f"synthK{K}", synth[K][0], synth[K][1], None)], time_backbone=timed)
+        recs = pipe.submit(img_batches[j], cams, batch_tags[j], extra=[(f"synthK{K}", synth[K][0], synth[K][1], None)],
+                           time_backbone=timed and args.full)
         if timed:
             dt = time.perf_counter() - t0
             host["submit"] += dt
             host.setdefault("steps", []).append(dt * 1e3)
+            last_step.update(j=j, K=K)
             if recs:
                 collected.extend(recs)
 
@@ -481,11 +585,13 @@ def main():
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
-    from benchkit.clocks import ClockSampler
-    sampler = ClockSampler(local)             # shader clock + package power the box holds during the timed region (sysfs reads, 50 Hz)
-    sampler.__enter__()
+    sampler = None
+    if args.full:
+        from benchkit.clocks import ClockSampler
+        sampler = ClockSampler(local)         # shader clock + package power the box holds during the timed region (sysfs reads, 50 Hz)
+        sampler.__enter__()
     cpu0 = time.process_time()
-    thr0 = thread_cpu_seconds()
+    thr0 = thread_cpu_seconds() if args.full else {}
     wait0 = pipe.wait_s
     t0 = time.perf_counter()
     for _ in range(args.steps):
@@ -504,11 +610,27 @@ def main():
         dist.barrier()
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
+    recs_per_rank = [collected] if gathered is None else [pickle.loads(b) for b in gathered]
+    n_rec = sum(len(r) for r in recs_per_rank)
+    if not args.full:
+        if args.dump_outputs and rank == 0:   # what the last timed step computed: its records on every rank
+            dump_records(args.dump_outputs, recs_per_rank, B, last_step["j"], last_step["K"])
+        if world > 1:
+            t = torch.tensor([dt], dtype=torch.float64, device=cdev)
+            dist.all_reduce(t, op=dist.ReduceOp.MAX)
+            dt = float(t.item())
+        if rank == 0:
+            print(json.dumps(headline(args, world, B, dt, pipe, NB, n_rec, len(recs_per_rank))), flush=True)
+        if dist.is_initialized():
+            dist.destroy_process_group()
+        return
+    cpu_ms_per_step = (time.process_time() - cpu0) / args.steps * 1e3
     sampler.__exit__()
     clocks = sampler.summary(t0, t0 + dt)
-    cpu_ms_per_step = (time.process_time() - cpu0) / args.steps * 1e3
     thr1 = thread_cpu_seconds()
     busiest = sorted(((n, (c - thr0.get(t, (n, 0.0))[1]) / args.steps * 1e3) for t, (n, c) in thr1.items()), key=lambda x: -x[1])[:4]
+    if args.dump_outputs and rank == 0:
+        dump_records(args.dump_outputs, recs_per_rank, B, last_step["j"], last_step["K"])
     bb_ms = [e0.elapsed_time(e1) for e0, e1 in pipe.bb_events]
     # idle time of a backbone stream between two consecutive schedules (batch k-depth's end -> batch k's start)
     ev = pipe.bb_events
@@ -591,7 +713,6 @@ def main():
         def hbm_view(nbytes):                                   # bytes per step -> GB/s over the timed region and its share of the HBM peak
             g = nbytes / step_s / 1e9
             return {"bytes_per_step": nbytes, "achieved": g, "frac": g / PEAK_HBM_GBPS}
-        n_rec = len(collected) if gathered is None else sum(len(pickle.loads(b)) for b in gathered)
         # the timed steps rotate over NB resident batches (and four synthetic scenes): records with one image_path must be identical, bit
         # for bit, whatever ran next to them on the GPU -- a guard the overlapped pipeline lacked until round 3 (EXPERIMENTS R3.6)
         n_rem = getattr(pipe, "remainder_records", 0)            # an odd step count leaves one batch to the batch-sized schedule, whose
@@ -600,16 +721,11 @@ def main():
             key = (np.asarray(r["pred_2d"]).tobytes(), np.asarray(r["pred_3d"]).tobytes(), np.asarray(r["root_d"]).tobytes())
             groups.setdefault(r["image_path"], set()).add(key)
         identical = all(len(v) == 1 for v in groups.values())
+        head = headline(args, world, B, dt, pipe, NB, n_rec, len(recs_per_rank))
         out = {
-            "metric": "frames/sec at 3x512x832 (SMAP backbone + depth-aware association + 3D lifting)",
-            "value": fps, "unit": "frames/sec", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True, "scaling": "weak",
-            "vs_baseline": None, "dtype": "f16x3" if x3 else "f16", "data": "synthetic",
-            "config": {"workload": f"batch={B} x 3x512x832 per GPU, full SMAP + depth-aware PAF association "
-                                   f"+ lifting{' + RefineNet (configs[4])' if args.refine else ''}{' + flip-TTA' if args.flip else ''} "
-                                   f"(BASELINE configs[2]; configs[3] when n_gpus=8)",
-                       "frames_per_step": B * world, "records_in_run": n_rec,
-                       "resident_batches_in_rotation": NB, "input_bytes_in_rotation": NB * B * 3 * H * W * 4,
+            **head,
+            "config": {**head["config"],
+                       "input_bytes_in_rotation": NB * B * 3 * H * W * 4,
                        # N > 1: every rank's own timed region (the headline divides by the MAX), so that a slow rank shows in ONE record
                        "per_rank": {"frames_per_sec": [B * args.steps / x for x in per_rank_dt],
                                     "ms_per_step_max": max(per_rank_dt) / args.steps * 1e3, "ms_per_step_min": min(per_rank_dt) / args.steps * 1e3,
@@ -625,12 +741,6 @@ def main():
                        "precision_modes": "x3 (this line unless --precision f16): meets the reference's fp32 results end to end "
                                           "(e2e_parity below); f16: ~2x the frames/s, ~0.36 cm mean / 1.06 cm max joint error at 3 m "
                                           "(profiles/r2_final_bench_f16.json) -- not within the 1e-3 m of the north star",
-                       "pipeline": f"post-processing of batch k overlaps later backbones; {args.depth} backbone(s) in flight; "
-                                   f"{pipe.frames_per_launch} frames per backbone launch"
-                                   + (f" (= {pipe.frames_per_launch // B} consecutive steps' batches coalesced; --launch-frames 0: one launch "
-                                      f"per step)" if pipe.frames_per_launch > B else "")
-                                   + "; one end-of-run gather of the records",
-                       "frames_per_launch": pipe.frames_per_launch,
                        # layer1's Bottlenecks and layer2's identity Bottlenecks as ONE launch each (csrc/convb.hip, convc.hip), the shared-input 1x1s
                        # of the Upsample_units as one launch with several outputs: conv launches per forward 206 -> 164 -> 152
                        "whole_block_launches": sum(1 for op in pipe.engine.graph.ops if "head" in op.p),
@@ -640,7 +750,6 @@ def main():
                        # back for its group), timed in this process right after the headline region
                        "value_launch_frames_0": fps_lf0 if fps_lf0 is not None else (fps if pipe.frames_per_launch == B * (2 if args.flip else 1) else None),
                        "added_latency_steps_by_coalescing": (pipe.frames_per_launch // (B * (2 if args.flip else 1)) - 1),
-                       "ranks_in_gather": len(gathered) if gathered is not None else 1,
                        # did the records go through torch.distributed (backend "nccl" = RCCL) and come back byte for byte?
                        "gather": ({"backend": dist.get_backend(), "payload_bytes": len(payload), "payload_device": str(cdev),
                                    "own_payload_returned_identical": gathered[rank] == payload} if gathered is not None else None),

@@ -311,6 +311,41 @@ def test_bench_control_flow_eight_ranks_gloo():
     assert pr["ms_per_step_min"] <= pr["ms_per_step_max"] <= d["ms_per_step"] * 1.0001
 
 
+def test_bench_dump_outputs_writes_the_last_steps_records(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: the records of the LAST timed step (batch j, scene set K) of every rank as float32 / float64 .npy
+    files, persons concatenated in frame order; a frame without a record counts 0 persons, an earlier step's record of the same
+    frame is superseded by the last one; beyond the size cap a fixed seeded sample of the frames, named in frames.npy."""
+    import bench
+    rng = np.random.default_rng(5)
+
+    def rec(path, P):
+        return {"pred_2d": rng.normal(size=(P, 15, 4)).astype(np.float32), "pred_3d": rng.normal(size=(P, 15, 4)),
+                "root_d": rng.normal(size=P), "image_path": path, "gt_3d": [], "gt_2d": []}
+    r0 = [rec("r0/b1/f0", 2), rec("r0/b0/f1", 3), rec("r0/b1/f0", 1), rec("r0/b1/f2", 4), rec("synthK8/r0/b1/f1", 8),
+          rec("synthK2/r0/b1/f1", 2)]
+    r1 = [rec("r1/b1/f1", 5)]
+    bench.dump_records(str(tmp_path / "d"), [r0, r1], 3, 1, 8)
+    ld = lambda n: np.load(tmp_path / "d" / f"{n}.npy")
+    assert ld("persons").dtype == np.float64 and ld("persons").tolist() == [1, 0, 4, 0, 5, 0]
+    p2 = ld("pred_2d")
+    assert p2.dtype == np.float32 and p2.shape == (10, 15, 4)
+    assert np.array_equal(p2, np.concatenate([r0[2]["pred_2d"], r0[3]["pred_2d"], r1[0]["pred_2d"]]))
+    assert ld("pred_3d").dtype == np.float64 and np.array_equal(ld("pred_3d")[1:5], r0[3]["pred_3d"])
+    assert np.array_equal(ld("root_d"), np.concatenate([r0[2]["root_d"], r0[3]["root_d"], r1[0]["root_d"]]))
+    assert ld("synth_persons").tolist() == [0, 8, 0, 0, 0, 0] and np.array_equal(ld("synth_pred_2d"), r0[4]["pred_2d"])
+    assert not (tmp_path / "d" / "frames.npy").exists()
+    # over the cap: a sample of whole frames that fits, the same one every time
+    many = [rec(f"r0/b0/f{i}", 20) for i in range(64)]
+    monkeypatch.setattr(bench, "DUMP_CAP_BYTES", (1 << 20) + 64 * 1024)
+    for d in ("s1", "s2"):
+        bench.dump_records(str(tmp_path / d), [many], 64, 0, 0)
+    files = sorted(os.listdir(tmp_path / "s1"))
+    assert "frames.npy" in files and sum(os.path.getsize(tmp_path / "s1" / f) for f in files) <= bench.DUMP_CAP_BYTES
+    kept = np.load(tmp_path / "s1" / "frames.npy").astype(int)
+    assert 0 < len(kept) < 64 and np.array_equal(kept, np.load(tmp_path / "s2" / "frames.npy"))
+    assert np.array_equal(np.load(tmp_path / "s1" / "pred_3d.npy"), np.concatenate([many[i]["pred_3d"] for i in kept]))
+
+
 def test_test_py_dry_run_eight_ranks(tmp_path):
     """exps/stage3_root2/test.py --dry_run 1 under an 8-rank launch: 37 images (not a multiple of ranks x batch) are split in
     contiguous blocks of ceil(37/8) = 5 (lib/utils/dataloader.py:80-85), ragged last batches are padded and their padding

@@ -117,7 +117,7 @@ def test_bench_main_two_ranks_on_one_gpu():
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", SMAP_BENCH_SHARE_GPU="1", SMAP_BENCH_BACKEND="gloo")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2",
                         "--master-addr", "127.0.0.1", "--master-port", "29541", os.path.join(ROOT, "bench.py"),
-                        "--gpus", "2", "--steps", "4", "--warmup", "2"], capture_output=True, text=True, timeout=900,
+                        "--gpus", "2", "--steps", "4", "--warmup", "2", "--full"], capture_output=True, text=True, timeout=900,
                        env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -139,8 +139,8 @@ def test_rccl_gather_runs_on_hardware_with_one_rank():
     (lib/utils/comm.py:47-87) and must come back byte for byte.  Then the helper alone on payloads of ragged sizes."""
     env = dict(os.environ, SMAP_FORCE_GATHER="1", SMAP_BENCH_NO_LF0="1")
     env.pop("SMAP_BENCH_BACKEND", None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "2", "--no-cpu-baseline"],
-                       capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "2", "--no-cpu-baseline",
+                        "--full"], capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     c = d["config"]
@@ -164,6 +164,27 @@ def test_rccl_gather_runs_on_hardware_with_one_rank():
     r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=600, cwd=ROOT,
                        env=dict(os.environ, PYTHONPATH=ROOT + os.pathsep + os.environ.get("PYTHONPATH", "")))
     assert r.returncode == 0 and "rccl ok" in r.stdout, r.stderr[-3000:]
+
+
+def test_plain_bench_run_prints_the_headline_and_dumps_the_last_steps_records(tmp_path):
+    """`bench.py --gpus 1 --steps K --warmup W` without --full: one JSON line with the headline fields and nothing that needs a run of
+    its own (no cpu_baseline, no roofline); --dump-outputs writes the records of the last timed step (the third: its synthetic
+    scenes hold K = 8 persons each), float32 / float64, consistent with each other and finite."""
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                        "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=900, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    d = json.loads(lines[0])
+    assert d["unit"] == "frames/sec" and d["higher_is_better"] is True and d["dtype"] == "f16x3" and d["steps"] == 3
+    assert d["value"] > 0 and abs(d["ms_per_step"] - 8 * 1e3 / d["value"]) < 1e-6 * d["ms_per_step"]
+    assert "cpu_baseline" not in d and "roofline" not in d and "e2e_parity" not in d["config"] and d["config"]["full"] is False
+    ld = lambda n: np.load(tmp_path / f"{n}.npy")
+    for pre, at_least in (("", 8), ("synth_", 8)):
+        persons, p2, p3, rz = ld(pre + "persons"), ld(pre + "pred_2d"), ld(pre + "pred_3d"), ld(pre + "root_d")
+        assert persons.shape == (8,) and p2.dtype == np.float32 and p3.dtype == np.float64 and rz.dtype == np.float64
+        assert p2.shape == p3.shape == (int(persons.sum()), 15, 4) and rz.shape == (int(persons.sum()),) and persons.sum() >= at_least
+        assert np.isfinite(p2).all() and np.isfinite(p3).all() and np.isfinite(rz).all()
 
 
 def test_two_stream_pipeline_equals_serial_path():

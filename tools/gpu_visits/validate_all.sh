@@ -10,14 +10,14 @@ export TMPDIR=/tmp
 timeout 2700 python -m pytest tests -m gpu -q --tb=short -p no:cacheprovider > $O/pytest.log 2>&1; echo "pytest rc $?" >> $O/pytest.log
 tail -8 $O/pytest.log
 timeout 300 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $O/smoke.log 2>&1; tail -2 $O/smoke.log
-timeout 400 python bench.py > $O/bench_x3.json 2> $O/bench_x3.err; echo "rc $?" >> $O/bench_x3.err
-timeout 400 python bench.py --steps 20 --warmup 5 > $O/bench_x3_driver_form.json 2>> $O/bench_x3.err
-timeout 400 python bench.py --flip --steps 40 > $O/bench_x3_flip.json 2> $O/bench_x3_flip.err
-timeout 400 python bench.py --refine --steps 60 > $O/bench_x3_refine.json 2> $O/bench_x3_refine.err
+timeout 400 python bench.py --full > $O/bench_x3.json 2> $O/bench_x3.err; echo "rc $?" >> $O/bench_x3.err
+timeout 400 python bench.py --full --steps 20 --warmup 5 > $O/bench_x3_driver_form.json 2>> $O/bench_x3.err
+timeout 400 python bench.py --full --flip --steps 40 > $O/bench_x3_flip.json 2> $O/bench_x3_flip.err
+timeout 400 python bench.py --full --refine --steps 60 > $O/bench_x3_refine.json 2> $O/bench_x3_refine.err
 timeout 300 python bench.py --forward-only --batch 1 --graph --steps 300 --warmup 30 > $O/bench_x3_forward_b1.json 2>> $O/bench_x3.err
 timeout 300 python bench.py --forward-only --batch 1 --steps 300 --warmup 30 > $O/bench_x3_forward_b1_kernel_by_kernel.json 2>> $O/bench_x3.err
-timeout 300 python bench.py --precision f16 --steps 60 > $O/bench_f16.json 2>> $O/bench_x3.err
-timeout 300 python bench.py --no-cpu-baseline --batch 1 --depth 1 --launch-frames 0 --steps 200 --warmup 20 > $O/bench_x3_batch1_full_path.json 2>> $O/bench_x3.err
+timeout 300 python bench.py --full --precision f16 --steps 60 > $O/bench_f16.json 2>> $O/bench_x3.err
+timeout 300 python bench.py --full --no-cpu-baseline --batch 1 --depth 1 --launch-frames 0 --steps 200 --warmup 20 > $O/bench_x3_batch1_full_path.json 2>> $O/bench_x3.err
 TAG=$TAG python - <<'PY'
 import json, os
 for f in ("bench_x3", "bench_x3_driver_form", "bench_x3_flip", "bench_x3_refine", "bench_x3_forward_b1", "bench_x3_forward_b1_kernel_by_kernel", "bench_f16", "bench_x3_batch1_full_path"):

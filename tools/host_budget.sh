@@ -12,7 +12,7 @@ for n in $NCPU 4 2 1; do
   last=$((n - 1))
   MASTER_ADDR=127.0.0.1 SMAP_BENCH_SHARE_GPU=1 SMAP_BENCH_BACKEND=gloo SMAP_BENCH_NO_LF0=1 timeout 600 taskset -c 0-$last \
     python -m torch.distributed.run --nnodes=1 --nproc-per-node=2 --master-addr 127.0.0.1 --master-port $((29600 + n)) \
-    bench.py --gpus 2 --steps $STEPS --warmup 5 --no-cpu-baseline 2>/dev/null | python -c "
+    bench.py --gpus 2 --steps $STEPS --warmup 5 --no-cpu-baseline --full 2>/dev/null | python -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{'):
