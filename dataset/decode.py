@@ -13,7 +13,8 @@ import numpy as np
 
 
 def read_bgr(path):
-    if path.endswith(".npy"):
+    """path: a file name, or a binary file object of an image file (smap_amd/jpeg.py's PIL fallback for bytes)."""
+    if isinstance(path, str) and path.endswith(".npy"):
         return np.load(path)
     from PIL import Image, ImageOps
     # cv2.imread(IMREAD_COLOR) applies the EXIF orientation; PIL does not by itself.  BGR order comes out of PIL's own packer (one C

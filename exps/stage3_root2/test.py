@@ -59,16 +59,25 @@ class DevicePreprocLoader:
     SMAP_DECODE_PROCS=<n>: the decoders as n WORKER PROCESSES (python -m dataset.decode: numpy + PIL only) writing into one shared-memory
     block, one slot per worker; the pool threads of this process then only talk to their worker and copy its slot into page-locked memory.
     What threads cannot scale past is the part of a decode that holds the interpreter lock (PIL's packers, file objects): ~600 frames/s on
-    the bench's image mix, below the engine (EXPERIMENTS R6.11).  SMAP_DECODE_SLOT_MB (default 16): a larger frame is decoded in-thread."""
+    the bench's image mix, below the engine (EXPERIMENTS R6.11).  SMAP_DECODE_SLOT_MB (default 16): a larger frame is decoded in-thread.
+    device_decode (`--device_decode 1`): the pool threads read the file bytes, parse the JPEG markers and Huffman-decode the coefficients
+    into page-locked memory (native code, no interpreter lock); the consumer uploads them and the GPU finishes the decode (smap_amd/jpeg.py),
+    bit for bit PIL's frame.  Whatever the native decoder does not take (progressive, PNG, damaged files ...) is decoded with PIL as before;
+    the count is logged at the end of the run.  Worker processes (SMAP_DECODE_PROCS) are not used then."""
 
-    def __init__(self, dataset, indices, batch_size, cfg, device):
+    def __init__(self, dataset, indices, batch_size, cfg, device, device_decode=False):
         self.ds, self.idx, self.bs, self.cfg, self.device = dataset, list(indices), batch_size, cfg, device
+        self.device_decode = bool(device_decode)
+        self.pil_frames = 0                                  # device_decode: frames that fell back to PIL
         try:
             allowed = len(os.sched_getaffinity(0))
         except AttributeError:
             allowed = os.cpu_count() or 1
         self.threads = int(os.environ.get("SMAP_DECODE_THREADS", "0")) or max(1, min(16, allowed))
         self.procs = int(os.environ.get("SMAP_DECODE_PROCS", "0"))
+        if self.procs > 0 and self.device_decode:
+            logging.getLogger(cfg.DATASET.NAME).info("SMAP_DECODE_PROCS=%d is not used with --device_decode 1", self.procs)
+            self.procs = 0
         if self.procs > 0:
             self.threads = self.procs                        # one pool thread per worker process
         self.slot_bytes = int(os.environ.get("SMAP_DECODE_SLOT_MB", "16")) << 20
@@ -77,10 +86,19 @@ class DevicePreprocLoader:
         return (len(self.idx) + self.bs - 1) // self.bs
 
     def __iter__(self):
+        yield from self._batches()
+        if self.device_decode:
+            logging.getLogger(self.cfg.DATASET.NAME).info("device decode: {} of {} frames fell back to PIL".format(self.pil_frames, len(self.idx)))
+
+    def _batches(self):
         from smap_amd.preprocess import preprocess_batch
+        self.pil_frames = 0
         if self.threads <= 1:
             for s in range(0, len(self.idx), self.bs):
-                raws, names = zip(*[self.ds.raw(i) for i in self.idx[s:s + self.bs]])
+                if self.device_decode:
+                    raws, names = zip(*[self._device_frame(self._coefficients(i, lambda img: img)) for i in self.idx[s:s + self.bs]])
+                else:
+                    raws, names = zip(*[self.ds.raw(i) for i in self.idx[s:s + self.bs]])
                 imgs, scales = preprocess_batch(raws, self.cfg.INPUT.MEANS, self.cfg.INPUT.STDS, self.device)
                 yield imgs, list(names), scales
             return
@@ -100,7 +118,10 @@ class DevicePreprocLoader:
             img, name = self.ds.raw(i)
             return pinned(img), name
         workers = contextlib.ExitStack()
-        if self.procs > 0:
+        if self.device_decode:
+            def decode(i):
+                return self._coefficients(i, pinned)
+        elif self.procs > 0:
             decode = self._process_decoders(workers, pinned)
         with workers, ThreadPoolExecutor(self.threads) as ex:
             todo, futs = iter(self.idx), collections.deque()
@@ -116,10 +137,36 @@ class DevicePreprocLoader:
                 n = min(self.bs, len(futs))
                 got = [futs.popleft().result() for _ in range(n)]       # in submission order: frame order is kept
                 fill()
+                if self.device_decode:
+                    got = [self._device_frame(g) for g in got]
                 raws, names = zip(*got)
                 imgs, scales = preprocess_batch(raws, self.cfg.INPUT.MEANS, self.cfg.INPUT.STDS, self.device)
                 yield imgs, list(names), scales
 
+
+    def _coefficients(self, i, pinned):
+        """device_decode, in a pool thread: (("jpeg", coefficients in page-locked memory, info) or a PIL frame, name)."""
+        from smap_amd import jpeg as J
+        path = self.ds.image_list[i].rstrip()
+        if not path.endswith(".npy"):
+            with open(path, "rb") as f:
+                data = f.read()
+            info = J.probe(data)
+            coeffs = J.decode_coefficients(data, info) if info is not None else None
+            if coeffs is not None:
+                return ("jpeg", coeffs, info), path.replace(self.ds.dataset_path, "").lstrip("/")
+        img, name = self.ds.raw(i)
+        return pinned(img), name
+
+    def _device_frame(self, item):
+        """device_decode, in the consumer: upload the coefficients and finish the decode on the GPU (current stream)."""
+        img, name = item
+        if isinstance(img, tuple):
+            from smap_amd import jpeg as J
+            return J.reconstruct(img[1], img[2], self.device), name
+        if not name.endswith(".npy"):
+            self.pil_frames += 1
+        return img, name
 
     def _process_decoders(self, stack, pinned):
         """Start SMAP_DECODE_PROCS workers (dataset/decode.py) over one shared-memory block; -> decode(i) for the pool threads.  A pool
@@ -329,7 +376,12 @@ def main():
                              "multi-rank launch does around the device work -- split, ragged batches, gather, result file")
     parser.add_argument("--device_preprocess", type=int, default=0,
                         help="(addition) 1: resize/pad/normalise on the GPU (smap_preprocess) instead of in the dataset")
+    parser.add_argument("--device_decode", type=int, default=0,
+                        help="(addition) 1: baseline JPEGs are Huffman-decoded on the host and finished on the GPU (smap_amd/jpeg.py), "
+                             "bit for bit the PIL frame; other files are decoded with PIL.  Requires --device_preprocess 1")
     args = parser.parse_args()
+    if args.device_decode and not args.device_preprocess:
+        parser.error("--device_decode 1 requires --device_preprocess 1")
     cfg.TEST_MODE = args.test_mode
     cfg.DATA_MODE = args.data_mode
     cfg.REFINE = len(args.RefineNet_path) > 0
@@ -372,7 +424,8 @@ def main():
     if dataset is None:
         pass
     elif args.device_preprocess:
-        data_loader = DevicePreprocLoader(dataset, indices, args.batch_size, cfg, torch.device(cfg.MODEL.DEVICE, local))
+        data_loader = DevicePreprocLoader(dataset, indices, args.batch_size, cfg, torch.device(cfg.MODEL.DEVICE, local),
+                                          device_decode=args.device_decode)
     else:
         data_loader = DataLoader(Subset(dataset, indices) if world > 1 else dataset, batch_size=args.batch_size,
                                  shuffle=False)

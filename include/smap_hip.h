@@ -372,6 +372,51 @@ int smap_plan_create_from_blob(const void* blob, size_t blob_bytes, smap_plan** 
 int smap_plan_run_range(const smap_plan* plan, int first, int count, const float* input,
                         void* arena, const void* weights, float* out, void* stream);
 
+/* ---- JPEG decode: replaces the image decode of dataset/custom_dataset.py (cv2.imread; here PIL + EXIF transpose) ----
+ *
+ * Split at the natural seam: the HOST (csrc/jpeg_host.cpp, plain C++, no HIP, no global state, safe to call from many threads at once)
+ * parses the markers and Huffman-decodes the entropy-coded data into quantised coefficients; the GPU (csrc/jpeg.hip) dequantises,
+ * runs libjpeg's ISLOW inverse DCT, upsamples the chroma ("fancy", as libjpeg does by default), converts YCbCr to BGR and applies
+ * the EXIF orientation -- bit for bit what libjpeg-turbo + PIL's exif_transpose hand the network (DESIGN.md "JPEG decode").
+ * Supported: 8-bit baseline / extended sequential Huffman, one interleaved scan, grey or YCbCr with luma sampling 1x1, 2x1 or 2x2
+ * and chroma 1x1 (4:4:4, 4:2:2, 4:2:0), restart intervals, EXIF orientation 1-8.  Anything else valid is SMAP_JPEG_UNSUPPORTED
+ * (the caller decodes it with PIL); malformed data is SMAP_JPEG_E_DATA (the caller also falls back, and PIL then raises). */
+#define SMAP_JPEG_UNSUPPORTED 1
+#define SMAP_JPEG_E_DATA (-2)
+
+typedef struct smap_jpeg_info {
+    int32_t width, height;              /* as stored (before the orientation)                                          */
+    int32_t orientation;                /* EXIF orientation 1-8 (1 = none; out-of-range values count as 1, as in PIL)   */
+    int32_t ncomp;                      /* 1 (grey) or 3 (YCbCr)                                                       */
+    int32_t h_samp[3], v_samp[3];       /* sampling factors (grey: 1, 1)                                               */
+    int32_t blocks_w[3], blocks_h[3];   /* 8x8 blocks per line / per column of each component, MCU padding included    */
+    uint16_t quant[3][64];              /* quantisation table of each component, NATURAL order                        */
+    int64_t coef_offset[3];             /* byte offset of each component's coefficient plane                          */
+    int64_t coef_bytes;                 /* all planes: int16 [component][block row][block col][64], natural order     */
+    int64_t scan_offset;                /* byte offset of the entropy-coded data in the file                          */
+    int32_t restart_interval;           /* MCUs per restart interval, 0 = none                                        */
+    int32_t reserved;
+} smap_jpeg_info;
+
+/* sizeof(smap_jpeg_info) as compiled (binding check, as smap_sizeof_op). */
+int smap_sizeof_jpeg_info(void);
+
+/* data: HOST bytes of a whole file.  Parses the markers up to the first SOS.  0 = supported (info filled), SMAP_JPEG_UNSUPPORTED,
+ * SMAP_JPEG_E_DATA or SMAP_E_ARG. */
+int smap_jpeg_probe(const uint8_t* data, size_t n, smap_jpeg_info* info);
+
+/* data / info / coeffs: HOST.  info must be what smap_jpeg_probe returned for these bytes.  Writes info->coef_bytes of QUANTISED
+ * coefficients (absolute DC, natural order, every block of the MCU grid).  Any surprise in the entropy-coded data -- a bad code, an
+ * early marker or end of file, a wrong RSTn, data left over after the last MCU -- is SMAP_JPEG_E_DATA. */
+int smap_jpeg_decode_coefficients(const uint8_t* data, size_t n, const smap_jpeg_info* info, int16_t* coeffs);
+
+/* Device scratch smap_jpeg_reconstruct needs for the component planes (bytes; = coef_bytes / 2).  info: HOST. */
+int64_t smap_jpeg_workspace_bytes(const smap_jpeg_info* info);
+
+/* coeffs: DEVICE copy of smap_jpeg_decode_coefficients' output; info: HOST; planes: DEVICE scratch of smap_jpeg_workspace_bytes;
+ * bgr: DEVICE uint8 [H'][W'][3], the orientation applied (orientations 5-8 swap width and height).  Two launches on `stream`. */
+int smap_jpeg_reconstruct(const int16_t* coeffs, const smap_jpeg_info* info, uint8_t* planes, uint8_t* bgr, void* stream);
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif

@@ -25,6 +25,8 @@ SOURCES = [
     ("convb.hip", []),
     ("convc.hip", []),
     ("plan.hip", []),
+    ("jpeg.hip", []),
+    ("jpeg_host.cpp", []),        # host-only C++ (marker parse + Huffman decode); no fast-math anywhere in this library
 ]
 # -fvisibility=hidden: the .so exports exactly what include/smap_hip.h declares (its visibility push / pop), nothing of the internals
 COMMON = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden", "-I" + os.path.join(ROOT, "include"),

@@ -20,6 +20,7 @@ SYMBOLS = [
     "smap_refine", "smap_register_gt", "smap_lift_gt", "smap_refine_gt", "smap_refine_mlp", "smap_preprocess", "smap_sizeof_op", "smap_conv_tile_dims", "smap_conv_tile_bk", "smap_conv_tile_tail_bn", "smap_plan_create", "smap_plan_destroy", "smap_plan_run", "smap_plan_run_range",
     "smap_plan_run_inputs", "smap_workspace_bytes", "smap_plan_create_from_blob", "smap_plan_set_lanes",
     "smap_nms_workspace_bytes", "smap_nms_ws",
+    "smap_sizeof_jpeg_info", "smap_jpeg_probe", "smap_jpeg_decode_coefficients", "smap_jpeg_workspace_bytes", "smap_jpeg_reconstruct",
 ]
 MAX_INPUTS = 8                         # SMAP_MAX_INPUTS
 
@@ -72,6 +73,17 @@ class BlobHeader(C.Structure):
                 ("arena_bytes", C.c_int64), ("out_bytes", C.c_int64), ("info", BlobInfo)]
 
 
+class JpegInfo(C.Structure):
+    """Mirror of `struct smap_jpeg_info`."""
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("orientation", C.c_int32), ("ncomp", C.c_int32),
+                ("h_samp", C.c_int32 * 3), ("v_samp", C.c_int32 * 3), ("blocks_w", C.c_int32 * 3), ("blocks_h", C.c_int32 * 3),
+                ("quant", (C.c_uint16 * 64) * 3), ("coef_offset", C.c_int64 * 3), ("coef_bytes", C.c_int64),
+                ("scan_offset", C.c_int64), ("restart_interval", C.c_int32), ("reserved", C.c_int32)]
+
+
+JPEG_UNSUPPORTED = 1      # SMAP_JPEG_UNSUPPORTED
+JPEG_E_DATA = -2          # SMAP_JPEG_E_DATA
+
 _lib = None
 
 
@@ -119,12 +131,19 @@ def load():
     lib.smap_plan_set_lanes.argtypes = [vp, ip]
     lib.smap_workspace_bytes.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     lib.smap_plan_create_from_blob.argtypes = [vp, C.c_size_t, C.POINTER(vp), C.POINTER(BlobInfo)]
+    lib.smap_jpeg_probe.argtypes = [vp, C.c_size_t, C.POINTER(JpegInfo)]
+    lib.smap_jpeg_decode_coefficients.argtypes = [vp, C.c_size_t, C.POINTER(JpegInfo), vp]
+    lib.smap_jpeg_workspace_bytes.argtypes = [C.POINTER(JpegInfo)]
+    lib.smap_jpeg_reconstruct.argtypes = [vp, C.POINTER(JpegInfo), vp, vp, vp]
     for s in SYMBOLS:
-        if s not in ("smap_version", "smap_plan_destroy", "smap_nms_workspace_bytes"):  # everything else returns int
+        if s not in ("smap_version", "smap_plan_destroy", "smap_nms_workspace_bytes", "smap_jpeg_workspace_bytes"):  # everything else returns int
             getattr(lib, s).restype = ip
     lib.smap_nms_workspace_bytes.restype = C.c_int64
+    lib.smap_jpeg_workspace_bytes.restype = C.c_int64
     if lib.smap_sizeof_op() != C.sizeof(SmapOp):
         raise ImportError(f"smap_op layout mismatch: C {lib.smap_sizeof_op()} vs ctypes {C.sizeof(SmapOp)}")
+    if lib.smap_sizeof_jpeg_info() != C.sizeof(JpegInfo):
+        raise ImportError(f"smap_jpeg_info layout mismatch: C {lib.smap_sizeof_jpeg_info()} vs ctypes {C.sizeof(JpegInfo)}")
     _lib = lib
     return lib
 

@@ -9,7 +9,10 @@ resolutions -- the bench's 8 frames as 832x512 PNGs and as 1664x1024 JPEGs (ever
 the frame back) -- so that the network sees the workload the bench line is quoted on (~20 skeletons per frame: association, lifting
 and record building do real work); a second folder holds the same pictures as .npy (no decoder).
 
-    python tools/cli_e2e.py [--images 256] [--out profiles/r5_cli_e2e.json]
+    python tools/cli_e2e.py [--images 256] [--out profiles/r5_cli_e2e.json] [--only jpeg]
+
+A third folder holds only the 1664x1024 JPEGs: there the PIL decoders (16 threads, 16 processes) run against `--device_decode 1`
+(Huffman decode on the host, the rest of the decode on the GPU) and the .npy frames.  --only jpeg runs those four legs alone.
 """
 import argparse
 import json
@@ -39,13 +42,14 @@ def main():
     ap.add_argument("--images", type=int, default=1024)
     ap.add_argument("--batch", type=int, default=8)
     ap.add_argument("--out", default=os.path.join(ROOT, "gpurun_out", "cli_e2e.json"))
+    ap.add_argument("--only", choices=["", "jpeg"], default="")
     args = ap.parse_args()
     from PIL import Image
     from benchkit.workload import make_cfg, people_state_dict
     from smap_amd.model.smap import SMAP
     tmp = tempfile.mkdtemp(prefix="smap_cli_e2e_")
-    enc, raw = os.path.join(tmp, "encoded"), os.path.join(tmp, "npy")
-    os.makedirs(enc), os.makedirs(raw)
+    enc, raw, jpg = os.path.join(tmp, "encoded"), os.path.join(tmp, "npy"), os.path.join(tmp, "jpg")
+    os.makedirs(enc), os.makedirs(raw), os.makedirs(jpg)
     from exps.stage3_root2.config import cfg as run_cfg
     t0 = time.perf_counter()
     base = bench_frames_as_images(list(run_cfg.INPUT.MEANS), list(run_cfg.INPUT.STDS))
@@ -69,6 +73,8 @@ def main():
             sizes.append(os.path.getsize(path))
         os.symlink(written[(f, big)][0], os.path.join(enc, f"im{i:05d}.{ext}"))
         os.symlink(written[(f, big)][1], os.path.join(raw, f"im{i:05d}.npy"))
+    for i in range(args.images):                                    # the JPEG-only folder: the 8 1664x1024 JPEGs, round robin
+        os.symlink(written[(i % 8, 1)][0], os.path.join(jpg, f"im{i:05d}.jpg"))
     gen_s = time.perf_counter() - t0
     torch.manual_seed(0)
     net = SMAP(make_cfg((128, 208))).eval()
@@ -83,6 +89,12 @@ def main():
              ("encoded jpg/png, GPU pre-processing, ONE decode thread (round-4 loader)", enc, ["--device_preprocess", "1"], {"SMAP_DECODE_THREADS": "1"}),
              (".npy frames (no decoder), GPU pre-processing", raw, ["--device_preprocess", "1"], {}),
              ("encoded jpg/png, host pre-processing (the reference's DataLoader path), first 128 images", enc + "_few", [], {})]
+    dd = ["--device_preprocess", "1", "--device_decode", "1"]
+    jpeg_cases = [("1664x1024 JPEG only, PIL, 16 decode threads", jpg, ["--device_preprocess", "1"], {"SMAP_DECODE_THREADS": "16"}),
+                  ("1664x1024 JPEG only, PIL, 16 decode PROCESSES (SMAP_DECODE_PROCS)", jpg, ["--device_preprocess", "1"], {"SMAP_DECODE_PROCS": "16"}),
+                  ("1664x1024 JPEG only, --device_decode 1 (host Huffman decode, default threads; IDCT / colour on the GPU)", jpg, dd, {}),
+                  (".npy frames (no decoder), GPU pre-processing", raw, ["--device_preprocess", "1"], {})]
+    cases = jpeg_cases if args.only == "jpeg" else cases + jpeg_cases[:3]
     os.makedirs(enc + "_few")
     for n in sorted(os.listdir(enc)):
         if n.startswith("im") and int(n[2:7]) < 128:
