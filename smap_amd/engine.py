@@ -1217,7 +1217,6 @@ class Graph:
         every = self.tensors + self.scratch_tensors + ([self.kcount] if self.kcount is not None else [])
         # arena[k * WINDOW : k * WINDOW + ZERO_PAGE] are the conv kernels' zero pages (csrc/plan.hip): never allocated, so no
         # tensor crosses a window boundary and every conv input is within 32 bits of its window's base
-        free, top = [], ZERO_PAGE    # free: list of (off, size)
         for t in every:
             if _rup(t.nbytes, ALIGN) > WINDOW - ZERO_PAGE:
                 raise ArenaTooLarge(f"{t.name}: {t.nbytes / 2 ** 30:.2f} GiB ({self.B} frames, precision {self.precision}) does not fit a "
@@ -1228,8 +1227,22 @@ class Graph:
         expiring = {}
         for t in every:
             expiring.setdefault(t.last, []).append(t)
+        # Both inputs of a two-input launch (conv_cat / conv_relusum) are addressed from one 64-bit base: they must share a window.  The
+        # builder makes such launches only where the reusing arena fits one window; an arena that keeps every tensor (reuse=False, for
+        # read_tensor) does not, and there the two are placed side by side when the first of them is.
+        group = {}
+        if not reuse:
+            for op in self.ops:
+                if op.kind == OP_CONV and "cat" in op.p:
+                    g = list({id(t): t for t in group.get(id(op.inp), [op.inp]) + group.get(id(op.aux2), [op.aux2])}.values())
+                    for t in g:
+                        group[id(t)] = g
+                        t.off = -1
+        free, top = [], ZERO_PAGE    # free: list of (off, size)
         for i in range(len(self.ops)):
             for t in by_first.get(i, []):
+                if t.off >= 0 and id(t) in group:                  # (placed with its partner)
+                    continue
                 need = _rup(t.nbytes, ALIGN)
                 pick = None
                 if reuse:
@@ -1242,13 +1255,16 @@ class Graph:
                     if sz > need:
                         free.append((o + need, sz - need))
                 else:
+                    members = [m for m in group.get(id(t), [t]) if m is t or m.off < 0]
+                    need = sum(_rup(m.nbytes, ALIGN) for m in members)
                     nxt = (top // WINDOW + 1) * WINDOW                 # start of the next window = its zero page
                     if top + need > nxt:                               # would run into it: leave the rest of this window free
                         if reuse and nxt > top:
                             free.append((top, nxt - top))
                         top = nxt + ZERO_PAGE
-                    t.off = top
-                    top += need
+                    for m in members:
+                        m.off = top
+                        top += _rup(m.nbytes, ALIGN)
             for t in expiring.get(i, []):
                 if reuse and t.off >= 0:
                     free.append((t.off, _rup(t.nbytes, ALIGN)))

@@ -25,9 +25,11 @@ def _split(t):
 
 
 def _run_single_conv(B, H, W, Cin, Cout, k, stride, tile, relu, use_res, use_adds, out_fp32=False,
-                     in_stride=None, in_off=0, seed=0, x3=False, x_scale=1.0):
+                     in_stride=None, in_off=0, seed=0, x3=False, x_scale=1.0, up=None, w_pairs=None, ksplit=1):
     """One CONV op through smap_plan_run.  x3: split-precision storage (hi/lo planes) and arithmetic; the operands are
-    then full fp32 values and the reference is the f64 conv of THOSE."""
+    then full fp32 values and the reference is the f64 conv of THOSE.  up = (h, w): a low-resolution [B, h, w, Cout] input,
+    bilinearly (align_corners) upsampled and added before the ReLU (smap_op.aux_off[0], smap.py:213-217).  w_pairs: layout of
+    the packed 32-half K tiles (default: seed % 2).  ksplit > 1: split K, with its own partial-tile scratch and tickets."""
     from smap_amd import lib as L
     from smap_amd.engine import TILES, ZERO_PAGE, split_f16
     lib = L.load()
@@ -46,6 +48,7 @@ def _run_single_conv(B, H, W, Cin, Cout, k, stride, tile, relu, use_res, use_add
     res = q(torch.randn(B, Ho, Wo, c8, generator=g) * x_scale) if use_res else None
     a1 = q(torch.randn(B, Ho, Wo, c8, generator=g) * x_scale) if use_adds else None
     a2 = q(torch.randn(B, Ho, Wo, c8, generator=g) * x_scale) if use_adds else None
+    lowres = q(torch.randn(B, up[0], up[1], c8, generator=g) * x_scale) if up else None
     acc_scale = 1.0
     if x3:
         hi, lo, acc_scale = split_f16(w.permute(0, 2, 3, 1).reshape(Cout, K).double())
@@ -55,19 +58,20 @@ def _run_single_conv(B, H, W, Cin, Cout, k, stride, tile, relu, use_res, use_add
         wk = torch.zeros(1, cout_pad, K, dtype=torch.float16)
         wk[0, :Cout] = w.permute(0, 2, 3, 1).reshape(Cout, K)
     from smap_amd.engine import pack_conv_weights, tile_family
-    w_pairs = seed % 2                                     # both layouts of the 32-half K tiles get exercised
+    if w_pairs is None:
+        w_pairs = seed % 2                                 # both layouts of the 32-half K tiles get exercised
     if tile in TILES and not (tile_family(tile) == "halo" and k != 3):     # (ops the plan must reject keep any bytes)
         wk = pack_conv_weights(wk, tile, x3, k, Cin, pairs=w_pairs)   # weight tiles as contiguous, pre-swizzled blocks (the conv ABI)
     bk = torch.zeros(cout_pad)
     bk[:Cout] = bias
-    # weight blob: [wk | bias]; arena: [x | res | a1 | a2 | out]
+    # weight blob: [wk | bias]; arena: [x | res | a1 | a2 | low-res | out | split-K partial tiles | tickets]
     al = lambda n: (n + 255) // 256 * 256
     w_bytes = al(wk.numel() * 2)
     blob = torch.zeros(w_bytes + al(bk.numel() * 4), dtype=torch.uint8)
     blob[:wk.numel() * 2] = wk.view(torch.uint8).reshape(-1)
     blob[w_bytes:w_bytes + bk.numel() * 4] = bk.view(torch.uint8).reshape(-1)
     store = _split if x3 else (lambda t: t)
-    parts, offs, cur = [x, res, a1, a2], [], ZERO_PAGE    # arena[0:ZERO_PAGE] = zero page
+    parts, offs, cur = [x, res, a1, a2, lowres], [], ZERO_PAGE    # arena[0:ZERO_PAGE] = zero page
     stored = [store(t) if t is not None else None for t in parts]
     for t in stored:
         offs.append(cur if t is not None else -1)
@@ -75,7 +79,11 @@ def _run_single_conv(B, H, W, Cin, Cout, k, stride, tile, relu, use_res, use_add
     out_off = cur
     esz = 4 if out_fp32 else 2
     npl = 2 if (x3 and not out_fp32) else 1
-    arena = torch.zeros(out_off + al(B * Ho * Wo * c8 * esz * npl) + 256, dtype=torch.uint8)
+    kpart_off = out_off + al(B * Ho * Wo * c8 * esz * npl)
+    bm = TILES.get(tile, (128, 64))[0]
+    n_tiles = -(-(B * Ho * Wo) // bm) * (cout_pad // bn)
+    kcount_off = kpart_off + (al(n_tiles * ksplit * bm * bn * 4) if ksplit > 1 else 0)
+    arena = torch.zeros(kcount_off + (al(4 * n_tiles) if ksplit > 1 else 0) + 256, dtype=torch.uint8)
     for t, o in zip(stored, offs):
         if t is not None:
             arena[o:o + t.numel() * 2] = t.contiguous().view(torch.uint8).reshape(-1)
@@ -90,6 +98,10 @@ def _run_single_conv(B, H, W, Cin, Cout, k, stride, tile, relu, use_res, use_add
     op.w_pairs = w_pairs
     for i in range(3):
         op.aux_off[i] = -1
+    if up:
+        op.aux_off[0], op.aux_h[0], op.aux_w[0] = offs[4], up[0], up[1]
+    if ksplit > 1:
+        op.ksplit, op.kpart_off, op.kcount_off = ksplit, kpart_off, kcount_off
     op.ext_off = -1
     h = C.c_void_p()
     L.check(lib.smap_plan_create(C.byref(op), 1, C.byref(h)), "create")
@@ -98,6 +110,8 @@ def _run_single_conv(B, H, W, Cin, Cout, k, stride, tile, relu, use_res, use_add
     L.check(lib.smap_plan_run(h, None, C.c_void_p(arena_d.data_ptr()), C.c_void_p(blob_d.data_ptr()), None, st), "run")
     torch.cuda.synchronize()
     lib.smap_plan_destroy(h)
+    if ksplit > 1:                                         # the last part of every tile leaves its ticket at zero for the next run
+        assert not arena_d[kcount_off:kcount_off + 4 * n_tiles].any()
     raw = arena_d[out_off:out_off + B * Ho * Wo * c8 * esz * npl].cpu()
     if npl == 2:
         got = raw.view(torch.float16).view(B, Ho, Wo, 2, c8).float()
@@ -109,6 +123,9 @@ def _run_single_conv(B, H, W, Cin, Cout, k, stride, tile, relu, use_res, use_add
     y = F.conv2d(xin.double(), w.double(), bias.double(), stride=stride, padding=pad).permute(0, 2, 3, 1)
     if use_res:
         y = y + res[..., :Cout].double()
+    if up:
+        lr = lowres[..., :Cout].double().permute(0, 3, 1, 2)
+        y = y + F.interpolate(lr, size=(Ho, Wo), mode="bilinear", align_corners=True).permute(0, 2, 3, 1)
     if relu:
         y = F.relu(y)
     if use_adds:
@@ -277,6 +294,119 @@ def test_single_conv_split_precision(case):
     err = (got[..., :cout] - ref).abs()
     assert torch.isfinite(got).all()
     assert err.max().item() < 3e-6 * ref.abs().max().item() + 1e-6, (err.max().item(), ref.abs().max().item())
+    assert not got[..., cout:].any()
+
+
+EDGE_CASES = [
+    # The conv launches of the shipped 512x832 schedules (1, 8 and 16 frames, x3 and f16, flip-TTA) whose combination of tile and
+    # epilogue no case above runs (tests/test_host_cpu.py::test_launch_inventory_every_shipped_conv_has_a_unit_case lists them):
+    # the launch's own Cin / Cout / taps / stride / split K / weight layout at a small ragged size (M = 273 per frame), and the
+    # fused bilinear add (smap_op.aux_off[0]) at the shipped up-sampling ratios.
+    # precision ("f16" / "x3" / "both"), B, H, W, Cin, Cout, k, s, tile, relu, res, adds, up (low-res size), out_fp32, ksplit, w_pairs
+    ('f16', 2, 13, 21, 256, 768, 1, 1, 0, True, False, False, None, 0, 1, 0),
+    ('f16', 1, 64, 104, 512, 256, 1, 1, 0, True, False, False, (32, 52), 0, 1, 0),
+    ('f16', 2, 13, 21, 64, 256, 1, 1, 0, True, True, False, None, 0, 1, 0),
+    ('f16', 2, 13, 21, 128, 128, 3, 1, 0, True, False, False, None, 0, 1, 0),
+    ('f16', 2, 26, 41, 128, 128, 3, 2, 0, True, False, False, None, 0, 1, 0),
+    ('f16', 2, 13, 21, 64, 256, 1, 1, 1, False, False, False, None, 0, 1, 0),
+    ('f16', 2, 13, 21, 64, 256, 1, 1, 1, True, True, True, None, 0, 1, 0),
+    ('f16', 2, 13, 21, 256, 43, 3, 1, 1, False, False, False, None, 1, 1, 0),
+    ('f16', 2, 13, 21, 64, 64, 3, 1, 1, True, False, False, None, 0, 1, 0),
+    ('f16', 2, 26, 41, 256, 256, 3, 2, 1, True, False, False, None, 0, 1, 0),
+    ('both', 2, 13, 21, 256, 256, 1, 1, 2, False, False, False, None, 0, 1, 0),
+    ('f16', 2, 13, 21, 64, 64, 1, 1, 2, True, False, False, None, 0, 1, 0),
+    ('f16', 1, 13, 21, 2048, 512, 1, 1, 2, True, False, False, None, 0, 4, 0),
+    ('f16', 2, 13, 21, 128, 512, 1, 1, 2, True, True, False, None, 0, 1, 0),
+    ('f16', 2, 13, 21, 128, 512, 1, 1, 2, True, True, True, None, 0, 1, 0),
+    ('f16', 2, 26, 41, 256, 512, 1, 2, 2, False, False, False, None, 0, 1, 0),
+    ('f16', 2, 13, 21, 256, 43, 3, 1, 2, False, False, False, None, 1, 1, 0),
+    ('f16', 1, 13, 21, 256, 14, 3, 1, 2, False, False, False, None, 1, 2, 0),
+    ('f16', 1, 13, 21, 256, 256, 3, 1, 2, True, False, False, None, 0, 2, 0),
+    ('f16', 1, 26, 41, 256, 256, 3, 2, 2, True, False, False, None, 0, 2, 0),
+    ('f16', 2, 13, 21, 256, 14, 3, 1, 3, False, False, False, None, 1, 1, 0),
+    ('f16', 2, 13, 21, 256, 256, 1, 1, 4, False, False, False, None, 0, 1, 0),
+    ('f16', 2, 13, 21, 256, 128, 1, 1, 4, True, False, False, None, 0, 1, 0),
+    ('f16', 1, 32, 52, 1024, 256, 1, 1, 4, True, False, False, (16, 26), 0, 1, 0),
+    ('f16', 2, 13, 21, 64, 256, 1, 1, 4, True, True, False, None, 0, 1, 0),
+    ('f16', 2, 13, 21, 64, 256, 1, 1, 4, True, True, True, None, 0, 1, 0),
+    ('f16', 2, 26, 41, 256, 256, 3, 2, 4, True, False, False, None, 0, 1, 0),
+    ('f16', 2, 13, 21, 256, 43, 3, 1, 30, False, False, False, None, 1, 1, 0),
+    ('both', 2, 13, 21, 256, 43, 3, 1, 36, False, False, False, None, 1, 1, 0),
+    ('f16', 2, 13, 21, 256, 256, 3, 1, 37, True, False, False, None, 0, 1, 0),
+    ('both', 2, 13, 21, 256, 14, 3, 1, 39, False, False, False, None, 1, 1, 0),
+    ('x3', 2, 13, 21, 512, 256, 1, 1, 2, True, False, False, None, 0, 1, 0),
+    ('x3', 2, 13, 21, 256, 1024, 1, 1, 2, True, True, False, None, 0, 1, 0),
+    ('x3', 2, 13, 21, 256, 1024, 1, 1, 2, True, True, True, None, 0, 1, 0),
+    ('x3', 2, 26, 41, 512, 1024, 1, 2, 2, False, False, False, None, 0, 1, 0),
+    ('x3', 2, 13, 21, 256, 256, 1, 1, 7, False, False, False, None, 0, 1, 0),
+    ('x3', 2, 13, 21, 512, 128, 1, 1, 7, True, False, False, None, 0, 1, 0),
+    ('x3', 1, 13, 21, 2048, 512, 1, 1, 7, True, False, False, None, 0, 4, 0),
+    ('x3', 1, 32, 52, 1024, 256, 1, 1, 7, True, False, False, (16, 26), 0, 1, 0),
+    ('x3', 2, 13, 21, 512, 2048, 1, 1, 7, True, True, False, None, 0, 1, 0),
+    ('x3', 2, 26, 41, 1024, 2048, 1, 2, 7, False, False, False, None, 0, 1, 0),
+    ('x3', 2, 13, 21, 256, 43, 3, 1, 7, False, False, False, None, 1, 1, 0),
+    ('x3', 1, 13, 21, 256, 43, 3, 1, 7, False, False, False, None, 1, 4, 0),
+    ('x3', 2, 13, 21, 128, 128, 3, 1, 7, True, False, False, None, 0, 1, 0),
+    ('x3', 1, 13, 21, 256, 256, 3, 1, 7, True, False, False, None, 0, 2, 0),
+    ('x3', 1, 26, 41, 256, 256, 3, 2, 7, True, False, False, None, 0, 2, 0),
+    ('x3', 2, 13, 21, 256, 512, 1, 1, 20, True, False, False, None, 0, 1, 0),
+    ('x3', 2, 13, 21, 256, 256, 1, 1, 23, False, False, False, None, 0, 1, 0),
+    ('x3', 2, 13, 21, 256, 64, 1, 1, 25, True, False, False, None, 0, 1, 0),
+    ('x3', 2, 13, 21, 2048, 256, 1, 1, 26, True, False, False, None, 0, 1, 0),
+    ('x3', 2, 13, 21, 256, 128, 1, 1, 27, True, False, False, None, 0, 1, 0),
+    ('x3', 2, 13, 21, 128, 512, 1, 1, 27, True, True, False, None, 0, 1, 0),
+    ('x3', 2, 13, 21, 256, 43, 3, 1, 34, False, False, False, None, 1, 1, 0),
+    ('x3', 2, 13, 21, 256, 14, 3, 1, 38, False, False, False, None, 1, 1, 0),
+    ('x3', 2, 13, 21, 256, 256, 1, 1, 50, False, False, False, None, 0, 1, 0),
+    ('x3', 2, 13, 21, 512, 256, 1, 1, 50, True, False, False, None, 0, 1, 0),
+    ('x3', 2, 13, 21, 512, 2048, 1, 1, 50, True, True, False, None, 0, 1, 0),
+    ('x3', 2, 13, 21, 512, 2048, 1, 1, 50, True, True, True, None, 0, 1, 0),
+    ('x3', 2, 26, 41, 256, 512, 1, 2, 50, False, False, False, None, 0, 1, 0),
+    ('x3', 2, 13, 21, 256, 128, 1, 1, 51, True, False, False, None, 0, 1, 0),
+    ('x3', 1, 13, 21, 256, 768, 1, 1, 51, True, False, False, None, 0, 1, 1),
+    ('x3', 2, 13, 21, 256, 1024, 1, 1, 51, True, True, False, None, 0, 1, 0),
+    ('x3', 2, 13, 21, 256, 1024, 1, 1, 51, True, True, True, None, 0, 1, 0),
+    ('x3', 2, 13, 21, 256, 256, 1, 1, 52, False, False, False, None, 0, 1, 0),
+    ('x3', 2, 13, 21, 256, 128, 1, 1, 52, True, False, False, None, 0, 1, 0),
+    ('x3', 2, 13, 21, 128, 512, 1, 1, 52, True, True, False, None, 0, 1, 0),
+    ('x3', 2, 13, 21, 128, 512, 1, 1, 52, True, True, True, None, 0, 1, 0),
+    ('x3', 2, 26, 41, 256, 512, 1, 2, 52, False, False, False, None, 0, 1, 0),
+    ('x3', 2, 13, 21, 256, 256, 3, 1, 52, True, False, False, None, 0, 1, 0),
+    ('x3', 1, 13, 21, 256, 256, 1, 1, 53, True, False, False, None, 0, 1, 1),
+    ('x3', 1, 64, 104, 512, 256, 1, 1, 53, True, False, False, (32, 52), 0, 1, 0),
+    ('x3', 1, 128, 208, 256, 256, 1, 1, 53, True, False, False, (64, 104), 0, 1, 1),
+    ('x3', 2, 13, 21, 256, 256, 1, 1, 54, False, False, False, None, 0, 1, 0),
+    ('x3', 2, 13, 21, 1024, 512, 1, 1, 54, True, False, False, None, 0, 1, 0),
+    ('x3', 2, 13, 21, 512, 2048, 1, 1, 54, True, True, False, None, 0, 1, 0),
+    ('x3', 2, 13, 21, 512, 2048, 1, 1, 54, True, True, True, None, 0, 1, 0),
+    ('x3', 2, 13, 21, 1024, 256, 1, 1, 55, True, False, False, None, 0, 1, 0),
+    ('x3', 1, 32, 52, 1024, 256, 1, 1, 55, True, False, False, (16, 26), 0, 1, 0),
+    ('x3', 2, 13, 21, 512, 256, 1, 1, 60, True, False, False, None, 0, 1, 0),
+    ('x3', 2, 26, 41, 256, 256, 3, 2, 60, True, False, False, None, 0, 1, 0),
+    ('x3', 2, 26, 41, 128, 128, 3, 2, 61, True, False, False, None, 0, 1, 0),
+    # the fused bilinear add at odd sizes: ragged M tile, an up-sampling ratio that is not 2, Cout not a multiple of the N tile
+    ('both', 3, 13, 21, 192, 320, 1, 1, 2, True, False, False, (7, 11), 0, 1, 0),
+    ('x3', 3, 13, 21, 192, 320, 1, 1, 54, True, False, False, (7, 11), 0, 1, 0),
+    # ... and at the finest shipped ratio (64x104 -> 128x208) in f16
+    ('f16', 1, 128, 208, 256, 256, 1, 1, 1, True, False, False, (64, 104), 0, 1, 0),
+]
+EDGE_PARAMS = [(c, pr) for c in EDGE_CASES for pr in (("f16", "x3") if c[0] == "both" else (c[0],))]
+
+
+@pytest.mark.parametrize("case,precision", EDGE_PARAMS,
+                         ids=["%s-%s" % (pr, "x".join(map(str, c[1:9])) + ("-up%dx%d" % c[12] if c[12] else "") + ("-fp32" if c[13] else "")
+                                          + ("-k%d" % c[14] if c[14] > 1 else "") + ("-wp" if c[15] else "")) for c, pr in EDGE_PARAMS])
+def test_single_conv_shipped_launch_edges(case, precision):
+    """One conv launch of a shipped signature against the f64 conv of the stored operands (+ residual, + the f64 align-corners bilinear
+    up-sampling of the stored low-resolution input before the ReLU, + addends after it); split K leaves every ticket at zero."""
+    _, B, H, W, cin, cout, k, s, tile, relu, res, adds, up, out_fp32, ksplit, w_pairs = case
+    x3 = precision == "x3"
+    got, ref, cout = _run_single_conv(B, H, W, cin, cout, k, s, tile, relu, res, adds, out_fp32=bool(out_fp32), x3=x3, up=up,
+                                      w_pairs=w_pairs, ksplit=ksplit, seed=B * 1000 + H * W + cin + cout + tile)
+    err = (got[..., :cout] - ref).abs()
+    tol = 3e-6 * ref.abs().max().item() + 1e-6 if x3 else 2e-3 * ref.abs().max().item() + 1e-3
+    assert torch.isfinite(got).all()
+    assert err.max().item() < tol, (err.max().item(), tol, np.unravel_index(err.argmax().item(), err.shape))
     assert not got[..., cout:].any()
 
 
@@ -921,7 +1051,7 @@ def test_split_k_batch_1_full_size_many_runs_bit_for_bit(monkeypatch):
     assert (o[:n] - ref[:n]).abs().max().item() <= 2e-5 * ref[:n].abs().max().item()
 
 
-SEG_CASES = [   # B, H, W, Cin, couts, relus, up (low-res size or None), tile
+SEG_CASES = [   # B, H, W, Cin, couts, relus, up (low-res size or None), tile[, w_pairs (default 1)]
     (2, 13, 21, 256, (256, 64), (1, 1), None, 20),
     (2, 13, 21, 256, (256, 64, 256), (1, 1, 0), None, 21),
     (1, 16, 26, 512, (256, 512), (1, 1), (8, 13), 54),
@@ -929,11 +1059,22 @@ SEG_CASES = [   # B, H, W, Cin, couts, relus, up (low-res size or None), tile
     (3, 16, 24, 256, (512, 256), (1, 0), None, 53),
     (1, 32, 52, 64, (256, 64), (1, 1), (16, 26), 50),
     (3, 16, 24, 256, (512, 256, 264), (1, 0, 1), None, 56),     # register-epilogue tile: every segment on its own 256-row N tile(s)
+    # the merged launches of the shipped 512x832 schedules on tiles the cases above do not reach, one 32-half K tile per block (w_pairs 0)
+    (2, 13, 21, 256, (256, 64), (1, 1), None, 0, 0),
+    (2, 13, 21, 256, (512, 256), (1, 0), None, 1, 0),
+    (2, 13, 21, 2048, (256, 2048), (1, 1), None, 2, 0),
+    (2, 13, 21, 2048, (256, 2048), (1, 1), None, 7, 0),
+    (2, 13, 21, 256, (1024, 256), (1, 0), None, 20, 0),
+    (2, 13, 21, 256, (256, 64), (1, 1), None, 21, 0),
+    (2, 13, 21, 256, (256, 256), (1, 0), None, 50, 0),
+    (2, 13, 21, 256, (512, 256), (1, 0), None, 52, 0),
+    (2, 13, 21, 2048, (256, 2048), (1, 1), None, 56, 0),
 ]
 
 
 @pytest.mark.parametrize("x3", [True, False], ids=["x3", "f16"])
-@pytest.mark.parametrize("case", SEG_CASES, ids=lambda c: "x".join(map(str, c[:4])) + "-" + "+".join(map(str, c[4])) + f"-t{c[7]}")
+@pytest.mark.parametrize("case", SEG_CASES, ids=lambda c: "x".join(map(str, c[:4])) + "-" + "+".join(map(str, c[4])) + f"-t{c[7]}"
+                         + (f"-wp{c[8]}" if len(c) > 8 else ""))
 def test_merged_1x1_launch_matches_torch(case, x3):
     """One launch, several 1x1 convs on one input, one dense output tensor each (include/smap_hip.h smap_op.seg_*): every output
     against an f64 torch conv of the same (rounded) operands; ragged M, a segment narrower than the N tile, the fused bilinear
@@ -941,7 +1082,7 @@ def test_merged_1x1_launch_matches_torch(case, x3):
     import torch.nn.functional as F
     from smap_amd import engine as E
     from smap_amd import lib as L
-    B, H, W, cin, couts, relus, up, tile = case
+    B, H, W, cin, couts, relus, up, tile, w_pairs = (case + (1,))[:9]
     if tile in E.REGEPI_TILES and not x3:
         pytest.skip("the register-epilogue tile has a split-precision instance only")
     gen = torch.Generator().manual_seed(sum(case[:4]) + tile)
@@ -956,7 +1097,7 @@ def test_merged_1x1_launch_matches_torch(case, x3):
         sd[pre + ".bn.running_var"] = torch.rand(c, generator=gen) + 0.5
         segs.append((f"y{j}", pre, bool(r)))
     g = E.Graph(sd, B, H * 4, W * 4, keep_ref=True, precision="x3" if x3 else "f16", build=False)
-    g.w_pairs = 1
+    g.w_pairs = w_pairs
     xt = g.tensor("x", H, W, cin)
     ut = g.tensor("up", up[0], up[1], couts[0]) if up else None
     outs = g.conv_seg(segs, xt, up=ut, tile=tile)
@@ -1003,8 +1144,11 @@ def test_merged_1x1_launch_matches_torch(case, x3):
         assert torch.isfinite(got).all() and err < ((3e-6 * mx + 1e-6) if x3 else 2e-3 * mx), (j, err, mx)
 
 
+TAP_SHAPES = [(2, 16, 24), (1, 13, 21), (3, 5, 7), (1, 32, 52)]    # B, H, W
+
+
 @pytest.mark.parametrize("x3", [True, False], ids=["x3", "f16"])
-@pytest.mark.parametrize("shape", [(2, 16, 24), (1, 13, 21), (3, 5, 7), (1, 32, 52)], ids=lambda c: "x".join(map(str, c)))
+@pytest.mark.parametrize("shape", TAP_SHAPES, ids=lambda c: "x".join(map(str, c)))
 def test_one_channel_3x3_head_as_tap_dots_and_a_stencil(shape, x3):
     """Graph.conv_tapdot + Graph.tapsum (smap_op.tap_n, SMAP_OP_TAPSUM): conv3x3_{256->1}(relu(conv1x1_{256->256}(x))) -- the root-depth head,
     smap.py:227-229 -- with the 256-channel activation never stored: the 1x1 launch keeps nine dot products per pixel, a stencil sums them.
@@ -1143,9 +1287,14 @@ def test_last_1x1_with_the_shortcut_conv_as_one_gemm(case, x3):
     assert lib.smap_plan_create(bad, 1, C.byref(h)) == -1
 
 
+RELUSUM_CASES = [   # B, H, W, c1 (skip1's K), c2 (skip2's K), cout, tile
+    (2, 8, 13, 512, 256, 512, 50), (1, 16, 26, 1024, 256, 1024, 51), (3, 5, 7, 2048, 256, 2048, 50), (2, 16, 24, 256, 256, 256, 51),
+    (1, 9, 11, 128, 192, 320, 50), (2, 8, 13, 512, 256, 512, 54), (1, 16, 26, 1024, 256, 1024, 53),
+]
+
+
 @pytest.mark.parametrize("x3", [True, False], ids=["x3", "f16"])
-@pytest.mark.parametrize("case", [(2, 8, 13, 512, 256, 512, 50), (1, 16, 26, 1024, 256, 1024, 51), (3, 5, 7, 2048, 256, 2048, 50), (2, 16, 24, 256, 256, 256, 51),
-                                  (1, 9, 11, 128, 192, 320, 50), (2, 8, 13, 512, 256, 512, 54), (1, 16, 26, 1024, 256, 1024, 53)], ids=lambda c: "x".join(map(str, c)))
+@pytest.mark.parametrize("case", RELUSUM_CASES, ids=lambda c: "x".join(map(str, c)))
 def test_two_activated_skip_convs_as_one_launch_and_one_tensor(case, x3):
     """Graph.conv_relusum / smap_op.in2_mode = 1: relu(skip1(x)) + relu(skip2(out)) (smap.py:218-241; only their sum is ever used, :142-153) as ONE
     launch writing ONE tensor -- the first conv's accumulators are activated and parked in registers while the second conv runs -- against the
@@ -1340,13 +1489,29 @@ def test_full_size_properties():
     assert a[0].abs().max().item() > 1e-3
 
 
+ROUND6_SWITCHES = ("SMAP_CAT", "SMAP_SKIPSUM", "SMAP_TAPHEAD")
+
+
+def _full_size_schedule(monkeypatch, schedule):
+    """"shipped": the schedule the product builds (tests/conftest.py forces round 6's launches on for the small test schedules; removed
+    here, so that batch 1 runs split K and the whole-block launches as configs[1] does); "round6": those launches forced on."""
+    for k in ROUND6_SWITCHES:
+        if schedule == "shipped":
+            monkeypatch.delenv(k, raising=False)
+        else:
+            monkeypatch.setenv(k, "1")
+
+
+@pytest.mark.parametrize("schedule", ["shipped", "round6"])
 @pytest.mark.parametrize("precision,tol_max,tol_mean", [("x3", 1e-4, 2e-5), ("f16", 1e-2, 2e-3)])
-def test_full_size_forward_vs_cpu_oracle(precision, tol_max, tol_mean):
+def test_full_size_forward_vs_cpu_oracle(monkeypatch, precision, tol_max, tol_mean, schedule):
     """BASELINE configs[1]: batch=1, 3x512x832, forward only -- HIP engine vs the CPU restatement of the
     reference forward (oracle/backbone_ref.py, fp32), recipe weights.  Split precision (the default) is held to the
-    fp32-roundoff level SURVEY.md 7 step 4 asks of an fp32-equivalent path; plain fp16 to its storage tolerance."""
+    fp32-roundoff level SURVEY.md 7 step 4 asks of an fp32-equivalent path; plain fp16 to its storage tolerance.
+    Both the batch-1 schedule the product builds and the one with round 6's launches forced on."""
     from smap_amd.model.smap import SMAP
     from oracle.backbone_ref import smap_forward
+    _full_size_schedule(monkeypatch, schedule)
     torch.manual_seed(0)
     net = SMAP(make_cfg((128, 208))).eval()
     sd = recipe_state_dict(net.state_dict())
@@ -1364,12 +1529,14 @@ def test_full_size_forward_vs_cpu_oracle(precision, tol_max, tol_mean):
         assert ((a - b).abs().mean() / b.abs().mean()).item() < tol_mean, k
 
 
-def test_full_size_forward_vs_imported_reference_digest(golden_dir):
+@pytest.mark.parametrize("schedule", ["shipped", "round6"])
+def test_full_size_forward_vs_imported_reference_digest(golden_dir, monkeypatch, schedule):
     """The HIP split-precision path at BASELINE configs[1] against the IMPORTED reference model itself (not the restatement):
     tests/golden/backbone_full.npz holds per-channel sums and 1024 sampled positions of each output of model.smap.SMAP at
     1x3x512x832 (tests/golden/gen_golden_full.py); 1e-4 as for the oracle comparison above."""
     from smap_amd.model.smap import SMAP
     from test_oracle_cpu import check_against_full_size_digest, full_size_input
+    _full_size_schedule(monkeypatch, schedule)
     z = np.load(f"{golden_dir}/backbone_full.npz")
     torch.manual_seed(0)
     net = SMAP(make_cfg((128, 208))).eval()
@@ -1379,6 +1546,55 @@ def test_full_size_forward_vs_imported_reference_digest(golden_dir):
     outs = [t.cpu() for t in net.to(DEV)(x.to(DEV))]
     worst = check_against_full_size_digest(z, outs, 1e-4)
     print("HIP x3 vs imported reference at full size (sampled, channel sums):", worst)
+
+
+@pytest.fixture(scope="module")
+def full_size_sd():
+    from smap_amd.model.smap import SMAP
+    torch.manual_seed(0)
+    return recipe_state_dict(SMAP(make_cfg((128, 208))).state_dict())
+
+
+@pytest.mark.parametrize("precision,tol", [("x3", 2e-5), ("f16", 2e-2)])
+@pytest.mark.parametrize("B", [1, 8, 16])
+def test_shipped_full_size_schedule_every_tensor(golden_dir, full_size_sd, monkeypatch, B, precision, tol):
+    """The schedules the product runs at 512x832 -- batch 1 (configs[1]: split K, fp32 heads under split K, whole layer1 blocks), one
+    8-frame step, and the 16-frame launch bench.py times (two 8-frame steps per launch) -- every tensor against the interpretation of
+    the same schedule (oracle/graph_interp.py): split precision against the f64 one, fp16 against the one that rounds where the engine
+    rounds; bounds of the small schedules.  Frames are independent (eval-mode BN), so the interpreter runs frames 0 and B - 1 only
+    (B - 1 holds the ragged M tiles).  Frame 0 is the input of tests/golden/backbone_full.npz: in split precision its maps must also
+    match the imported reference model's digest (1e-4, as at batch 1)."""
+    from smap_amd.engine import BackboneEngine, Graph
+    from oracle.graph_interp import run_graph
+    from test_oracle_cpu import check_against_full_size_digest, full_size_input
+    _full_size_schedule(monkeypatch, "shipped")
+    sd = full_size_sd
+    z = np.load(f"{golden_dir}/backbone_full.npz")
+    x = torch.randn(B, 3, 512, 832, generator=torch.Generator().manual_seed(100 + B))
+    x[0] = full_size_input(z)[0]
+    frames = sorted({0, B - 1})
+    eng = BackboneEngine(sd, B, 512, 832, DEV, reuse=False, precision=precision)
+    outs = [o[frames].cpu() for o in eng.run(x.to(DEV))]
+    torch.cuda.synchronize()
+    got = {t.name: eng.read_tensor(t.name)[frames].cpu() for t in eng.graph.tensors}
+    torch.cuda.synchronize()
+    g = Graph(sd, B, 512, 832, keep_ref=True, precision=precision)
+    assert [t.name for t in g.tensors] == list(got)
+    torch.set_num_threads(min(16, torch.get_num_threads()))
+    with torch.no_grad():
+        *ref, T = run_graph(g, x[frames].double() if precision == "x3" else x[frames], quantize=precision == "f16", keep=True)
+    worst = []
+    for name, v in got.items():
+        want = T[name].double()
+        e = (v.double().permute(0, 3, 1, 2)[:, :want.shape[1]] - want).abs().max().item()
+        worst.append((e / (want.abs().max().item() + 1e-6), name))
+    worst.sort(reverse=True)
+    print(f"B={B} {precision}: {len(worst)} tensors, worst error / max:", [(f"{r:.3g}", n) for r, n in worst[:5]])
+    assert worst[0][0] < tol, worst[:5]
+    for a, b, k in zip(outs, ref, ("hms", "det_d", "root_d")):
+        assert (a.double() - b.double()).abs().max().item() < (2e-5 if precision == "x3" else 5e-3) * b.abs().max().item(), k
+    if precision == "x3":
+        print("frame 0 vs imported reference (sampled, channel sums):", check_against_full_size_digest(z, [o[:1] for o in outs], 1e-4))
 
 
 @pytest.mark.parametrize("scale,stem_gain", [(1e-4, 1.0), (1.0, 1.0), (3e3, 1.0), (1e5, 1.0), (1.0, 1e-4), (1.0, 1e3), (1.0, 1e5)])

@@ -524,3 +524,111 @@ def test_merged_launch_descriptors_and_validation(small_sd, monkeypatch):
                 else:
                     setattr(bad[i], field, val)
                 assert L.load().smap_plan_create(bad, len(g.ops), C.byref(h)) != 0, field
+
+
+# -- launch inventory: every conv launch the shipped schedules run has a unit case in tests/test_backbone_gpu.py --------------------------
+
+SHIPPED_SCHEDULES = [   # frames, precision, flip-TTA: BASELINE configs[1] (batch 1), one 8-frame step, the 16-frame launch bench.py times
+    (1, "x3", False), (8, "x3", False), (16, "x3", False), (1, "f16", False), (8, "f16", False), (16, "f16", False),
+    (8, "x3", True),                                   # 8-frame steps with flip-TTA (16 frames per launch)
+    (16, "x3", True),                                  # exps/stage3_root2/test.sh: --batch_size 16 --do_flip 1
+]
+SIG_FIELDS = ("precision", "tile", "ksize", "stride", "relu", "res", "adds", "bilinear", "out_fp32", "split_k", "w_pairs", "segments",
+              "in2", "tap", "fused")
+
+
+def _signature(precision, tile, ksize, stride, relu, res, adds, up, out_fp32, ksplit, w_pairs, segments=0, in2="", tap=False, fused=""):
+    """What decides which code a conv launch runs.  w_pairs only changes the layout of 32-half K tiles (smap_op.w_pairs): 0 elsewhere."""
+    from smap_amd.engine import tile_bk, tile_family
+    x3 = precision == "x3"
+    wp = int(bool(w_pairs)) if (tile_family(tile) != "halo" and tile < 80 and tile_bk(tile, x3) == 32) else 0
+    return (precision, int(tile), int(ksize), int(stride), int(bool(relu)), bool(res), bool(adds), bool(up), int(bool(out_fp32)),
+            ksplit > 1, wp, int(segments), in2, bool(tap), fused)
+
+
+def launch_signature(g, op):
+    p = op.p
+    fused = ("block_first" if "short" in p else "block") if "head" in p else "tail" if "tail" in p else ""
+    in2 = ("relusum" if p["cat"].get("relusum") else "cat") if "cat" in p else ""
+    return _signature(g.precision, p["tile"], p["ksize"], p["stride"], p["relu"], op.res is not None,
+                      op.add1 is not None or op.add2 is not None, bool(op.aux), p["out_fp32"], p.get("ksplit", 1), p["w_pairs"],
+                      len(p.get("segs", [])), in2, "tap" in p, fused)
+
+
+def unit_case_signatures(T):
+    """The signatures the unit cases of tests/test_backbone_gpu.py (module T) run, derived from its case lists as its tests run them."""
+    from smap_amd.engine import REGEPI_TILES
+    cov = set()
+    for cases, prec in ((T.CASES, "f16"), (T.X3_CASES, "x3")):      # _run_single_conv(*case, seed=hash(case) % 1000): w_pairs = seed % 2
+        for c in cases:
+            _, _, _, _, _, k, s, tile, relu, res, adds = c
+            cov.add(_signature(prec, tile, k, s, relu, res, adds, None, 0, 1, hash(c) % 1000 % 2))
+    for c in getattr(T, "EDGE_CASES", []):
+        prec, _, _, _, _, _, k, s, tile, relu, res, adds, up, out_fp32, ksplit, w_pairs = c
+        for pr in (("f16", "x3") if prec == "both" else (prec,)):
+            cov.add(_signature(pr, tile, k, s, relu, res, adds, up, out_fp32, ksplit, w_pairs))
+    for c in T.TAIL_CASES:
+        _, _, _, _, _, _, tile, relu, res, adds = c
+        for pr in ("f16", "x3"):
+            cov.add(_signature(pr, tile, 3, 1, relu, res, adds, None, 0, 1, 0, fused="tail"))
+    for _, _, _, tile, adds in T.BLOCK_CASES:                       # split precision only; the first block's shortcut replaces the residual
+        first = tile in (92, 93)
+        cov.add(_signature("x3", tile, 3, 1, 1, not first, adds, None, 0, 1, 0, fused="block_first" if first else "block"))
+    for c in T.SEG_CASES:
+        _, _, _, _, couts, relus, up, tile, w_pairs = (c + (1,))[:9]
+        for pr in ("f16", "x3"):
+            if pr == "x3" or tile not in REGEPI_TILES:
+                cov.add(_signature(pr, tile, 1, 1, relus[0], False, False, up, 0, 1, w_pairs, segments=len(couts) - 1))
+    for c in T.CAT_CASES:                                             # w_pairs = (B == 1) in these harnesses
+        for pr in ("f16", "x3"):
+            cov.add(_signature(pr, c[7], 1, 1, 1, False, False, None, 0, 1, c[0] == 1, in2="cat"))
+    for c in getattr(T, "RELUSUM_CASES", []):
+        for pr in ("f16", "x3"):
+            cov.add(_signature(pr, c[6], 1, 1, 0, False, False, None, 0, 1, c[0] == 1, in2="relusum"))
+    for B, _, _ in getattr(T, "TAP_SHAPES", []):
+        for pr in ("f16", "x3"):
+            cov.add(_signature(pr, 54, 1, 1, 1, False, False, None, 1, 1, B == 1, tap=True))
+    return cov
+
+
+def test_launch_inventory_every_shipped_conv_has_a_unit_case(monkeypatch):
+    """The schedules the product builds at 512x832 (round 6's switches as the product sets them, not as conftest forces them for the
+    small test schedules) reduced to one signature per conv launch: tile, taps, stride, every epilogue input, split K, weight layout,
+    segments, second input, tap head, fused block.  Each must be run by a unit case of tests/test_backbone_gpu.py against an f64
+    reference: a kernel path that only a full-size schedule reaches is otherwise checked only through the end-to-end outputs."""
+    import test_backbone_gpu as T
+    from smap_amd.engine import Graph, OP_CONV
+    for k in ("SMAP_CAT", "SMAP_SKIPSUM", "SMAP_TAPHEAD"):
+        monkeypatch.delenv(k, raising=False)
+    sd = _full_size_sd()
+    shipped = {}
+    for B, prec, flip in SHIPPED_SCHEDULES:
+        g = Graph(sd, B, 512, 832, precision=prec, flip_pair=list(range(43)) if flip else None)
+        for op in g.ops:
+            if op.kind == OP_CONV:
+                shipped.setdefault(launch_signature(g, op), f"{B}{'xflip' if flip else ''} {prec}: {op.out.name}")
+    assert len(shipped) > 100
+    missing = sorted(set(shipped) - unit_case_signatures(T))
+    assert not missing, "conv launches of the shipped schedules without a unit case:\n" + "\n".join(
+        f"  {dict(zip(SIG_FIELDS, s))}  (e.g. {shipped[s]})" for s in missing)
+
+
+@pytest.mark.parametrize("B", [8, 16])
+def test_arena_without_reuse_keeps_two_input_launches_in_one_window(monkeypatch, B):
+    """reuse=False (every tensor kept, for BackboneEngine.read_tensor) makes an 8-frame x3 arena of 8 GiB: both inputs of every conv_cat /
+    conv_relusum launch must still share a 4 GiB window (one base address per launch), and the library must accept the plan.  The
+    reusing arena -- what the product runs -- keeps its layout."""
+    import ctypes as C
+    from smap_amd import lib as L
+    from smap_amd.engine import Graph, OP_CONV, WINDOW
+    for k in ("SMAP_CAT", "SMAP_SKIPSUM", "SMAP_TAPHEAD"):
+        monkeypatch.delenv(k, raising=False)
+    g = Graph(_full_size_sd(), B, 512, 832, precision="x3")
+    assert g.allocate(reuse=False) > 2 * WINDOW
+    two = [op for op in g.ops if op.kind == OP_CONV and "cat" in op.p]
+    assert len(two) >= 10 and all(op.inp.off // WINDOW == op.aux2.off // WINDOW for op in two)
+    spans = sorted((t.off, t.off + t.nbytes) for t in g.tensors + g.scratch_tensors + [g.kcount] if t is not None and t.off >= 0)
+    assert all(a[1] <= b[0] for a, b in zip(spans, spans[1:]))          # nothing shares bytes
+    h = C.c_void_p()
+    assert L.load().smap_plan_create(g.emit(), len(g.ops), C.byref(h)) == 0
+    L.load().smap_plan_destroy(h)
