@@ -302,8 +302,8 @@ int smap_sizeof_op(void);
  * unknown id) and the halves per staged K tile for `precision` (0 for an unknown id). */
 int smap_conv_tile_dims(int tile, int* bm, int* bn);
 int smap_conv_tile_bk(int tile, int precision);
-/* Tile ids 80..89 (3x3 + fused 1x1 tail): output channels per chunk of the tail (its weight rows are padded to a multiple); 0 for
- * every other id. */
+/* Tile ids with a fused 1x1 tail (80..89: 3x3 + tail; 90..99: whole Bottleneck): output channels per chunk of the tail (its weight
+ * rows are padded to a multiple); 0 for every other id. */
 int smap_conv_tile_tail_bn(int tile);
 
 typedef struct smap_plan smap_plan;

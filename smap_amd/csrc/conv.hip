@@ -730,10 +730,19 @@ __global__ __launch_bounds__(WM * WN * 64) void conv_igemm_kernel(const ConvArgs
     SMAP_TL_END(a)
 }
 
-// the split-K instances (tile ids smap_conv_tile_has_splitk: 2, 20, 22 -- what the small schedules run)
-template <int BM, int BN, int WM, int WN, int STAGES, int BK, bool X3>
+// Launch helpers: TILE selects the row of csrc/tiles.h that BM, BN and BK come from; WM x WN (the wave grid) and STAGES are the kernel's own
+// business and stay on the dispatch lines of smap_launch_conv.  An instance the row does not announce does not build.
+#define SMAP_IGEMM_ROW(cap)                                                                                      \
+    constexpr TileRow t = tile_row(TILE);                                                                        \
+    static_assert(t.family == TF_IGEMM && tile_has(t, X3, cap),                                                  \
+                  "csrc/tiles.h: the row of this tile id does not list this instance");                          \
+    constexpr int BM = t.bm, BN = t.bn, BK = tile_bk(t, X3)
+
+// the split-K instances (what the small schedules run)
+template <int TILE, bool X3, int WM, int WN, int STAGES>
 hipError_t launch_splitk(const ConvArgs& a, hipStream_t st)
 {
+    SMAP_IGEMM_ROW(TC_SPLITK);
     const dim3 grid(a.m_tiles * a.n_tiles * a.ksplit);
     if (a.up || a.add1 || a.add2)
         hipLaunchKernelGGL((conv_igemm_kernel<BM, BN, WM, WN, STAGES, BK, true, X3, true>), grid, dim3(WM * WN * 64), 0, st, a);
@@ -742,214 +751,182 @@ hipError_t launch_splitk(const ConvArgs& a, hipStream_t st)
     return hipGetLastError();
 }
 
-template <int BM, int BN, int WM, int WN, int STAGES, int BK = 64>
+// the plain instances: the same tile ids select the fp16 or the split-precision (X3) one as the op says
+template <int TILE, bool X3, int WM, int WN, int STAGES>
 hipError_t launch(const ConvArgs& a, hipStream_t st)
 {
-    if (a.x3) return hipErrorInvalidValue;                 // split-precision ops use the tiles of launch_x3 only
+    SMAP_IGEMM_ROW(0);
+    static_assert(!(t.caps & TC_REGEPI), "register-epilogue tiles go through launch_regepi");
     if (a.up || a.add1 || a.add2)
-        hipLaunchKernelGGL((conv_igemm_kernel<BM, BN, WM, WN, STAGES, BK, true, false>), dim3(a.m_tiles * a.n_tiles), dim3(WM * WN * 64), 0, st, a);
+        hipLaunchKernelGGL((conv_igemm_kernel<BM, BN, WM, WN, STAGES, BK, true, X3>), dim3(a.m_tiles * a.n_tiles), dim3(WM * WN * 64), 0, st, a);
     else
-        hipLaunchKernelGGL((conv_igemm_kernel<BM, BN, WM, WN, STAGES, BK, false, false>), dim3(a.m_tiles * a.n_tiles), dim3(WM * WN * 64), 0, st, a);
+        hipLaunchKernelGGL((conv_igemm_kernel<BM, BN, WM, WN, STAGES, BK, false, X3>), dim3(a.m_tiles * a.n_tiles), dim3(WM * WN * 64), 0, st, a);
     return hipGetLastError();
 }
 
-// split-precision (X3) instances: the same tile ids select them when the op says precision = 1
-template <int BM, int BN, int WM, int WN, int STAGES, int BK>
-hipError_t launch_x3(const ConvArgs& a, hipStream_t st)
-{
-    if (a.up || a.add1 || a.add2)
-        hipLaunchKernelGGL((conv_igemm_kernel<BM, BN, WM, WN, STAGES, BK, true, true>), dim3(a.m_tiles * a.n_tiles), dim3(WM * WN * 64), 0, st, a);
-    else
-        hipLaunchKernelGGL((conv_igemm_kernel<BM, BN, WM, WN, STAGES, BK, false, true>), dim3(a.m_tiles * a.n_tiles), dim3(WM * WN * 64), 0, st, a);
-    return hipGetLastError();
-}
-
-}  // namespace
-
-// the register-epilogue instance (tile 56): split precision, plain epilogue only (plan.hip::validate keeps everything else away)
-template <int BM, int BN, int WM, int WN, int STAGES, int BK>
+// the register-epilogue instance: split precision, plain epilogue only (plan.hip::validate keeps everything else away)
+template <int TILE, bool X3, int WM, int WN, int STAGES>
 hipError_t launch_regepi(const ConvArgs& a, hipStream_t st)
 {
-    if (!a.x3 || a.up || a.add1 || a.add2 || a.out_fp32 || a.ksplit > 1) return hipErrorInvalidValue;
-    hipLaunchKernelGGL((conv_igemm_kernel<BM, BN, WM, WN, STAGES, BK, false, true, false, true>), dim3(a.m_tiles * a.n_tiles), dim3(WM * WN * 64), 0, st, a);
+    SMAP_IGEMM_ROW(TC_REGEPI);
+    if (a.up || a.add1 || a.add2 || a.out_fp32 || a.ksplit > 1) return hipErrorInvalidValue;
+    hipLaunchKernelGGL((conv_igemm_kernel<BM, BN, WM, WN, STAGES, BK, false, X3, false, true>), dim3(a.m_tiles * a.n_tiles), dim3(WM * WN * 64), 0, st, a);
     return hipGetLastError();
 }
 
-// the second-input instances (smap_op.in2_C > 0; tiles 20, 50, 51: plan.hip::validate keeps the rest away)
-template <int BM, int BN, int WM, int WN, int STAGES, int BK, bool X3>
+// the second-input instances (smap_op.in2_C > 0)
+template <int TILE, bool X3, int WM, int WN, int STAGES>
 hipError_t launch_dual(const ConvArgs& a, hipStream_t st)
 {
+    SMAP_IGEMM_ROW(TC_DUAL);
     if (a.up || a.add1 || a.add2 || a.ksplit > 1 || a.ksize != 1) return hipErrorInvalidValue;
     hipLaunchKernelGGL((conv_igemm_kernel<BM, BN, WM, WN, STAGES, BK, false, X3, false, false, true>), dim3(a.m_tiles * a.n_tiles), dim3(WM * WN * 64), 0, st, a);
     return hipGetLastError();
 }
 
-template <int BM, int BN, int WM, int WN, int STAGES, int BK, bool X3>
+template <int TILE, bool X3, int WM, int WN, int STAGES>
 hipError_t launch_relusum(const ConvArgs& a, hipStream_t st)
 {
+    SMAP_IGEMM_ROW(TC_DUAL | TC_RELUSUM);
     if (a.up || a.add1 || a.add2 || a.res || a.ksplit > 1 || a.ksize != 1 || a.relu || !a.bias_b) return hipErrorInvalidValue;
     hipLaunchKernelGGL((conv_igemm_kernel<BM, BN, WM, WN, STAGES, BK, false, X3, false, false, true, false, true>), dim3(a.m_tiles * a.n_tiles), dim3(WM * WN * 64), 0, st, a);
     return hipGetLastError();
 }
 
-int smap_conv_tile_has_dual(int tile) { return tile == 20 || tile == 50 || tile == 51 || tile == 53 || tile == 54; }
-int smap_conv_tile_has_relusum(int tile) { return tile == 50 || tile == 51 || tile == 53 || tile == 54; }
-
-// the tap-dot instance (smap_op.tap_n = 9; tile 54 only: one N tile of 256 channels)
-template <bool X3>
+// the tap-dot instance (smap_op.tap_n = 9): one N tile of 256 channels
+template <int TILE, bool X3, int WM, int WN, int STAGES>
 hipError_t launch_tapdot(const ConvArgs& a, hipStream_t st)
 {
+    SMAP_IGEMM_ROW(TC_TAPDOT);
     if (a.up || a.add1 || a.add2 || a.res || a.ksplit > 1 || a.Cin2 > 0 || a.n_tiles != 1 || a.tap_n != 9 || !a.tap_w) return hipErrorInvalidValue;
-    hipLaunchKernelGGL((conv_igemm_kernel<128, 256, 2, 4, 2, 32, false, X3, false, false, false, true>), dim3(a.m_tiles), dim3(512), 0, st, a);
+    hipLaunchKernelGGL((conv_igemm_kernel<BM, BN, WM, WN, STAGES, BK, false, X3, false, false, false, true>), dim3(a.m_tiles), dim3(WM * WN * 64), 0, st, a);
     return hipGetLastError();
 }
+#undef SMAP_IGEMM_ROW
 
-// halves per staged K tile (= the packing unit of the weight blob, include/smap_hip.h); mirrors the BK template arguments
-// of smap_launch_conv below and smap_amd/engine.py::tile_bk (tests/test_host_cpu.py compares the two)
-extern "C" int smap_conv_tile_bk(int tile, int precision)
-{
-    int bm, bn;
-    if (smap_conv_tile_dims(tile, &bm, &bn)) return 0;
-    if ((tile >= 30 && tile < 50) || (tile >= 80 && tile < 100)) return precision ? 32 : 64;
-    if (tile >= 60 && tile < 80) return 32;
-    if (precision) return (tile <= 4 || tile == 7 || tile == 52) ? 64 : 32;
-    return ((tile >= 20 && tile <= 27) || tile == 50 || tile == 51 || tile == 53 || tile == 54 || tile == 55) ? 32 : 64;
-}
+// one dispatch line for both precisions of an instance: HELPER<tile id, X3, WM, WN, STAGES>
+#define SMAP_BOTH(HELPER, TILE, ...) (a.x3 ? HELPER<TILE, true, __VA_ARGS__>(a, st) : HELPER<TILE, false, __VA_ARGS__>(a, st))
 
-// tiles 80..89 (3x3 + fused 1x1 tail): channels per chunk of the TAIL's output (its weights are padded to a multiple), else 0
-extern "C" int smap_conv_tile_tail_bn(int tile)
-{
-    int bm, bn, bn2;
-    if (tile >= 90 && tile < 100) return smap_convb_tile_dims(tile, &bm, &bn, &bn2) ? 0 : bn2;
-    return (tile >= 80 && tile < 90 && !smap_convf_tile_dims(tile, &bm, &bn, &bn2)) ? bn2 : 0;
-}
+}  // namespace
 
-// tile selector -> (BM, BN).  Keep in sync with smap_amd/engine.py::TILES.
-//   0..4 : 2-stage (double-buffered) variants; 5..9 : the same tiles with deeper LDS-DMA pipelines
+// The three ABI lookups (include/smap_hip.h): rows of csrc/tiles.h.
 extern "C" int smap_conv_tile_dims(int tile, int* bm, int* bn)
 {
-    if (tile >= 30 && tile < 50) return smap_conv3_tile_dims(tile, bm, bn);
-    if (tile >= 60 && tile < 80) return smap_convp_tile_dims(tile, bm, bn);
-    if (tile >= 80 && tile < 90) { int bn2; return smap_convf_tile_dims(tile, bm, bn, &bn2); }
-    if (tile >= 90 && tile < 100) { int bn2; return smap_convb_tile_dims(tile, bm, bn, &bn2); }
-    switch (tile) {
-        case 20: case 24: *bm = 128; *bn = 128; return 0;      // 20..27: BK = 32 staging (smaller LDS, more workgroups per CU)
-        case 21: case 25: *bm = 128; *bn = 64; return 0;
-        case 22: case 26: *bm = 64; *bn = 64; return 0;
-        case 23: case 27: *bm = 64; *bn = 128; return 0;
-        case 55: *bm = 128; *bn = 128; return 0;                    // 55: deep pipeline (3 K tiles in flight; 56, 57 retired: no table entry)
-        case 50: case 51: case 52: *bm = 128; *bn = 128; return 0;   // 50..54: eight-wave workgroups
-        case 53: *bm = 256; *bn = 128; return 0;
-        case 54: *bm = 128; *bn = 256; return 0;
-        case 56: *bm = 256; *bn = 256; return 0;                    // 56: eight waves of 128 x 64, register epilogue (split precision only)
-        case 0: case 5: *bm = 128; *bn = 128; return 0;
-        case 1: case 6: *bm = 128; *bn = 64; return 0;
-        case 2: case 7: *bm = 64; *bn = 64; return 0;
-        case 3: case 8: *bm = 128; *bn = 32; return 0;
-        case 4: case 9: *bm = 64; *bn = 128; return 0;
-        default: return -1;
-    }
+    const TileRow* t = tile_find(tile);
+    if (!t) return -1;
+    *bm = t->bm;
+    *bn = t->bn;
+    return 0;
 }
 
-// tiles that have a split-K instance (both precisions)
-int smap_conv_tile_has_splitk(int tile) { return tile == 2 || tile == 7 || tile == 20 || tile == 22; }
-
-// tiles that have a split-precision instance (plan.hip::validate asks)
-int smap_conv_tile_has_x3(int tile)
+extern "C" int smap_conv_tile_bk(int tile, int precision)
 {
-    return (tile >= 0 && tile <= 4) || tile == 7 || (tile >= 20 && tile <= 27) || (tile >= 30 && tile <= 45) || (tile >= 50 && tile <= 56) || (tile >= 60 && tile <= 65) ||
-           (tile >= 80 && tile <= 82) || (tile >= 90 && tile <= 94);
+    const TileRow* t = tile_find(tile);
+    return t ? tile_bk(*t, precision != 0) : 0;
+}
+
+extern "C" int smap_conv_tile_tail_bn(int tile)
+{
+    const TileRow* t = tile_find(tile);
+    return t ? t->tail_bn : 0;
 }
 
 hipError_t smap_launch_conv(const ConvArgs& a, int tile, hipStream_t st)
 {
-    if (tile >= 60 && tile < 80) return smap_launch_convp(a, tile, st);      // persistent wave-specialised kernel, both precisions
-    if (tile >= 80 && tile < 90) return smap_launch_convf(a, tile, st);      // 3x3 + fused 1x1 tail, both precisions
-    if (tile >= 90 && tile < 100) return smap_launch_convb(a, tile, st);     // whole identity Bottleneck, split precision
-    if (a.tap_n > 0) return tile == 54 ? (a.x3 ? launch_tapdot<true>(a, st) : launch_tapdot<false>(a, st)) : hipErrorInvalidValue;
-    if (a.Cin2 > 0 && a.bias_b) {                           // ... as the sum of two ACTIVATED convs (smap_op.in2_mode = 1): the eight-wave tiles only
-        switch (tile) {                                     // (the four-wave 128 x 128 instance needs 288 registers: one wave per SIMD)
-            case 50: return a.x3 ? launch_relusum<128, 128, 2, 4, 2, 32, true>(a, st) : launch_relusum<128, 128, 2, 4, 2, 32, false>(a, st);
-            case 51: return a.x3 ? launch_relusum<128, 128, 4, 2, 2, 32, true>(a, st) : launch_relusum<128, 128, 4, 2, 2, 32, false>(a, st);
-            case 53: return a.x3 ? launch_relusum<256, 128, 4, 2, 2, 32, true>(a, st) : launch_relusum<256, 128, 4, 2, 2, 32, false>(a, st);     // 249 / 251 registers:
-            case 54: return a.x3 ? launch_relusum<128, 256, 2, 4, 2, 32, true>(a, st) : launch_relusum<128, 256, 2, 4, 2, 32, false>(a, st);     // two waves per SIMD still
-            default: return hipErrorInvalidValue;
-        }
+    const TileRow* t = tile_find(tile);
+    if (!t || !tile_has(*t, a.x3)) return hipErrorInvalidValue;      // unknown id, or no instance in the op's precision
+    switch (t->family) {
+        case TF_HALO: return smap_launch_conv3(a, tile, st);
+        case TF_PERSIST: return smap_launch_convp(a, tile, st);
+        case TF_TAIL: return smap_launch_convf(a, tile, st);
+        case TF_BLOCK: return smap_launch_convb(a, tile, st);
+        case TF_IGEMM: break;
     }
-    if (a.Cin2 > 0) {                                       // second input along K: its own instances of three tiles (smap_conv_tile_has_dual)
+    if (a.tap_n > 0) {
         switch (tile) {
-            case 20: return a.x3 ? launch_dual<128, 128, 2, 2, 2, 32, true>(a, st) : launch_dual<128, 128, 2, 2, 2, 32, false>(a, st);
-            case 50: return a.x3 ? launch_dual<128, 128, 2, 4, 2, 32, true>(a, st) : launch_dual<128, 128, 2, 4, 2, 32, false>(a, st);
-            case 51: return a.x3 ? launch_dual<128, 128, 4, 2, 2, 32, true>(a, st) : launch_dual<128, 128, 4, 2, 2, 32, false>(a, st);
-            case 53: return a.x3 ? launch_dual<256, 128, 4, 2, 2, 32, true>(a, st) : launch_dual<256, 128, 4, 2, 2, 32, false>(a, st);
-            case 54: return a.x3 ? launch_dual<128, 256, 2, 4, 2, 32, true>(a, st) : launch_dual<128, 256, 2, 4, 2, 32, false>(a, st);
+            case 54: return SMAP_BOTH(launch_tapdot, 54, 2, 4, 2);
             default: return hipErrorInvalidValue;
         }
     }
-    if (a.ksplit > 1) {                                     // split K: its own instances of three tiles (plan.hip::validate asked smap_conv_tile_has_splitk)
+    if (a.Cin2 > 0 && a.bias_b) {                           // ... as the sum of two ACTIVATED convs (smap_op.in2_mode = 1)
         switch (tile) {
-            case 2: return a.x3 ? launch_splitk<64, 64, 2, 2, 2, 64, true>(a, st) : launch_splitk<64, 64, 2, 2, 2, 64, false>(a, st);
-            case 22: return a.x3 ? launch_splitk<64, 64, 2, 2, 2, 32, true>(a, st) : launch_splitk<64, 64, 2, 2, 2, 32, false>(a, st);
-            case 7: return a.x3 ? launch_splitk<64, 64, 2, 2, 4, 64, true>(a, st) : launch_splitk<64, 64, 2, 2, 4, 64, false>(a, st);
-            case 20: return a.x3 ? launch_splitk<128, 128, 2, 2, 2, 32, true>(a, st) : launch_splitk<128, 128, 2, 2, 2, 32, false>(a, st);
+            case 50: return SMAP_BOTH(launch_relusum, 50, 2, 4, 2);
+            case 51: return SMAP_BOTH(launch_relusum, 51, 4, 2, 2);
+            case 53: return SMAP_BOTH(launch_relusum, 53, 4, 2, 2);     // 249 / 251 registers:
+            case 54: return SMAP_BOTH(launch_relusum, 54, 2, 4, 2);     // two waves per SIMD still
             default: return hipErrorInvalidValue;
         }
     }
-    if (a.x3) {
-        if (tile >= 30 && tile < 50) return smap_launch_conv3(a, tile, st);     // halo-tiled 3x3, split-precision instance
-        switch (tile) {                                     // LDS = max(STAGES * 2 * (BM + BN) * row bytes, fp32 epilogue tile)
-            case 0: return launch_x3<128, 128, 2, 2, 2, 64>(a, st);   // 128 KiB: BK = 64, half the barriers per K
-            case 1: return launch_x3<128, 64, 2, 2, 2, 64>(a, st);    // 96 KiB
-            case 2: return launch_x3<64, 64, 2, 2, 2, 64>(a, st);     // 64 KiB
-            case 4: return launch_x3<64, 128, 2, 2, 2, 64>(a, st);    // 96 KiB
-            case 3: return launch_x3<128, 32, 4, 1, 2, 64>(a, st);    // 80 KiB (Cout <= 32 heads)
-            case 20: return launch_x3<128, 128, 2, 2, 2, 32>(a, st);  // 64 KiB
-            case 21: return launch_x3<128, 64, 2, 2, 2, 32>(a, st);   // 48 KiB
-            case 22: return launch_x3<64, 64, 2, 2, 2, 32>(a, st);    // 32 KiB
-            case 23: return launch_x3<64, 128, 2, 2, 2, 32>(a, st);   // 48 KiB
-            case 24: return launch_x3<128, 128, 2, 2, 3, 32>(a, st);  // 96 KiB, 2 tiles in flight (fp16 id 24 is 4-stage)
-            case 25: return launch_x3<128, 64, 2, 2, 3, 32>(a, st);   // 72 KiB, 2 tiles in flight
-            case 26: return launch_x3<64, 64, 2, 2, 4, 32>(a, st);    // 64 KiB, 3 tiles in flight
-            case 7: return launch_x3<64, 64, 2, 2, 4, 64>(a, st);     // 128 KiB: THREE 64-half K tiles in flight (round 5: the small grids of batch-1
-                                                                      // schedules leave the LDS of a CU to one workgroup anyway; their K loops are bound by
-                                                                      // the latency of the one tile a two-stage pipeline keeps in flight)
-            case 27: return launch_x3<64, 128, 2, 2, 3, 32>(a, st);   // 72 KiB
-            case 50: return launch_x3<128, 128, 2, 4, 2, 32>(a, st);  // 64 KiB, 8 waves of 64x32
-            case 51: return launch_x3<128, 128, 4, 2, 2, 32>(a, st);  // 64 KiB, 8 waves of 32x64
-            case 52: return launch_x3<128, 128, 2, 4, 2, 64>(a, st);  // 128 KiB, BK = 64
-            case 53: return launch_x3<256, 128, 4, 2, 2, 32>(a, st);  // 96 KiB, 8 waves of 64x64
-            case 54: return launch_x3<128, 256, 2, 4, 2, 32>(a, st);  // 96 KiB, 8 waves of 64x64
-            case 55: return launch_x3<128, 128, 2, 4, 4, 32>(a, st);  // 128 KiB: 8 waves, 3 K tiles (96 KiB) in flight
-            case 56: return launch_regepi<256, 256, 2, 4, 2, 32>(a, st);   // 128 KiB: 8 waves of 128 x 64, two 64 KiB stages, register epilogue
+    if (a.Cin2 > 0) {                                       // second input along K
+        switch (tile) {
+            case 20: return SMAP_BOTH(launch_dual, 20, 2, 2, 2);
+            case 50: return SMAP_BOTH(launch_dual, 50, 2, 4, 2);
+            case 51: return SMAP_BOTH(launch_dual, 51, 4, 2, 2);
+            case 53: return SMAP_BOTH(launch_dual, 53, 4, 2, 2);
+            case 54: return SMAP_BOTH(launch_dual, 54, 2, 4, 2);
             default: return hipErrorInvalidValue;
         }
     }
-    if (tile >= 30 && tile < 50) return smap_launch_conv3(a, tile, st);
+    if (a.ksplit > 1) {                                     // split K
+        switch (tile) {
+            case 2: return SMAP_BOTH(launch_splitk, 2, 2, 2, 2);
+            case 22: return SMAP_BOTH(launch_splitk, 22, 2, 2, 2);
+            case 7: return SMAP_BOTH(launch_splitk, 7, 2, 2, 4);
+            case 20: return SMAP_BOTH(launch_splitk, 20, 2, 2, 2);
+            default: return hipErrorInvalidValue;
+        }
+    }
+    if (a.x3) {                                             // <tile id, X3, WM, WN, STAGES>; LDS per row: csrc/tiles.h
+        switch (tile) {
+            case 0: return launch<0, true, 2, 2, 2>(a, st);
+            case 1: return launch<1, true, 2, 2, 2>(a, st);
+            case 2: return launch<2, true, 2, 2, 2>(a, st);
+            case 4: return launch<4, true, 2, 2, 2>(a, st);
+            case 3: return launch<3, true, 4, 1, 2>(a, st);
+            case 20: return launch<20, true, 2, 2, 2>(a, st);
+            case 21: return launch<21, true, 2, 2, 2>(a, st);
+            case 22: return launch<22, true, 2, 2, 2>(a, st);
+            case 23: return launch<23, true, 2, 2, 2>(a, st);
+            case 24: return launch<24, true, 2, 2, 3>(a, st);     // (fp16 id 24 is 4-stage)
+            case 25: return launch<25, true, 2, 2, 3>(a, st);
+            case 26: return launch<26, true, 2, 2, 4>(a, st);
+            case 7: return launch<7, true, 2, 2, 4>(a, st);
+            case 27: return launch<27, true, 2, 2, 3>(a, st);
+            case 50: return launch<50, true, 2, 4, 2>(a, st);
+            case 51: return launch<51, true, 4, 2, 2>(a, st);
+            case 52: return launch<52, true, 2, 4, 2>(a, st);
+            case 53: return launch<53, true, 4, 2, 2>(a, st);
+            case 54: return launch<54, true, 2, 4, 2>(a, st);
+            case 55: return launch<55, true, 2, 4, 4>(a, st);
+            case 56: return launch_regepi<56, true, 2, 4, 2>(a, st);
+            default: return hipErrorInvalidValue;
+        }
+    }
     switch (tile) {
-        case 20: return launch<128, 128, 2, 2, 2, 32>(a, st);   // 64 KiB (fp32 epilogue tile)
-        case 21: return launch<128, 64, 2, 2, 2, 32>(a, st);    // 32 KiB
-        case 22: return launch<64, 64, 2, 2, 2, 32>(a, st);     // 16 KiB
-        case 23: return launch<64, 128, 2, 2, 2, 32>(a, st);    // 32 KiB
-        case 24: return launch<128, 128, 2, 2, 4, 32>(a, st);   // 64 KiB, 3 tiles in flight
-        case 25: return launch<128, 64, 2, 2, 3, 32>(a, st);    // 36 KiB
-        case 26: return launch<64, 64, 2, 2, 4, 32>(a, st);     // 32 KiB
-        case 27: return launch<64, 128, 2, 2, 3, 32>(a, st);    // 36 KiB
-        case 0: return launch<128, 128, 2, 2, 2>(a, st);
-        case 1: return launch<128, 64, 2, 2, 2>(a, st);
-        case 2: return launch<64, 64, 2, 2, 2>(a, st);
-        case 3: return launch<128, 32, 4, 1, 2>(a, st);
-        case 4: return launch<64, 128, 2, 2, 2>(a, st);
-        case 5: return launch<128, 128, 2, 2, 4>(a, st);    // 128 KiB LDS, 1 block/CU, 3 tiles in flight
-        case 6: return launch<128, 64, 2, 2, 3>(a, st);     //  72 KiB, 2 blocks/CU
-        case 7: return launch<64, 64, 2, 2, 4>(a, st);      //  64 KiB, 2 blocks/CU
-        case 8: return launch<128, 32, 4, 1, 3>(a, st);     //  60 KiB, 2 blocks/CU
-        case 9: return launch<64, 128, 2, 2, 3>(a, st);     //  72 KiB, 2 blocks/CU
-        case 50: return launch<128, 128, 2, 4, 2, 32>(a, st);   // eight-wave workgroups (fp16: 64 KiB = the fp32 epilogue tile)
-        case 51: return launch<128, 128, 4, 2, 2, 32>(a, st);
-        case 52: return launch<128, 128, 2, 4, 2, 64>(a, st);
-        case 53: return launch<256, 128, 4, 2, 2, 32>(a, st);   // 128 KiB (fp32 epilogue tile)
-        case 54: return launch<128, 256, 2, 4, 2, 32>(a, st);
-        case 55: return launch<128, 128, 2, 4, 4, 32>(a, st);   // 64 KiB: 8 waves, 3 K tiles in flight
+        case 20: return launch<20, false, 2, 2, 2>(a, st);
+        case 21: return launch<21, false, 2, 2, 2>(a, st);
+        case 22: return launch<22, false, 2, 2, 2>(a, st);
+        case 23: return launch<23, false, 2, 2, 2>(a, st);
+        case 24: return launch<24, false, 2, 2, 4>(a, st);
+        case 25: return launch<25, false, 2, 2, 3>(a, st);
+        case 26: return launch<26, false, 2, 2, 4>(a, st);
+        case 27: return launch<27, false, 2, 2, 3>(a, st);
+        case 0: return launch<0, false, 2, 2, 2>(a, st);
+        case 1: return launch<1, false, 2, 2, 2>(a, st);
+        case 2: return launch<2, false, 2, 2, 2>(a, st);
+        case 3: return launch<3, false, 4, 1, 2>(a, st);
+        case 4: return launch<4, false, 2, 2, 2>(a, st);
+        case 5: return launch<5, false, 2, 2, 4>(a, st);
+        case 6: return launch<6, false, 2, 2, 3>(a, st);
+        case 7: return launch<7, false, 2, 2, 4>(a, st);
+        case 8: return launch<8, false, 4, 1, 3>(a, st);
+        case 9: return launch<9, false, 2, 2, 3>(a, st);
+        case 50: return launch<50, false, 2, 4, 2>(a, st);
+        case 51: return launch<51, false, 4, 2, 2>(a, st);
+        case 52: return launch<52, false, 2, 4, 2>(a, st);
+        case 53: return launch<53, false, 4, 2, 2>(a, st);
+        case 54: return launch<54, false, 2, 4, 2>(a, st);
+        case 55: return launch<55, false, 2, 4, 4>(a, st);
         default: return hipErrorInvalidValue;
     }
 }

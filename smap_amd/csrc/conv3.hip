@@ -419,10 +419,14 @@ __global__ __launch_bounds__(NWV * 64, WPE) void conv3x3_halo_kernel(const ConvA
     SMAP_TL_END(a)
 }
 
-template <int BN, int TW, int NB, int BM = 128, int NWV = 4, int WN = (BN >= 64 ? 2 : 1), int WPE = 1, bool STAG = false>
+// TILE: the row of csrc/tiles.h that BM and BN come from; the kernel's own arguments (TW = width of the pixel patch, NB = weight buffers,
+// NWV waves of which WN along N, WPE = waves per SIMD of __launch_bounds__, STAG) stay on the dispatch line
+template <int TILE, int TW, int NB, int NWV = 4, int WN = (tile_row(TILE).bn >= 64 ? 2 : 1), int WPE = 1, bool STAG = false>
 hipError_t launch3(const ConvArgs& a, hipStream_t st)
 {
-    constexpr int TH = BM / TW;
+    constexpr TileRow t = tile_row(TILE);
+    static_assert(t.family == TF_HALO, "csrc/tiles.h: not a halo tile id");
+    constexpr int BM = t.bm, BN = t.bn, TH = BM / TW;
     const int B = a.M / (a.Ho * a.Wo);
     const int tiles_x = (a.Wo + TW - 1) / TW, tiles_y = (a.Ho + TH - 1) / TH;
     const dim3 grid(tiles_x * tiles_y * B * a.n_tiles), block(NWV * 64);
@@ -440,42 +444,28 @@ hipError_t launch3(const ConvArgs& a, hipStream_t st)
 
 }  // namespace
 
-// tile ids 30..49: halo-tiled 3x3 (30..39: 128 output pixels, four waves; 40..49: eight waves, 128 or 256 pixels)
-int smap_conv3_tile_dims(int tile, int* bm, int* bn)
-{
-    switch (tile) {
-        case 30: case 32: case 34: case 36: *bm = 128; *bn = 64; return 0;       // 8x16 / 4x32 pixel tiles
-        case 31: case 33: case 35: case 37: *bm = 128; *bn = 128; return 0;
-        case 38: case 39: *bm = 128; *bn = 32; return 0;
-        case 40: *bm = 128; *bn = 128; return 0;                                   // 40..43: eight waves
-        case 41: case 43: case 44: case 45: *bm = 256; *bn = 128; return 0;       // 44, 45: 41, 43 with the staggered schedule
-        case 42: *bm = 256; *bn = 64; return 0;
-        default: return -1;
-    }
-}
-
 // Only plain 3x3 stride-1 convs qualify (no residual / addends / bilinear add): the schedule's Bottleneck
 // 3x3s and head convs.  Returns hipErrorInvalidValue otherwise (plan validation rejects such ops earlier).
 hipError_t smap_launch_conv3(const ConvArgs& a, int tile, hipStream_t st)
 {
     if (a.ksize != 3 || a.stride != 1 || a.pad != 1 || a.res || a.add1 || a.add2 || a.up) return hipErrorInvalidValue;
-    switch (tile) {
-        case 30: return launch3<64, 16, 2>(a, st);      //  64 KiB LDS
-        case 31: return launch3<128, 16, 2>(a, st);     //  80 KiB
-        case 32: return launch3<64, 32, 2>(a, st);      //  72 KiB
-        case 33: return launch3<128, 32, 2>(a, st);     //  88 KiB
-        case 34: return launch3<64, 16, 4>(a, st);      //  80 KiB: three weight tiles in flight
-        case 35: return launch3<128, 16, 3>(a, st);     //  96 KiB: two
-        case 36: return launch3<64, 32, 3>(a, st);      //  80 KiB: two
-        case 37: return launch3<128, 32, 3>(a, st);     // 104 KiB: two
-        case 38: return launch3<32, 16, 4>(a, st);      //  64 KiB: Cout <= 32 heads, 4 x 1 waves
-        case 39: return launch3<32, 32, 4>(a, st);      //  72 KiB
-        case 40: return launch3<128, 16, 2, 128, 8, 2, 4>(a, st);   //  80 KiB: 8x16 pixels, waves of 32 px x 64 ch, two workgroups per CU (64 x 32 waves spill at 128 VGPRs)
-        case 41: return launch3<128, 16, 3, 256, 8, 2, 2>(a, st);   // 144 KiB: 16x16 pixels, waves of 64 x 64, two weight tiles in flight
-        case 42: return launch3<64, 16, 4, 256, 8, 2, 2>(a, st);    // 128 KiB: 16x16 pixels x 64 channels (the 43-channel heads), waves of 64 x 32
-        case 43: return launch3<128, 32, 3, 256, 8, 2, 2>(a, st);   // 144 KiB: 8x32 pixels
-        case 44: return launch3<128, 16, 3, 256, 8, 2, 2, true>(a, st);   // 41, the two waves of a SIMD half an iteration apart
-        case 45: return launch3<128, 32, 3, 256, 8, 2, 2, true>(a, st);   // 43, staggered
+    switch (tile) {                                     // <tile id, TW, NB, NWV, WN, WPE, STAG>
+        case 30: return launch3<30, 16, 2>(a, st);
+        case 31: return launch3<31, 16, 2>(a, st);
+        case 32: return launch3<32, 32, 2>(a, st);
+        case 33: return launch3<33, 32, 2>(a, st);
+        case 34: return launch3<34, 16, 4>(a, st);
+        case 35: return launch3<35, 16, 3>(a, st);
+        case 36: return launch3<36, 32, 3>(a, st);
+        case 37: return launch3<37, 32, 3>(a, st);
+        case 38: return launch3<38, 16, 4>(a, st);
+        case 39: return launch3<39, 32, 4>(a, st);
+        case 40: return launch3<40, 16, 2, 8, 2, 4>(a, st);
+        case 41: return launch3<41, 16, 3, 8, 2, 2>(a, st);
+        case 42: return launch3<42, 16, 4, 8, 2, 2>(a, st);
+        case 43: return launch3<43, 32, 3, 8, 2, 2>(a, st);
+        case 44: return launch3<44, 16, 3, 8, 2, 2, true>(a, st);
+        case 45: return launch3<45, 32, 3, 8, 2, 2, true>(a, st);
         default: return hipErrorInvalidValue;
     }
 }

@@ -999,30 +999,25 @@ __global__ __launch_bounds__(256, TH == 4 ? SMAP_CONVB_WGS4 : 2) void bottleneck
     SMAP_TL_END(a)
 }
 
-template <int TH, bool FIRST>
+// TILE: the row of csrc/tiles.h; its BM = TH rows of 16 pixels, `first` selects the kernel with the shortcut conv
+template <int TILE>
 hipError_t launchb(const ConvArgs& a, hipStream_t st)
 {
+    constexpr TileRow t = tile_row(TILE);
+    static_assert(t.family == TF_BLOCK && t.planes == 64 && t.tail_bn == 64 && t.bm % 16 == 0, "csrc/tiles.h: not a 64-plane whole-block tile id");
+    constexpr int TH = t.bm / 16;
+    if (!a.x3 || a.ksize != 3 || a.stride != 1 || a.pad != 1 || a.up || a.out_fp32 || !a.w0 || !a.w2 || a.Cin != t.planes ||
+        a.tail_cout8 != 4 * t.planes || a.H != a.Ho || a.W != a.Wo)
+        return hipErrorInvalidValue;
+    if (t.first ? (a.head_cin != t.planes || !a.wd || a.res || a.add1 || a.add2) : (a.head_cin != 4 * t.planes || a.wd)) return hipErrorInvalidValue;
     const int B = a.M / (a.Ho * a.Wo);
     const int tiles_x = (a.Wo + 15) / 16, tiles_y = (a.Ho + TH - 1) / TH;
-    if (FIRST) hipLaunchKernelGGL((bottleneck_first_kernel<TH>), dim3(tiles_x * tiles_y * B), dim3(256), 0, st, a, tiles_x, tiles_y);
+    if (t.first) hipLaunchKernelGGL((bottleneck_first_kernel<TH>), dim3(tiles_x * tiles_y * B), dim3(256), 0, st, a, tiles_x, tiles_y);
     else hipLaunchKernelGGL((bottleneck_kernel<TH>), dim3(tiles_x * tiles_y * B), dim3(256), 0, st, a, tiles_x, tiles_y);
     return hipGetLastError();
 }
 
 }  // namespace
-
-// tile ids 90..99: the fused identity Bottleneck (P = 64 planes; *bm = output pixels per workgroup, *bn = P, *bn2 = tail chunk)
-int smap_convb_tile_dims(int tile, int* bm, int* bn, int* bn2)
-{
-    switch (tile) {
-        case 90: *bm = 64; *bn = 64; *bn2 = 64; return 0;       // 4 x 16 pixel tiles
-        case 91: *bm = 128; *bn = 64; *bn2 = 64; return 0;      // 8 x 16
-        case 92: *bm = 64; *bn = 64; *bn2 = 64; return 0;       // FIRST block of a layer (64 input channels, 1x1 shortcut conv): 4 x 16
-        case 93: *bm = 128; *bn = 64; *bn2 = 64; return 0;      //   8 x 16
-        case 94: *bm = 128; *bn = 128; *bn2 = 128; return 0;    // csrc/convc.hip: identity blocks of 128 planes / 512 channels, 8 x 16
-        default: return -1;
-    }
-}
 
 // tools only (not part of include/smap_hip.h; exported from diagnostics builds with -DSMAP_DEBUG_EXPORTS, tools/build_ablate.py): resident
 // workgroups per CU the runtime reports for a tile id's kernel
@@ -1045,17 +1040,12 @@ extern "C" int smap_debug_convb_occupancy(int tile)
 
 hipError_t smap_launch_convb(const ConvArgs& a, int tile, hipStream_t st)
 {
-    if (tile == 94) return smap_launch_convc(a, st);
-    if (!a.x3 || a.ksize != 3 || a.stride != 1 || a.pad != 1 || a.up || a.out_fp32 || !a.w0 || !a.w2 || a.Cin != 64 ||
-        a.tail_cout8 != 256 || a.H != a.Ho || a.W != a.Wo)
-        return hipErrorInvalidValue;
-    const bool first = tile == 92 || tile == 93;
-    if (first ? (a.head_cin != 64 || !a.wd || a.res || a.add1 || a.add2) : (a.head_cin != 256 || a.wd)) return hipErrorInvalidValue;
     switch (tile) {
-        case 90: return launchb<4, false>(a, st);
-        case 91: return launchb<8, false>(a, st);
-        case 92: return launchb<4, true>(a, st);
-        case 93: return launchb<8, true>(a, st);
+        case 90: return launchb<90>(a, st);
+        case 91: return launchb<91>(a, st);
+        case 92: return launchb<92>(a, st);
+        case 93: return launchb<93>(a, st);
+        case 94: return smap_launch_convc(a, st);       // 128 planes: csrc/convc.hip
         default: return hipErrorInvalidValue;
     }
 }

@@ -751,7 +751,7 @@ __global__ __launch_bounds__(512, 2) void bottleneck128_kernel(const ConvArgs a,
 
 }  // namespace
 
-// tile id 94 (smap_convb_tile_dims / smap_launch_convb in convb.hip route it here): 8 x 16 pixels, 128 planes, 512 channels
+// the whole-block tile of 128 planes (csrc/tiles.h; smap_launch_convb in convb.hip routes it here): 8 x 16 pixels, 512 channels
 hipError_t smap_launch_convc(const ConvArgs& a, hipStream_t st)
 {
     if (!a.x3 || a.ksize != 3 || a.stride != 1 || a.pad != 1 || a.up || a.out_fp32 || !a.w0 || !a.w2 || a.wd || a.Cin != 128 || a.head_cin != 512 ||

@@ -412,10 +412,13 @@ __global__ __launch_bounds__(256) void conv3_tail_kernel(const ConvArgs a, int t
     SMAP_TL_END(a)
 }
 
-template <int P, int TW, int NB, int BN2>
+// TILE: the row of csrc/tiles.h that P (= BN, the 3x3's planes) and the tail chunk come from; TW = patch width, NB = weight buffers
+template <int TILE, int TW, int NB>
 hipError_t launchf(const ConvArgs& a, hipStream_t st)
 {
-    constexpr int TH = 128 / TW;
+    constexpr TileRow t = tile_row(TILE);
+    static_assert(t.family == TF_TAIL && t.tail_bn > 0 && t.bm == 128, "csrc/tiles.h: not a fused-tail tile id (the kernel's patch is 128 pixels)");
+    constexpr int P = t.bn, BN2 = t.tail_bn, TH = t.bm / TW;
     const int B = a.M / (a.Ho * a.Wo);
     const int tiles_x = (a.Wo + TW - 1) / TW, tiles_y = (a.Ho + TH - 1) / TH;
     if (a.x3)
@@ -427,24 +430,13 @@ hipError_t launchf(const ConvArgs& a, hipStream_t st)
 
 }  // namespace
 
-// tile ids 80..89: 3x3 (P = BN output channels, all of them in one tile) + 1x1 tail in chunks of *bn2 channels
-int smap_convf_tile_dims(int tile, int* bm, int* bn, int* bn2)
-{
-    switch (tile) {
-        case 80: *bm = 128; *bn = 64; *bn2 = 64; return 0;
-        case 81: *bm = 128; *bn = 64; *bn2 = 128; return 0;
-        case 82: *bm = 128; *bn = 128; *bn2 = 64; return 0;
-        default: return -1;
-    }
-}
-
 hipError_t smap_launch_convf(const ConvArgs& a, int tile, hipStream_t st)
 {
     if (a.ksize != 3 || a.stride != 1 || a.pad != 1 || a.up || a.out_fp32 || !a.w2) return hipErrorInvalidValue;
-    switch (tile) {
-        case 80: return launchf<64, 32, 3, 64>(a, st);       // 80 KiB both phases: two workgroups per CU
-        case 81: return launchf<64, 32, 3, 128>(a, st);      // 96 KiB
-        case 82: return launchf<128, 32, 2, 64>(a, st);      // 128 KiB
+    switch (tile) {                                     // <tile id, TW, NB>
+        case 80: return launchf<80, 32, 3>(a, st);
+        case 81: return launchf<81, 32, 3>(a, st);
+        case 82: return launchf<82, 32, 2>(a, st);
         default: return hipErrorInvalidValue;
     }
 }

@@ -519,52 +519,42 @@ int cu_count()
     return n;
 }
 
-template <int BM, int BN, int WM, int WN, int STAGES, bool X3, int NLA = 0, int BK = 32, int P_NLW = 4>
+// TILE: the row of csrc/tiles.h that BM, BN and BK come from; WM x WN compute waves and STAGES stay on the dispatch line
+template <int TILE, bool X3, int WM, int WN, int STAGES, int NLA = 0, int P_NLW = 4>
 hipError_t launchp(const ConvArgs& a, hipStream_t st)
 {
+    constexpr TileRow t = tile_row(TILE);
+    static_assert(t.family == TF_PERSIST && tile_has(t, X3), "csrc/tiles.h: no persistent instance of this tile id in this precision");
     const int tiles = a.m_tiles * a.n_tiles;
     const int cus = cu_count();
     const int grid = tiles < cus ? tiles : cus;
-    hipLaunchKernelGGL((convp_kernel<BM, BN, WM, WN, STAGES, X3, NLA, BK, P_NLW>), dim3(grid), dim3((WM * WN + P_NLW) * 64), 0, st, a, tiles);
+    hipLaunchKernelGGL((convp_kernel<t.bm, t.bn, WM, WN, STAGES, X3, NLA, tile_bk(t, X3), P_NLW>), dim3(grid), dim3((WM * WN + P_NLW) * 64), 0, st, a, tiles);
     return hipGetLastError();
 }
 
 }  // namespace
 
-int smap_convp_tile_dims(int tile, int* bm, int* bn)
-{
-    // (ids 66, 68, 69, 70 -- split loaders, 64-half K tiles, eight loader waves -- were round-3 experiments that no measured table
-    //  entry selects: retired from the shipped library in round 4; the template parameters NLA / P_BK / P_NLW they instantiated remain)
-    switch (tile) {
-        case 60: *bm = 128; *bn = 256; return 0;      // 8 compute waves of 64 px x 64 ch
-        case 61: *bm = 256; *bn = 128; return 0;
-        case 62: *bm = 128; *bn = 128; return 0;      // 8 compute waves of 32 px x 64 ch
-        case 63: case 64: case 65: *bm = 128; *bn = 64; return 0;
-        default: return -1;
-    }
-}
-
 hipError_t smap_launch_convp(const ConvArgs& a, int tile, hipStream_t st)
 {
     if (a.up || a.out_fp32) return hipErrorInvalidValue;
     if (a.x3) {
-        switch (tile) {
-            case 60: return launchp<128, 256, 2, 4, 3, true>(a, st);     // 3 x 48 KiB
-            case 61: return launchp<256, 128, 4, 2, 3, true>(a, st);     // 3 x 48 KiB
-            case 62: return launchp<128, 128, 4, 2, 4, true>(a, st);     // 4 x 32 KiB
-            case 63: return launchp<128, 64, 4, 2, 6, true>(a, st);      // 6 x 24 KiB
-            case 64: return launchp<128, 64, 4, 2, 3, true>(a, st);
-            case 65: return launchp<128, 64, 4, 2, 2, true>(a, st);
+        switch (tile) {                                 // <tile id, X3, WM, WN, STAGES>
+            case 60: return launchp<60, true, 2, 4, 3>(a, st);
+            case 61: return launchp<61, true, 4, 2, 3>(a, st);
+            case 62: return launchp<62, true, 4, 2, 4>(a, st);
+            case 63: return launchp<63, true, 4, 2, 6>(a, st);
+            case 64: return launchp<64, true, 4, 2, 3>(a, st);
+            case 65: return launchp<65, true, 4, 2, 2>(a, st);
             default: return hipErrorInvalidValue;
         }
     }
     switch (tile) {
-        case 60: return launchp<128, 256, 2, 4, 4, false>(a, st);        // 4 x 24 KiB
-        case 61: return launchp<256, 128, 4, 2, 4, false>(a, st);
-        case 62: return launchp<128, 128, 4, 2, 4, false>(a, st);        // 4 x 16 KiB
-        case 63: return launchp<128, 64, 4, 2, 6, false>(a, st);
-        case 64: return launchp<128, 64, 4, 2, 3, false>(a, st);
-        case 65: return launchp<128, 64, 4, 2, 2, false>(a, st);
+        case 60: return launchp<60, false, 2, 4, 4>(a, st);
+        case 61: return launchp<61, false, 4, 2, 4>(a, st);
+        case 62: return launchp<62, false, 4, 2, 4>(a, st);
+        case 63: return launchp<63, false, 4, 2, 6>(a, st);
+        case 64: return launchp<64, false, 4, 2, 3>(a, st);
+        case 65: return launchp<65, false, 4, 2, 2>(a, st);
         default: return hipErrorInvalidValue;
     }
 }

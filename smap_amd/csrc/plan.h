@@ -1,7 +1,8 @@
-// plan.h -- internal declarations shared by conv.hip and plan.hip (not part of the C ABI).
+// plan.h -- internal declarations shared by the conv*.hip files and plan.hip (not part of the C ABI).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "tiles.h"
 
 struct ConvArgs {
     const void* arena;       // activation arena base; its first 256 bytes are zeros (padding taps read them)
@@ -26,18 +27,18 @@ struct ConvArgs {
     long long w_lo;          // bytes from the hi weight matrix to the lo weight matrix
     float acc_scale;         // accumulator multiplier undoing the power-of-two weight pre-scale
     int w_pairs;             // 32-half K tiles of the packed weights come in pairs (128-byte rows [tile 2p | tile 2p+1])
-    // fused 1x1 tail (convf.hip, tile ids 80..89): out / res / add1 / add2 / relu then belong to the TAIL's output
+    // fused 1x1 tail (convf.hip, family TF_TAIL): out / res / add1 / add2 / relu then belong to the TAIL's output
     const _Float16* w2;      // packed [n2 chunk][k chunk][BN2 rows][128 B] weights of the 1x1, or null
     const float* bias2;      // [tail cout_pad] fp32
     int tail_cout8;          // channels the tail writes (multiple of 8)
     int tail_chunks;         // tail cout_pad / BN2
     float tail_acc_scale;
-    // fused leading 1x1 (convb.hip, tile ids 90..99): the op's INPUT tensor then has head_cin channels, w / bias are the 3x3's
+    // fused leading 1x1 (convb.hip / convc.hip, family TF_BLOCK): the op's INPUT tensor then has head_cin channels, w / bias are the 3x3's
     const _Float16* w0;      // packed [k chunk][P rows][128 B] weights of the leading 1x1, or null
     const float* bias0;      // [P] fp32
     int head_cin;            // channels of the block's input (= of its output)
     float acc_scale0;
-    const _Float16* wd;      // tile ids 92, 93: packed [n chunk][k chunk][64 rows][128 B] weights of the 1x1 SHORTCUT conv of a layer's first
+    const _Float16* wd;      // first-block tiles: packed [n chunk][k chunk][64 rows][128 B] weights of the 1x1 SHORTCUT conv of a layer's first
     float acc_scale_d;       // block (head_cin -> tail_cout, no ReLU; its bias is folded into bias2), or null
     // split K (smap_op.ksplit, conv.hip only): K parts per output tile, scratch for the raw partial tiles, one ticket per tile
     int ksplit;
@@ -87,20 +88,13 @@ __device__ __forceinline__ Lerp lerp_index(int dst, int in_size, int out_size)
     return r;
 }
 
-int smap_conv_tile_has_splitk(int tile);                                    // conv.hip: tile ids with a split-K instance
-int smap_conv_tile_has_relusum(int tile);                                   // ... with a relu(conv) + relu(conv) instance (smap_op.in2_mode = 1)
-int smap_conv_tile_has_dual(int tile);                                      // conv.hip: tile ids with a second-input (K-concatenated) instance
-int smap_conv_tile_has_x3(int tile);                                        // conv.hip: tile ids with a split-precision instance
+// launches by kernel family (csrc/tiles.h); smap_launch_conv routes every tile id
 hipError_t smap_launch_conv(const ConvArgs& a, int tile, hipStream_t st);
-int smap_conv3_tile_dims(int tile, int* bm, int* bn);                       // conv3.hip (tile ids 30..33, halo-tiled 3x3)
-hipError_t smap_launch_conv3(const ConvArgs& a, int tile, hipStream_t st);
-int smap_convp_tile_dims(int tile, int* bm, int* bn);                       // convp.hip (tile ids 60..69, persistent wave-specialised GEMM)
-hipError_t smap_launch_convp(const ConvArgs& a, int tile, hipStream_t st);
-int smap_convf_tile_dims(int tile, int* bm, int* bn, int* bn2);             // convf.hip (tile ids 80..89, 3x3 + fused 1x1 tail)
-hipError_t smap_launch_convf(const ConvArgs& a, int tile, hipStream_t st);
-int smap_convb_tile_dims(int tile, int* bm, int* bn, int* bn2);             // convb.hip (tile ids 90..99, whole identity Bottleneck)
-hipError_t smap_launch_convb(const ConvArgs& a, int tile, hipStream_t st);
-hipError_t smap_launch_convc(const ConvArgs& a, hipStream_t st);           // convc.hip (tile id 94: the same for 128 planes / 512 channels)
+hipError_t smap_launch_conv3(const ConvArgs& a, int tile, hipStream_t st);      // conv3.hip: halo-tiled 3x3
+hipError_t smap_launch_convp(const ConvArgs& a, int tile, hipStream_t st);      // convp.hip: persistent wave-specialised GEMM
+hipError_t smap_launch_convf(const ConvArgs& a, int tile, hipStream_t st);      // convf.hip: 3x3 + fused 1x1 tail
+hipError_t smap_launch_convb(const ConvArgs& a, int tile, hipStream_t st);      // convb.hip: whole Bottleneck of 64 planes
+hipError_t smap_launch_convc(const ConvArgs& a, hipStream_t st);                // convc.hip: the same for 128 planes / 512 channels
 
 #ifdef SMAP_TIMELINE
 // every workgroup of a conv kernel calls these two (first / last statement): 100 MHz device-wide clock

@@ -614,26 +614,27 @@ static int validate(const smap_op& o)
         return SMAP_E_ARG;                               // UPADD has no split-precision instance
     switch (o.kind) {
         case SMAP_OP_CONV: {
-            int bm, bn;
-            if (smap_conv_tile_dims(o.tile, &bm, &bn)) return SMAP_E_ARG;
+            const TileRow* t = tile_find(o.tile);          // csrc/tiles.h: what the id's kernel is and which instances it has
+            if (!t || !tile_has(*t, o.precision == 1)) return SMAP_E_ARG;      // unknown id, or no instance in this precision
+            const int bm = t->bm, bn = t->bn;
             if (o.Cin % 64 || o.Cin * 2 + 16 > SMAP_ZERO_PAGE || o.cout_pad % bn || o.cout_pad < o.Cout) return SMAP_E_ARG;
             if (o.precision == 1) {
-                if (!smap_conv_tile_has_x3(o.tile) || o.in_stride_c % 16 || (!o.out_fp32 && o.out_stride_c % 16)) return SMAP_E_ARG;
+                if (o.in_stride_c % 16 || (!o.out_fp32 && o.out_stride_c % 16)) return SMAP_E_ARG;
                 if (o.Cin * 2 + o.in_stride_c + 16 > SMAP_ZERO_PAGE || !(o.acc_scale > 0.f)) return SMAP_E_ARG;
                 if (o.in_c_off + o.Cin > o.in_stride_c / 2) return SMAP_E_ARG;
             }
             if (o.ksize != 1 && o.ksize != 3) return SMAP_E_ARG;
             if (o.w_pairs != 0 && o.w_pairs != 1) return SMAP_E_ARG;
-            if (o.tile >= 30 && o.tile < 50 && (o.ksize != 3 || o.stride != 1 || o.pad != 1 || o.res_off >= 0 || o.add1_off >= 0 ||
+            if (t->family == TF_HALO && (o.ksize != 3 || o.stride != 1 || o.pad != 1 || o.res_off >= 0 || o.add1_off >= 0 ||
                                  o.add2_off >= 0 || o.aux_off[0] >= 0))
                 return SMAP_E_ARG;                       // halo-tiled kernel: plain 3x3 stride-1 convs only
-            if ((o.tile >= 80 && o.tile < 100) != (o.tail_cout > 0)) return SMAP_E_ARG;
-            if ((o.tile >= 90 && o.tile < 100) != (o.head_cin > 0)) return SMAP_E_ARG;
-            if (o.tile >= 90 && o.tile < 100) {          // whole Bottleneck (convb.hip): split precision, P = 64 planes, 256 output channels
-                const bool first = o.tile == 92 || o.tile == 93;       // a layer's FIRST block: 64 input channels, 1x1 shortcut conv instead of + x
-                if (o.precision != 1 || o.ksize != 3 || o.stride != 1 || o.pad != 1 || o.out_fp32 || o.aux_off[0] >= 0) return SMAP_E_ARG;
-                const int planes = o.tile == 94 ? 128 : 64;            // 94: csrc/convc.hip, 128 planes / 512 channels
-                if (o.Cin != planes || o.Cout != planes || o.cout_pad != planes || o.head_cin != (first ? 64 : 4 * planes) || o.tail_cout != 4 * planes ||
+            if ((t->tail_bn > 0) != (o.tail_cout > 0)) return SMAP_E_ARG;
+            if ((t->family == TF_BLOCK) != (o.head_cin > 0)) return SMAP_E_ARG;
+            if (t->family == TF_BLOCK) {                 // whole Bottleneck (convb.hip / convc.hip): `planes` planes, 4 x planes output channels
+                const bool first = t->first;             // a layer's FIRST block: `planes` input channels, 1x1 shortcut conv instead of + x
+                if (o.ksize != 3 || o.stride != 1 || o.pad != 1 || o.out_fp32 || o.aux_off[0] >= 0) return SMAP_E_ARG;
+                const int planes = t->planes;
+                if (o.Cin != planes || o.Cout != planes || o.cout_pad != planes || o.head_cin != (first ? planes : 4 * planes) || o.tail_cout != 4 * planes ||
                     o.tail_cout_pad != 4 * planes)
                     return SMAP_E_ARG;
                 if (o.in_stride_c != 2 * o.head_cin || o.in_c_off != 0) return SMAP_E_ARG;
@@ -644,8 +645,8 @@ static int validate(const smap_op& o)
                 if (!(o.head_acc_scale > 0.f) || !(o.tail_acc_scale > 0.f) || o.out_stride_c < o.tail_cout) return SMAP_E_ARG;
                 if ((int64_t)o.B * o.Ho * o.Wo * o.tail_cout * 2 >= ((int64_t)1 << 31)) return SMAP_E_ARG;
             } else if (o.short_acc_scale != 0.f) return SMAP_E_ARG;      // (a zero-initialised op has no shortcut conv)
-            if (o.tile >= 80 && o.tile < 90) {           // 3x3 + fused 1x1 tail: the op's Cout is the tile's whole N extent
-                const int bn2 = smap_conv_tile_tail_bn(o.tile);
+            if (t->family == TF_TAIL) {                  // 3x3 + fused 1x1 tail: the op's Cout is the tile's whole N extent
+                const int bn2 = t->tail_bn;
                 if (o.ksize != 3 || o.stride != 1 || o.pad != 1 || o.out_fp32 || o.aux_off[0] >= 0 || o.Cout != bn || o.cout_pad != bn)
                     return SMAP_E_ARG;
                 if (o.tail_cout % 8 || o.tail_cout_pad % bn2 || o.tail_cout_pad < o.tail_cout || o.tail_w_off < 0 || o.tail_bias_off < 0)
@@ -654,9 +655,9 @@ static int validate(const smap_op& o)
                 if (o.out_stride_c < o.tail_cout) return SMAP_E_ARG;
                 if ((int64_t)o.B * o.Ho * o.Wo * o.tail_cout * (1 + o.precision) >= ((int64_t)1 << 31)) return SMAP_E_ARG;
             }
-            if (o.tile == 56 && (o.precision != 1 || o.out_fp32 || o.aux_off[0] >= 0 || o.add1_off >= 0 || o.add2_off >= 0 || o.Cout % 8 || o.ksplit > 1))
-                return SMAP_E_ARG;                       // register-epilogue tile of conv.hip: split precision, fp16 outputs, residual + ReLU only
-            if (o.tile >= 60 && o.tile < 80 && (o.out_fp32 || o.aux_off[0] >= 0 || o.Cout % 8 || o.cout_pad > 2048))
+            if ((t->caps & TC_REGEPI) && (o.out_fp32 || o.aux_off[0] >= 0 || o.add1_off >= 0 || o.add2_off >= 0 || o.Cout % 8 || o.ksplit > 1))
+                return SMAP_E_ARG;                       // register-epilogue tiles of conv.hip: fp16 outputs, residual + ReLU only
+            if (t->family == TF_PERSIST && (o.out_fp32 || o.aux_off[0] >= 0 || o.Cout % 8 || o.cout_pad > 2048))
                 return SMAP_E_ARG;                       // persistent kernel: register epilogue, fp16 outputs, no fused bilinear add, bias table of 2048 channels in LDS
             if (o.in_stride_c % 8 || o.in_c_off % 8 || o.out_stride_c % 8 || o.out_c_off % 8) return SMAP_E_ARG;
             if (o.out_stride_c < ((o.Cout + 7) & ~7) && o.tap_n == 0) return SMAP_E_ARG;      // (tap-dot: `out` is the [M][16] tap tensor)
@@ -678,22 +679,22 @@ static int validate(const smap_op& o)
             if ((int64_t)o.cout_pad * o.ksize * o.ksize * o.Cin * 2 * (1 + o.precision) > ((int64_t)1 << 32)) return SMAP_E_ARG;
             if (o.ksplit < 0 || o.ksplit > 16) return SMAP_E_ARG;
             if (o.ksplit > 1) {                          // split K: conv.hip's tiles; scratch and tickets inside the arena, off the zero pages
-                const int bk = smap_conv_tile_bk(o.tile, o.precision);
-                if (!smap_conv_tile_has_splitk(o.tile) || bk <= 0 || o.ksplit > o.ksize * o.ksize * o.Cin / bk) return SMAP_E_ARG;
+                const int bk = tile_bk(*t, o.precision == 1);
+                if (!(t->caps & TC_SPLITK) || o.ksplit > o.ksize * o.ksize * o.Cin / bk) return SMAP_E_ARG;
                 const int64_t tiles = (((int64_t)o.B * o.Ho * o.Wo + bm - 1) / bm) * (o.cout_pad / bn);
                 const int64_t pbytes = tiles * o.ksplit * bm * bn * 4, cbytes = tiles * 4;
                 if (o.kpart_off < SMAP_ZERO_PAGE || o.kcount_off < SMAP_ZERO_PAGE || o.kpart_off % 16 || o.kcount_off % 4) return SMAP_E_ARG;
                 if (hits_zero_page(o.kpart_off, pbytes) || hits_zero_page(o.kcount_off, cbytes)) return SMAP_E_ARG;
             }
-            if (o.tap_n != 0) {                          // tap-dot epilogue: tile 54, one N tile of 256 channels, t = fp32 [M][16]
-                if (o.tap_n != 9 || o.tile != 54 || o.cout_pad != 256 || o.Cout != 256 || o.ksize != 1 || o.stride != 1 || !o.out_fp32 || o.out_stride_c != 16 ||
+            if (o.tap_n != 0) {                          // tap-dot epilogue: one N tile of 256 channels, t = fp32 [M][16]
+                if (o.tap_n != 9 || !(t->caps & TC_TAPDOT) || o.cout_pad != 256 || o.Cout != 256 || o.ksize != 1 || o.stride != 1 || !o.out_fp32 || o.out_stride_c != 16 ||
                     o.out_c_off != 0 || o.res_off >= 0 || o.add1_off >= 0 || o.add2_off >= 0 || o.aux_off[0] >= 0 || o.seg_n[0] != 0 || o.ksplit > 1 || o.in2_C != 0 ||
                     o.tap_w_off < 0 || !(o.tap_scale > 0.f))
                     return SMAP_E_ARG;
             }
             if (o.in2_C < 0) return SMAP_E_ARG;
-            if (o.in2_C > 0) {                           // second input along K: conv.hip's tiles 20 / 50 / 51, 1x1 stride 1 on the first input, plain epilogue
-                if (!smap_conv_tile_has_dual(o.tile) || o.ksize != 1 || o.stride != 1 || o.pad != 0 || o.ksplit > 1 || o.seg_n[0] != 0 || o.aux_off[0] >= 0 ||
+            if (o.in2_C > 0) {                           // second input along K: 1x1 stride 1 on the first input, plain epilogue
+                if (!(t->caps & TC_DUAL) || o.ksize != 1 || o.stride != 1 || o.pad != 0 || o.ksplit > 1 || o.seg_n[0] != 0 || o.aux_off[0] >= 0 ||
                     o.add1_off >= 0 || o.add2_off >= 0 || o.out_fp32 || o.in_c_off != 0)
                     return SMAP_E_ARG;
                 if (o.in2_C % 64 || o.in2_stride < 1 || o.in2_stride > 2 || o.in2_H <= 0 || o.in2_W <= 0 || o.in2_off < SMAP_ZERO_PAGE) return SMAP_E_ARG;
@@ -705,13 +706,12 @@ static int validate(const smap_op& o)
                     return SMAP_E_ARG;
                 if ((int64_t)o.cout_pad * (o.Cin + o.in2_C) * 2 * (1 + o.precision) > ((int64_t)1 << 32)) return SMAP_E_ARG;
                 if (o.in2_mode != 0 && o.in2_mode != 1) return SMAP_E_ARG;
-                if (o.in2_mode == 1 && (!smap_conv_tile_has_relusum(o.tile) || o.in2_stride != 1 || o.res_off >= 0 || o.relu != 0 || o.in2_bias_off < 0 || (o.precision == 1 && !(o.in2_acc_scale > 0.f))))
+                if (o.in2_mode == 1 && (!(t->caps & TC_RELUSUM) || o.in2_stride != 1 || o.res_off >= 0 || o.relu != 0 || o.in2_bias_off < 0 || (o.precision == 1 && !(o.in2_acc_scale > 0.f))))
                     return SMAP_E_ARG;               // relu(W1 x + b1) + relu(W2 x2 + b2): its own activations, no residual
             } else if (o.in2_mode != 0) return SMAP_E_ARG;
             if (o.seg_n[0] == 0 && o.seg_n[1] != 0) return SMAP_E_ARG;
             if (o.seg_n[0] != 0) {                       // N segments: conv.hip's tiles, 1x1, fp16 outputs; every segment starts on an N tile
-                const bool igemm = (o.tile >= 0 && o.tile < 30) || (o.tile >= 50 && o.tile < 60);
-                if (!igemm || o.ksize != 1 || o.out_fp32 || o.out_c_off != 0) return SMAP_E_ARG;
+                if (t->family != TF_IGEMM || o.ksize != 1 || o.out_fp32 || o.out_c_off != 0) return SMAP_E_ARG;
                 int prev = 0;
                 for (int j = 0; j < 2 && o.seg_n[j] != 0; ++j) {
                     if (o.seg_n[j] <= prev || o.seg_n[j] % bn || o.seg_n[j] >= o.cout_pad) return SMAP_E_ARG;

@@ -26,6 +26,8 @@ bits) with three MFMAs per K step (csrc/conv.hip, template X3): ~1e-6 relative e
 ~1e-3, at 3x the matrix work and 2x the bytes.
 """
 import ctypes as C
+import os
+from collections import namedtuple
 from dataclasses import dataclass, field
 
 import torch
@@ -33,40 +35,85 @@ import torch
 from . import lib as _L
 
 OP_CONV, OP_STEM, OP_MAXPOOL, OP_UPADD, OP_HEADSUM, OP_STEMPOOL, OP_TAPSUM = range(7)
-import os
 
-# tile id -> (BM, BN); ids 5..9 are the same tiles with deeper LDS-DMA pipelines (csrc/conv.hip)
-TILES = {0: (128, 128), 1: (128, 64), 2: (64, 64), 3: (128, 32), 4: (64, 128),
-         5: (128, 128), 6: (128, 64), 7: (64, 64), 8: (128, 32), 9: (64, 128),
-         # 20..27: csrc/conv.hip with BK = 32 staging (LDS-staged epilogue kept)
-         20: (128, 128), 21: (128, 64), 22: (64, 64), 23: (64, 128), 24: (128, 128), 25: (128, 64), 26: (64, 64),
-         27: (64, 128),
-         # 30..39: csrc/conv3.hip halo-tiled 3x3 stride-1 (BM = 128 output pixels as an 8x16 / 4x32 patch)
-         30: (128, 64), 31: (128, 128), 32: (128, 64), 33: (128, 128),
-         34: (128, 64), 35: (128, 128), 36: (128, 64), 37: (128, 128),     # 34..37: deeper weight pipeline
-         38: (128, 32), 39: (128, 32),                                     # Cout <= 32 heads
-         # 40..43: the same kernel with EIGHT waves: 8x16 pixels (two workgroups per CU), 16x16 / 16x16 x 64 channels / 8x32 (one)
-         40: (128, 128), 41: (256, 128), 42: (256, 64), 43: (256, 128),
-         44: (256, 128), 45: (256, 128),                                   # 41 / 43 with the two waves of a SIMD half an iteration apart
-         # 50..54: csrc/conv.hip with EIGHT waves per workgroup (two per SIMD from one workgroup: the low-resolution layers)
-         50: (128, 128), 51: (128, 128), 52: (128, 128), 53: (256, 128), 54: (128, 256),
-         # 55: 4-stage pipeline (three K tiles in flight per workgroup: bytes in flight, not occupancy, for the streaming layers)
-         55: (128, 128),
-         # 56 (round 6): 256 x 256, eight waves of 128 x 64, REGISTER epilogue (two 64 KiB LDS stages leave no room for a staging tile): half the
-         # L2 -> LDS bytes per MFMA of the 128 x 128 tiles.  Split precision, fp16 outputs, residual + ReLU only (no bilinear add / addends)
-         56: (256, 256),
-         # 60..62: csrc/convp.hip, persistent workgroups with loader waves and a register epilogue (no fused bilinear add, no fp32 out)
-         60: (128, 256), 61: (256, 128), 62: (128, 128), 63: (128, 64), 64: (128, 64), 65: (128, 64),
-         # 80..82: csrc/convf.hip, a Bottleneck's 3x3 (BN = all of its planes) with the following 1x1 fused in (TAIL_BN)
-         80: (128, 64), 81: (128, 64), 82: (128, 128),
-         # 90..91: csrc/convb.hip, a whole identity Bottleneck of 64 planes (1x1 -> 3x3 -> 1x1 + residual) per 4x16 / 8x16 pixel tile
-         90: (64, 64), 91: (128, 64),
-         # 92..93: the same for the FIRST block of layer1 (64 input channels, 1x1 shortcut conv instead of the identity residual)
-         92: (64, 64), 93: (128, 64),
-         # 94: csrc/convc.hip, the whole identity Bottleneck of 128 planes / 512 channels (layer2) per 8x16 pixel tile, eight waves
-         94: (128, 128)}
+# ----------------------------------------------------------------------------- tile ids
+# What every conv tile id (smap_op.tile) means, written down ONCE for the Python side; the C side keeps the same rows in csrc/tiles.h
+# (per-row notes on LDS size / waves / why a variant exists live there), tests/test_host_cpu.py compares the two fact by fact.
+#   family: "igemm" (csrc/conv.hip), "halo" (csrc/conv3.hip: plain 3x3 stride-1), "persist" (csrc/convp.hip: persistent workgroups, register
+#           epilogue), "tail" (csrc/convf.hip: a Bottleneck's 3x3 with the following 1x1 fused in), "block" (csrc/convb.hip / convc.hip: a
+#           whole Bottleneck per launch)
+#   bm, bn: output tile, pixels x channels;  bk16, bkx3: halves per staged K tile in fp16 / split precision
+#   prec:   the precisions the id has an instance in ("f16 x3" unless said)
+#   caps:   further instances of the conv.hip kernel: "splitk", "dual" (second input along K), "relusum" (relu(conv) + relu(conv)),
+#           "regepi" (register epilogue INSTEAD of the LDS-staged one), "tapdot"
+#   tail_bn: output channels per chunk of the fused 1x1 tail;  planes, first: the Bottleneck a "block" tile runs (first = with a shortcut conv)
+Tile = namedtuple("Tile", "family bm bn bk16 bkx3 caps tail_bn planes first prec", defaults=("", 0, 0, False, "f16 x3"))
+TILE_TABLE = {
+    # 0..4: two-stage pipelines of 64-half K tiles; 5..9: the same tiles with deeper LDS-DMA pipelines
+    0: Tile("igemm", 128, 128, 64, 64), 1: Tile("igemm", 128, 64, 64, 64), 2: Tile("igemm", 64, 64, 64, 64, "splitk"),
+    3: Tile("igemm", 128, 32, 64, 64), 4: Tile("igemm", 64, 128, 64, 64),
+    5: Tile("igemm", 128, 128, 64, 32, prec="f16"), 6: Tile("igemm", 128, 64, 64, 32, prec="f16"), 7: Tile("igemm", 64, 64, 64, 64, "splitk"),
+    8: Tile("igemm", 128, 32, 64, 32, prec="f16"), 9: Tile("igemm", 64, 128, 64, 32, prec="f16"),
+    # (ids 10..18 belonged to a register-epilogue GEMM that no measured table entry selected: tools/experiments/, outside the product build)
+    # 20..27: BK = 32 staging (LDS-staged epilogue kept)
+    20: Tile("igemm", 128, 128, 32, 32, "splitk dual"), 21: Tile("igemm", 128, 64, 32, 32), 22: Tile("igemm", 64, 64, 32, 32, "splitk"),
+    23: Tile("igemm", 64, 128, 32, 32), 24: Tile("igemm", 128, 128, 32, 32), 25: Tile("igemm", 128, 64, 32, 32),
+    26: Tile("igemm", 64, 64, 32, 32), 27: Tile("igemm", 64, 128, 32, 32),
+    # 30..39: halo-tiled 3x3, BM = 128 output pixels as an 8x16 / 4x32 patch (34..37: deeper weight pipeline; 38, 39: Cout <= 32 heads)
+    30: Tile("halo", 128, 64, 64, 32), 31: Tile("halo", 128, 128, 64, 32), 32: Tile("halo", 128, 64, 64, 32), 33: Tile("halo", 128, 128, 64, 32),
+    34: Tile("halo", 128, 64, 64, 32), 35: Tile("halo", 128, 128, 64, 32), 36: Tile("halo", 128, 64, 64, 32), 37: Tile("halo", 128, 128, 64, 32),
+    38: Tile("halo", 128, 32, 64, 32), 39: Tile("halo", 128, 32, 64, 32),
+    # 40..45: the same kernel with EIGHT waves: 8x16 pixels (two workgroups per CU), 16x16 / 16x16 x 64 channels / 8x32 (one); 44, 45 = 41, 43
+    # with the two waves of a SIMD half an iteration apart
+    40: Tile("halo", 128, 128, 64, 32), 41: Tile("halo", 256, 128, 64, 32), 42: Tile("halo", 256, 64, 64, 32), 43: Tile("halo", 256, 128, 64, 32),
+    44: Tile("halo", 256, 128, 64, 32), 45: Tile("halo", 256, 128, 64, 32),
+    # 50..55: conv.hip with EIGHT waves per workgroup (the low-resolution layers); 55: 4-stage pipeline (bytes in flight for the streaming layers)
+    50: Tile("igemm", 128, 128, 32, 32, "dual relusum"), 51: Tile("igemm", 128, 128, 32, 32, "dual relusum"), 52: Tile("igemm", 128, 128, 64, 64),
+    53: Tile("igemm", 256, 128, 32, 32, "dual relusum"), 54: Tile("igemm", 128, 256, 32, 32, "dual relusum tapdot"), 55: Tile("igemm", 128, 128, 32, 32),
+    # 56: 256 x 256, half the L2 -> LDS bytes per MFMA of the 128 x 128 tiles.  Split precision, fp16 outputs, residual + ReLU only
+    56: Tile("igemm", 256, 256, 64, 32, "regepi", prec="x3"),
+    # 60..65: persistent workgroups with loader waves (no fused bilinear add, no fp32 out)
+    60: Tile("persist", 128, 256, 32, 32), 61: Tile("persist", 256, 128, 32, 32), 62: Tile("persist", 128, 128, 32, 32),
+    63: Tile("persist", 128, 64, 32, 32), 64: Tile("persist", 128, 64, 32, 32), 65: Tile("persist", 128, 64, 32, 32),
+    # 80..82: a Bottleneck's 3x3 (BN = all of its planes) with the following 1x1 fused in
+    80: Tile("tail", 128, 64, 64, 32, tail_bn=64), 81: Tile("tail", 128, 64, 64, 32, tail_bn=128), 82: Tile("tail", 128, 128, 64, 32, tail_bn=64),
+    # 90, 91: a whole identity Bottleneck of 64 planes (1x1 -> 3x3 -> 1x1 + residual) per 4x16 / 8x16 pixel tile; 92, 93: the same for the FIRST
+    # block of layer1 (64 input channels, 1x1 shortcut conv instead of the identity residual); 94: 128 planes / 512 channels (layer2), eight waves
+    90: Tile("block", 64, 64, 64, 32, tail_bn=64, planes=64, prec="x3"), 91: Tile("block", 128, 64, 64, 32, tail_bn=64, planes=64, prec="x3"),
+    92: Tile("block", 64, 64, 64, 32, tail_bn=64, planes=64, first=True, prec="x3"), 93: Tile("block", 128, 64, 64, 32, tail_bn=64, planes=64, first=True, prec="x3"),
+    94: Tile("block", 128, 128, 64, 32, tail_bn=128, planes=128, prec="x3")}
+
+
+def tile_family(tile):
+    return TILE_TABLE[tile].family
+
+
+def tile_bk(tile, x3):
+    """Halves per K chunk of the LDS rows a tile id stages = the packing unit of its weights.  The halo
+    kernels' rows are always 128 bytes: 64 channels, or [hi32 | lo32] of 32 channels in split precision."""
+    return TILE_TABLE[tile].bkx3 if x3 else TILE_TABLE[tile].bk16
+
+
+def tile_has(tile, cap=None, x3=False):
+    """Does tile id `tile` have an instance in this precision -- and, with `cap`, that further instance of it?"""
+    row = TILE_TABLE.get(tile)
+    return row is not None and ("x3" if x3 else "f16") in row.prec.split() and (cap is None or cap in row.caps.split())
+
+
+def tile_ids(family=None, cap=None, x3=None):
+    """Tile ids, ascending: of these families (one name or several), with this capability, with an instance in this precision (None: any)."""
+    fams = None if family is None else (family,) if isinstance(family, str) else tuple(family)
+    return tuple(t for t, r in sorted(TILE_TABLE.items()) if (fams is None or r.family in fams)
+                 and (tile_has(t, cap, x3) if x3 is not None else tile_has(t, cap, False) or tile_has(t, cap, True)))
+
+
+# names older call sites import: one-line views of the table
+X3_TILES = tuple(t for t in tile_ids(("igemm", "persist"), x3=True) if TILE_TABLE[t].bn >= 64)      # conv.hip / convp.hip, split precision, any Cout > 32
+REGEPI_TILES = tile_ids(cap="regepi")
+TILES = {t: (r.bm, r.bn) for t, r in TILE_TABLE.items()}                      # tile id -> (BM, BN)
+TAIL_BN = {t: r.tail_bn for t, r in TILE_TABLE.items() if r.tail_bn}          # tile id -> output channels per chunk of the fused 1x1
+HALO_ROWS = ("halo", "tail", "block")     # families whose 3x3 weights are packed as 128-byte halo rows (pack_halo_rows)
 TAIL_DEFAULT = {}                          # Bottleneck planes -> fused tile id (empty: every block runs c2 and c3 as two launches)
-TAIL_BN = {80: 64, 81: 128, 82: 64, 90: 64, 91: 64, 92: 64, 93: 64, 94: 128}      # output channels per chunk of the fused 1x1 (csrc/convf.hip::smap_convf_tile_dims)
 # Bottleneck planes -> tile id of the WHOLE-block launch (csrc/convb.hip) for stride-1 identity blocks in split precision; {} = off.
 # SMAP_BLOCK="64:91" overrides (A/B hook; "" = off).  BLOCK_FIRST_DEFAULT / SMAP_BLOCK_FIRST="64:93": the same for the first block of
 # layer1 (the one with a shortcut conv; 64 input channels).
@@ -74,8 +121,6 @@ TAIL_BN = {80: 64, 81: 128, 82: 64, 90: 64, 91: 64, 92: 64, 93: 64, 94: 128}    
 # frames/s (+ first blocks); 4 x 16 tiles: 816.
 BLOCK_DEFAULT = {64: 91, 128: 94}       # layer1 (csrc/convb.hip) and layer2 (csrc/convc.hip) identity blocks
 BLOCK_FIRST_DEFAULT = {64: 93}
-# (ids 10..18 belonged to a register-epilogue GEMM that no measured table entry selected; it lives on as an experiment under
-#  tools/experiments/, outside the product build.  ids 40..45 are live: the eight-wave halo tiles of csrc/conv3.hip.)
 
 
 def _tile_remap():
@@ -93,8 +138,6 @@ ALIGN = 256
 ZERO_PAGE = 16384             # csrc/plan.hip SMAP_ZERO_PAGE
 WINDOW = 1 << 32              # csrc/plan.hip SMAP_WINDOW: bytes [k * WINDOW, k * WINDOW + ZERO_PAGE) of the arena are reserved
 PRECISIONS = ("f16", "x3")
-SPLITK_TILES = (2, 7, 20, 22)     # csrc/conv.hip tiles with a split-K instance (smap_conv_tile_has_splitk)
-X3_TILES = (0, 1, 2, 4, 7, 20, 21, 22, 23, 24, 25, 26, 27, 50, 51, 52, 53, 54, 55, 56, 60, 61, 62, 63, 64, 65)   # conv.hip tiles with a split-precision instance (+ 3: Cout <= 32)
 
 
 def split_f16(w, scaled=True):
@@ -120,20 +163,16 @@ def _table_entry(v):
     return [int(t) for t in v] if isinstance(v, (list, tuple)) else [int(v)]
 
 
-REGEPI_TILES = (56,)               # csrc/conv.hip tiles with the register epilogue
-DUAL_TILES = (20, 50, 51, 53, 54)  # csrc/conv.hip tiles with a second-input (K-concatenated) instance (smap_conv_tile_has_dual)
-RELUSUM_TILES = (50, 51, 53, 54)   # ... with a relu(conv) + relu(conv) instance (smap_conv_tile_has_relusum)
-
-
 def tile_legal(tile, *, cout, cout_pad=None, plain3=True, up=False, out_fp32=False, adds=False, x3=True):
     """Can tile id `tile` run an op with these properties?  Mirrors csrc/plan.hip::validate."""
-    if tile in REGEPI_TILES:
+    fam = tile_family(tile)
+    if tile_has(tile, "regepi", True):
         return x3 and not up and not out_fp32 and not adds and cout % 8 == 0
-    if 30 <= tile < 50:
+    if fam == "halo":
         return plain3
-    if 80 <= tile < 100:
+    if fam in ("tail", "block"):
         return False                     # only Graph.conv_tail / Graph.conv_block build these
-    if 60 <= tile < 80:
+    if fam == "persist":
         cp = cout_pad if cout_pad is not None else _rup(cout, TILES[tile][1])
         return not up and not out_fp32 and cout % 8 == 0 and cp <= 2048
     return True
@@ -172,26 +211,6 @@ def pick_tile_x3(M, cout, key=None):
     return cands + [best]
 
 
-def tile_family(tile):
-    """Which kernel a tile id selects: "halo" (csrc/conv3.hip; csrc/convf.hip = the same 3x3 with a fused 1x1 tail),
-    "persist" (csrc/convp.hip) or "igemm" (csrc/conv.hip)."""
-    return "halo" if (30 <= tile < 50 or 80 <= tile < 100) else "persist" if 60 <= tile < 80 else "igemm"
-
-
-def tile_bk(tile, x3):
-    """Halves per K chunk of the LDS rows a tile id stages (csrc/conv.hip::smap_launch_conv, csrc/convp.hip; the C side exports
-    the same table as smap_conv_tile_bk, tests/test_host_cpu.py keeps the two in step).  The halo kernel's rows are always
-    128 bytes: 64 channels, or [hi32 | lo32] of 32 channels in split precision."""
-    fam = tile_family(tile)
-    if fam == "halo":
-        return 32 if x3 else 64
-    if fam == "persist":
-        return 32
-    if x3:
-        return 64 if tile in (0, 1, 2, 3, 4, 7, 52) else 32
-    return 32 if tile in (20, 21, 22, 23, 24, 25, 26, 27, 50, 51, 53, 54, 55) else 64
-
-
 # 32-half K tiles of the packed weights are stored in PAIRS (128-byte rows [tile 2p | tile 2p+1]) for SMALL schedules (<= 2 frames of
 # 512x832 worth of pixels): every launch of those is latency-bound and lives on the L1 hit the second half of each fetched line
 # gives the next K tile (batch 1: 226 vs 195 frames/s); larger schedules are bandwidth-bound and prefer one contiguous block
@@ -228,7 +247,7 @@ def pack_conv_weights(w2, tile, x3, ksize, cin, pairs=True):
     nt = cout_pad // bn
     assert nt * bn == cout_pad
     r = torch.arange(bn)
-    if tile_family(tile) == "halo":
+    if tile_family(tile) in HALO_ROWS:
         assert ksize == 3
         return pack_halo_rows(w2, bn, 9, cin, x3)
     bk = tile_bk(tile, x3)
@@ -399,9 +418,6 @@ def pick_tile(M, cout, key=None):
     return pick_tile_heuristic(M, cout)
 
 
-DEFAULT_REMAP = {}
-
-
 class ArenaTooLarge(ValueError):
     """The schedule does not fit: ONE activation tensor exceeds a 4 GiB window (the conv kernels address their input with 32-bit
     byte offsets from a 4 GiB-aligned base, csrc/plan.hip: 52 frames of the widest split-precision tensor), or the whole arena
@@ -500,7 +516,7 @@ class Graph:
         and 16x26 levels run 26-104 workgroups of 16-72 K tiles each there.  SMAP_SPLITK=0 switches it off, SMAP_SPLITK=<n> forces n
         parts wherever the tile allows."""
         env = os.environ.get("SMAP_SPLITK", "")
-        if env == "0" or tile not in SPLITK_TILES:
+        if env == "0" or not tile_has(tile, "splitk", self.x3):
             return 1
         bm, bn = TILES[tile]
         tiles = -(-M // bm) * (cout_pad // bn)
@@ -571,7 +587,7 @@ class Graph:
             tile = _tile_remap().get(tile, tile)             # A/B hook (SMAP_TILE_REMAP="2:7"): same tile shape, other pipeline depth
         else:
             tile = pick_tile(M, cout, key)
-            tile = {**DEFAULT_REMAP, **_tile_remap()}.get(tile, tile)
+            tile = _tile_remap().get(tile, tile)
             if not legal(tile):                                 # the table is keyed by shape only
                 tile = pick_tile_heuristic(M, cout)
         halo = os.environ.get("SMAP_HALO3", "")     # A/B hook: "16" / "32" = pixel-tile width, optional ":64" / ":128" = BN
@@ -627,8 +643,8 @@ class Graph:
             # per 128-channel N tile) 860-864 frames/s against 847 with the 128 x 128 tiles; the K-concatenated launches (conv_cat) do not care
             cands = (pick_tile_x3(M, cout, key) if self.x3 else []) + [54, 53, 50, 51]
             forced = os.environ.get("SMAP_RELUSUM_TILE", "")                     # A/B hook
-            tile = int(forced) if forced else next(t for t in cands if t in RELUSUM_TILES)
-        assert tile in RELUSUM_TILES, tile
+            tile = int(forced) if forced else next(t for t in cands if tile_has(t, "relusum", self.x3))
+        assert tile_has(tile, "relusum", self.x3), tile
         bn = TILES[tile][1]
         cout_pad = _rup(cout, bn)
         sc1 = sc2 = 1.0
@@ -668,7 +684,7 @@ class Graph:
         w3, b3 = fold_conv_bn(self.sd, pre3)
         cout, cin = w1.shape[0], w1.shape[1]
         assert cout == 256 == w3.shape[1] and w3.shape[0] == 1 and w3.shape[2] == 3 and cin == x.C and w1.shape[2] == 1
-        tile = 54
+        tile = tile_ids(cap="tapdot", x3=self.x3)[0]
         nfr = self.B if frames is None else frames
         M = nfr * x.H * x.W
         acc_scale = 1.0
@@ -722,8 +738,8 @@ class Graph:
             key = f"{self.B},{Ho},{Wo},{c1}+{c2}cat,{cout},1,1"
             cands = (pick_tile_x3(M, cout, key) if self.x3 else []) + [50, 51, 20]
             forced = os.environ.get("SMAP_CAT_TILE", "")                         # A/B hook
-            tile = int(forced) if forced else next(t for t in cands if t in DUAL_TILES)
-        assert tile in DUAL_TILES, tile
+            tile = int(forced) if forced else next(t for t in cands if tile_has(t, "dual", self.x3))
+        assert tile_has(tile, "dual", self.x3), tile
         bn = TILES[tile][1]
         cout_pad = _rup(cout, bn)
         w = torch.cat([w1.reshape(cout, c1), w2.reshape(cout, c2)], 1)           # [cout][K = (x channels | x2 channels)]
@@ -772,8 +788,8 @@ class Graph:
         # widest conv alone (same input, same K: the nearest measured relative)
         key = f"{self.B},{x.H},{x.W},{cin},{'+'.join(map(str, couts))},1,1"
         wide = f"{self.B},{x.H},{x.W},{cin},{max(couts)},1,1"
-        legal = lambda t: (tile_family(t) == "igemm" and (t in X3_TILES or not self.x3) and t not in (3, 8)
-                           and (t not in REGEPI_TILES or (self.x3 and up is None)))
+        legal = lambda t: (tile_family(t) == "igemm" and tile_has(t, None, self.x3) and TILES[t][1] >= 64       # (not the Cout <= 32 tiles)
+                           and (not tile_has(t, "regepi", True) or (self.x3 and up is None)))
         if tile is not None:
             assert legal(tile), tile
         elif self.x3:
@@ -829,7 +845,7 @@ class Graph:
 
     def conv_tail(self, name, pre3, pre1, x, tile, res=None, add1=None, add2=None):
         """A Bottleneck's 3x3 stride-1 conv (prefix pre3, bias + ReLU) and the 1x1 behind it (prefix pre1, + res, ReLU, + add1,
-        + add2) as ONE launch (csrc/convf.hip, tile ids 80..89): the 3x3's output never leaves the CU."""
+        + add2) as ONE launch (csrc/convf.hip, the "tail" tile ids): the 3x3's output never leaves the CU."""
         w3, b3 = fold_conv_bn(self.sd, pre3)
         w1, b1 = fold_conv_bn(self.sd, pre1)
         P, cin = w3.shape[0], w3.shape[1]
@@ -873,7 +889,7 @@ class Graph:
 
     def conv_block_first(self, name, pre, x, tile):
         """The FIRST Bottleneck of layer1 (smap.py:48-77 with the 1x1 shortcut conv of :124-129; 64 input channels, stride 1) as ONE
-        launch (csrc/convb.hip, tile ids 92, 93): relu(c3(c2(c1(x))) + downsample(x)); x is read once."""
+        launch (csrc/convb.hip, the "block" tile ids with first = True): relu(c3(c2(c1(x))) + downsample(x)); x is read once."""
         assert self.x3
         w1, b1 = fold_conv_bn(self.sd, pre + ".conv_bn_relu1")
         w3, b3 = fold_conv_bn(self.sd, pre + ".conv_bn_relu2")
@@ -911,7 +927,7 @@ class Graph:
 
     def conv_block(self, name, pre, x, tile, add1=None, add2=None):
         """A whole stride-1 identity Bottleneck (smap.py:48-77: conv_bn_relu1 1x1 -> conv_bn_relu2 3x3 -> conv_bn_relu3 1x1, + x,
-        ReLU, + add1, + add2) as ONE launch (csrc/convb.hip, tile ids 90..99, split precision): x is read once, the two
+        ReLU, + add1, + add2) as ONE launch (csrc/convb.hip / convc.hip, the "block" tile ids, split precision): x is read once, the two
         intermediates and the residual never leave the CU."""
         assert self.x3, "the whole-block kernel has a split-precision instance only"
         w1, b1 = fold_conv_bn(self.sd, pre + ".conv_bn_relu1")
@@ -920,7 +936,7 @@ class Graph:
         P, C = w1.shape[0], w1.shape[1]
         bn2 = TAIL_BN[tile]
         assert P == TILES[tile][1] and C == 4 * P == x.C == wt.shape[0] and w3.shape[:2] == (P, P) and w3.shape[2] == 3 and wt.shape[1] == P
-        assert (P == 128) == (tile == 94) and P in (64, 128)
+        assert tile_family(tile) == "block" and not TILE_TABLE[tile].first and P == TILE_TABLE[tile].planes
         M = self.B * x.H * x.W
         hi, lo, sc1 = split_f16(w1.reshape(P, C))
         if P == 64:

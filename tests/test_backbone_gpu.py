@@ -57,10 +57,10 @@ def _run_single_conv(B, H, W, Cin, Cout, k, stride, tile, relu, use_res, use_add
     else:
         wk = torch.zeros(1, cout_pad, K, dtype=torch.float16)
         wk[0, :Cout] = w.permute(0, 2, 3, 1).reshape(Cout, K)
-    from smap_amd.engine import pack_conv_weights, tile_family
+    from smap_amd.engine import HALO_ROWS, pack_conv_weights, tile_family
     if w_pairs is None:
         w_pairs = seed % 2                                 # both layouts of the 32-half K tiles get exercised
-    if tile in TILES and not (tile_family(tile) == "halo" and k != 3):     # (ops the plan must reject keep any bytes)
+    if tile in TILES and not (tile_family(tile) in HALO_ROWS and k != 3):     # (ops the plan must reject keep any bytes)
         wk = pack_conv_weights(wk, tile, x3, k, Cin, pairs=w_pairs)   # weight tiles as contiguous, pre-swizzled blocks (the conv ABI)
     bk = torch.zeros(cout_pad)
     bk[:Cout] = bias
@@ -512,7 +512,8 @@ TAIL_CASES = [
 
 
 def _run_block(B, H, W, tile, use_adds, seed=0, mode="full", relu=True, check=True):
-    if tile in (92, 93):
+    from smap_amd.engine import TILE_TABLE
+    if TILE_TABLE[tile].first:
         return _run_block_first(B, H, W, tile, seed=seed, mode=mode, check=check)
     """One whole-Bottleneck op (csrc/convb.hip, split precision): relu(W3 relu(W2 * relu(W1 x + b1) + b2) + b3 + x) [+ adds],
     P = 64 planes, C = 256 channels.  `mode` switches parts of the block off so that a failure names the phase
@@ -521,7 +522,7 @@ def _run_block(B, H, W, tile, use_adds, seed=0, mode="full", relu=True, check=Tr
     from smap_amd import lib as L
     from smap_amd.engine import TAIL_BN, ZERO_PAGE, pack_halo_rows, pack_rows16, split_f16
     lib = L.load()
-    P, Cc = (128, 512) if tile == 94 else (64, 256)           # 94: csrc/convc.hip (layer2's width)
+    P, Cc = TILE_TABLE[tile].planes, 4 * TILE_TABLE[tile].planes      # 128 planes: csrc/convc.hip (layer2's width)
     g = torch.Generator().manual_seed(seed)
     x = torch.randn(B, H, W, Cc, generator=g)
     w1 = torch.randn(P, Cc, 1, 1, generator=g) * (1.0 / Cc) ** 0.5
@@ -860,8 +861,8 @@ def test_small_schedule_split_precision_every_tensor(golden_dir, small, monkeypa
     z = np.load(f"{golden_dir}/backbone_small.npz")
     x = torch.from_numpy(z["x"])
     eng = BackboneEngine(sd, 2, 64, 96, DEV, reuse=False, precision="x3")
-    from smap_amd.engine import X3_TILES
-    assert all(op.p["tile"] in X3_TILES + (3,) + tuple(range(30, 46)) for op in eng.graph.ops if op.kind == 0)
+    from smap_amd.engine import tile_ids
+    assert all(op.p["tile"] in tile_ids(("igemm", "halo", "persist"), x3=True) for op in eng.graph.ops if op.kind == 0)
     outs = [o.cpu() for o in eng.run(x.to(DEV))]
     torch.cuda.synchronize()
     g = Graph(sd, 2, 64, 96, keep_ref=True)
@@ -1083,7 +1084,7 @@ def test_merged_1x1_launch_matches_torch(case, x3):
     from smap_amd import engine as E
     from smap_amd import lib as L
     B, H, W, cin, couts, relus, up, tile, w_pairs = (case + (1,))[:9]
-    if tile in E.REGEPI_TILES and not x3:
+    if E.tile_has(tile, "regepi", True) and not x3:
         pytest.skip("the register-epilogue tile has a split-precision instance only")
     gen = torch.Generator().manual_seed(sum(case[:4]) + tile)
     sd, segs = {}, []

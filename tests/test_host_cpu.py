@@ -39,7 +39,7 @@ def test_split_f16_reconstructs_to_22_bits():
 
 @pytest.mark.parametrize("blocks", [False, True], ids=["layer_by_layer", "whole_blocks"])
 def test_x3_graph_emits_split_strides_and_weights(small_sd, monkeypatch, blocks):
-    from smap_amd.engine import Graph, OP_CONV, OP_HEADSUM, OP_MAXPOOL, OP_STEM, X3_TILES, ZERO_PAGE
+    from smap_amd.engine import Graph, OP_CONV, OP_HEADSUM, OP_MAXPOOL, OP_STEM, ZERO_PAGE, tile_ids
     if not blocks:                      # the layer-by-layer schedule: op for op the fp16 one (the default fuses layer1's Bottlenecks)
         monkeypatch.setenv("SMAP_BLOCK", "")
         monkeypatch.setenv("SMAP_BLOCK_FIRST", "")
@@ -66,7 +66,7 @@ def test_x3_graph_emits_split_strides_and_weights(small_sd, monkeypatch, blocks)
         if op.kind == OP_CONV:
             x, y = op.inp, op.out
             assert x.planes == 2 and o.in_stride_c == 2 * x.C and o.in_c_off + o.Cin <= x.C
-            assert o.tile in X3_TILES + (3,) + tuple(range(30, 46)) + (90, 91, 92, 93, 94) and o.acc_scale > 0
+            assert o.tile in tile_ids(("igemm", "halo", "persist", "block"), x3=True) and o.acc_scale > 0
             assert (y.planes, o.out_stride_c) == ((1, y.C) if o.out_fp32 else (2, 2 * y.C))
             assert o.in_off >= ZERO_PAGE and o.Cin * 2 + o.in_stride_c + 16 <= ZERO_PAGE
             for t in (op.res, op.add1, op.add2):
@@ -154,11 +154,11 @@ def test_shipped_launcher_settings_are_plannable():
 
 
 def test_tile_tables_name_existing_tiles():
-    from smap_amd.engine import TILES, X3_TILES, _table_entry, tile_family
+    from smap_amd.engine import TILES, _table_entry, tile_family, tile_has, tile_ids
     t16 = json.load(open(os.path.join(ROOT, "smap_amd", "tile_table.json")))
     tx3 = json.load(open(os.path.join(ROOT, "smap_amd", "tile_table_x3.json")))
     assert t16 and all(t in TILES for v in t16.values() for t in _table_entry(v))
-    assert tx3 and all(t in X3_TILES + (3,) + tuple(range(30, 46)) for v in tx3.values() for t in _table_entry(v))
+    assert tx3 and all(t in tile_ids(("igemm", "halo", "persist"), x3=True) for v in tx3.values() for t in _table_entry(v))
     for key, v in tx3.items():
         f = key.split(",")                                                   # optional 8th field: "up" (ops with a fused bilinear add)
         merged = "+" in f[4]                                                 # "c0+c1[+c2]": a merged 1x1 launch (Graph.conv_seg, tools/autotune_seg.py)
@@ -167,13 +167,13 @@ def test_tile_tables_name_existing_tiles():
         assert f[7:] in ([], ["up"])
         assert not merged or (k == 1 and s == 1 and all(tile_family(t) == "igemm" for t in _table_entry(v)))
         for t in _table_entry(v):
-            assert B in (1, 8, 16) and (t < 30 or t >= 40 or (k == 3 and s == 1))   # (1 = configs[1], 16 = the flip-TTA schedule of batch 8); halo tiles: plain 3x3 stride 1 only
-            assert cout > 32 or t in (3, 38, 39)
-        assert not 60 <= _table_entry(v)[-1] < 80                            # a ranked list ends on a tile that takes every op
+            assert B in (1, 8, 16) and (tile_family(t) != "halo" or (k == 3 and s == 1))   # (1 = configs[1], 16 = the flip-TTA schedule of batch 8); halo tiles: plain 3x3 stride 1 only
+            assert cout > 32 or (TILES[t][1] == 32 and tile_has(t, None, True))      # the Cout <= 32 tiles: 3, 38, 39
+        assert tile_family(_table_entry(v)[-1]) != "persist"                         # a ranked list ends on a tile that takes every op
 
 
 def test_tile_geometry_tables_agree_with_the_library():
-    """engine.py packs the weight blob per tile (BN rows x BK halves blocks); the kernels' template arguments are the truth."""
+    """engine.py packs the weight blob per tile (BN rows x BK halves blocks); the kernels' template arguments (csrc/tiles.h) are the truth."""
     import ctypes as C
     from smap_amd import lib as L
     from smap_amd.engine import TILES, tile_bk
@@ -190,6 +190,81 @@ def test_tile_geometry_tables_agree_with_the_library():
                 assert lib.smap_conv_tile_bk(t, prec) == tile_bk(t, bool(prec)), (t, prec)
         else:
             assert lib.smap_conv_tile_bk(t, 0) == 0
+
+
+def _capability_probe(tile, x3, variant):
+    """The smallest CONV op that csrc/plan.hip::validate can only refuse for what tile id `tile` is: laid out from the PYTHON table's row
+    (unknown ids: as a 1x1 on a 128 x 64 tile), 1 frame of 8 x 8 pixels, every tensor a MiB apart inside the first window.
+    variant: "plain", "fp32out", "splitk" (ksplit = 2), "dual" (in2_C), "relusum" (in2_mode = 1), "segments" (two N segments), "tapdot"."""
+    from smap_amd import lib as L
+    from smap_amd.engine import TILE_TABLE, Tile
+    row = TILE_TABLE.get(tile, Tile("igemm", 128, 64, 64, 64))
+    MiB, pl = 1 << 20, 2 if x3 else 1
+    o = L.SmapOp()
+    o.kind, o.B, o.H, o.W, o.Ho, o.Wo, o.tile, o.precision, o.acc_scale, o.relu = 0, 1, 8, 8, 8, 8, tile, int(x3), 1.0, 1
+    o.in_off, o.out_off, o.w_off, o.bias_off, o.res_off, o.add1_off, o.add2_off, o.ext_off = 1 * MiB, 2 * MiB, 0, 0, -1, -1, -1, -1
+    for i in range(3):
+        o.aux_off[i] = -1
+    if row.family in ("igemm", "persist"):                 # a 1x1, 256 -> 256 channels (every N extent divides 256; four K tiles of 64 halves)
+        o.ksize, o.stride, o.pad, o.Cin, o.Cout, o.cout_pad = 1, 1, 0, 256, 256, 256
+    else:                                                  # a plain 3x3 on 64 channels, one N tile
+        o.ksize, o.stride, o.pad, o.Cin, o.Cout, o.cout_pad = 3, 1, 1, max(64, row.planes), row.bn, row.bn
+    o.in_stride_c, o.out_stride_c = o.Cin * pl, o.Cout * pl
+    if row.tail_bn:                                        # "tail" / "block": the fused 1x1 behind the 3x3, 4 x its planes
+        o.tail_cout = o.tail_cout_pad = 4 * row.bn
+        o.tail_w_off, o.tail_bias_off, o.tail_acc_scale, o.out_stride_c = 0, 0, 1.0, 4 * row.bn * pl
+    if row.family == "block":                              # (split precision only: the layout is the split one in both probes)
+        o.head_cin = row.planes if row.first else 4 * row.planes
+        o.in_stride_c, o.out_stride_c, o.head_w_off, o.head_bias_off, o.head_acc_scale = 2 * o.head_cin, 8 * row.planes, 0, 0, 1.0
+        if row.first:
+            o.short_w_off, o.short_acc_scale = 0, 1.0
+        else:
+            o.res_off = o.in_off
+    if variant == "fp32out":
+        o.out_fp32, o.out_stride_c = 1, o.out_stride_c // pl
+    elif variant == "splitk":
+        o.ksplit, o.kpart_off, o.kcount_off = 2, 32 * MiB, 48 * MiB
+    elif variant in ("dual", "relusum"):
+        o.in2_C, o.in2_stride, o.in2_H, o.in2_W, o.in2_stride_c, o.in2_off = 64, 1, 8, 8, 64 * pl, 3 * MiB
+        if variant == "relusum":
+            o.in2_mode, o.relu, o.in2_bias_off, o.in2_acc_scale = 1, 0, 0, 1.0
+    elif variant == "segments":                            # two N tiles, one segment each
+        o.Cout, o.cout_pad, o.out_stride_c = row.bn, 2 * row.bn, row.bn * pl
+        o.seg_n[0], o.seg_cout[0], o.seg_out_stride_c[0], o.seg_acc_scale[0], o.seg_out_off[0] = row.bn, row.bn, row.bn * pl, 1.0, 4 * MiB
+    elif variant == "tapdot":
+        o.tap_n, o.out_fp32, o.out_stride_c, o.tap_w_off, o.tap_scale = 9, 1, 16, 0, 1.0
+    else:
+        assert variant == "plain"
+    return o
+
+
+def test_tile_capabilities_agree_with_what_the_plan_accepts():
+    """The facts of a tile id that no ABI function exports -- which precisions it has an instance in, its kernel family, split K, second
+    input, relu-sum, register epilogue, tap-dot, the planes / first-block flag of a whole-block tile -- compared through
+    csrc/plan.hip::validate: for every id 0..99 and both precisions, smap_plan_create accepts a minimal op that needs the fact exactly
+    when the Python table (smap_amd/engine.py TILE_TABLE) says the id has it.  Plan creation touches no GPU."""
+    import ctypes as C
+    from smap_amd import lib as L
+    from smap_amd.engine import TILE_TABLE, tile_family, tile_has
+    lib = L.load()
+    want = {"plain": lambda t, x3: True,
+            "fp32out": lambda t, x3: tile_family(t) in ("igemm", "halo") and not tile_has(t, "regepi", x3),
+            "splitk": lambda t, x3: tile_has(t, "splitk", x3),
+            "dual": lambda t, x3: tile_has(t, "dual", x3),
+            "relusum": lambda t, x3: tile_has(t, "relusum", x3),
+            "segments": lambda t, x3: tile_family(t) == "igemm",
+            "tapdot": lambda t, x3: tile_has(t, "tapdot", x3)}
+    accepted = 0
+    for t in range(100):
+        for x3 in (False, True):
+            for variant, rule in want.items():
+                o, h = _capability_probe(t, x3, variant), C.c_void_p()
+                rc = lib.smap_plan_create(C.byref(o), 1, C.byref(h))
+                if rc == 0:
+                    lib.smap_plan_destroy(h)
+                assert (rc == 0) == (tile_has(t, None, x3) and rule(t, x3)), (t, "x3" if x3 else "f16", variant, rc)
+                accepted += rc == 0
+    assert accepted > 2 * len(TILE_TABLE)                  # (the probes are legal ops: most ids take the plain one in both precisions)
 
 
 def test_weight_packing_is_a_permutation_and_inverts():
@@ -434,7 +509,7 @@ def test_batch_1_schedule_rules_and_arena(monkeypatch):
     op of another lane and nothing a side-lane op touches is reused before the end of the schedule."""
     import ctypes as C
     from smap_amd import lib as L
-    from smap_amd.engine import Graph, OP_CONV, TILES, tile_bk
+    from smap_amd.engine import Graph, OP_CONV, TILES, tile_bk, tile_family
     sd = _full_size_sd()
     for k in ("SMAP_CAT", "SMAP_SKIPSUM", "SMAP_TAPHEAD"):          # (conftest forces round 6's launches on for the small TEST schedules; this is the real batch-1 rule)
         monkeypatch.delenv(k, raising=False)
@@ -444,7 +519,7 @@ def test_batch_1_schedule_rules_and_arena(monkeypatch):
         g.allocate()
         ops = g.emit()
         convs = [(op, o) for op, o in zip(g.ops, ops) if op.kind == OP_CONV]
-        assert sorted({op.p["tile"] for op, _ in convs if op.p["tile"] >= 90}) == [90, 92]              # layer1: 4 x 16 tiles; no tile 94
+        assert sorted({op.p["tile"] for op, _ in convs if tile_family(op.p["tile"]) in ("tail", "block")}) == [90, 92]              # layer1: 4 x 16 tiles; no tile 94
         split = [(op, o) for op, o in convs if o.ksplit > 1]
         assert 30 <= len(split) <= 40
         tickets = set()
@@ -541,7 +616,7 @@ def _signature(precision, tile, ksize, stride, relu, res, adds, up, out_fp32, ks
     """What decides which code a conv launch runs.  w_pairs only changes the layout of 32-half K tiles (smap_op.w_pairs): 0 elsewhere."""
     from smap_amd.engine import tile_bk, tile_family
     x3 = precision == "x3"
-    wp = int(bool(w_pairs)) if (tile_family(tile) != "halo" and tile < 80 and tile_bk(tile, x3) == 32) else 0
+    wp = int(bool(w_pairs)) if (tile_family(tile) in ("igemm", "persist") and tile_bk(tile, x3) == 32) else 0
     return (precision, int(tile), int(ksize), int(stride), int(bool(relu)), bool(res), bool(adds), bool(up), int(bool(out_fp32)),
             ksplit > 1, wp, int(segments), in2, bool(tap), fused)
 
@@ -557,7 +632,7 @@ def launch_signature(g, op):
 
 def unit_case_signatures(T):
     """The signatures the unit cases of tests/test_backbone_gpu.py (module T) run, derived from its case lists as its tests run them."""
-    from smap_amd.engine import REGEPI_TILES
+    from smap_amd.engine import TILE_TABLE, tile_has, tile_ids
     cov = set()
     for cases, prec in ((T.CASES, "f16"), (T.X3_CASES, "x3")):      # _run_single_conv(*case, seed=hash(case) % 1000): w_pairs = seed % 2
         for c in cases:
@@ -572,12 +647,12 @@ def unit_case_signatures(T):
         for pr in ("f16", "x3"):
             cov.add(_signature(pr, tile, 3, 1, relu, res, adds, None, 0, 1, 0, fused="tail"))
     for _, _, _, tile, adds in T.BLOCK_CASES:                       # split precision only; the first block's shortcut replaces the residual
-        first = tile in (92, 93)
+        first = TILE_TABLE[tile].first
         cov.add(_signature("x3", tile, 3, 1, 1, not first, adds, None, 0, 1, 0, fused="block_first" if first else "block"))
     for c in T.SEG_CASES:
         _, _, _, _, couts, relus, up, tile, w_pairs = (c + (1,))[:9]
         for pr in ("f16", "x3"):
-            if pr == "x3" or tile not in REGEPI_TILES:
+            if pr == "x3" or not tile_has(tile, "regepi", True):
                 cov.add(_signature(pr, tile, 1, 1, relus[0], False, False, up, 0, 1, w_pairs, segments=len(couts) - 1))
     for c in T.CAT_CASES:                                             # w_pairs = (B == 1) in these harnesses
         for pr in ("f16", "x3"):
@@ -587,7 +662,7 @@ def unit_case_signatures(T):
             cov.add(_signature(pr, c[6], 1, 1, 0, False, False, None, 0, 1, c[0] == 1, in2="relusum"))
     for B, _, _ in getattr(T, "TAP_SHAPES", []):
         for pr in ("f16", "x3"):
-            cov.add(_signature(pr, 54, 1, 1, 1, False, False, None, 1, 1, B == 1, tap=True))
+            cov.add(_signature(pr, tile_ids(cap="tapdot")[0], 1, 1, 1, False, False, None, 1, 1, B == 1, tap=True))
     return cov
 
 

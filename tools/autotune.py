@@ -82,11 +82,13 @@ def main():
             cands = [t for t, (bm, bn) in TILES.items() if bn >= 64]
         cands = [t for t in cands if t < 30 or (halo_ok and t < 40)]
         if x3:
-            from smap_amd.engine import X3_TILES
-            cands = [3] if Cout <= 32 else [t for t in X3_TILES if not (Cout <= 64 and TILES[t][1] > 64) and t not in (66, 68)
-                                            and not (Cout > 64 and TILES[t][1] == 64 and t >= 60)]
-            if halo_ok:      # halo-tiled 3x3 kernel has split-precision instances too
-                cands += [38, 39] if Cout <= 32 else [t for t in range(30, 38) if not (Cout <= 64 and TILES[t][1] > 64)]
+            from smap_amd.engine import tile_family, tile_ids
+            cands = [3] if Cout <= 32 else [t for t in tile_ids(("igemm", "persist"), x3=True) if TILES[t][1] >= 64
+                                            and not (Cout <= 64 and TILES[t][1] > 64)
+                                            and not (Cout > 64 and TILES[t][1] == 64 and tile_family(t) == "persist")]
+            if halo_ok:      # halo-tiled 3x3 kernel has split-precision instances too (the four-wave tiles: ids below 40)
+                cands += [t for t in tile_ids("halo", x3=True) if t < 40 and (TILES[t][1] == 32 if Cout <= 32 else
+                                                                             TILES[t][1] >= 64 and not (Cout <= 64 and TILES[t][1] > 64))]
         if args.halo:
             cands = [old[skey]] + [t for t in cands if t >= 30] + ([40, 41] if ws_ok else [])
         if convp:

@@ -71,7 +71,7 @@ def main():
             seen[key] = [1, (op.inp.H, op.inp.W, op.inp.C), segs, up_shape, op.p["tile"]]
         for key, (count, x_shape, segs, up_shape, cur) in seen.items():
             res = {}
-            for t in [t for t in E.X3_TILES if E.tile_family(t) == "igemm" and t != 3]:
+            for t in [t for t in E.tile_ids("igemm", x3=True) if E.TILES[t][1] >= 64]:
                 try:
                     g = single_op_graph(sd, B, x_shape, segs, up_shape, t)
                     ops = g.emit()

@@ -15,7 +15,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 import torch  # noqa: E402
 from smap_amd import lib as L  # noqa: E402
-from smap_amd.engine import TILES, _table_entry  # noqa: E402
+from smap_amd.engine import TILES, _table_entry, tile_ids  # noqa: E402
 from bench_conv import build  # noqa: E402
 
 SHAPES = [(64, 104, 128, 128), (32, 52, 256, 256), (16, 26, 512, 512), (128, 208, 256, 43), (64, 104, 256, 43), (32, 52, 256, 43),
@@ -39,7 +39,7 @@ def main():
     for H, W, Cin, Cout in shapes:
         key = f"{args.batch},{H},{W},{Cin},{Cout},3,1"
         shipped = _table_entry(table[key])[:2] if key in table else []
-        new = [t for t in (40, 41, 42, 43, 44, 45) if not (Cout <= 64 and TILES[t][1] > 64) and not (Cout > 64 and TILES[t][1] == 64)]
+        new = [t for t in tile_ids("halo") if t >= 40 and not (Cout <= 64 and TILES[t][1] > 64) and not (Cout > 64 and TILES[t][1] == 64)]
         res = {}
         cands = shipped + [t for t in (31, 35, 34, 36, 52, 60) if t not in shipped and not (Cout <= 64 and TILES[t][1] > 64)
                            and not (Cout > 64 and TILES[t][1] == 64)] + new

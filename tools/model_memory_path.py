@@ -24,7 +24,7 @@ def main():
     B = int(sys.argv[2]) if len(sys.argv) > 2 else 8
     import torch
     from types import SimpleNamespace as NS
-    from smap_amd.engine import Graph, OP_CONV, TILES, tile_family
+    from smap_amd.engine import Graph, HALO_ROWS, OP_CONV, TILES, tile_family
     from smap_amd.model.smap import SMAP
     cfg = NS(MODEL=NS(STAGE_NUM=3, UPSAMPLE_CHANNEL_NUM=256), DATASET=NS(KEYPOINT=NS(NUM=15), PAF=NS(NUM=14)),
              OUTPUT_SHAPE=(128, 208), LOSS=NS(OHKM=True, TOPK=8, COARSE_TO_FINE=True))
@@ -60,13 +60,13 @@ def main():
         flops = p.get("flops", 2.0 * M * cout * K)
         if p.get("kinds") == "block":              # whole Bottleneck (convb / convc): x patch with halo once, every weight of the block per workgroup
             hc = p["head"]["cin"]
-            th, tw = (4, 16) if tile in (90, 92) else (8, 16)
+            th, tw = TILES[tile][0] // 16, 16
             wgs = -(-y.W // tw) * -(-y.H // th) * nfr
             wall = (cin * hc + 9 * cin * cin + y.C * cin + (y.C * hc if "short" in p else 0)) * 2 * planes
             inb = nfr * x.H * x.W * hc * 2 * planes
             fabric = inb + extra - (op.res.nbytes if op.res is not None else 0) + wall * min(8, wgs)    # the residual IS the input: read once
             l2lds = wgs * ((th + 2) * (tw + 2) * hc * 2 * planes + wall)
-        elif tile_family(tile) == "halo":
+        elif tile_family(tile) in HALO_ROWS:
             tw = 16 if tile in (30, 31, 34, 35, 38) else 32
             th = 128 // tw
             prow = -(-((th + 2) * (tw + 2)) // 32) * 32
