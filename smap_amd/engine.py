@@ -123,6 +123,12 @@ BLOCK_DEFAULT = {64: 91, 128: 94}       # layer1 (csrc/convb.hip) and layer2 (cs
 BLOCK_FIRST_DEFAULT = {64: 93}
 
 
+def _planes_table(env, default):
+    """SMAP_BLOCK / SMAP_BLOCK_FIRST / SMAP_TAIL="64:91,128:94": Bottleneck planes -> tile id (A/B hooks, "" = none); unset: `default`."""
+    spec = os.environ.get(env)
+    return default if spec is None else {int(k): int(v) for k, v in (kv.split(":") for kv in spec.split(",") if ":" in kv)}
+
+
 def _tile_remap():
     """SMAP_TILE_REMAP="0:5,1:6" swaps tile variants without touching the schedule (A/B runs)."""
     out = {}
@@ -224,9 +230,9 @@ def use_lanes(frames, H, W):
     return int(os.environ.get("SMAP_LANES", "0") == "1")
 
 
-def use_w_pairs(frames, H, W):
+def use_w_pairs(small):
     forced = os.environ.get("SMAP_WPAIRS", "")
-    return int(forced) if forced in ("0", "1") else int(frames * H * W <= 2 * 512 * 832)
+    return int(forced) if forced in ("0", "1") else int(small)
 
 
 def pack_conv_weights(w2, tile, x3, ksize, cin, pairs=True):
@@ -464,7 +470,7 @@ class Graph:
             B = 2 * B                         # frames of every activation tensor
         assert not build or (H % 32 == 0 and W % 32 == 0), "input must be a multiple of 32 (5 stride-2 levels)"
         self.sd, self.B, self.H, self.W = sd, B, H, W
-        self.w_pairs = use_w_pairs(B, H, W)                  # layout of the packed 32-half weight tiles (whole schedule)
+        self.w_pairs = use_w_pairs(self.small)               # layout of the packed 32-half weight tiles (whole schedule)
         self.lanes = use_lanes(B, H, W)                      # head chains on forked streams (BackboneEngine switches the plan's lanes on)
         self.cur_lane = 0                                    # lane of the ops being appended (Graph.on_lane)
         self.ops, self.tensors = [], []
@@ -559,6 +565,69 @@ class Graph:
         self.woff = _rup(off + raw.numel(), ALIGN)
         return off
 
+    # -- what every conv emitter below shares
+    @property
+    def small(self):
+        """A SMALL schedule: at most 2 frames of 512x832 worth of pixels (batch 1).  Its launches are latency-bound: split K, the deep-pipeline
+        64 x 64 tile and paired weight tiles instead of the two-input launches and the widest whole-block tiles."""
+        return self.B * self.H * self.W <= 2 * 512 * 832
+
+    @property
+    def one_window(self):
+        """Does the reusing arena fit ONE 4 GiB window?  Both inputs of a two-input launch are addressed from one base (allocate)."""
+        return self.B * self.H * self.W <= 20 * 512 * 832
+
+    def _weights(self, name, rows, cout_pad=None):
+        """[cout][K] folded rows -> (wk [planes][cout_pad][K] fp16 with zero rows behind cout, acc_scale).  Split precision: hi | lo of
+        rows * 2^s and 2^-s (split_f16: ONE scale per call, and its assertion that they are finite); fp16: the cast and 1.0, weights beyond
+        fp16's range are an error of op `name`."""
+        cout, K = rows.shape
+        wk = torch.zeros((2 if self.x3 else 1, cout_pad or cout, K), dtype=torch.float16)
+        acc_scale = 1.0
+        if self.x3:
+            wk[0, :cout], wk[1, :cout], acc_scale = split_f16(rows)
+        else:
+            wk[0, :cout] = rows.to(torch.float16)
+            self._check_fp16(name, wk, rows)
+        return wk, acc_scale
+
+    def _check_fp16(self, name, wk, *folded):
+        if not torch.isfinite(wk).all():
+            raise ValueError(f"{name}: folded weights exceed the fp16 range (max |w| = {max(float(w.abs().max()) for w in folded):.3g})")
+
+    def _bias(self, b, cout_pad=None):
+        bk = torch.zeros((cout_pad or b.numel(),), dtype=torch.float32)
+        bk[:b.numel()] = b.to(torch.float32)
+        return bk
+
+    def _ref(self, **folded):
+        """w_ref / b_ref of an op's p (sub-)dict: the folded f64 parameters under keep_ref (oracle/graph_interp.py, tests), else None."""
+        return {k + "_ref": v if self.keep_ref else None for k, v in folded.items()}
+
+    def _forced_or_first(self, env, cands, cap):
+        """Tile of a two-input launch: the one the A/B hook `env` names, else the first candidate with an instance of `cap` in this precision."""
+        forced = os.environ.get(env, "")
+        return int(forced) if forced else next(t for t in cands if tile_has(t, cap, self.x3))
+
+    def _conv_op(self, out, x, wk, bias, *, flops, alg_bytes, kinds, Cin, Cout, cout_pad, tile, acc_scale, ref, relu=1, ksize=1, stride=1,
+                 in_c_off=0, out_fp32=0, frames=None, w_pairs=None, split_k=None, sub=None, **tensors):
+        """Append ONE conv launch writing `out` from `x`: the accounting, the p keys every launch has (a 1x1 stride-1 ReLU conv on all frames
+        unless said) and the main weights / bias in the weight section.  split_k = (M, K): the launch may split its K loop.  sub(): the emitter's
+        own sub-dicts -- called AFTER the main weights are placed, the weight section is laid out in call order.  tensors: further Op fields."""
+        self.flops += flops
+        self.alg_bytes += alg_bytes
+        skf, scratch = {}, []
+        if split_k:
+            M, K = split_k
+            skf, scratch = self._split_k_fields(out.name, tile, M, cout_pad, self.split_k(tile, M, cout_pad, K))
+        p = dict(flops=flops, alg_bytes=alg_bytes, kinds=kinds, **skf,
+                 Cin=Cin, in_c_off=in_c_off, Cout=Cout, ksize=ksize, stride=stride, pad=ksize // 2, relu=int(relu),
+                 cout_pad=cout_pad, tile=tile, out_fp32=int(out_fp32), w_off=self._add_w(wk), bias_off=self._add_w(bias),
+                 acc_scale=acc_scale, frames=self.B if frames is None else frames, w_pairs=self.w_pairs if w_pairs is None else w_pairs)
+        p.update(sub() if sub else {}, **ref)
+        self.ops.append(Op(OP_CONV, out=out, inp=x, scratch=scratch, p=p, **tensors))
+        return out
+
     def conv(self, name, prefixes, x, ksize=1, stride=1, relu=True, res=None, add1=None, add2=None,
              in_c_off=0, cin=None, out_fp32=False, up=None, frames=None):
         """One conv launch; `prefixes` (list) are concatenated along Cout (shared input).  frames: run on the first
@@ -572,7 +641,7 @@ class Graph:
         Ho = (x.H + 2 * pad - ksize) // stride + 1
         Wo = (x.W + 2 * pad - ksize) // stride + 1
         nfr = self.B if frames is None else frames
-        M = nfr * Ho * Wo
+        M, K = nfr * Ho * Wo, ksize * ksize * cin
         key = f"{nfr},{x.H},{x.W},{cin},{cout},{ksize},{stride}"
         plain3 = ksize == 3 and stride == 1 and res is None and add1 is None and add2 is None and up is None
         legal = lambda t: tile_legal(t, cout=cout, plain3=plain3, up=up is not None, out_fp32=out_fp32,
@@ -596,38 +665,17 @@ class Graph:
             hbn = int(hbn) if hbn else min(TILES[tile][1], 128 if cout > 64 else 64)
             tile = {(16, 64): 30, (16, 128): 31, (32, 64): 32, (32, 128): 33}[(int(tw), max(hbn, 64))]
             tile += 4 if os.environ.get("SMAP_HALO3_DEEP") else 0
-        tile = self.deep_pipeline_tile(tile, M, _rup(cout, TILES[tile][1]), ksize * ksize * cin)
-        bn = TILES[tile][1]
-        cout_pad = _rup(cout, bn)
-        K = ksize * ksize * cin
-        acc_scale = 1.0
-        if self.x3:                     # [cout_pad][K] hi | [cout_pad][K] lo of w * 2^s
-            hi, lo, acc_scale = split_f16(w.permute(0, 2, 3, 1).reshape(cout, K))
-            wk = torch.zeros((2, cout_pad, K), dtype=torch.float16)
-            wk[0, :cout], wk[1, :cout] = hi, lo
-        else:
-            wk = torch.zeros((1, cout_pad, K), dtype=torch.float16)
-            wk[0, :cout] = w.permute(0, 2, 3, 1).reshape(cout, K).to(torch.float16)
-            if not torch.isfinite(wk).all():
-                raise ValueError(f"{name}: folded weights exceed the fp16 range (max |w| = {float(w.abs().max()):.3g})")
-        w_pairs = self.w_pairs
-        wk = pack_conv_weights(wk, tile, self.x3, ksize, cin, pairs=w_pairs)   # one contiguous block per staged weight tile (pair)
-        bk = torch.zeros((cout_pad,), dtype=torch.float32)
-        bk[:cout] = b.to(torch.float32)
+        tile = self.deep_pipeline_tile(tile, M, _rup(cout, TILES[tile][1]), K)
+        cout_pad = _rup(cout, TILES[tile][1])
+        wk, acc_scale = self._weights(name, w.permute(0, 2, 3, 1).reshape(cout, K), cout_pad)
+        wk = pack_conv_weights(wk, tile, self.x3, ksize, cin, pairs=self.w_pairs)   # one contiguous block per staged weight tile (pair)
         out = self.tensor(name, Ho, Wo, _rup(cout, 8), 4 if out_fp32 else 2)
-        fl = 2 * M * cout * K
         by = (nfr * x.H * x.W * cin * 2 * x.planes + nfr * Ho * Wo * out.C * out.esize * out.planes
               + wk.numel() * 2 + sum(t.nbytes * nfr // self.B for t in (res, add1, add2, up) if t is not None))
-        self.flops += fl
-        self.alg_bytes += by
-        skf, scratch = self._split_k_fields(name, tile, M, cout_pad, self.split_k(tile, M, cout_pad, K))
-        self.ops.append(Op(OP_CONV, out=out, inp=x, res=res, add1=add1, add2=add2, aux=[up] if up is not None else [], scratch=scratch, p=dict(
-            flops=fl, alg_bytes=by, kinds="1x1" if ksize == 1 else "3x3", **skf,
-            Cin=cin, in_c_off=in_c_off, Cout=cout, ksize=ksize, stride=stride, pad=pad, relu=int(relu),
-            cout_pad=cout_pad, tile=tile, out_fp32=int(out_fp32), w_off=self._add_w(wk), bias_off=self._add_w(bk),
-            acc_scale=acc_scale, frames=nfr, w_pairs=w_pairs,
-            w_ref=w if self.keep_ref else None, b_ref=b if self.keep_ref else None)))
-        return out
+        return self._conv_op(out, x, wk, self._bias(b, cout_pad), flops=2 * M * cout * K, alg_bytes=by, kinds="1x1" if ksize == 1 else "3x3",
+                             Cin=cin, Cout=cout, cout_pad=cout_pad, tile=tile, acc_scale=acc_scale, ref=self._ref(w=w, b=b), relu=relu,
+                             ksize=ksize, stride=stride, in_c_off=in_c_off, out_fp32=out_fp32, frames=nfr, split_k=(M, K),
+                             res=res, add1=add1, add2=add2, aux=[up] if up is not None else [])
 
     def conv_relusum(self, name, pre1, x, pre2, x2, tile=None):
         """relu(conv1(x)) + relu(conv2(x2)) as ONE launch and ONE tensor (include/smap_hip.h smap_op.in2_mode = 1): the two inter-stage skips of an
@@ -641,39 +689,17 @@ class Graph:
             key = f"{self.B},{x.H},{x.W},{c1}+{c2}relusum,{cout},1,1"
             # measured in situ (profiles/r6_v14_ab_two_input_tiles.log): the 128 x 256 tile (both inputs' rows staged once per launch instead of once
             # per 128-channel N tile) 860-864 frames/s against 847 with the 128 x 128 tiles; the K-concatenated launches (conv_cat) do not care
-            cands = (pick_tile_x3(M, cout, key) if self.x3 else []) + [54, 53, 50, 51]
-            forced = os.environ.get("SMAP_RELUSUM_TILE", "")                     # A/B hook
-            tile = int(forced) if forced else next(t for t in cands if tile_has(t, "relusum", self.x3))
+            tile = self._forced_or_first("SMAP_RELUSUM_TILE", (pick_tile_x3(M, cout, key) if self.x3 else []) + [54, 53, 50, 51], "relusum")
         assert tile_has(tile, "relusum", self.x3), tile
-        bn = TILES[tile][1]
-        cout_pad = _rup(cout, bn)
-        sc1 = sc2 = 1.0
-        if self.x3:
-            h1, l1, sc1 = split_f16(w1.reshape(cout, c1))
-            h2, l2, sc2 = split_f16(w2.reshape(cout, c2))
-            wk = torch.zeros((2, cout_pad, K), dtype=torch.float16)
-            wk[0, :cout], wk[1, :cout] = torch.cat([h1, h2], 1), torch.cat([l1, l2], 1)
-        else:
-            wk = torch.zeros((1, cout_pad, K), dtype=torch.float16)
-            wk[0, :cout] = torch.cat([w1.reshape(cout, c1), w2.reshape(cout, c2)], 1).to(torch.float16)
-            if not torch.isfinite(wk).all():
-                raise ValueError(f"{name}: folded weights exceed the fp16 range")
-        wk = pack_conv_weights(wk, tile, self.x3, 1, K, pairs=self.w_pairs)
-        bk1, bk2 = torch.zeros((cout_pad,), dtype=torch.float32), torch.zeros((cout_pad,), dtype=torch.float32)
-        bk1[:cout], bk2[:cout] = b1.to(torch.float32), b2.to(torch.float32)
+        cout_pad = _rup(cout, TILES[tile][1])
+        wk1, sc1 = self._weights(name, w1.reshape(cout, c1), cout_pad)
+        wk2, sc2 = self._weights(name, w2.reshape(cout, c2), cout_pad)
+        wk = pack_conv_weights(torch.cat([wk1, wk2], 2), tile, self.x3, 1, K, pairs=self.w_pairs)
         out = self.tensor(name, x.H, x.W, cout)
-        fl = 2 * M * cout * K
-        by = x.nbytes + x2.nbytes + out.nbytes + wk.numel() * 2
-        self.flops += fl
-        self.alg_bytes += by
-        keep = self.keep_ref
-        self.ops.append(Op(OP_CONV, out=out, inp=x, aux2=x2, p=dict(
-            flops=fl, alg_bytes=by, kinds="1x1",
-            Cin=c1, in_c_off=0, Cout=cout, ksize=1, stride=1, pad=0, relu=0, cout_pad=cout_pad, tile=tile, out_fp32=0,
-            w_off=self._add_w(wk), bias_off=self._add_w(bk1), acc_scale=sc1, frames=self.B, w_pairs=self.w_pairs,
-            cat=dict(cin=c2, stride=1, relusum=True, acc_scale=sc2, bias_off=self._add_w(bk2), w_ref=w2 if keep else None, b_ref=b2 if keep else None),
-            w_ref=w1 if keep else None, b_ref=b1 if keep else None)))
-        return out
+        return self._conv_op(out, x, wk, self._bias(b1, cout_pad), flops=2 * M * cout * K, alg_bytes=x.nbytes + x2.nbytes + out.nbytes + wk.numel() * 2,
+                             kinds="1x1", Cin=c1, Cout=cout, cout_pad=cout_pad, tile=tile, acc_scale=sc1, ref=self._ref(w=w1, b=b1), relu=0, aux2=x2,
+                             sub=lambda: dict(cat=dict(cin=c2, stride=1, relusum=True, acc_scale=sc2, bias_off=self._add_w(self._bias(b2, cout_pad)),
+                                                       **self._ref(w=w2, b=b2))))
 
     def conv_tapdot(self, name, pre1, pre3, x, frames=None):
         """A 1x1 conv + ReLU (prefix pre1, 256 -> 256) whose ONLY consumer is a 3x3 conv with one output channel (prefix pre3) -- smap.py:227-229,
@@ -687,12 +713,7 @@ class Graph:
         tile = tile_ids(cap="tapdot", x3=self.x3)[0]
         nfr = self.B if frames is None else frames
         M = nfr * x.H * x.W
-        acc_scale = 1.0
-        if self.x3:
-            hi, lo, acc_scale = split_f16(w1.reshape(cout, cin))
-            wk = torch.stack([hi, lo])
-        else:
-            wk = w1.reshape(1, cout, cin).to(torch.float16)
+        wk, acc_scale = self._weights(name, w1.reshape(cout, cin))
         wk = pack_conv_weights(wk, tile, self.x3, 1, cin, pairs=self.w_pairs)
         # the 3x3's weights as B fragments of v_mfma_f32_16x16x32_f16 (include/smap_hip.h smap_op.tap_n): [K step][hi, lo][lane][8 halves],
         # lane l = tap l % 16 (9..15: zeros), channels 32 step + 8 (l / 16) .. +7; pre-scaled by a power of two like every split weight matrix
@@ -704,24 +725,17 @@ class Graph:
         tapw = torch.stack([thi[(lane % 16)[None, :, None], kidx], tlo[(lane % 16)[None, :, None], kidx]], 1).contiguous()              # [step][2][64][8]
         t = Tensor(name, self.B, x.H, x.W, 16, 4, 1)
         self.tensors.append(t)
-        fl = 2 * M * cout * cin + 2 * M * 9 * cout
         by = nfr * x.H * x.W * cin * 2 * x.planes + nfr * x.H * x.W * 16 * 4 + wk.numel() * 2
-        self.flops += fl
-        self.alg_bytes += by
-        keep = self.keep_ref
-        self.ops.append(Op(OP_CONV, out=t, inp=x, p=dict(
-            flops=fl, alg_bytes=by, kinds="1x1",
-            Cin=cin, in_c_off=0, Cout=cout, ksize=1, stride=1, pad=0, relu=1, cout_pad=cout, tile=tile, out_fp32=1,
-            w_off=self._add_w(wk), bias_off=self._add_w(b1.to(torch.float32)), acc_scale=acc_scale, frames=nfr, w_pairs=self.w_pairs,
-            tap=dict(w_off=self._add_w(tapw), scale=tap_scale, w_ref=w3 if keep else None),
-            w_ref=w1 if keep else None, b_ref=b1 if keep else None)))
+        self._conv_op(t, x, wk, self._bias(b1), flops=2 * M * cout * cin + 2 * M * 9 * cout, alg_bytes=by, kinds="1x1", Cin=cin, Cout=cout,
+                      cout_pad=cout, tile=tile, acc_scale=acc_scale, ref=self._ref(w=w1, b=b1), out_fp32=1, frames=nfr,
+                      sub=lambda: dict(tap=dict(w_off=self._add_w(tapw), scale=tap_scale, **self._ref(w=w3))))
         return t, b3
 
     def tapsum(self, t, b3, ext_off):
         """The stencil half of conv_tapdot's 3x3: out[b,0,y,x] = b3 + sum over taps of t[b, y+kh-1, x+kw-1][3 kh + kw] -> the fp32 NCHW map at
         ext_off of the output buffer (SMAP_OP_TAPSUM; stands where the head sum of that map stood)."""
         self.ops.append(Op(OP_TAPSUM, aux=[t], p=dict(Cout=1, ext_off=ext_off, bias_off=self._add_w(b3.to(torch.float32).reshape(1)),
-                                                       b_ref=b3 if self.keep_ref else None)))
+                                                       **self._ref(b=b3))))
 
     def conv_cat(self, name, pre1, x, pre2, x2, stride2, relu=True, tile=None):
         """The last 1x1 of a Bottleneck (prefix pre1, on x) TOGETHER with the block's 1x1 shortcut conv (prefix pre2, on x2 sampled with spatial
@@ -736,40 +750,17 @@ class Graph:
         M, K = self.B * Ho * Wo, c1 + c2
         if tile is None:
             key = f"{self.B},{Ho},{Wo},{c1}+{c2}cat,{cout},1,1"
-            cands = (pick_tile_x3(M, cout, key) if self.x3 else []) + [50, 51, 20]
-            forced = os.environ.get("SMAP_CAT_TILE", "")                         # A/B hook
-            tile = int(forced) if forced else next(t for t in cands if tile_has(t, "dual", self.x3))
+            tile = self._forced_or_first("SMAP_CAT_TILE", (pick_tile_x3(M, cout, key) if self.x3 else []) + [50, 51, 20], "dual")
         assert tile_has(tile, "dual", self.x3), tile
-        bn = TILES[tile][1]
-        cout_pad = _rup(cout, bn)
-        w = torch.cat([w1.reshape(cout, c1), w2.reshape(cout, c2)], 1)           # [cout][K = (x channels | x2 channels)]
-        b = b1 + b2
-        acc_scale = 1.0
-        if self.x3:
-            hi, lo, acc_scale = split_f16(w)                                       # ONE power-of-two scale: the two matrices share the accumulators
-            wk = torch.zeros((2, cout_pad, K), dtype=torch.float16)
-            wk[0, :cout], wk[1, :cout] = hi, lo
-        else:
-            wk = torch.zeros((1, cout_pad, K), dtype=torch.float16)
-            wk[0, :cout] = w.to(torch.float16)
-            if not torch.isfinite(wk).all():
-                raise ValueError(f"{name}: folded weights exceed the fp16 range")
+        cout_pad = _rup(cout, TILES[tile][1])
+        # [cout][K = (x channels | x2 channels)] with ONE power-of-two scale: the two matrices share the accumulators
+        wk, acc_scale = self._weights(name, torch.cat([w1.reshape(cout, c1), w2.reshape(cout, c2)], 1), cout_pad)
         wk = pack_conv_weights(wk, tile, self.x3, 1, K, pairs=self.w_pairs)
-        bk = torch.zeros((cout_pad,), dtype=torch.float32)
-        bk[:cout] = b.to(torch.float32)
         out = self.tensor(name, Ho, Wo, cout)
-        fl = 2 * M * cout * K
         by = x.nbytes + self.B * Ho * Wo * c2 * 2 * x2.planes + out.nbytes + wk.numel() * 2      # (the strided shortcut touches the sampled pixels only)
-        self.flops += fl
-        self.alg_bytes += by
-        keep = self.keep_ref
-        self.ops.append(Op(OP_CONV, out=out, inp=x, aux2=x2, p=dict(
-            flops=fl, alg_bytes=by, kinds="1x1",
-            Cin=c1, in_c_off=0, Cout=cout, ksize=1, stride=1, pad=0, relu=int(relu), cout_pad=cout_pad, tile=tile, out_fp32=0,
-            w_off=self._add_w(wk), bias_off=self._add_w(bk), acc_scale=acc_scale, frames=self.B, w_pairs=self.w_pairs,
-            cat=dict(cin=c2, stride=stride2, w_ref=w2 if keep else None, b_ref=b2 if keep else None),
-            w_ref=w1 if keep else None, b_ref=b1 if keep else None)))
-        return out
+        return self._conv_op(out, x, wk, self._bias(b1 + b2, cout_pad), flops=2 * M * cout * K, alg_bytes=by, kinds="1x1", Cin=c1, Cout=cout,
+                             cout_pad=cout_pad, tile=tile, acc_scale=acc_scale, ref=self._ref(w=w1, b=b1), relu=relu, aux2=x2,
+                             sub=lambda: dict(cat=dict(cin=c2, stride=stride2, **self._ref(w=w2, b=b2))))
 
     def conv_seg(self, segs, x, up=None, tile=None):
         """Several 1x1 stride-1 convs that read the SAME input as ONE launch with one output tensor per conv (include/smap_hip.h
@@ -811,36 +802,22 @@ class Graph:
             starts.append(n)
             n = _rup(n + c, bn)
         cout_pad = n
-        planes = 2 if self.x3 else 1
-        wk = torch.zeros((planes, cout_pad, cin), dtype=torch.float16)
+        wk = torch.zeros((2 if self.x3 else 1, cout_pad, cin), dtype=torch.float16)
         bk = torch.zeros((cout_pad,), dtype=torch.float32)
         scales = []
         for (w, b), st, c in zip(folded, starts, couts):
-            if self.x3:
-                hi, lo, sc = split_f16(w.reshape(c, cin))
-                wk[0, st:st + c], wk[1, st:st + c] = hi, lo
-            else:
-                sc = 1.0
-                wk[0, st:st + c] = w.reshape(c, cin).to(torch.float16)
-            scales.append(sc)
+            wk[:, st:st + c], sc = self._weights(segs[0][0], w.reshape(c, cin))
             bk[st:st + c] = b.to(torch.float32)
-        if not torch.isfinite(wk).all():
-            raise ValueError(f"{segs[0][0]}: folded weights exceed the fp16 range")
+            scales.append(sc)
+        self._check_fp16(segs[0][0], wk, *[w for w, _ in folded])       # (in both precisions, as this emitter always did)
         wk = pack_conv_weights(wk, tile, self.x3, 1, cin, pairs=self.w_pairs)
         outs = [self.tensor(nm, x.H, x.W, c) for (nm, _, _), c in zip(segs, couts)]
-        fl = 2 * M * sum(couts) * cin
         by = x.nbytes + sum(t.nbytes for t in outs) + wk.numel() * 2 + (up.nbytes if up is not None else 0)
-        self.flops += fl
-        self.alg_bytes += by
-        keep = self.keep_ref
-        skf, scratch = self._split_k_fields(segs[0][0], tile, M, cout_pad, self.split_k(tile, M, cout_pad, cin))
-        self.ops.append(Op(OP_CONV, out=outs[0], inp=x, aux=[up] if up is not None else [], outs=outs[1:], scratch=scratch, p=dict(
-            flops=fl, alg_bytes=by, kinds="1x1", **skf,
-            Cin=cin, in_c_off=0, Cout=couts[0], ksize=1, stride=1, pad=0, relu=int(segs[0][2]), cout_pad=cout_pad, tile=tile, out_fp32=0,
-            w_off=self._add_w(wk), bias_off=self._add_w(bk), acc_scale=scales[0], frames=self.B, w_pairs=self.w_pairs,
-            segs=[dict(n0=st, cout=c, relu=int(r), acc_scale=sc, w_ref=w if keep else None, b_ref=b if keep else None)
-                  for st, c, (_, _, r), sc, (w, b) in list(zip(starts, couts, segs, scales, folded))[1:]],
-            w_ref=folded[0][0] if keep else None, b_ref=folded[0][1] if keep else None)))
+        self._conv_op(outs[0], x, wk, bk, flops=2 * M * sum(couts) * cin, alg_bytes=by, kinds="1x1", Cin=cin, Cout=couts[0], cout_pad=cout_pad,
+                      tile=tile, acc_scale=scales[0], ref=self._ref(w=folded[0][0], b=folded[0][1]), relu=segs[0][2], split_k=(M, cin),
+                      aux=[up] if up is not None else [], outs=outs[1:],
+                      sub=lambda: dict(segs=[dict(n0=st, cout=c, relu=int(r), acc_scale=sc, **self._ref(w=w, b=b))
+                                             for st, c, (_, _, r), sc, (w, b) in list(zip(starts, couts, segs, scales, folded))[1:]]))
         return outs
 
     def conv_tail(self, name, pre3, pre1, x, tile, res=None, add1=None, add2=None):
@@ -855,37 +832,17 @@ class Graph:
         cout_pad = _rup(cout, bn2)
         M = self.B * x.H * x.W
         K3 = 9 * cin
-        sc3 = sc1 = 1.0
-        if self.x3:
-            hi, lo, sc3 = split_f16(w3.permute(0, 2, 3, 1).reshape(P, K3))
-            wk3 = torch.stack([hi, lo])
-            hi, lo, sc1 = split_f16(w1.reshape(cout, P))
-            wk1 = torch.zeros((2, cout_pad, P), dtype=torch.float16)
-            wk1[0, :cout], wk1[1, :cout] = hi, lo
-        else:
-            wk3 = w3.permute(0, 2, 3, 1).reshape(1, P, K3).to(torch.float16)
-            wk1 = torch.zeros((1, cout_pad, P), dtype=torch.float16)
-            wk1[0, :cout] = w1.reshape(cout, P).to(torch.float16)
-            if not (torch.isfinite(wk3).all() and torch.isfinite(wk1).all()):
-                raise ValueError(f"{name}: folded weights exceed the fp16 range")
+        wk3, sc3 = self._weights(name, w3.permute(0, 2, 3, 1).reshape(P, K3))
+        wk1, sc1 = self._weights(name, w1.reshape(cout, P), cout_pad)
         wk3 = pack_halo_rows(wk3, P, 9, cin, self.x3)
         wk1 = pack_halo_rows(wk1, bn2, 1, P, self.x3)
-        bk1 = torch.zeros((cout_pad,), dtype=torch.float32)
-        bk1[:cout] = b1.to(torch.float32)
         out = self.tensor(name, x.H, x.W, cout)
-        fl = 2 * M * (P * K3 + cout * P)
         by = (x.nbytes + out.nbytes + (wk3.numel() + wk1.numel()) * 2
               + sum(t.nbytes for t in (res, add1, add2) if t is not None))
-        self.flops += fl
-        self.alg_bytes += by
-        self.ops.append(Op(OP_CONV, out=out, inp=x, res=res, add1=add1, add2=add2, p=dict(
-            flops=fl, alg_bytes=by, kinds="3x3+1x1",
-            Cin=cin, in_c_off=0, Cout=P, ksize=3, stride=1, pad=1, relu=1, cout_pad=P, tile=tile, out_fp32=0,
-            w_off=self._add_w(wk3), bias_off=self._add_w(b3.to(torch.float32)), acc_scale=sc3, frames=self.B, w_pairs=0,
-            tail=dict(cout=cout, cout_pad=cout_pad, w_off=self._add_w(wk1), bias_off=self._add_w(bk1), acc_scale=sc1,
-                      w_ref=w1 if self.keep_ref else None, b_ref=b1 if self.keep_ref else None),
-            w_ref=w3 if self.keep_ref else None, b_ref=b3 if self.keep_ref else None)))
-        return out
+        return self._conv_op(out, x, wk3, self._bias(b3), flops=2 * M * (P * K3 + cout * P), alg_bytes=by, kinds="3x3+1x1", Cin=cin, Cout=P, cout_pad=P,
+                             tile=tile, acc_scale=sc3, ref=self._ref(w=w3, b=b3), ksize=3, w_pairs=0, res=res, add1=add1, add2=add2,
+                             sub=lambda: dict(tail=dict(cout=cout, cout_pad=cout_pad, w_off=self._add_w(wk1), bias_off=self._add_w(self._bias(b1, cout_pad)),
+                                                        acc_scale=sc1, **self._ref(w=w1, b=b1))))
 
     def conv_block_first(self, name, pre, x, tile):
         """The FIRST Bottleneck of layer1 (smap.py:48-77 with the 1x1 shortcut conv of :124-129; 64 input channels, stride 1) as ONE
@@ -899,31 +856,23 @@ class Graph:
         C = wt.shape[0]
         assert P == 64 == Cin == x.C and C == 256 and tuple(wd.shape[:2]) == (C, Cin) and wd.shape[2] == 1 and w3.shape[2] == 3
         M = self.B * x.H * x.W
-        hi, lo, sc1 = split_f16(w1.reshape(P, Cin))
-        wk1 = pack_halo_rows(torch.stack([hi, lo]), P, 1, Cin, True)                  # [1][2 chunks][1][64 rows][128 B]
-        hi, lo, sc3 = split_f16(w3.permute(0, 2, 3, 1).reshape(P, 9 * P))
-        wk3 = pack_halo_rows(torch.stack([hi, lo]), P, 9, P, True)
-        hi, lo, sct = split_f16(wt.reshape(C, P))
-        wkt = pack_halo_rows(torch.stack([hi, lo]), 64, 1, P, True)
-        hi, lo, scd = split_f16(wd.reshape(C, Cin))
-        wkd = pack_halo_rows(torch.stack([hi, lo]), 64, 1, Cin, True)                 # [4 n chunks][2 k chunks][1][64 rows][128 B]
+        wk1, sc1 = self._weights(name, w1.reshape(P, Cin))
+        wk1 = pack_halo_rows(wk1, P, 1, Cin, True)                                    # [1][2 chunks][1][64 rows][128 B]
+        wk3, sc3 = self._weights(name, w3.permute(0, 2, 3, 1).reshape(P, 9 * P))
+        wk3 = pack_halo_rows(wk3, P, 9, P, True)
+        wkt, sct = self._weights(name, wt.reshape(C, P))
+        wkt = pack_halo_rows(wkt, 64, 1, P, True)
+        wkd, scd = self._weights(name, wd.reshape(C, Cin))
+        wkd = pack_halo_rows(wkd, 64, 1, Cin, True)                                   # [4 n chunks][2 k chunks][1][64 rows][128 B]
         out = self.tensor(name, x.H, x.W, C)
-        fl = 2 * M * (P * Cin + P * 9 * P + C * P + C * Cin)
         by = x.nbytes + out.nbytes + (wk1.numel() + wk3.numel() + wkt.numel() + wkd.numel()) * 2
-        self.flops += fl
-        self.alg_bytes += by
-        keep = self.keep_ref
-        self.ops.append(Op(OP_CONV, out=out, inp=x, p=dict(
-            flops=fl, alg_bytes=by, kinds="block",
-            Cin=P, in_c_off=0, Cout=P, ksize=3, stride=1, pad=1, relu=1, cout_pad=P, tile=tile, out_fp32=0,
-            w_off=self._add_w(wk3), bias_off=self._add_w(b3.to(torch.float32)), acc_scale=sc3, frames=self.B, w_pairs=0,
-            head=dict(cin=Cin, w_off=self._add_w(wk1), bias_off=self._add_w(b1.to(torch.float32)), acc_scale=sc1,
-                      w_ref=w1 if keep else None, b_ref=b1 if keep else None),
-            tail=dict(cout=C, cout_pad=C, w_off=self._add_w(wkt), bias_off=self._add_w((bt + bd).to(torch.float32)), acc_scale=sct,
-                      w_ref=wt if keep else None, b_ref=bt if keep else None),
-            short=dict(w_off=self._add_w(wkd), acc_scale=scd, w_ref=wd if keep else None, b_ref=bd if keep else None),
-            w_ref=w3 if keep else None, b_ref=b3 if keep else None)))
-        return out
+        return self._conv_op(out, x, wk3, self._bias(b3), flops=2 * M * (P * Cin + P * 9 * P + C * P + C * Cin), alg_bytes=by, kinds="block", Cin=P,
+                             Cout=P, cout_pad=P, tile=tile, acc_scale=sc3, ref=self._ref(w=w3, b=b3), ksize=3, w_pairs=0,
+                             sub=lambda: dict(
+                                 head=dict(cin=Cin, w_off=self._add_w(wk1), bias_off=self._add_w(self._bias(b1)), acc_scale=sc1, **self._ref(w=w1, b=b1)),
+                                 tail=dict(cout=C, cout_pad=C, w_off=self._add_w(wkt), bias_off=self._add_w(self._bias(bt + bd)), acc_scale=sct,
+                                           **self._ref(w=wt, b=bt)),
+                                 short=dict(w_off=self._add_w(wkd), acc_scale=scd, **self._ref(w=wd, b=bd))))
 
     def conv_block(self, name, pre, x, tile, add1=None, add2=None):
         """A whole stride-1 identity Bottleneck (smap.py:48-77: conv_bn_relu1 1x1 -> conv_bn_relu2 3x3 -> conv_bn_relu3 1x1, + x,
@@ -938,32 +887,24 @@ class Graph:
         assert P == TILES[tile][1] and C == 4 * P == x.C == wt.shape[0] and w3.shape[:2] == (P, P) and w3.shape[2] == 3 and wt.shape[1] == P
         assert tile_family(tile) == "block" and not TILE_TABLE[tile].first and P == TILE_TABLE[tile].planes
         M = self.B * x.H * x.W
-        hi, lo, sc1 = split_f16(w1.reshape(P, C))
+        wk1, sc1 = self._weights(name, w1.reshape(P, C))
         if P == 64:
-            wk1 = pack_rows16(torch.stack([hi, lo]))                                  # [C/16 stages][P rows][64 B]
+            wk1 = pack_rows16(wk1)                                                    # [C/16 stages][P rows][64 B]
         else:
-            wk1 = pack_halo_rows(torch.stack([hi, lo]), P, 1, C, True)                # csrc/convc.hip: [1][C/32 chunks][1][P rows][128 B]
-        hi, lo, sc3 = split_f16(w3.permute(0, 2, 3, 1).reshape(P, 9 * P))
-        wk3 = pack_halo_rows(torch.stack([hi, lo]), P, 9, P, True)                    # [1][P/32][9 taps][P rows][128 B]
-        hi, lo, sct = split_f16(wt.reshape(C, P))
-        wkt = pack_halo_rows(torch.stack([hi, lo]), bn2, 1, P, True)                  # [C/64][P/32][1][64 rows][128 B]
+            wk1 = pack_halo_rows(wk1, P, 1, C, True)                                  # csrc/convc.hip: [1][C/32 chunks][1][P rows][128 B]
+        wk3, sc3 = self._weights(name, w3.permute(0, 2, 3, 1).reshape(P, 9 * P))
+        wk3 = pack_halo_rows(wk3, P, 9, P, True)                                      # [1][P/32][9 taps][P rows][128 B]
+        wkt, sct = self._weights(name, wt.reshape(C, P))
+        wkt = pack_halo_rows(wkt, bn2, 1, P, True)                                    # [C/64][P/32][1][64 rows][128 B]
         out = self.tensor(name, x.H, x.W, C)
-        fl = 2 * M * (P * C + P * 9 * P + C * P)
         by = (x.nbytes + out.nbytes + (wk1.numel() + wk3.numel() + wkt.numel()) * 2
               + sum(t.nbytes for t in (add1, add2) if t is not None))
-        self.flops += fl
-        self.alg_bytes += by
-        keep = self.keep_ref
-        self.ops.append(Op(OP_CONV, out=out, inp=x, res=x, add1=add1, add2=add2, p=dict(
-            flops=fl, alg_bytes=by, kinds="block",
-            Cin=P, in_c_off=0, Cout=P, ksize=3, stride=1, pad=1, relu=1, cout_pad=P, tile=tile, out_fp32=0,
-            w_off=self._add_w(wk3), bias_off=self._add_w(b3.to(torch.float32)), acc_scale=sc3, frames=self.B, w_pairs=0,
-            head=dict(cin=C, w_off=self._add_w(wk1), bias_off=self._add_w(b1.to(torch.float32)), acc_scale=sc1,
-                      w_ref=w1 if keep else None, b_ref=b1 if keep else None),
-            tail=dict(cout=C, cout_pad=C, w_off=self._add_w(wkt), bias_off=self._add_w(bt.to(torch.float32)), acc_scale=sct,
-                      w_ref=wt if keep else None, b_ref=bt if keep else None),
-            w_ref=w3 if keep else None, b_ref=b3 if keep else None)))
-        return out
+        return self._conv_op(out, x, wk3, self._bias(b3), flops=2 * M * (P * C + P * 9 * P + C * P), alg_bytes=by, kinds="block", Cin=P, Cout=P,
+                             cout_pad=P, tile=tile, acc_scale=sc3, ref=self._ref(w=w3, b=b3), ksize=3, w_pairs=0, res=x, add1=add1, add2=add2,
+                             sub=lambda: dict(
+                                 head=dict(cin=C, w_off=self._add_w(wk1), bias_off=self._add_w(self._bias(b1)), acc_scale=sc1, **self._ref(w=w1, b=b1)),
+                                 tail=dict(cout=C, cout_pad=C, w_off=self._add_w(wkt), bias_off=self._add_w(self._bias(bt)), acc_scale=sct,
+                                           **self._ref(w=wt, b=bt))))
 
     def block_tile(self, planes, stride, has_ds):
         """Tile id of the whole-block launch for this Bottleneck, or None.  Identity blocks (no shortcut conv) of stride 1 in
@@ -973,14 +914,9 @@ class Graph:
         workgroups: profiles/r5_v11_ab_b1_whole_block_tiles.log)."""
         if stride != 1 or has_ds or not self.x3:
             return None
-        spec = os.environ.get("SMAP_BLOCK")
-        table = BLOCK_DEFAULT if spec is None else {int(k): int(v) for k, v in (kv.split(":") for kv in spec.split(",") if ":" in kv)}
-        small = self.B * self.H * self.W <= 2 * 512 * 832
-        if spec is None and planes == 128 and small:
-            return None
-        if spec is None and planes == 64 and small:
-            return 90                    # 4 x 16 pixel tiles: 416 workgroups of half the work at batch 1 (2.91 -> 2.84 ms per frame)
-        return table.get(planes)
+        if "SMAP_BLOCK" not in os.environ and self.small:
+            return {64: 90}.get(planes)  # 4 x 16 pixel tiles: 416 workgroups of half the work at batch 1 (2.91 -> 2.84 ms per frame)
+        return _planes_table("SMAP_BLOCK", BLOCK_DEFAULT).get(planes)
 
     # -- the network (smap.py:313-353 structure, :403-419 data flow)
     def _build(self):
@@ -1020,9 +956,8 @@ class Graph:
         blk = self.block_tile(planes, stride, has_ds)
         if blk is not None:         # c1 + c2 + c3 + residual in one launch (csrc/convb.hip)
             return self.conv_block(pre + ".c3", pre, x, blk, add1=add1, add2=add2)
-        spec = os.environ.get("SMAP_BLOCK_FIRST")
-        first = (BLOCK_FIRST_DEFAULT if spec is None else {int(k): int(v) for k, v in (kv.split(":") for kv in spec.split(",") if ":" in kv)}).get(planes)
-        if spec is None and first == 93 and self.B * self.H * self.W <= 2 * 512 * 832:
+        first = _planes_table("SMAP_BLOCK_FIRST", BLOCK_FIRST_DEFAULT).get(planes)
+        if "SMAP_BLOCK_FIRST" not in os.environ and first == 93 and self.small:
             first = 92                   # small schedules: the 4 x 16 tiles here too
         if first is not None and self.x3 and has_ds and stride == 1 and x.C == 64 and planes == 64 and add1 is None and add2 is None:
             return self.conv_block_first(pre + ".c3", pre, x, first)
@@ -1033,7 +968,7 @@ class Graph:
         #  two-input instances do not have: batch 1 measured 3.4 ms per frame with them against 2.9 without, profiles/r6_final_*.)
         cat_env = os.environ.get("SMAP_CAT", "")
         cat = (has_ds and add1 is None and add2 is None and cat_env != "0" and self.tail_tile(planes, stride) is None
-               and self.B * self.H * self.W <= 20 * 512 * 832 and (cat_env == "1" or self.B * self.H * self.W > 2 * 512 * 832))
+               and self.one_window and (cat_env == "1" or not self.small))
         idn = x if (not has_ds or cat) else self.conv(pre + ".downsample", [pre + ".downsample"], x, 1, stride, relu=False)
         y = self.conv(pre + ".c1", [pre + ".conv_bn_relu1"], x, 1, 1, relu=True)
         if cat:
@@ -1050,9 +985,7 @@ class Graph:
         SMAP_TAIL="64:80,128:82" chooses per width (A/B hook); default: see TAIL_DEFAULT."""
         if stride != 1:
             return None
-        spec = os.environ.get("SMAP_TAIL")
-        table = TAIL_DEFAULT if spec is None else {int(k): int(v) for k, v in (kv.split(":") for kv in spec.split(",") if ":" in kv)}
-        return table.get(planes)
+        return _planes_table("SMAP_TAIL", TAIL_DEFAULT).get(planes)
 
     def _stage(self, s, x, skip1, skip2, gen_skip, heads):
         pre = f"stage{s}."
@@ -1088,8 +1021,7 @@ class Graph:
             # The inter-stage skips as ONE tensor per level: skip1(x) + skip2(out) in one launch (conv_relusum); the next stage adds that one tensor.
             # SMAP_SKIPSUM=0: round 5's two tensors (skip1 beside u_skip, skip2 as a segment of the launch on `out`).  Not beyond one 4 GiB window.
             ss_env = os.environ.get("SMAP_SKIPSUM", "")
-            skipsum = (gen_skip and merge and ss_env != "0" and self.B * self.H * self.W <= 20 * 512 * 832
-                       and (ss_env == "1" or self.B * self.H * self.W > 2 * 512 * 832))          # (small schedules: as conv_cat, see _bottleneck)
+            skipsum = gen_skip and merge and ss_env != "0" and self.one_window and (ss_env == "1" or not self.small)    # (small schedules: as conv_cat)
             if merge:
                 # launch 1, on x:   out = relu(u_skip(x) [+ bilinear(up_conv@low)])  |  skip1 = relu(skip1(x))
                 if gen_skip and not skipsum and (tl is None or merge_mode == "2"):
@@ -1127,7 +1059,7 @@ class Graph:
                         # keeps nine dot products per pixel instead of the 256-channel activation, + a nine-term stencil (conv_tapdot / tapsum):
                         # 0.87 GB per 16 frames and the N = 1 MFMA launch (8.9 TFLOP/s) gone.  SMAP_TAPHEAD=0: round 5's three-way 1x1 + 3x3.
                         tap_env = os.environ.get("SMAP_TAPHEAD", "")
-                        tap = self.chl == 256 and tap_env != "0" and (tap_env == "1" or self.B * self.H * self.W > 2 * 512 * 832)
+                        tap = self.chl == 256 and tap_env != "0" and (tap_env == "1" or not self.small)
                         m = self.conv(u + ".heads1x1", [u + ".res_conv1", u + ".res_d_conv1"] + ([] if tap else [u + ".res_rd_conv1"]), out, relu=True)
                         c = self.chl
                         head_t["res4"] = self.conv(u + ".res", [u + ".res_conv2"], m, 3, relu=False, in_c_off=0, cin=c, out_fp32=True)

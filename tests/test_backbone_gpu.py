@@ -12,16 +12,9 @@ import torch.nn.functional as F
 
 from helpers import make_cfg
 from recipe import recipe_state_dict
+from single_op import DEV, arena_of, get, graph_arena, put, read_act, run_plan, stored, weight_blob
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
-
-
-def _split(t):
-    """fp32 tensor [..., C] -> fp16 [..., 2C] = [hi(C) | lo(C)] (the split-precision storage of csrc/conv.hip X3)."""
-    hi = t.to(torch.float16)
-    lo = (t - hi.float()).to(torch.float16)
-    return torch.cat([hi, lo], -1)
 
 
 def _run_single_conv(B, H, W, Cin, Cout, k, stride, tile, relu, use_res, use_adds, out_fp32=False,
@@ -31,8 +24,7 @@ def _run_single_conv(B, H, W, Cin, Cout, k, stride, tile, relu, use_res, use_add
     bilinearly (align_corners) upsampled and added before the ReLU (smap_op.aux_off[0], smap.py:213-217).  w_pairs: layout of
     the packed 32-half K tiles (default: seed % 2).  ksplit > 1: split K, with its own partial-tile scratch and tickets."""
     from smap_amd import lib as L
-    from smap_amd.engine import TILES, ZERO_PAGE, split_f16
-    lib = L.load()
+    from smap_amd.engine import TILES, split_f16
     g = torch.Generator().manual_seed(seed)
     in_stride = in_stride or Cin
     pad = k // 2
@@ -65,28 +57,14 @@ def _run_single_conv(B, H, W, Cin, Cout, k, stride, tile, relu, use_res, use_add
     bk = torch.zeros(cout_pad)
     bk[:Cout] = bias
     # weight blob: [wk | bias]; arena: [x | res | a1 | a2 | low-res | out | split-K partial tiles | tickets]
-    al = lambda n: (n + 255) // 256 * 256
-    w_bytes = al(wk.numel() * 2)
-    blob = torch.zeros(w_bytes + al(bk.numel() * 4), dtype=torch.uint8)
-    blob[:wk.numel() * 2] = wk.view(torch.uint8).reshape(-1)
-    blob[w_bytes:w_bytes + bk.numel() * 4] = bk.view(torch.uint8).reshape(-1)
-    store = _split if x3 else (lambda t: t)
-    parts, offs, cur = [x, res, a1, a2, lowres], [], ZERO_PAGE    # arena[0:ZERO_PAGE] = zero page
-    stored = [store(t) if t is not None else None for t in parts]
-    for t in stored:
-        offs.append(cur if t is not None else -1)
-        cur += al(t.numel() * 2) if t is not None else 0
-    out_off = cur
+    blob, (_, w_bytes) = weight_blob([wk, bk])
     esz = 4 if out_fp32 else 2
     npl = 2 if (x3 and not out_fp32) else 1
-    kpart_off = out_off + al(B * Ho * Wo * c8 * esz * npl)
     bm = TILES.get(tile, (128, 64))[0]
     n_tiles = -(-(B * Ho * Wo) // bm) * (cout_pad // bn)
-    kcount_off = kpart_off + (al(n_tiles * ksplit * bm * bn * 4) if ksplit > 1 else 0)
-    arena = torch.zeros(kcount_off + (al(4 * n_tiles) if ksplit > 1 else 0) + 256, dtype=torch.uint8)
-    for t, o in zip(stored, offs):
-        if t is not None:
-            arena[o:o + t.numel() * 2] = t.contiguous().view(torch.uint8).reshape(-1)
+    arena, offs = arena_of([t if t is None else stored(t, 1 + x3) for t in (x, res, a1, a2, lowres)], B * Ho * Wo * c8 * esz * npl,
+                           n_tiles * ksplit * bm * bn * 4 if ksplit > 1 else 0, 4 * n_tiles if ksplit > 1 else 0)
+    out_off, kpart_off, kcount_off = offs[5:]
     op = L.SmapOp()
     pl_in = 2 if x3 else 1
     op.kind, op.B, op.H, op.W, op.Cin, op.in_stride_c, op.in_c_off = 0, B, H, W, Cin, in_stride * pl_in, in_off
@@ -103,21 +81,10 @@ def _run_single_conv(B, H, W, Cin, Cout, k, stride, tile, relu, use_res, use_add
     if ksplit > 1:
         op.ksplit, op.kpart_off, op.kcount_off = ksplit, kpart_off, kcount_off
     op.ext_off = -1
-    h = C.c_void_p()
-    L.check(lib.smap_plan_create(C.byref(op), 1, C.byref(h)), "create")
-    arena_d, blob_d = arena.to(DEV), blob.to(DEV)
-    st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-    L.check(lib.smap_plan_run(h, None, C.c_void_p(arena_d.data_ptr()), C.c_void_p(blob_d.data_ptr()), None, st), "run")
-    torch.cuda.synchronize()
-    lib.smap_plan_destroy(h)
+    arena_d = run_plan(op, 1, arena, blob)
     if ksplit > 1:                                         # the last part of every tile leaves its ticket at zero for the next run
         assert not arena_d[kcount_off:kcount_off + 4 * n_tiles].any()
-    raw = arena_d[out_off:out_off + B * Ho * Wo * c8 * esz * npl].cpu()
-    if npl == 2:
-        got = raw.view(torch.float16).view(B, Ho, Wo, 2, c8).float()
-        got = got[..., 0, :] + got[..., 1, :]
-    else:
-        got = raw.view(torch.float32 if out_fp32 else torch.float16).view(B, Ho, Wo, c8).float()
+    got = read_act(arena_d, out_off, (B, Ho, Wo, c8), npl, torch.float32 if out_fp32 else torch.float16)
     # reference: f64 conv of the same stored operands
     xin = x[..., in_off:in_off + Cin].float().permute(0, 3, 1, 2)
     y = F.conv2d(xin.double(), w.double(), bias.double(), stride=stride, padding=pad).permute(0, 2, 3, 1)
@@ -413,8 +380,7 @@ def test_single_conv_shipped_launch_edges(case, precision):
 def _run_tail(B, H, W, Cin, P, Cout, tile, relu, use_res, use_adds, x3, seed=0):
     """One fused Bottleneck-tail op (csrc/convf.hip): 3x3 Cin -> P (bias, ReLU) then 1x1 P -> Cout (+ res, ReLU, + adds)."""
     from smap_amd import lib as L
-    from smap_amd.engine import TAIL_BN, TILES, ZERO_PAGE, pack_halo_rows, split_f16
-    lib = L.load()
+    from smap_amd.engine import TAIL_BN, pack_halo_rows, split_f16
     g = torch.Generator().manual_seed(seed)
     bn2 = TAIL_BN[tile]
     cout_pad = (Cout + bn2 - 1) // bn2 * bn2
@@ -441,27 +407,10 @@ def _run_tail(B, H, W, Cin, P, Cout, tile, relu, use_res, use_adds, x3, seed=0):
     wk3, wk1 = pack_halo_rows(wk3, P, 9, Cin, x3), pack_halo_rows(wk1, bn2, 1, P, x3)
     bk1 = torch.zeros(cout_pad)
     bk1[:Cout] = b1
-    al = lambda n: (n + 255) // 256 * 256
-    chunks, woffs, cur = [wk3.view(torch.uint8).reshape(-1), b3.view(torch.uint8).reshape(-1), wk1.view(torch.uint8).reshape(-1),
-                          bk1.view(torch.uint8).reshape(-1)], [], 0
-    for c in chunks:
-        woffs.append(cur)
-        cur += al(c.numel())
-    blob = torch.zeros(cur, dtype=torch.uint8)
-    for c, o in zip(chunks, woffs):
-        blob[o:o + c.numel()] = c
-    store = _split if x3 else (lambda t: t)
-    parts, offs, cur = [x, res, a1, a2], [], ZERO_PAGE
-    stored = [store(t) if t is not None else None for t in parts]
-    for t in stored:
-        offs.append(cur if t is not None else -1)
-        cur += al(t.numel() * 2) if t is not None else 0
-    out_off = cur
+    blob, woffs = weight_blob([wk3, b3, wk1, bk1])
     npl = 2 if x3 else 1
-    arena = torch.zeros(out_off + al(B * H * W * Cout * 2 * npl) + 256, dtype=torch.uint8)
-    for t, o in zip(stored, offs):
-        if t is not None:
-            arena[o:o + t.numel() * 2] = t.contiguous().view(torch.uint8).reshape(-1)
+    arena, offs = arena_of([t if t is None else stored(t, npl) for t in (x, res, a1, a2)], B * H * W * Cout * 2 * npl)
+    out_off = offs[4]
     op = L.SmapOp()
     op.kind, op.B, op.H, op.W, op.Cin, op.in_stride_c, op.in_c_off = 0, B, H, W, Cin, Cin * npl, 0
     op.Ho, op.Wo, op.Cout, op.ksize, op.stride, op.pad, op.relu = H, W, P, 3, 1, 1, int(relu)
@@ -473,19 +422,7 @@ def _run_tail(B, H, W, Cin, P, Cout, tile, relu, use_res, use_adds, x3, seed=0):
     for i in range(3):
         op.aux_off[i] = -1
     op.ext_off = -1
-    h = C.c_void_p()
-    L.check(lib.smap_plan_create(C.byref(op), 1, C.byref(h)), "create")
-    arena_d, blob_d = arena.to(DEV), blob.to(DEV)
-    st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-    L.check(lib.smap_plan_run(h, None, C.c_void_p(arena_d.data_ptr()), C.c_void_p(blob_d.data_ptr()), None, st), "run")
-    torch.cuda.synchronize()
-    lib.smap_plan_destroy(h)
-    raw = arena_d[out_off:out_off + B * H * W * Cout * 2 * npl].cpu()
-    if x3:
-        got = raw.view(torch.float16).view(B, H, W, 2, Cout).float()
-        got = got[..., 0, :] + got[..., 1, :]
-    else:
-        got = raw.view(torch.float16).view(B, H, W, Cout).float()
+    got = read_act(run_plan(op, 1, arena, blob), out_off, (B, H, W, Cout), npl)
     y = F.relu(F.conv2d(x.double().permute(0, 3, 1, 2), w3.double(), b3.double(), padding=1))
     if not x3:
         y = y.half().double()                                  # the 3x3's output is an fp16 activation in that mode
@@ -520,8 +457,7 @@ def _run_block(B, H, W, tile, use_adds, seed=0, mode="full", relu=True, check=Tr
     (tools/debug/convb_probe.py): "residual" (W3 = b3 = 0: out = relu(x)), "no_c1" (W1 = 0: y1 = relu(b1) inside the image),
     "centre_tap" (only the centre tap of the 3x3 is non-zero: no shifted views), "full"."""
     from smap_amd import lib as L
-    from smap_amd.engine import TAIL_BN, ZERO_PAGE, pack_halo_rows, pack_rows16, split_f16
-    lib = L.load()
+    from smap_amd.engine import TAIL_BN, pack_halo_rows, pack_rows16, split_f16
     P, Cc = TILE_TABLE[tile].planes, 4 * TILE_TABLE[tile].planes      # 128 planes: csrc/convc.hip (layer2's width)
     g = torch.Generator().manual_seed(seed)
     x = torch.randn(B, H, W, Cc, generator=g)
@@ -548,25 +484,9 @@ def _run_block(B, H, W, tile, use_adds, seed=0, mode="full", relu=True, check=Tr
     wk3 = pack_halo_rows(torch.stack([hi, lo]), P, 9, P, True)
     hi, lo, sct = split_f16(wt.reshape(Cc, P).double())
     wkt = pack_halo_rows(torch.stack([hi, lo]), bn2, 1, P, True)
-    al = lambda n: (n + 255) // 256 * 256
-    raw8 = lambda t: t.contiguous().view(torch.uint8).reshape(-1)
-    chunks, woffs, cur = [raw8(wk3), raw8(b3), raw8(wkt), raw8(bt), raw8(wk1), raw8(b1)], [], 0
-    for c in chunks:
-        woffs.append(cur)
-        cur += al(c.numel())
-    blob = torch.zeros(cur, dtype=torch.uint8)
-    for c, o in zip(chunks, woffs):
-        blob[o:o + c.numel()] = c
-    parts, offs, cur = [x, a1, a2], [], ZERO_PAGE
-    stored = [_split(t) if t is not None else None for t in parts]
-    for t in stored:
-        offs.append(cur if t is not None else -1)
-        cur += al(t.numel() * 2) if t is not None else 0
-    out_off = cur
-    arena = torch.zeros(out_off + al(B * H * W * Cc * 4) + 256, dtype=torch.uint8)
-    for t, o in zip(stored, offs):
-        if t is not None:
-            arena[o:o + t.numel() * 2] = raw8(t)
+    blob, woffs = weight_blob([wk3, b3, wkt, bt, wk1, b1])
+    arena, offs = arena_of([t if t is None else stored(t) for t in (x, a1, a2)], B * H * W * Cc * 4)
+    out_off = offs[3]
     op = L.SmapOp()
     op.kind, op.B, op.H, op.W, op.Cin, op.in_stride_c, op.in_c_off = 0, B, H, W, P, Cc * 2, 0
     op.Ho, op.Wo, op.Cout, op.ksize, op.stride, op.pad, op.relu = H, W, P, 3, 1, 1, int(relu)
@@ -579,17 +499,10 @@ def _run_block(B, H, W, tile, use_adds, seed=0, mode="full", relu=True, check=Tr
     for i in range(3):
         op.aux_off[i] = -1
     op.ext_off = -1
-    h = C.c_void_p()
-    L.check(lib.smap_plan_create(C.byref(op), 1, C.byref(h)), "create")
-    arena_d, blob_d = arena.to(DEV), blob.to(DEV)
-    st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-    L.check(lib.smap_plan_run(h, None, C.c_void_p(arena_d.data_ptr()), C.c_void_p(blob_d.data_ptr()), None, st), "run")
-    torch.cuda.synchronize()
-    lib.smap_plan_destroy(h)
+    arena_d = run_plan(op, 1, arena, blob)
     if not check:                                            # tools/trace_convb.py: the launch is what matters
         return None, None
-    got = arena_d[out_off:out_off + B * H * W * Cc * 4].cpu().view(torch.float16).view(B, H, W, 2, Cc).float()
-    got = got[..., 0, :] + got[..., 1, :]
+    got = read_act(arena_d, out_off, (B, H, W, Cc), 2)
     xin = x.double().permute(0, 3, 1, 2)
     y = F.relu(F.conv2d(xin, w1.double(), b1.double()))
     y = F.relu(F.conv2d(y, w3.double(), b3.double(), padding=1))
@@ -606,8 +519,7 @@ def _run_block_first(B, H, W, tile, seed=0, mode="full", check=True):
     relu(W3 relu(W2 * relu(W1 x + b1) + b2) + b3 + Wd x + bd).  Modes: "residual" (W3 = 0: out = relu(Wd x + bd + b3)), "no_c1",
     "centre_tap", "full"."""
     from smap_amd import lib as L
-    from smap_amd.engine import ZERO_PAGE, pack_halo_rows, split_f16
-    lib = L.load()
+    from smap_amd.engine import pack_halo_rows, split_f16
     P, Cin, Cc = 64, 64, 256
     g = torch.Generator().manual_seed(seed)
     x = torch.randn(B, H, W, Cin, generator=g)
@@ -631,20 +543,8 @@ def _run_block_first(B, H, W, tile, seed=0, mode="full", check=True):
     sc1, sc3, sct, scd = (split_f16(t.double())[2] for t in (w1.reshape(P, Cin), w3.permute(0, 2, 3, 1).reshape(P, 9 * P), wt.reshape(Cc, P), wd.reshape(Cc, Cin)))
     wk1, wk3 = pk(w1.reshape(P, Cin), P, 1, Cin), pk(w3.permute(0, 2, 3, 1).reshape(P, 9 * P), P, 9, P)
     wkt, wkd = pk(wt.reshape(Cc, P), 64, 1, P), pk(wd.reshape(Cc, Cin), 64, 1, Cin)
-    al = lambda n: (n + 255) // 256 * 256
-    raw8 = lambda t: t.contiguous().view(torch.uint8).reshape(-1)
-    chunks, woffs, cur = [raw8(wk3), raw8(b3), raw8(wkt), raw8(bt + bd), raw8(wk1), raw8(b1), raw8(wkd)], [], 0
-    for c in chunks:
-        woffs.append(cur)
-        cur += al(c.numel())
-    blob = torch.zeros(cur, dtype=torch.uint8)
-    for c, o in zip(chunks, woffs):
-        blob[o:o + c.numel()] = c
-    xs = _split(x)
-    in_off = ZERO_PAGE
-    out_off = in_off + al(xs.numel() * 2)
-    arena = torch.zeros(out_off + al(B * H * W * Cc * 4) + 256, dtype=torch.uint8)
-    arena[in_off:in_off + xs.numel() * 2] = raw8(xs)
+    blob, woffs = weight_blob([wk3, b3, wkt, bt + bd, wk1, b1, wkd])
+    arena, (in_off, out_off) = arena_of([stored(x)], B * H * W * Cc * 4)
     op = L.SmapOp()
     op.kind, op.B, op.H, op.W, op.Cin, op.in_stride_c, op.in_c_off = 0, B, H, W, P, Cin * 2, 0
     op.Ho, op.Wo, op.Cout, op.ksize, op.stride, op.pad, op.relu = H, W, P, 3, 1, 1, 1
@@ -658,17 +558,10 @@ def _run_block_first(B, H, W, tile, seed=0, mode="full", check=True):
     for i in range(3):
         op.aux_off[i] = -1
     op.ext_off = -1
-    h = C.c_void_p()
-    L.check(lib.smap_plan_create(C.byref(op), 1, C.byref(h)), "create")
-    arena_d, blob_d = arena.to(DEV), blob.to(DEV)
-    st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-    L.check(lib.smap_plan_run(h, None, C.c_void_p(arena_d.data_ptr()), C.c_void_p(blob_d.data_ptr()), None, st), "run")
-    torch.cuda.synchronize()
-    lib.smap_plan_destroy(h)
+    arena_d = run_plan(op, 1, arena, blob)
     if not check:
         return None, None
-    got = arena_d[out_off:out_off + B * H * W * Cc * 4].cpu().view(torch.float16).view(B, H, W, 2, Cc).float()
-    got = got[..., 0, :] + got[..., 1, :]
+    got = read_act(arena_d, out_off, (B, H, W, Cc), 2)
     xin = x.double().permute(0, 3, 1, 2)
     y = F.relu(F.conv2d(xin, w1.double(), b1.double()))
     y = F.relu(F.conv2d(y, w3.double(), b3.double(), padding=1))
@@ -1082,7 +975,6 @@ def test_merged_1x1_launch_matches_torch(case, x3):
     add on segment 0 only, per-segment ReLU and accumulator scale."""
     import torch.nn.functional as F
     from smap_amd import engine as E
-    from smap_amd import lib as L
     B, H, W, cin, couts, relus, up, tile, w_pairs = (case + (1,))[:9]
     if E.tile_has(tile, "regepi", True) and not x3:
         pytest.skip("the register-epilogue tile has a split-precision instance only")
@@ -1102,39 +994,14 @@ def test_merged_1x1_launch_matches_torch(case, x3):
     xt = g.tensor("x", H, W, cin)
     ut = g.tensor("up", up[0], up[1], couts[0]) if up else None
     outs = g.conv_seg(segs, xt, up=ut, tile=tile)
-    xt.first = 0
-    if ut is not None:
-        ut.first = 0
-    g.allocate(reuse=False)
-    ops = g.emit()
-    lib = L.load()
-    h = C.c_void_p()
-    L.check(lib.smap_plan_create(ops, 1, C.byref(h)), "smap_plan_create")
-    arena = torch.zeros(g.arena_bytes, dtype=torch.uint8, device=DEV)
-
-    def put(t, v):                    # NCHW fp32 -> the tensor's storage (fp16, or hi | lo planes)
-        v = v.permute(0, 2, 3, 1).contiguous()
-        hi = v.to(torch.float16)
-        if t.planes == 2:
-            lo = (v - hi.float()).to(torch.float16)
-            raw = torch.stack([hi, lo], 3).reshape(-1)
-            val = (hi.double() + lo.double())
-        else:
-            raw, val = hi.reshape(-1), hi.double()
-        arena[t.off:t.off + t.nbytes].view(torch.float16).copy_(raw.to(DEV))
-        return val.permute(0, 3, 1, 2)
-    xv = put(xt, torch.randn(B, cin, H, W, generator=gen))
-    uv = put(ut, torch.randn(B, couts[0], up[0], up[1], generator=gen)) if up else None
-    blob = g.weight_blob().to(DEV)
-    st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-    L.check(lib.smap_plan_run(h, None, C.c_void_p(arena.data_ptr()), C.c_void_p(blob.data_ptr()), None, st), "run")
-    torch.cuda.synchronize()
-    lib.smap_plan_destroy(h)
+    arena = graph_arena(g, *([xt, ut] if up else [xt]))
+    xv = put(arena, xt, torch.randn(B, cin, H, W, generator=gen))
+    uv = put(arena, ut, torch.randn(B, couts[0], up[0], up[1], generator=gen)) if up else None
+    run_plan(g.emit(), 1, arena, g.weight_blob())
     p = g.ops[0].p
     refs = [(p["w_ref"], p["b_ref"], p["relu"])] + [(sg["w_ref"], sg["b_ref"], sg["relu"]) for sg in p["segs"]]
     for j, (t, (w, b, r)) in enumerate(zip(outs, refs)):
-        raw = arena[t.off:t.off + t.nbytes].view(torch.float16).cpu()
-        got = (raw.view(B, H, W, 2, t.C).double().sum(3) if t.planes == 2 else raw.view(B, H, W, t.C).double()).permute(0, 3, 1, 2)
+        got = get(arena, t)
         wq = w.double() if x3 else w.to(torch.float16).double()
         want = F.conv2d(xv, wq, b.double())
         if j == 0 and up:
@@ -1173,28 +1040,11 @@ def test_one_channel_3x3_head_as_tap_dots_and_a_stencil(shape, x3):
     xt = g.tensor("x", H, W, 256)
     t, b3 = g.conv_tapdot("t", "c1", "c3", xt)
     g.tapsum(t, b3, 0)
-    xt.first = 0
-    g.allocate(reuse=False)
-    ops = g.emit()
-    lib = L.load()
-    h = C.c_void_p()
-    L.check(lib.smap_plan_create(ops, 2, C.byref(h)), "smap_plan_create")
-    arena = torch.zeros(g.arena_bytes, dtype=torch.uint8, device=DEV)
-    v = torch.randn(B, 256, H, W, generator=gen).permute(0, 2, 3, 1).contiguous()
-    hi = v.to(torch.float16)
-    if xt.planes == 2:
-        lo = (v - hi.float()).to(torch.float16)
-        raw, val = torch.stack([hi, lo], 3).reshape(-1), hi.double() + lo.double()
-    else:
-        raw, val = hi.reshape(-1), hi.double()
-    arena[xt.off:xt.off + xt.nbytes].view(torch.float16).copy_(raw.to(DEV))
-    xv = val.permute(0, 3, 1, 2)
-    blob = g.weight_blob().to(DEV)
+    arena = graph_arena(g, xt)
+    xv = put(arena, xt, torch.randn(B, 256, H, W, generator=gen))
     out = torch.full((B * H * W + 1,), 7.0, dtype=torch.float32, device=DEV)
-    st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-    L.check(lib.smap_plan_run(h, None, C.c_void_p(arena.data_ptr()), C.c_void_p(blob.data_ptr()), C.c_void_p(out.data_ptr()), st), "run")
-    torch.cuda.synchronize()
-    lib.smap_plan_destroy(h)
+    ops, lib, h = g.emit(), L.load(), C.c_void_p()
+    run_plan(ops, 2, arena, g.weight_blob(), out)
     p = g.ops[0].p
     q = (lambda w: w.double()) if x3 else (lambda w: w.to(torch.float16).double())
     y = F.relu(F.conv2d(xv, q(p["w_ref"]), p["b_ref"].double()))
@@ -1202,8 +1052,7 @@ def test_one_channel_3x3_head_as_tap_dots_and_a_stencil(shape, x3):
     got = out[:B * H * W].view(B, 1, H, W).cpu().double()
     err, mx = (got - want).abs().max().item(), want.abs().max().item()
     assert int(out[-1:].view(torch.int32).item()) == 0 and err < ((3e-6 * mx + 1e-6) if x3 else 2e-3 * mx), (err, mx)
-    tt = arena[t.off:t.off + t.nbytes].view(torch.float32).view(B, H, W, 16).cpu()
-    assert not tt[..., 9:].any()                                                 # the padding lanes of a pixel's 16 floats
+    assert not get(arena, t)[:, 9:].any()                                                # the padding lanes of a pixel's 16 floats
     bad = (L.SmapOp * 2)(ops[0], ops[1])
     bad[0].tile = 50                                                             # only the one-N-tile 128 x 256 instance has the epilogue
     assert lib.smap_plan_create(bad, 2, C.byref(h)) == -1
@@ -1244,36 +1093,15 @@ def test_last_1x1_with_the_shortcut_conv_as_one_gemm(case, x3):
     g.w_pairs = int(B == 1)
     yt, xt = g.tensor("y", H, W, c1), g.tensor("x", H2, W2, c2)
     out = g.conv_cat("out", "c3", yt, "ds", xt, st2, relu=True, tile=tile)
-    yt.first = xt.first = 0
-    g.allocate(reuse=False)
-    ops = g.emit()
-    lib = L.load()
-    h = C.c_void_p()
-    L.check(lib.smap_plan_create(ops, 1, C.byref(h)), "smap_plan_create")
-    arena = torch.zeros(g.arena_bytes, dtype=torch.uint8, device=DEV)
-
-    def put(t, v):
-        v = v.permute(0, 2, 3, 1).contiguous()
-        hi = v.to(torch.float16)
-        if t.planes == 2:
-            lo = (v - hi.float()).to(torch.float16)
-            raw, val = torch.stack([hi, lo], 3).reshape(-1), hi.double() + lo.double()
-        else:
-            raw, val = hi.reshape(-1), hi.double()
-        arena[t.off:t.off + t.nbytes].view(torch.float16).copy_(raw.to(DEV))
-        return val.permute(0, 3, 1, 2)
-    yv = put(yt, torch.randn(B, c1, H, W, generator=gen))
-    xv = put(xt, torch.randn(B, c2, H2, W2, generator=gen))
-    blob = g.weight_blob().to(DEV)
-    st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-    L.check(lib.smap_plan_run(h, None, C.c_void_p(arena.data_ptr()), C.c_void_p(blob.data_ptr()), None, st), "run")
-    torch.cuda.synchronize()
-    lib.smap_plan_destroy(h)
+    arena = graph_arena(g, yt, xt)
+    yv = put(arena, yt, torch.randn(B, c1, H, W, generator=gen))
+    xv = put(arena, xt, torch.randn(B, c2, H2, W2, generator=gen))
+    ops, lib, h = g.emit(), L.load(), C.c_void_p()
+    run_plan(ops, 1, arena, g.weight_blob())
     p = g.ops[0].p
     q = (lambda w: w.double()) if x3 else (lambda w: w.to(torch.float16).double())
     want = F.relu(F.conv2d(yv, q(p["w_ref"]), p["b_ref"].double()) + F.conv2d(xv[:, :, ::st2, ::st2], q(p["cat"]["w_ref"]), p["cat"]["b_ref"].double()))
-    raw = arena[out.off:out.off + out.nbytes].view(torch.float16).cpu()
-    got = (raw.view(B, H, W, 2, out.C).double().sum(3) if out.planes == 2 else raw.view(B, H, W, out.C).double()).permute(0, 3, 1, 2)
+    got = get(arena, out)
     err, mx = (got - want).abs().max().item(), want.abs().max().item()
     assert torch.isfinite(got).all() and err < ((3e-6 * mx + 1e-6) if x3 else 2e-3 * mx), (err, mx)
     # and the plan refuses what the kernel cannot do: a second input on a tile without the instance, with split K, beyond the first input's window
@@ -1317,37 +1145,16 @@ def test_two_activated_skip_convs_as_one_launch_and_one_tensor(case, x3):
     g.w_pairs = int(B == 1)
     xt, ot = g.tensor("x", H, W, c1), g.tensor("o", H, W, c2)
     out = g.conv_relusum("s", "s1", xt, "s2", ot, tile=tile)
-    xt.first = ot.first = 0
-    g.allocate(reuse=False)
-    ops = g.emit()
-    lib = L.load()
-    h = C.c_void_p()
-    L.check(lib.smap_plan_create(ops, 1, C.byref(h)), "smap_plan_create")
-    arena = torch.zeros(g.arena_bytes, dtype=torch.uint8, device=DEV)
-
-    def put(t, v):
-        v = v.permute(0, 2, 3, 1).contiguous()
-        hi = v.to(torch.float16)
-        if t.planes == 2:
-            lo = (v - hi.float()).to(torch.float16)
-            raw, val = torch.stack([hi, lo], 3).reshape(-1), hi.double() + lo.double()
-        else:
-            raw, val = hi.reshape(-1), hi.double()
-        arena[t.off:t.off + t.nbytes].view(torch.float16).copy_(raw.to(DEV))
-        return val.permute(0, 3, 1, 2)
-    xv, ov = put(xt, torch.randn(B, c1, H, W, generator=gen) * 3), put(ot, torch.randn(B, c2, H, W, generator=gen))
-    blob = g.weight_blob().to(DEV)
-    st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-    L.check(lib.smap_plan_run(h, None, C.c_void_p(arena.data_ptr()), C.c_void_p(blob.data_ptr()), None, st), "run")
-    torch.cuda.synchronize()
-    lib.smap_plan_destroy(h)
+    arena = graph_arena(g, xt, ot)
+    xv, ov = put(arena, xt, torch.randn(B, c1, H, W, generator=gen) * 3), put(arena, ot, torch.randn(B, c2, H, W, generator=gen))
+    ops, lib, h = g.emit(), L.load(), C.c_void_p()
+    run_plan(ops, 1, arena, g.weight_blob())
     p = g.ops[0].p
     q = (lambda w: w.double()) if x3 else (lambda w: w.to(torch.float16).double())
     a, b = F.conv2d(xv, q(p["w_ref"]), p["b_ref"].double()), F.conv2d(ov, q(p["cat"]["w_ref"]), p["cat"]["b_ref"].double())
     want = F.relu(a) + F.relu(b)
     assert (a < 0).any() and (b < 0).any() and (a > 0).any() and (b > 0).any()          # both activations matter
-    raw = arena[out.off:out.off + out.nbytes].view(torch.float16).cpu()
-    got = (raw.view(B, H, W, 2, out.C).double().sum(3) if out.planes == 2 else raw.view(B, H, W, out.C).double()).permute(0, 3, 1, 2)
+    got = get(arena, out)
     err, mx = (got - want).abs().max().item(), want.abs().max().item()
     assert torch.isfinite(got).all() and err < ((3e-6 * mx + 1e-6) if x3 else 2e-3 * mx), (err, mx)
     bad = (L.SmapOp * 1)(ops[0])
