@@ -21,6 +21,7 @@
 #include <stdint.h>
 #include <type_traits>
 #include "smap_hip.h"
+#include "hip_rc.h"
 
 namespace {
 
@@ -32,8 +33,6 @@ __constant__ float c_bone_length[NL] = {
     26.42178982f, 48.36980909f, 14.88291009f, 31.28002332f, 23.915707f,
     14.97674918f, 31.28002549f, 23.91570732f, 12.4644364f,  48.26604433f,
     39.03553194f, 12.4644364f,  48.19076948f, 39.03553252f};
-
-inline int hip_rc(hipError_t e) { return e == hipSuccess ? 0 : -(1000 + (int)e); }
 
 // ------------------------------------------------------------------ scale --
 __global__ void scale_hms_kernel(float* __restrict__ hms, int HW4, int total4)

@@ -30,13 +30,9 @@
 #include <stdint.h>
 #include "smap_hip.h"
 #include "plan.h"
+#include "conv_device.h"
 
 namespace {
-
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __attribute__((address_space(3))) void lds_void;
-typedef const __attribute__((address_space(1))) void gbl_void;
 
 #ifndef SMAP_ABLATE
 #define SMAP_ABLATE 0            // experiments only (tools/build_ablate.py): 1 no loads, 2 no MFMA, 4 no stores, 8 no epilogue, 32 no bilinear tap loads, 64 no bilinear index math
@@ -118,12 +114,7 @@ __global__ __launch_bounds__(WM * WN * 64) void conv_igemm_kernel(const ConvArgs
     // ---- XCD-aware block order: blocks b, b+8, b+16.. run on one XCD; give each XCD a
     //      contiguous range of logical tiles so that the N-tiles of one M-tile (which
     //      re-read the same activation rows) share an L2.
-    int logical;
-    {
-        const int nblk = gridDim.x, bid = blockIdx.x;
-        const int q = nblk >> 3, r = nblk & 7, xcd = bid & 7, loc = bid >> 3;
-        logical = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + loc;
-    }
+    const int logical = xcd_logical_block();
     // SPLIT K (a.ksplit = S > 1: the launches of small schedules whose m_tiles x n_tiles do not fill the chip): S consecutive workgroups
     // -- neighbours in the logical order, hence mostly on one XCD / one L2 -- share an output tile and take the K tiles
     // [ks n / S, (ks + 1) n / S) each; their raw accumulators meet in a scratch buffer and the LAST one to arrive (a ticket per tile) sums
@@ -180,7 +171,7 @@ __global__ __launch_bounds__(WM * WN * 64) void conv_igemm_kernel(const ConvArgs
         const char* gB = wpair ? wt_tile + (long long)(it >> 1) * wblk + (it & 1) * 64 : wt_tile + (long long)it * wblk;   // wave-uniform
 #pragma unroll
         for (int j = 0; j < NPL * LB; ++j)
-            __builtin_amdgcn_global_load_lds((gbl_void*)(gB + w_off[j]), (lds_void*)(sB + (j * RPR + wave * RPW) * ROWB), 16, 0, 0);
+            lds_dma16(gB + w_off[j], sB + (j * RPR + wave * RPW) * ROWB);
     };
     // (the K range of a split-K workgroup is known only further down: its first weight tile goes out there)
     if (!(SMAP_ABLATE & 1) && !SPLITK) issue_b(0, 0);
@@ -269,7 +260,7 @@ __global__ __launch_bounds__(WM * WN * 64) void conv_igemm_kernel(const ConvArgs
             const char* gA = arena + (unsigned)(s_cc * ROWB + (X3 ? pl * ((DUAL && s_in2) ? a.in2_lo : a.in_lo) * 2 : 0));
 #pragma unroll
             for (int i = 0; i < LA; ++i)
-                __builtin_amdgcn_global_load_lds((gbl_void*)(gA + a_cur[i]), (lds_void*)(sA + (i * RPR + wave * RPW) * ROWB), 16, 0, 0);
+                lds_dma16(gA + a_cur[i], sA + (i * RPR + wave * RPW) * ROWB);
         }
     };
     auto advance = [&]() {
@@ -468,11 +459,9 @@ __global__ __launch_bounds__(WM * WN * 64) void conv_igemm_kernel(const ConvArgs
                 for (int j = 0; j < 2; ++j)
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
-                        const float xf = c[8 * j + e], yf = c[8 * j + 4 + e];
-                        const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(xf), __float_as_uint(yf), false, false);
-                        const unsigned s0 = sw[0], s1 = sw[1];
-                        c[8 * j + e] = o_scale * __uint_as_float(s0);                       // (bias inside)
-                        c[8 * j + 4 + e] = o_scale * __uint_as_float(s1);
+                        const float2 sw = halfwave_swap(c[8 * j + e], c[8 * j + 4 + e]);
+                        c[8 * j + e] = o_scale * sw.x;                       // (bias inside)
+                        c[8 * j + 4 + e] = o_scale * sw.y;
                     }
                 if (o_res) {
 #pragma unroll
@@ -480,10 +469,7 @@ __global__ __launch_bounds__(WM * WN * 64) void conv_igemm_kernel(const ConvArgs
 #pragma unroll
                         for (int e = 0; e < 8; ++e) c[8 * j + e] += (float)rr[blk & 1][j][0][e] + (float)rr[blk & 1][j][NPL - 1][e];
                 }
-                if (o_relu) {
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) c[r] = c[r] < 0.f ? 0.f : c[r];            // NaN stays NaN (torch's ReLU)
-                }
+                if (o_relu) relu16(c);
 #pragma unroll
                 for (int j = 0; j < 2; ++j) {
                     const int n = n_of(ni) + 16 * j;
@@ -580,8 +566,7 @@ __global__ __launch_bounds__(WM * WN * 64) void conv_igemm_kernel(const ConvArgs
         //      order.  Lane l: A = 8 channels 32 ks + 8 (l / 16) .. of pixel row l % 16 (one 32-byte LDS read; the row stride is padded by 8
         //      floats, so the 16 rows of a lane group fall on different banks); D[i] = pixel 4 (l / 16) + i, tap l % 16.
         static_assert(BM == 128 && BN == 256 && NW == 8, "one 16-row MFMA tile per wave");
-        typedef float f32x4 __attribute__((ext_vector_type(4)));
-        const int prow = wave * 16 + (lane & 15), kq = lane >> 4;
+                const int prow = wave * 16 + (lane & 15), kq = lane >> 4;
         const half8* __restrict__ wfrag = reinterpret_cast<const half8*>(a.tap_w) + lane;
         f32x4 d = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll

@@ -25,6 +25,7 @@
 #include <stdint.h>
 #include "smap_hip.h"
 #include "plan.h"
+#include "conv_device.h"
 
 #ifndef SMAP_STAG_DMA_IN_MFMA
 #define SMAP_STAG_DMA_IN_MFMA 0   // staggered schedule: LDS-DMA requests issued from inside the MFMA burst instead of the read phase
@@ -37,23 +38,6 @@
 #endif
 
 namespace {
-
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __attribute__((address_space(3))) void lds_void;
-typedef const __attribute__((address_space(1))) void gbl_void;
-
-// s_waitcnt vmcnt(n) for a value that is a constant after unrolling (the switch folds away)
-__device__ __forceinline__ void wait_vm(int n)
-{
-    switch (n) {
-#define W_(k) case k: asm volatile("s_waitcnt vmcnt(" #k ")" ::: "memory"); break;
-        W_(0) W_(1) W_(2) W_(3) W_(4) W_(5) W_(6) W_(7) W_(8) W_(9) W_(10) W_(11) W_(12) W_(13) W_(14) W_(15) W_(16)
-        W_(17) W_(18) W_(19) W_(20) W_(21) W_(22) W_(23) W_(24)
-#undef W_
-        default: asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
-}
 
 // ONE = the layer has a single 64-channel chunk (Cin = 64: the layer1 3x3s): no second patch buffer, which takes the
 // workgroup from 80 to 52 KB of LDS (three per CU instead of two; residency is what these kernels are short of).
@@ -105,12 +89,7 @@ __global__ __launch_bounds__(NWV * 64, WPE) void conv3x3_halo_kernel(const ConvA
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
 
-    int logical;                                                // XCD-aware order, n tile fastest
-    {
-        const int nblk = gridDim.x, bid = blockIdx.x;
-        const int q = nblk >> 3, r = nblk & 7, xcd = bid & 7, loc = bid >> 3;
-        logical = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + loc;
-    }
+    const int logical = xcd_logical_block();                    // XCD-aware order, n tile fastest
     const int n_tile = logical % a.n_tiles;
     int t = logical / a.n_tiles;
     const int tx = t % tiles_x;

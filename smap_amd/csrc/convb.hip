@@ -32,6 +32,7 @@
 #include <stdint.h>
 #include "smap_hip.h"
 #include "plan.h"
+#include "conv_device.h"
 
 #ifndef SMAP_CONVB_LDS_KB
 #define SMAP_CONVB_LDS_KB 80     // LDS per workgroup (two per CU); experiments: 64
@@ -76,30 +77,6 @@ __device__ __forceinline__ void convb_stagger()
 #endif                           // 4 no global stores, 8 no weight loads (W1 stages and the slot ring)
 
 namespace {
-
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef _Float16 half4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __attribute__((address_space(3))) void lds_void;
-typedef const __attribute__((address_space(1))) void gbl_void;
-
-__device__ __forceinline__ void wait_vm(int n)
-{
-    switch (n) {
-#define W_(k) case k: asm volatile("s_waitcnt vmcnt(" #k ")" ::: "memory"); break;
-        W_(0) W_(1) W_(2) W_(3) W_(4) W_(5) W_(6) W_(7) W_(8) W_(9) W_(10) W_(11) W_(12) W_(13) W_(14) W_(15) W_(16)
-#undef W_
-        default: asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
-}
-
-// every LDS read of this wave has returned, then the workgroup barrier (raw: an LDS-DMA in flight must survive it)
-__device__ __forceinline__ void lds_barrier()
-{
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-}
 
 // (diagnostics: an MFMA that can be compiled out, keeping its operands alive)
 __device__ __forceinline__ f32x16 MFMA_(half8 x, half8 y, f32x16 c, int, int, int)
@@ -154,13 +131,7 @@ __global__ __launch_bounds__(256, TH == 4 ? SMAP_CONVB_WGS4 : 2) void bottleneck
 #define TRB(i)
 #endif
     TRB(0);
-    int logical;                                                // XCD-aware order (conv.hip): neighbouring tiles share an L2
-    {
-        const int nblk = gridDim.x, bid = blockIdx.x;
-        const int q = nblk >> 3, r = nblk & 7, xcd = bid & 7, loc = bid >> 3;
-        logical = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + loc;
-    }
-    int t = logical;
+    int t = xcd_logical_block();                                // XCD-aware order (conv.hip): neighbouring tiles share an L2
     const int tx = t % tiles_x;
     t /= tiles_x;
     const int ty = t % tiles_y, b = t / tiles_y;
@@ -192,11 +163,11 @@ __global__ __launch_bounds__(256, TH == 4 ? SMAP_CONVB_WGS4 : 2) void bottleneck
         const char* gA = arena + (unsigned)(ks * CH1 * 2);      // invalid rows: zero page + stage offset
 #pragma unroll
         for (int i = 0; i < ((SMAP_CONVB_ABLATE & 1) ? 0 : LA); ++i)
-            __builtin_amdgcn_global_load_lds((gbl_void*)(gA + a_off[i]), (lds_void*)(sX + (i * 64 + wave * 16) * ROW1), 16, 0, 0);
+            lds_dma16(gA + a_off[i], sX + (i * 64 + wave * 16) * ROW1);
         const char* gW = w1g + (long long)ks * WS1 + (unsigned)(wave * 1024 + lane * 16);
 #pragma unroll
         for (int i = 0; i < ((SMAP_CONVB_ABLATE & 8) ? 0 : LB1); ++i)
-            __builtin_amdgcn_global_load_lds((gbl_void*)(gW + i * 4096), (lds_void*)(sX + XS + i * 4096 + wave * 1024), 16, 0, 0);
+            lds_dma16(gW + i * 4096, sX + XS + i * 4096 + wave * 1024);
     };
     // centre pixels of this lane in phases 2 and 3: p = wm*(MI*32) + mi*32 + l31 -> patch row of the pixel itself
     int crow[MI];
@@ -241,7 +212,7 @@ __global__ __launch_bounds__(256, TH == 4 ? SMAP_CONVB_WGS4 : 2) void bottleneck
     for (int ks = 0; ks < KS1; ++ks) {
         if (ks + NS1 - 1 <= KS1) wait_vm((NS1 - 2) * LPT1);     // stage ks has landed; younger stages stay in flight
         else wait_vm((KS1 - 1 - ks) * LPT1);
-        lds_barrier();
+        lds_barrier_asm();
         if (ks + NS1 - 1 < KS1) issue1((ks + NS1 - 1) % NS1, ks + NS1 - 1);     // into the buffer stage ks-1 was read from
         const char* sX = smem + (ks % NS1) * ST1;
         const char* sW = sX + XS;
@@ -282,7 +253,7 @@ __global__ __launch_bounds__(256, TH == 4 ? SMAP_CONVB_WGS4 : 2) void bottleneck
         }
         CONVB_PRIO(0);
     }
-    lds_barrier();                                              // every wave is done with the staging buffers (all DMA has landed)
+    lds_barrier_asm();                                              // every wave is done with the staging buffers (all DMA has landed)
     TRB(2);
     // phase 2's accumulators start at b2 / scale: the loads go out now, ahead of the first weight slots, and are consumed after
     // y1 has been written (the wait hipcc puts there covers slot 0, which is needed then anyway)
@@ -301,7 +272,7 @@ __global__ __launch_bounds__(256, TH == 4 ? SMAP_CONVB_WGS4 : 2) void bottleneck
         const char* g = (s < NS2 ? w2g + (long long)((s % KC2) * NTAP + s / KC2) * SLOT : w3g + (long long)(s - NS2) * SLOT) + wlane;
 #pragma unroll
         for (int i = 0; i < ((SMAP_CONVB_ABLATE & 8) ? 0 : LS); ++i)
-            __builtin_amdgcn_global_load_lds((gbl_void*)(g + i * 4096), (lds_void*)(dst + i * 4096), 16, 0, 0);
+            lds_dma16(g + i * 4096, dst + i * 4096);
     };
 #pragma unroll
     for (int s = 0; s < NS - 1; ++s) issue_slot(s);
@@ -364,7 +335,7 @@ __global__ __launch_bounds__(256, TH == 4 ? SMAP_CONVB_WGS4 : 2) void bottleneck
 
 #pragma unroll
     for (int s = 0; s < NS2; ++s) {
-        lds_barrier();                                          // slot s landed for every wave; y1 complete (s = 0); slot s-1's buffer is free
+        lds_barrier_asm();                                          // slot s landed for every wave; y1 complete (s = 0); slot s-1's buffer is free
         if (s + NS - 1 < NSLOT) issue_slot(s + NS - 1);
         const char* sB = ring + (s % NS) * SLOT;
         const int tap = s / KC2, cc = s % KC2;
@@ -393,7 +364,7 @@ __global__ __launch_bounds__(256, TH == 4 ? SMAP_CONVB_WGS4 : 2) void bottleneck
         }
         wait_slots(s, s + 1 < NS2 ? s + 1 : s + 2);            // the last tap also waits for both slots of the first tail chunk
     }
-    lds_barrier();                                              // every wave is done with y1: y2 may overwrite it
+    lds_barrier_asm();                                              // every wave is done with y1: y2 may overwrite it
     TRB(4);
 
     // ---- accumulators -> y2 [KC2][BM][128 B] (rows = tile pixels).  acc2[mi][4*q + e] = channel wn*32 + 8*q + 4*lhi + e
@@ -443,7 +414,7 @@ __global__ __launch_bounds__(256, TH == 4 ? SMAP_CONVB_WGS4 : 2) void bottleneck
 #pragma unroll
         for (int kc = 0; kc < KC2; ++kc) {
             const int s = NS2 + nc * KC2 + kc;
-            lds_barrier();                                      // slot s landed for every wave; y2 + bias table complete (first slot); slot s-1's buffer is free
+            lds_barrier_asm();                                      // slot s landed for every wave; y2 + bias table complete (first slot); slot s-1's buffer is free
             if (s + NS - 1 < NSLOT) issue_slot(s + NS - 1);
             const char* sW = ring + (s % NS) * SLOT;
             if (kc == 0) {
@@ -486,11 +457,9 @@ __global__ __launch_bounds__(256, TH == 4 ? SMAP_CONVB_WGS4 : 2) void bottleneck
             for (int j = 0; j < 2; ++j)
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
-                    const float xf = acc3[mi][8 * j + e], yf = acc3[mi][8 * j + 4 + e];   // (bit_cast of a vector ELEMENT lvalue reads element 0)
-                    const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(xf), __float_as_uint(yf), false, false);
-                    const unsigned s0 = sw[0], s1 = sw[1];
-                    acc3[mi][8 * j + e] = a.tail_acc_scale * __uint_as_float(s0);       // (bias inside)
-                    acc3[mi][8 * j + 4 + e] = a.tail_acc_scale * __uint_as_float(s1);
+                    const float2 sw = halfwave_swap(acc3[mi][8 * j + e], acc3[mi][8 * j + 4 + e]);
+                    acc3[mi][8 * j + e] = a.tail_acc_scale * sw.x;       // (bias inside)
+                    acc3[mi][8 * j + 4 + e] = a.tail_acc_scale * sw.y;
                 }
 #pragma unroll
         for (int mi = 0; mi < MI; ++mi)                          // + x, from the registers filled in phase 1
@@ -500,9 +469,7 @@ __global__ __launch_bounds__(256, TH == 4 ? SMAP_CONVB_WGS4 : 2) void bottleneck
                 for (int e = 0; e < 8; ++e) acc3[mi][8 * j + e] += (float)rs[nc][mi][j][0][e] + (float)rs[nc][mi][j][1][e];
         if (a.relu) {
 #pragma unroll
-            for (int mi = 0; mi < MI; ++mi)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc3[mi][r] = acc3[mi][r] < 0.f ? 0.f : acc3[mi][r];
+            for (int mi = 0; mi < MI; ++mi) relu16(acc3[mi]);
         }
         auto add_tensor = [&](const _Float16* __restrict__ tsr) {       // post-ReLU skip adds of the last block of a layer
             half8 h[MI][2][2];
@@ -516,9 +483,7 @@ __global__ __launch_bounds__(256, TH == 4 ? SMAP_CONVB_WGS4 : 2) void bottleneck
 #pragma unroll
             for (int mi = 0; mi < MI; ++mi)
 #pragma unroll
-                for (int j = 0; j < 2; ++j)
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) acc3[mi][8 * j + e] += (float)h[mi][j][0][e] + (float)h[mi][j][1][e];
+                for (int j = 0; j < 2; ++j) add_planes8(acc3[mi], j, h[mi][j]);
         };
         if (a.add1) add_tensor(a.add1);
         if (a.add2) add_tensor(a.add2);
@@ -590,13 +555,7 @@ __global__ __launch_bounds__(256, TH == 4 ? SMAP_CONVB_WGS4 : 2) void bottleneck
 #define TRB(i)
 #endif
     TRB(0);
-    int logical;                                                // XCD-aware order (conv.hip): neighbouring tiles share an L2
-    {
-        const int nblk = gridDim.x, bid = blockIdx.x;
-        const int q = nblk >> 3, r = nblk & 7, xcd = bid & 7, loc = bid >> 3;
-        logical = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + loc;
-    }
-    int t = logical;
+    int t = xcd_logical_block();                                // XCD-aware order (conv.hip): neighbouring tiles share an L2
     const int tx = t % tiles_x;
     t /= tiles_x;
     const int ty = t % tiles_y, b = t / tiles_y;
@@ -661,7 +620,7 @@ __global__ __launch_bounds__(256, TH == 4 ? SMAP_CONVB_WGS4 : 2) void bottleneck
                          t2 < NS2 ? w2g + (long long)((t2 % KC2) * NTAP + t2 / KC2) * SLOT : w3g + (long long)(t2 - NS2) * SLOT) + wlane;
 #pragma unroll
         for (int i = 0; i < LS; ++i)
-            __builtin_amdgcn_global_load_lds((gbl_void*)(g + i * 4096), (lds_void*)(dst + i * 4096), 16, 0, 0);
+            lds_dma16(g + i * 4096, dst + i * 4096);
     };
 #pragma unroll
     for (int s = 0; s < NS - 1; ++s) issue_slot(s);
@@ -716,7 +675,7 @@ __global__ __launch_bounds__(256, TH == 4 ? SMAP_CONVB_WGS4 : 2) void bottleneck
     // ================================================================= phase 1a: y1 = relu(W1 x + b1) on the halo patch (K = 64: two slots)
 #pragma unroll
     for (int s = 0; s < S1; ++s) {
-        lds_barrier();
+        lds_barrier_asm();
         if (s + NS - 1 < NSLOT) issue_slot(s + NS - 1);
         const char* sW = ring + (s % NS) * SLOT;
 #pragma unroll
@@ -766,7 +725,7 @@ __global__ __launch_bounds__(256, TH == 4 ? SMAP_CONVB_WGS4 : 2) void bottleneck
 #pragma unroll
         for (int kc = 0; kc < KC2; ++kc) {
             const int s = S1 + nc * KC2 + kc;
-            lds_barrier();
+            lds_barrier_asm();
             if (s + NS - 1 < NSLOT) issue_slot(s + NS - 1);
             const char* sW = ring + (s % NS) * SLOT;
 #pragma unroll
@@ -789,7 +748,7 @@ __global__ __launch_bounds__(256, TH == 4 ? SMAP_CONVB_WGS4 : 2) void bottleneck
             }
             wait_slots(s, s + 1);
         }
-    lds_barrier();                                              // every wave is done with the x patch: y1 takes its place
+    lds_barrier_asm();                                              // every wave is done with the x patch: y1 takes its place
     TRB(2);
     put_y1(acc1[0], 0, wave);
     put_y1(acc1[1], 1, wave);
@@ -810,7 +769,7 @@ __global__ __launch_bounds__(256, TH == 4 ? SMAP_CONVB_WGS4 : 2) void bottleneck
 #pragma unroll
     for (int t2 = 0; t2 < NS2; ++t2) {
         const int s = SB + t2;
-        lds_barrier();                                          // slot s landed for every wave; y1 complete (first tap); slot s-1's buffer is free
+        lds_barrier_asm();                                          // slot s landed for every wave; y1 complete (first tap); slot s-1's buffer is free
         if (s + NS - 1 < NSLOT) issue_slot(s + NS - 1);
         const char* sB = ring + (s % NS) * SLOT;
         const int tap = t2 / KC2, cc = t2 % KC2;
@@ -837,7 +796,7 @@ __global__ __launch_bounds__(256, TH == 4 ? SMAP_CONVB_WGS4 : 2) void bottleneck
         }
         wait_slots(s, t2 + 1 < NS2 ? s + 1 : s + 2);           // the last tap also waits for both slots of the first tail chunk
     }
-    lds_barrier();                                              // every wave is done with y1: y2 may overwrite it
+    lds_barrier_asm();                                              // every wave is done with y1: y2 may overwrite it
     TRB(4);
 
     // ---- bias tables in the part of y1's region that y2 leaves free: [C] (b3 + shortcut bias) / tail scale, [P] b2
@@ -845,7 +804,7 @@ __global__ __launch_bounds__(256, TH == 4 ? SMAP_CONVB_WGS4 : 2) void bottleneck
     float* sB2 = sB3 + C;
     sB3[tid] = b3_mine * (1.f / a.tail_acc_scale);
     if (tid < P) sB2[tid] = b2_mine;
-    lds_barrier();
+    lds_barrier_asm();
     // ---- accumulators -> y2 [KC2][BM][128 B] (rows = tile pixels).  acc2[mi][4*q + e] = channel wn*32 + 8*q + 4*lhi + e
     char* sY2 = smem;
 #pragma unroll
@@ -891,7 +850,7 @@ __global__ __launch_bounds__(256, TH == 4 ? SMAP_CONVB_WGS4 : 2) void bottleneck
 #pragma unroll
         for (int kc = 0; kc < KC2; ++kc) {
             const int s = SB + NS2 + nc * KC2 + kc;
-            lds_barrier();                                      // slot s landed for every wave; y2 + bias table complete (first slot); slot s-1's buffer is free
+            lds_barrier_asm();                                      // slot s landed for every wave; y2 + bias table complete (first slot); slot s-1's buffer is free
             if (s + NS - 1 < NSLOT) issue_slot(s + NS - 1);
             const char* sW = ring + (s % NS) * SLOT;
             if (kc == 0) {
@@ -939,17 +898,13 @@ __global__ __launch_bounds__(256, TH == 4 ? SMAP_CONVB_WGS4 : 2) void bottleneck
             for (int j = 0; j < 2; ++j)
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
-                    const float xf = acc3[mi][8 * j + e], yf = acc3[mi][8 * j + 4 + e];   // (bit_cast of a vector ELEMENT lvalue reads element 0)
-                    const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(xf), __float_as_uint(yf), false, false);
-                    const unsigned s0 = sw[0], s1 = sw[1];
-                    acc3[mi][8 * j + e] = a.tail_acc_scale * __uint_as_float(s0);       // (bias inside)
-                    acc3[mi][8 * j + 4 + e] = a.tail_acc_scale * __uint_as_float(s1);
+                    const float2 sw = halfwave_swap(acc3[mi][8 * j + e], acc3[mi][8 * j + 4 + e]);
+                    acc3[mi][8 * j + e] = a.tail_acc_scale * sw.x;       // (bias inside)
+                    acc3[mi][8 * j + 4 + e] = a.tail_acc_scale * sw.y;
                 }
         if (a.relu) {
 #pragma unroll
-            for (int mi = 0; mi < MI; ++mi)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc3[mi][r] = acc3[mi][r] < 0.f ? 0.f : acc3[mi][r];
+            for (int mi = 0; mi < MI; ++mi) relu16(acc3[mi]);
         }
         auto add_tensor = [&](const _Float16* __restrict__ tsr) {       // post-ReLU skip adds of the last block of a layer
             half8 h[MI][2][2];
@@ -963,9 +918,7 @@ __global__ __launch_bounds__(256, TH == 4 ? SMAP_CONVB_WGS4 : 2) void bottleneck
 #pragma unroll
             for (int mi = 0; mi < MI; ++mi)
 #pragma unroll
-                for (int j = 0; j < 2; ++j)
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) acc3[mi][8 * j + e] += (float)h[mi][j][0][e] + (float)h[mi][j][1][e];
+                for (int j = 0; j < 2; ++j) add_planes8(acc3[mi], j, h[mi][j]);
         };
         if (a.add1) add_tensor(a.add1);
         if (a.add2) add_tensor(a.add2);

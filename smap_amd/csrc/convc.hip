@@ -24,15 +24,9 @@
 #include <stdint.h>
 #include "smap_hip.h"
 #include "plan.h"
+#include "conv_device.h"
 
 namespace {
-
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef _Float16 half4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) void lds_void;
-typedef const __attribute__((address_space(1))) void gbl_void;
 
 // Residual chunks (of four) whose values are copied into registers while x streams through LDS in phase 1; the others are read again from
 // L2 / Infinity Cache while their chunk of the tail is multiplied.  Round 6: 2 (64 registers) instead of 3 (96) -- the registers pay for a
@@ -44,31 +38,14 @@ typedef const __attribute__((address_space(1))) void gbl_void;
 #define SMAP_CONVC_PIPE 1          // 0 = round 5's loops (fragments single-buffered, read -> wait -> multiply inside every K step)
 #endif
 
-__device__ __forceinline__ void wait_vm(int n)
-{
-    switch (n) {
-#define W_(k) case k: asm volatile("s_waitcnt vmcnt(" #k ")" ::: "memory"); break;
-        W_(0) W_(1) W_(2) W_(3) W_(4) W_(5) W_(6) W_(7) W_(8) W_(9) W_(10) W_(11) W_(12) W_(13) W_(14) W_(15) W_(16)
-#undef W_
-        default: asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
-}
-
-// every LDS read of this wave has returned, then the workgroup barrier (raw: an LDS-DMA in flight must survive it)
-// all LDS reads of this wave have landed (the builtin: hipcc's wait-count pass sees it and adds no lgkmcnt(0) of its own further down)
-__device__ __forceinline__ void lds_reads_landed() { __builtin_amdgcn_s_waitcnt(0xC07F); }
-
+// SMAP_CONVC_PIPE: the barrier whose wait hipcc's wait-count pass sees (conv_device.h says why); round 5's loops keep the inline-asm form
 __device__ __forceinline__ void lds_barrier()
 {
 #if SMAP_CONVC_PIPE
-    // the BUILTIN, not inline asm: hipcc's wait-count pass then knows that the fragment set read before the barrier has landed and puts no
-    // lgkmcnt(0) in front of the MFMAs that use it behind the barrier (gfx9 encoding: vmcnt = 63 and expcnt = 7 "don't wait", lgkmcnt = 0)
-    __builtin_amdgcn_s_waitcnt(0xC07F);
+    lds_barrier_builtin();
 #else
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    lds_barrier_asm();
 #endif
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
 }
 
 #ifndef SMAP_CONVC_ABLATE
@@ -109,13 +86,7 @@ __global__ __launch_bounds__(512, 2) void bottleneck128_kernel(const ConvArgs a,
     SMAP_TL_BEGIN
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    int logical;                                                // XCD-aware order (conv.hip): neighbouring tiles share an L2
-    {
-        const int nblk = gridDim.x, bid = blockIdx.x;
-        const int q = nblk >> 3, r = nblk & 7, xcd = bid & 7, loc = bid >> 3;
-        logical = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + loc;
-    }
-    int t = logical;
+    int t = xcd_logical_block();                                // XCD-aware order (conv.hip): neighbouring tiles share an L2
     const int tx = t % tiles_x;
     t /= tiles_x;
     const int ty = t % tiles_y, b = t / tiles_y;
@@ -148,11 +119,11 @@ __global__ __launch_bounds__(512, 2) void bottleneck128_kernel(const ConvArgs a,
         const char* gA = arena + (unsigned)(ks * CH * 2);       // invalid rows: zero page + stage offset
 #pragma unroll
         for (int i = 0; i < ((SMAP_CONVC_ABLATE & 1) ? 0 : LA); ++i)
-            __builtin_amdgcn_global_load_lds((gbl_void*)(gA + a_off[i]), (lds_void*)(sX + (i * 64 + wave * 8) * ROWB), 16, 0, 0);
+            lds_dma16(gA + a_off[i], sX + (i * 64 + wave * 8) * ROWB);
         const char* gW = w1g + (long long)ks * WS1 + wlane;
 #pragma unroll
         for (int i = 0; i < ((SMAP_CONVC_ABLATE & 8) ? 0 : LB1); ++i)
-            __builtin_amdgcn_global_load_lds((gbl_void*)(gW + i * (NW * 1024)), (lds_void*)(sX + XS + i * (NW * 1024) + wave * 1024), 16, 0, 0);
+            lds_dma16(gW + i * (NW * 1024), sX + XS + i * (NW * 1024) + wave * 1024);
     };
     // centre pixels of this lane in phases 2 and 3: p = wm*64 + mi*32 + l31 -> patch row of the pixel itself
     int crow[MI];
@@ -308,7 +279,7 @@ __global__ __launch_bounds__(512, 2) void bottleneck128_kernel(const ConvArgs a,
         const char* g = (s < NS2 ? w2g + (long long)((s % KC) * NTAP + s / KC) * SLOT : w3g + (long long)(s - NS2) * SLOT) + wlane;
 #pragma unroll
         for (int i = 0; i < ((SMAP_CONVC_ABLATE & 8) ? 0 : LS); ++i)
-            __builtin_amdgcn_global_load_lds((gbl_void*)(g + i * (NW * 1024)), (lds_void*)(dst + i * (NW * 1024)), 16, 0, 0);
+            lds_dma16(g + i * (NW * 1024), dst + i * (NW * 1024));
     };
 #pragma unroll
     for (int s = 0; s < NS - 1; ++s) issue_slot(s);
@@ -540,11 +511,9 @@ __global__ __launch_bounds__(512, 2) void bottleneck128_kernel(const ConvArgs a,
             for (int j = 0; j < 2; ++j)
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
-                    const float xf = acc3[mi][8 * j + e], yf = acc3[mi][8 * j + 4 + e];   // (bit_cast of a vector ELEMENT lvalue reads element 0)
-                    const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(xf), __float_as_uint(yf), false, false);
-                    const unsigned s0 = sw[0], s1 = sw[1];
-                    acc3[mi][8 * j + e] = a.tail_acc_scale * __uint_as_float(s0);       // (bias inside)
-                    acc3[mi][8 * j + 4 + e] = a.tail_acc_scale * __uint_as_float(s1);
+                    const float2 sw = halfwave_swap(acc3[mi][8 * j + e], acc3[mi][8 * j + 4 + e]);
+                    acc3[mi][8 * j + e] = a.tail_acc_scale * sw.x;       // (bias inside)
+                    acc3[mi][8 * j + 4 + e] = a.tail_acc_scale * sw.y;
                 }
 #pragma unroll
         for (int mi = 0; mi < MI; ++mi)                          // + x, from the registers filled in phase 1
@@ -556,9 +525,7 @@ __global__ __launch_bounds__(512, 2) void bottleneck128_kernel(const ConvArgs a,
                                                     : (float)rl[mi][j][0][e] + (float)rl[mi][j][1][e];
         if (a.relu) {
 #pragma unroll
-            for (int mi = 0; mi < MI; ++mi)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc3[mi][r] = acc3[mi][r] < 0.f ? 0.f : acc3[mi][r];
+            for (int mi = 0; mi < MI; ++mi) relu16(acc3[mi]);
         }
         auto add_tensor = [&](const _Float16* __restrict__ tsr) {       // post-ReLU skip adds of the last block of a layer; one pixel block at
 #pragma unroll                                                          // a time: the residual registers leave room for 16 more, not 32
@@ -691,11 +658,9 @@ __global__ __launch_bounds__(512, 2) void bottleneck128_kernel(const ConvArgs a,
             for (int j = 0; j < 2; ++j)
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
-                    const float xf = acc3[mi][8 * j + e], yf = acc3[mi][8 * j + 4 + e];   // (bit_cast of a vector ELEMENT lvalue reads element 0)
-                    const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(xf), __float_as_uint(yf), false, false);
-                    const unsigned s0 = sw[0], s1 = sw[1];
-                    acc3[mi][8 * j + e] = a.tail_acc_scale * __uint_as_float(s0);       // (bias inside)
-                    acc3[mi][8 * j + 4 + e] = a.tail_acc_scale * __uint_as_float(s1);
+                    const float2 sw = halfwave_swap(acc3[mi][8 * j + e], acc3[mi][8 * j + 4 + e]);
+                    acc3[mi][8 * j + e] = a.tail_acc_scale * sw.x;       // (bias inside)
+                    acc3[mi][8 * j + 4 + e] = a.tail_acc_scale * sw.y;
                 }
 #pragma unroll
         for (int mi = 0; mi < MI; ++mi)                          // + x, from the registers filled in phase 1
@@ -707,9 +672,7 @@ __global__ __launch_bounds__(512, 2) void bottleneck128_kernel(const ConvArgs a,
                                                     : (float)rl[mi][j][0][e] + (float)rl[mi][j][1][e];
         if (a.relu) {
 #pragma unroll
-            for (int mi = 0; mi < MI; ++mi)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc3[mi][r] = acc3[mi][r] < 0.f ? 0.f : acc3[mi][r];
+            for (int mi = 0; mi < MI; ++mi) relu16(acc3[mi]);
         }
         auto add_tensor = [&](const _Float16* __restrict__ tsr) {       // post-ReLU skip adds of the last block of a layer; one pixel block at
 #pragma unroll                                                          // a time: the residual registers leave room for 16 more, not 32

@@ -18,25 +18,9 @@
 #include <stdint.h>
 #include "smap_hip.h"
 #include "plan.h"
+#include "conv_device.h"
 
 namespace {
-
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef _Float16 half4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __attribute__((address_space(3))) void lds_void;
-typedef const __attribute__((address_space(1))) void gbl_void;
-
-__device__ __forceinline__ void wait_vm(int n)
-{
-    switch (n) {
-#define W_(k) case k: asm volatile("s_waitcnt vmcnt(" #k ")" ::: "memory"); break;
-        W_(0) W_(1) W_(2) W_(3) W_(4) W_(5) W_(6) W_(7) W_(8) W_(9) W_(10) W_(11) W_(12) W_(13) W_(14) W_(15) W_(16)
-        W_(17) W_(18) W_(19) W_(20) W_(21) W_(22) W_(23) W_(24)
-#undef W_
-        default: asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
-}
 
 // (Phase-2 scheduling variants measured in situ and dropped, profiles/r3_ab_tail_variants.log: first weight chunk prefetched
 // under the 3x3's last channel chunk: +-0; chunk barrier before the stores and the residual requested a chunk ahead: -0.5 %.)
@@ -67,13 +51,7 @@ __global__ __launch_bounds__(256) void conv3_tail_kernel(const ConvArgs a, int t
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
 
-    int logical;                                                // XCD-aware order (one N tile: P channels)
-    {
-        const int nblk = gridDim.x, bid = blockIdx.x;
-        const int q = nblk >> 3, r = nblk & 7, xcd = bid & 7, loc = bid >> 3;
-        logical = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + loc;
-    }
-    int t = logical;
+    int t = xcd_logical_block();                                // XCD-aware order (one N tile: P channels)
     const int tx = t % tiles_x;
     t /= tiles_x;
     const int ty = t % tiles_y, b = t / tiles_y;
@@ -95,7 +73,7 @@ __global__ __launch_bounds__(256) void conv3_tail_kernel(const ConvArgs a, int t
         const char* gB = wt_tile + (long long)blk * B_BYTES;
 #pragma unroll
         for (int i = 0; i < LB; ++i)
-            __builtin_amdgcn_global_load_lds((gbl_void*)(gB + w_off[i]), (lds_void*)(sB + (i * 32 + wave * 8) * ROWB), 16, 0, 0);
+            lds_dma16(gB + w_off[i], sB + (i * 32 + wave * 8) * ROWB);
     };
     issue_b(0, 0);
 
@@ -117,7 +95,7 @@ __global__ __launch_bounds__(256) void conv3_tail_kernel(const ConvArgs a, int t
         const char* gA = arena + (unsigned)(cc * CH * 2);
 #pragma unroll
         for (int i = 0; i < LA; ++i)
-            __builtin_amdgcn_global_load_lds((gbl_void*)(gA + a_off[i]), (lds_void*)(sA + (i * 32 + wave * 8) * ROWB), 16, 0, 0);
+            lds_dma16(gA + a_off[i], sA + (i * 32 + wave * 8) * ROWB);
     };
     issue_a(0, 0);
 
@@ -148,7 +126,7 @@ __global__ __launch_bounds__(256) void conv3_tail_kernel(const ConvArgs a, int t
         char* s = smem + ((nc & 1) ? w2_off1 : w2_off0) + wave * 1024;
 #pragma unroll
         for (int i = 0; i < L2R; ++i)
-            __builtin_amdgcn_global_load_lds((gbl_void*)(g + i * 4096 + w2_lane), (lds_void*)(s + i * 4096), 16, 0, 0);
+            lds_dma16(g + i * 4096 + w2_lane, s + i * 4096);
     };
 #pragma unroll
     for (int d = 1; d < D; ++d) issue_b(d, d);
@@ -330,11 +308,9 @@ __global__ __launch_bounds__(256) void conv3_tail_kernel(const ConvArgs a, int t
                 for (int j = 0; j < 2; ++j)
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
-                        const float xf = acc2[ni][mi][8 * j + e], yf = acc2[ni][mi][8 * j + 4 + e];   // (bit_cast of a vector ELEMENT lvalue reads element 0)
-                        const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(xf), __float_as_uint(yf), false, false);
-                        const unsigned s0 = sw[0], s1 = sw[1];
-                        acc2[ni][mi][8 * j + e] = (X3 ? a.tail_acc_scale : 1.f) * __uint_as_float(s0) + bias[j][e];
-                        acc2[ni][mi][8 * j + 4 + e] = (X3 ? a.tail_acc_scale : 1.f) * __uint_as_float(s1) + bias[j][4 + e];
+                        const float2 sw = halfwave_swap(acc2[ni][mi][8 * j + e], acc2[ni][mi][8 * j + 4 + e]);
+                        acc2[ni][mi][8 * j + e] = (X3 ? a.tail_acc_scale : 1.f) * sw.x + bias[j][e];
+                        acc2[ni][mi][8 * j + 4 + e] = (X3 ? a.tail_acc_scale : 1.f) * sw.y + bias[j][4 + e];
                     }
         }
         auto add_tensor = [&](const _Float16* __restrict__ tsr) {
@@ -356,12 +332,7 @@ __global__ __launch_bounds__(256) void conv3_tail_kernel(const ConvArgs a, int t
 #pragma unroll
                 for (int ni = 0; ni < NI2; ++ni)
 #pragma unroll
-                    for (int j = 0; j < 2; ++j) {
-                        const int c = (mi * NI2 + ni) * 2 + j;
-#pragma unroll
-                        for (int e = 0; e < 8; ++e)
-                            acc2[ni][mi][8 * j + e] += X3 ? (float)h[c][0][e] + (float)h[c][NPL - 1][e] : (float)h[c][0][e];
-                    }
+                    for (int j = 0; j < 2; ++j) add_planes8(acc2[ni][mi], j, h[(mi * NI2 + ni) * 2 + j]);
         };
         if (a.res) {
 #pragma unroll
@@ -369,20 +340,13 @@ __global__ __launch_bounds__(256) void conv3_tail_kernel(const ConvArgs a, int t
 #pragma unroll
                 for (int ni = 0; ni < NI2; ++ni)
 #pragma unroll
-                    for (int j = 0; j < 2; ++j) {
-                        const int c = (mi * NI2 + ni) * 2 + j;
-#pragma unroll
-                        for (int e = 0; e < 8; ++e)
-                            acc2[ni][mi][8 * j + e] += X3 ? (float)rs[c][0][e] + (float)rs[c][NPL - 1][e] : (float)rs[c][0][e];
-                    }
+                    for (int j = 0; j < 2; ++j) add_planes8(acc2[ni][mi], j, rs[(mi * NI2 + ni) * 2 + j]);
         }
         if (a.relu) {
 #pragma unroll
             for (int ni = 0; ni < NI2; ++ni)
 #pragma unroll
-                for (int mi = 0; mi < MI; ++mi)
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) acc2[ni][mi][r] = acc2[ni][mi][r] < 0.f ? 0.f : acc2[ni][mi][r];
+                for (int mi = 0; mi < MI; ++mi) relu16(acc2[ni][mi]);
         }
         if (a.add1) add_tensor(a.add1);
         if (a.add2) add_tensor(a.add2);

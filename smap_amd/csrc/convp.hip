@@ -23,13 +23,9 @@
 #include <stdint.h>
 #include "smap_hip.h"
 #include "plan.h"
+#include "conv_device.h"
 
 namespace {
-
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __attribute__((address_space(3))) void lds_void;
-typedef const __attribute__((address_space(1))) void gbl_void;
 
 constexpr int P_BIAS_MAX = 2048;       // output channels (cout_pad) the LDS bias table holds
 #ifndef SMAP_CONVP_ABLATE
@@ -157,7 +153,7 @@ __global__ __launch_bounds__((WM * WN + P_NLW) * 64) void convp_kernel(const Con
                     const char* gA = arena + (unsigned)(s_cc * P_ROWB + (X3 ? pl * a.in_lo * 2 : 0));
 #pragma unroll
                     for (int i = 0; i < LA2; ++i)
-                        __builtin_amdgcn_global_load_lds((gbl_void*)(gA + a_cur[i]), (lds_void*)(sA + (i * RPRA + lw * P_RPW) * P_ROWB), 16, 0, 0);
+                        lds_dma16(gA + a_cur[i], sA + (i * RPRA + lw * P_RPW) * P_ROWB);
                 }
                 if (++s_cc == cchunks) {
                     s_cc = 0;
@@ -213,7 +209,7 @@ __global__ __launch_bounds__((WM * WN + P_NLW) * 64) void convp_kernel(const Con
                     const char* gB = wpair ? wt_tile + (long long)(s_it >> 1) * WBLK + (s_it & 1) * 64 : wt_tile + (long long)s_it * WBLK;
 #pragma unroll
                     for (int j = 0; j < NPL * LB2; ++j)
-                        __builtin_amdgcn_global_load_lds((gbl_void*)(gB + w_off[j]), (lds_void*)(sB + (j * RPRB + wi * P_RPW) * P_ROWB), 16, 0, 0);
+                        lds_dma16(gB + w_off[j], sB + (j * RPRB + wi * P_RPW) * P_ROWB);
                 }
                 if (++s_it == kt_per_tile && ++s_tile < t_count) setup_tile();
             };
@@ -296,14 +292,14 @@ __global__ __launch_bounds__((WM * WN + P_NLW) * 64) void convp_kernel(const Con
                 const char* gA = arena + (unsigned)(s_cc * P_ROWB + (X3 ? pl * a.in_lo * 2 : 0));   // a_cur = 0: zero page
 #pragma unroll
                 for (int i = 0; i < LA; ++i)
-                    __builtin_amdgcn_global_load_lds((gbl_void*)(gA + a_cur[i]), (lds_void*)(sA + (i * P_RPR + lw * P_RPW) * P_ROWB), 16, 0, 0);
+                    lds_dma16(gA + a_cur[i], sA + (i * P_RPR + lw * P_RPW) * P_ROWB);
             }
             if (!(SMAP_CONVP_ABLATE & (1 | 32))) {                // the weight tile: one contiguous block, already in LDS order
                 char* sB = sbase + NPL * BM * P_ROWB;
                 const char* gB = wpair ? wt_tile + (long long)(s_it >> 1) * WBLK + (s_it & 1) * 64 : wt_tile + (long long)s_it * WBLK;
 #pragma unroll
                 for (int j = 0; j < NPL * LB; ++j)
-                    __builtin_amdgcn_global_load_lds((gbl_void*)(gB + w_off[j]), (lds_void*)(sB + (j * P_RPR + lw * P_RPW) * P_ROWB), 16, 0, 0);
+                    lds_dma16(gB + w_off[j], sB + (j * P_RPR + lw * P_RPW) * P_ROWB);
             }
             ++s_it;
             if (++s_cc == cchunks) {
@@ -421,11 +417,9 @@ __global__ __launch_bounds__((WM * WN + P_NLW) * 64) void convp_kernel(const Con
                     for (int j = 0; j < 2; ++j)
 #pragma unroll
                         for (int e = 0; e < 4; ++e) {
-                            const float xf = acc[ni][mi][8 * j + e], yf = acc[ni][mi][8 * j + 4 + e];   // (bit_cast of a vector ELEMENT lvalue reads element 0)
-                            const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(xf), __float_as_uint(yf), false, false);
-                            const unsigned s0 = sw[0], s1 = sw[1];
-                            acc[ni][mi][8 * j + e] = (X3 ? a.acc_scale : 1.f) * __uint_as_float(s0);
-                            acc[ni][mi][8 * j + 4 + e] = (X3 ? a.acc_scale : 1.f) * __uint_as_float(s1);
+                            const float2 sw = halfwave_swap(acc[ni][mi][8 * j + e], acc[ni][mi][8 * j + 4 + e]);
+                            acc[ni][mi][8 * j + e] = (X3 ? a.acc_scale : 1.f) * sw.x;
+                            acc[ni][mi][8 * j + 4 + e] = (X3 ? a.acc_scale : 1.f) * sw.y;
                         }
             unsigned m_dense[MI], m_out[MI];                      // per-pixel element offsets (32-bit: plan.hip::validate bounds the tensors)
             bool m_ok[MI];
@@ -457,21 +451,14 @@ __global__ __launch_bounds__((WM * WN + P_NLW) * 64) void convp_kernel(const Con
 #pragma unroll
                     for (int ni = 0; ni < NI; ++ni)
 #pragma unroll
-                        for (int j = 0; j < 2; ++j) {
-                            const int c = (mi * NI + ni) * 2 + j;
-#pragma unroll
-                            for (int e = 0; e < 8; ++e)
-                                acc[ni][mi][8 * j + e] += X3 ? (float)h[c][0][e] + (float)h[c][NPL - 1][e] : (float)h[c][0][e];
-                        }
+                        for (int j = 0; j < 2; ++j) add_planes8(acc[ni][mi], j, h[(mi * NI + ni) * 2 + j]);
             };
             if (a.res) add_tensor(a.res);
             if (a.relu) {
 #pragma unroll
                 for (int ni = 0; ni < NI; ++ni)
 #pragma unroll
-                    for (int mi = 0; mi < MI; ++mi)
-#pragma unroll
-                        for (int r = 0; r < 16; ++r) acc[ni][mi][r] = acc[ni][mi][r] < 0.f ? 0.f : acc[ni][mi][r];   // NaN stays NaN (torch's ReLU)
+                    for (int mi = 0; mi < MI; ++mi) relu16(acc[ni][mi]);
             }
             if (a.add1) add_tensor(a.add1);
             if (a.add2) add_tensor(a.add2);

@@ -13,10 +13,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "smap_hip.h"
+#include "hip_rc.h"
 
 namespace {
-
-inline int hip_rc(hipError_t e) { return e == hipSuccess ? 0 : -(1000 + (int)e); }
 
 struct IdctMatrix { int32_t m[8][8]; };
 

@@ -1,4 +1,5 @@
 // plan.h -- internal declarations shared by the conv*.hip files and plan.hip (not part of the C ABI).
+// The device primitives those units share (typedefs, wait counts, barriers, block order, register-epilogue steps) are in conv_device.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -17,12 +17,10 @@
 #include <type_traits>
 #include "smap_hip.h"
 #include "plan.h"
+#include "conv_device.h"
+#include "hip_rc.h"
 
 namespace {
-
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-
-inline int hip_rc(hipError_t e) { return e == hipSuccess ? 0 : -(1000 + (int)e); }
 
 // ------------------------------------------------------------------ stem --
 // ResNet_top conv 7x7 s2 p3, 3 -> 64, + folded BN + ReLU, fp32 NCHW image -> NHWC fp16.
@@ -38,8 +36,6 @@ inline int hip_rc(hipError_t e) { return e == hipSuccess ? 0 : -(1000 + (int)e);
 #endif
 constexpr int ST_T = 16, ST_PH = ST_T * 2 + 5, ST_PW = 40;     // tile edge, patch rows, padded patch row (halves)
 constexpr int ST_K = 176;                                      // 22 granules x 8
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef _Float16 half4 __attribute__((ext_vector_type(4)));
 
 // The images of a schedule may come as up to SMAP_MAX_INPUTS separate [frames_per,3,H,W] buffers (smap_plan_run_inputs: a
 // launch that coalesces several of the caller's batches reads them where they are -- no gather copy in front of the stem).
@@ -149,11 +145,9 @@ __global__ __launch_bounds__(256) void stem_kernel(const StemIn in, const _Float
                 float v[8];
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
-                    const float xf = acc[nt][t][8 * j + e], yf = acc[nt][t][8 * j + 4 + e];    // channels 16j + e + 4 lhi and + 8
-                    const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(xf), __float_as_uint(yf), false, false);
-                    const unsigned s0 = sw[0], s1 = sw[1];
-                    v[e] = __uint_as_float(s0);
-                    v[4 + e] = __uint_as_float(s1);
+                    const float2 sw = halfwave_swap(acc[nt][t][8 * j + e], acc[nt][t][8 * j + 4 + e]);    // channels 16j + e + 4 lhi and + 8
+                    v[e] = sw.x;
+                    v[4 + e] = sw.y;
                 }
                 const int n0 = nt * 32 + 16 * j + 8 * lhi;     // this lane now holds channels n0 .. n0 + 7 of its pixel
                 const float4 b0 = *reinterpret_cast<const float4*>(bias + n0), b1 = *reinterpret_cast<const float4*>(bias + n0 + 4);
