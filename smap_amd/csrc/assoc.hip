@@ -1005,8 +1005,9 @@ int smap_refine_gt(const double* pred_2d, const double* pred_3d, const int32_t* 
 extern "C" int smap_refine_mlp(const float* x, int N, const float* const* wt, const float* const* bs, float* y,
                                void* stream)
 {
-    if (!x || !y || !wt || !bs || N < 0) return SMAP_E_ARG;
-    if (N == 0) return 0;
+    if (!wt || !bs || N < 0) return SMAP_E_ARG;
+    if (N == 0) return 0;                       // no rows: x / y may be the null pointers of empty tensors
+    if (!x || !y) return SMAP_E_ARG;
     RefineW w;
     for (int l = 0; l < 5; ++l) {
         if (!wt[l] || !bs[l]) return SMAP_E_ARG;

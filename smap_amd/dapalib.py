@@ -203,6 +203,8 @@ def refine_mlp(x, wt, bs):
         raise ValueError("x must be a float32 GPU tensor [N,75]")
     x = x.contiguous()
     y = torch.empty((x.shape[0], 45), dtype=torch.float32, device=x.device)
+    if x.shape[0] == 0:            # nothing to launch (an empty tensor has no storage: its data pointer is null)
+        return y
     wp = (C.c_void_p * 5)(*[w.data_ptr() for w in wt])
     bp = (C.c_void_p * 5)(*[b.data_ptr() for b in bs])
     with torch.cuda.device(x.device):

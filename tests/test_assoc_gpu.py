@@ -205,6 +205,7 @@ def test_lift_and_refine_match_reference_golden(golden_dir):
                                     torch.from_numpy(np.stack(root)).to(DEV), np.stack(cams))
     ref = dapalib.refine_batch(p2, p3, counts.to(DEV), wt, bs)
     p2, p3, rz, ref = p2.cpu().numpy(), p3.cpu().numpy(), rz.cpu().numpy(), ref.cpu().numpy()
+    Wn, Bn = [w.t().contiguous().cpu().numpy() for w in wt], [b.cpu().numpy() for b in bs]
     for c in range(n):
         p = f"c{c}_"
         P = int(counts[c])
@@ -216,6 +217,8 @@ def test_lift_and_refine_match_reference_golden(golden_dir):
         assert not p3[c, P:].any() and not ref[c, P:].any()
         o2, o3, orz = O.lift(z[p + "bodys"], det[c], root[c], cams[c])
         assert np.array_equal(p3[c, :P], o3) and np.array_equal(p2[c, :P], o2) and np.array_equal(rz[c, :P], orz)
+        # same accumulation order on both sides, no contraction: the fp32 refinement equals the oracle's bit for bit
+        assert np.array_equal(ref[c, :P], O.refine(p2[c, :P], p3[c, :P], Wn, Bn))
 
 
 def test_ground_truth_modes_match_reference_golden(golden_dir):
