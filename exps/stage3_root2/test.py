@@ -16,7 +16,11 @@ post-processing of batch k overlaps the backbone of batch k+1 (smap_amd/pipeline
 The ground-truth modes (test.py:73-95,142-143) run on the same pipeline: `-t generate_result` registers the
 persons to the annotations of cfg.TEST.JSON_PATH on the device (smap_register_gt) and writes one record per frame
 with the ground truth attached (the input of lib/eval/convert.py); `-t generate_train -d generation|test` writes
-one record per matched person, the RefineNet training pairs (dataset/p2p_dataset.py)."""
+one record per matched person, the RefineNet training pairs (dataset/p2p_dataset.py).
+
+`-t generate_result --eval_3d 1` (addition) scores the run while it runs: MPJPE, root-relative error, PCK, point / person recall
+and the depth-order reverse rate of lib/eval/test_util_panoptic.py (eval_3d, calculate_and_log), accumulated on the GPU
+(smap_amd/evaluate.py) and written as `error` into the result file, as the reference's Panoptic test does."""
 import argparse
 import json
 import logging
@@ -248,10 +252,14 @@ class _DryRunPipeline:
         return out or None
 
 
-def generate_3d_point_pairs(model, refine_model, data_loader, cfg, logger, device, output_dir="", pipeline_cls=None):
+def generate_3d_point_pairs(model, refine_model, data_loader, cfg, logger, device, output_dir="", pipeline_cls=None, eval_3d=False):
     os.makedirs(output_dir, exist_ok=True)
     if pipeline_cls is None:       # batches of <= 8 frames share a backbone launch (smap_amd/pipeline.py::make_pipeline, SMAP_LAUNCH_FRAMES)
         pipeline_cls = lambda m, c, b, h, w, d, rw, **kw: make_pipeline(m, c, b, h, w, d, refine_weights=rw, **kw)
+    evaluator = None
+    if eval_3d:                    # the reference's `error` dict, accumulated on the device by every batch's post-processing
+        from smap_amd.evaluate import Eval3D
+        evaluator = Eval3D(device, refine=refine_model is not None)
     if model is not None:
         model.eval()
     refine_w = None
@@ -313,7 +321,8 @@ def generate_3d_point_pairs(model, refine_model, data_loader, cfg, logger, devic
                 retire(pipe)
             pipe = pipeline_cls(model, cfg, len(imgs), imgs.shape[-2], imgs.shape[-1], device, refine_w,
                                 do_flip=bool(cfg.DO_FLIP), record_mode=cfg.TEST_MODE, numpy_records=True,
-                                depth=int(os.environ.get("SMAP_PIPELINE_DEPTH", 2)))   # two backbones in flight (+19 %)
+                                depth=int(os.environ.get("SMAP_PIPELINE_DEPTH", 2)),   # two backbones in flight (+19 %)
+                                **({} if evaluator is None else {"evaluator": evaluator}))
         with torch.no_grad():
             drain(pipe.submit(imgs, cams, list(img_path), annotations=annotations))
         clock["submit_s"] += time.perf_counter() - t_sub
@@ -342,6 +351,15 @@ def generate_3d_point_pairs(model, refine_model, data_loader, cfg, logger, devic
         result["dropped_frames"] = list(dropped)
         logger.warning("{} frame(s) have no result (non-finite maps: an activation exceeded the fp16 range, INTEGRATION.md section 5): {}".format(
             len(dropped), dropped[:20]))
+    if evaluator is not None:
+        from smap_amd.evaluate import log_lines, merge, summarize
+        raw = evaluator.raw()                                                   # the run's only read-back of the scores
+        if dist.is_initialized() and (dist.get_world_size() > 1 or os.environ.get("SMAP_FORCE_GATHER", "") == "1"):
+            raw = merge(gather_records(raw, device))                            # rank order; evaluate.merge says what that costs
+        if rank == 0:
+            for line in log_lines(raw):                                         # calculate_and_log's lines (test_util_panoptic.py:388-400)
+                logger.info(line)
+            result["error"] = summarize(raw)
     if rank == 0:
         dir_name = os.path.split(os.path.split(os.path.realpath(__file__))[0])[1]
         name = os.path.join(output_dir, "{}_{}_{}_{}.json".format(dir_name, cfg.TEST_MODE, cfg.DATA_MODE,
@@ -379,9 +397,16 @@ def main():
     parser.add_argument("--device_decode", type=int, default=0,
                         help="(addition) 1: baseline JPEGs are Huffman-decoded on the host and finished on the GPU (smap_amd/jpeg.py), "
                              "bit for bit the PIL frame; other files are decoded with PIL.  Requires --device_preprocess 1")
+    parser.add_argument("--eval_3d", type=int, default=0, choices=[0, 1],
+                        help="(addition) 1, with -t generate_result: score the run on the GPU (MPJPE, PCK, recall, reverse rate: "
+                             "lib/eval/test_util_panoptic.py eval_3d) and write the `error` dict into the result file")
     args = parser.parse_args()
     if args.device_decode and not args.device_preprocess:
         parser.error("--device_decode 1 requires --device_preprocess 1")
+    if args.eval_3d and args.test_mode != "generate_result":
+        parser.error("--eval_3d 1 requires -t generate_result")
+    if args.eval_3d and args.dry_run:
+        parser.error("--eval_3d 1 scores on the GPU: not available with --dry_run 1")
     cfg.TEST_MODE = args.test_mode
     cfg.DATA_MODE = args.data_mode
     cfg.REFINE = len(args.RefineNet_path) > 0
@@ -447,7 +472,7 @@ def main():
                 logger.info("No such RefineNet checkpoint of {}".format(args.RefineNet_path))
                 return
         result = generate_3d_point_pairs(model, refine_model, data_loader, cfg, logger, device,
-                                         output_dir=os.path.join(cfg.OUTPUT_DIR, "result"))
+                                         output_dir=os.path.join(cfg.OUTPUT_DIR, "result"), eval_3d=bool(args.eval_3d))
         if dist.is_initialized():
             dist.destroy_process_group()
         if result.get("dropped_frames"):

@@ -417,6 +417,35 @@ int64_t smap_jpeg_workspace_bytes(const smap_jpeg_info* info);
  * bgr: DEVICE uint8 [H'][W'][3], the orientation applied (orientations 5-8 swap width and height).  Two launches on `stream`. */
 int smap_jpeg_reconstruct(const int16_t* coeffs, const smap_jpeg_info* info, uint8_t* planes, uint8_t* bgr, void* stream);
 
+/* ---- scoring: lib/eval/test_util_panoptic.py eval_3d (:273-307), initialization (:332-355) on the device ----
+ * The accumulator is SMAP_EVAL_ACC_DOUBLES f64 on the device, kept across calls:
+ *   real_error[15] | root_error[15] | count_point[15] | real_PCK[15] | root_PCK[15] |
+ *   count_people, total_people_gt, total_pair_count, reverse_pair_count, less_15.
+ * A person's term row has the SAME layout: field f of the row is what eval_3d adds to accumulator field f for that person
+ * (0 where the reference adds nothing: x + 0.0 == x for every x the sums can hold, which are never -0.0). */
+#define SMAP_EVAL_ACC_DOUBLES 80
+#define SMAP_EVAL_TERM_DOUBLES 80
+#define SMAP_EVAL_MAXG 64
+
+/* acc = zeros, total_pair_count = 1e-8 (:351). */
+int smap_eval3d_acc_init(double* acc, void* stream);
+
+/* The per-person part of eval_3d, parallel over (frame, person, joint).
+ * pred_3d: [B,127,15,4] f64 (smap_lift_gt / smap_refine_gt layout); counts: [B] int32, persons of the frame = its kept annotations
+ * (values outside 0..G are clamped); gt: [B,G,15,4] f64 = (X,Y,Z,score) of the kept annotations (columns 4:7 and 3 of the annotation
+ * rows), 1 <= G <= SMAP_EVAL_MAXG.  terms: [B,G,SMAP_EVAL_TERM_DOUBLES] f64 out.  Rows >= counts[b] of pred_3d, gt and terms are
+ * neither read nor written.  float64 without contraction, correctly rounded square root: bit for bit numpy's. */
+int smap_eval3d_terms(const double* pred_3d, const int32_t* counts, const double* gt, int B, int G, double* terms, void* stream);
+
+/* The ordered part: acc[f] += terms[b][g][f] for b = 0..B-1, g = 0..counts[b]-1 IN THAT ORDER, one thread per field -- the
+ * reference's running sums, person by person (a per-frame partial sum would re-associate the float64 additions). */
+int smap_eval3d_fold(const double* terms, const int32_t* counts, int B, int G, double* acc, void* stream);
+
+/* Both parts on `stream`: ONE launch (a single workgroup computes the terms, then folds them) while B * G <= 1024, otherwise
+ * smap_eval3d_terms followed by smap_eval3d_fold.  Same bits either way.  terms: caller's scratch [B,G,SMAP_EVAL_TERM_DOUBLES]. */
+int smap_eval3d_update(const double* pred_3d, const int32_t* counts, const double* gt, int B, int G, double* terms, double* acc,
+                       void* stream);
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif

@@ -15,9 +15,10 @@ CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "libsmap_hip.so")
 OBJ = os.path.join(CSRC, "obj")
 
-# (source, extra flags).  assoc.hip is bit-exact float work: contraction OFF.
+# (source, extra flags).  assoc.hip and eval.hip are bit-exact float work: contraction OFF.
 SOURCES = [
     ("assoc.hip", ["-ffp-contract=off"]),
+    ("eval.hip", ["-ffp-contract=off"]),
     ("conv.hip", []),
     ("conv3.hip", []),
     ("convp.hip", []),

@@ -20,6 +20,7 @@ SYMBOLS = [
     "smap_refine", "smap_register_gt", "smap_lift_gt", "smap_refine_gt", "smap_refine_mlp", "smap_preprocess", "smap_sizeof_op", "smap_conv_tile_dims", "smap_conv_tile_bk", "smap_conv_tile_tail_bn", "smap_plan_create", "smap_plan_destroy", "smap_plan_run", "smap_plan_run_range",
     "smap_plan_run_inputs", "smap_workspace_bytes", "smap_plan_create_from_blob", "smap_plan_set_lanes",
     "smap_nms_workspace_bytes", "smap_nms_ws",
+    "smap_eval3d_acc_init", "smap_eval3d_terms", "smap_eval3d_fold", "smap_eval3d_update",
     "smap_sizeof_jpeg_info", "smap_jpeg_probe", "smap_jpeg_decode_coefficients", "smap_jpeg_workspace_bytes", "smap_jpeg_reconstruct",
 ]
 MAX_INPUTS = 8                         # SMAP_MAX_INPUTS
@@ -135,6 +136,10 @@ def load():
     lib.smap_jpeg_decode_coefficients.argtypes = [vp, C.c_size_t, C.POINTER(JpegInfo), vp]
     lib.smap_jpeg_workspace_bytes.argtypes = [C.POINTER(JpegInfo)]
     lib.smap_jpeg_reconstruct.argtypes = [vp, C.POINTER(JpegInfo), vp, vp, vp]
+    lib.smap_eval3d_acc_init.argtypes = [vp, vp]
+    lib.smap_eval3d_terms.argtypes = [vp, vp, vp, ip, ip, vp, vp]
+    lib.smap_eval3d_fold.argtypes = [vp, vp, ip, ip, vp, vp]
+    lib.smap_eval3d_update.argtypes = [vp, vp, vp, ip, ip, vp, vp, vp]
     for s in SYMBOLS:
         if s not in ("smap_version", "smap_plan_destroy", "smap_nms_workspace_bytes", "smap_jpeg_workspace_bytes"):  # everything else returns int
             getattr(lib, s).restype = ip
