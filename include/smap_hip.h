@@ -176,7 +176,8 @@ typedef struct smap_op {
     int64_t add1_off, add2_off;     /* dense tensors added AFTER ReLU (smap.py:142-153), or -1   */
     int64_t aux_off[3];             /* CONV: aux[0] = optional low-res fp16 [B,aux_h,aux_w,Cout] tensor, bilinearly
                                        (align_corners) upsampled and added before ReLU (smap.py:213-217);
-                                       UPADD: aux[0] = low-res t ; HEADSUM: fp32 NHWC head tensors (arena) */
+                                       UPADD: aux[0] = low-res t [B,aux_h,aux_w,Cout] (in_off / out_off: [B,Ho,Wo,Cout]), required;
+                                       HEADSUM: n_aux fp32 NHWC head tensors (arena) of [B (2 B with flip_from),aux_h,aux_w,Cin], required */
     int32_t aux_h[3], aux_w[3];     /* their spatial sizes                                       */
     int64_t ext_off;                /* HEADSUM: byte offset of the [B,Cout,Ho,Wo] block in the fp32 output buffer */
     int32_t precision;              /* CONV/STEM/MAXPOOL: 0 = fp16 activations and weights (one rounding per stored value,
@@ -313,7 +314,11 @@ typedef struct smap_plan smap_plan;
  * base (the input's WINDOW: its arena offset rounded down to a multiple of 4 GiB) plus 32-bit lane offsets, and read zeros
  * for padding taps at the start of that window.  So bytes [k * 2^32, k * 2^32 + 16384) are RESERVED for every k >= 0
  * (smap_plan_run zeroes the ones its launches use), no tensor overlaps them (hence no tensor crosses a 4 GiB boundary and
- * none exceeds 4 GiB - 16 KiB), and the arena may be of any size. */
+ * none exceeds 4 GiB - 16 KiB), and the arena may be of any size.  This holds for EVERY arena range of EVERY op kind -- in_off /
+ * out_off of MAXPOOL and UPADD, out_off of STEM and STEMPOOL, UPADD's aux_off[0], the n_aux sources of a HEADSUM, TAPSUM's aux_off[0],
+ * a CONV's second input, segment outputs and split-K scratch and tickets: each is required (>= 16384; -1 = absent only for res_off,
+ * add1_off, add2_off and aux_off[0] of a CONV).  A split-K ticket slice shares no byte with any other arena range of the schedule.
+ * Weight-blob offsets of the operands an op uses are >= 0; a size that does not fit int64 makes the op invalid. */
 int smap_plan_create(const smap_op* ops, int n_ops, smap_plan** plan);
 void smap_plan_destroy(smap_plan* plan);
 /* Runs the whole schedule on `stream`.

@@ -26,6 +26,7 @@ SOURCES = [
     ("convb.hip", []),
     ("convc.hip", []),
     ("plan.hip", []),
+    ("plan_check.cpp", []),       # host-only C++: which schedules and plan blobs the library runs (also built alone under sanitizers)
     ("jpeg.hip", []),
     ("jpeg_host.cpp", []),        # host-only C++ (marker parse + Huffman decode); no fast-math anywhere in this library
 ]

@@ -749,7 +749,7 @@ hipError_t launch(const ConvArgs& a, hipStream_t st)
     return hipGetLastError();
 }
 
-// the register-epilogue instance: split precision, plain epilogue only (plan.hip::validate keeps everything else away)
+// the register-epilogue instance: split precision, plain epilogue only (plan_check.cpp::validate keeps everything else away)
 template <int TILE, bool X3, int WM, int WN, int STAGES>
 hipError_t launch_regepi(const ConvArgs& a, hipStream_t st)
 {
@@ -793,28 +793,6 @@ hipError_t launch_tapdot(const ConvArgs& a, hipStream_t st)
 #define SMAP_BOTH(HELPER, TILE, ...) (a.x3 ? HELPER<TILE, true, __VA_ARGS__>(a, st) : HELPER<TILE, false, __VA_ARGS__>(a, st))
 
 }  // namespace
-
-// The three ABI lookups (include/smap_hip.h): rows of csrc/tiles.h.
-extern "C" int smap_conv_tile_dims(int tile, int* bm, int* bn)
-{
-    const TileRow* t = tile_find(tile);
-    if (!t) return -1;
-    *bm = t->bm;
-    *bn = t->bn;
-    return 0;
-}
-
-extern "C" int smap_conv_tile_bk(int tile, int precision)
-{
-    const TileRow* t = tile_find(tile);
-    return t ? tile_bk(*t, precision != 0) : 0;
-}
-
-extern "C" int smap_conv_tile_tail_bn(int tile)
-{
-    const TileRow* t = tile_find(tile);
-    return t ? t->tail_bn : 0;
-}
 
 hipError_t smap_launch_conv(const ConvArgs& a, int tile, hipStream_t st)
 {

@@ -10,6 +10,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <new>
+#include <memory>
 #include <cstdlib>
 #include <cstring>
 #include <climits>
@@ -17,6 +18,7 @@
 #include <type_traits>
 #include "smap_hip.h"
 #include "plan.h"
+#include "plan_check.h"
 #include "conv_device.h"
 #include "hip_rc.h"
 
@@ -35,7 +37,7 @@ namespace {
 #define SMAP_STEM_STORE16 1
 #endif
 constexpr int ST_T = 16, ST_PH = ST_T * 2 + 5, ST_PW = 40;     // tile edge, patch rows, padded patch row (halves)
-constexpr int ST_K = 176;                                      // 22 granules x 8
+constexpr int ST_K = SMAP_STEM_K;                              // 22 granules x 8 = 176
 
 // The images of a schedule may come as up to SMAP_MAX_INPUTS separate [frames_per,3,H,W] buffers (smap_plan_run_inputs: a
 // launch that coalesces several of the caller's batches reads them where they are -- no gather copy in front of the stem).
@@ -566,199 +568,13 @@ inline int grid_for(long long total, int block)
 
 }  // namespace
 
-struct smap_plan {
-    std::vector<smap_op> ops;
-    std::vector<int64_t> windows;          // arena offsets of the zero pages this schedule's conv launches address through
-    struct Ticket { int64_t off, bytes; int op; };
-    std::vector<Ticket> tickets;           // arena byte range of every split-K op's ticket slice (zeroed per op by smap_plan_run)
+struct smap_plan : PlanCheck {                 // the checked schedule (csrc/plan_check.h) + what running it with lanes on needs
     // lanes (smap_op.lane): side streams 1 .. SMAP_MAX_LANES - 1 and one event per op some other lane waits for; created on first use
     bool lanes_on = false, lanes_ready = false;
-    int n_lanes = 1;
     hipStream_t side[SMAP_MAX_LANES] = {};
     std::vector<hipEvent_t> ev;            // per op, null unless signalled
-    std::vector<char> signalled;
     hipEvent_t join_ev[SMAP_MAX_LANES] = {};
 };
-
-// ZERO PAGES and WINDOWS.  The conv kernels address their input with (64-bit uniform base in SGPRs) + (32-bit byte offset per
-// lane); offset 0..SMAP_ZERO_PAGE of that base must read as zeros (padding taps and rows past M fetch their 16 bytes there).
-// The base of a launch is the WINDOW of its input: the arena offset in_off rounded down to a multiple of SMAP_WINDOW (4 GiB); as
-// no tensor crosses a window boundary, an input tensor anywhere in an arena of any size is within 32 bits of its base.  Arena contract: bytes
-// [k * SMAP_WINDOW, k * SMAP_WINDOW + SMAP_ZERO_PAGE) are reserved for every k >= 0 (no tensor overlaps them); smap_plan_run
-// clears the ones its launches use on the stream before the first op.
-constexpr int64_t SMAP_ZERO_PAGE = 16384;  // >= max Cin * 2 bytes + 16 (+ the lo-plane offset, <= 4096, in split precision):
-                                           // a padding tap reads zero page + chunk*128 (+ lo offset)
-constexpr int64_t SMAP_WINDOW = (int64_t)1 << 32;
-inline int64_t window_of(int64_t off) { return off & ~(SMAP_WINDOW - 1); }
-// does [off, off + bytes) touch a reserved zero page?
-inline bool hits_zero_page(int64_t off, int64_t bytes)
-{
-    if (off < 0 || bytes <= 0) return false;
-    const int64_t k0 = off / SMAP_WINDOW, k1 = (off + bytes - 1) / SMAP_WINDOW;
-    if (off < k0 * SMAP_WINDOW + SMAP_ZERO_PAGE) return true;
-    return k1 > k0;                        // crosses the start of the next window = its zero page
-}
-
-static int validate(const smap_op& o)
-{
-    if (o.B <= 0 || o.H <= 0 || o.W <= 0 || o.Ho <= 0 || o.Wo <= 0 || o.Cout <= 0) return SMAP_E_ARG;
-    if (o.precision != 0 && o.precision != 1) return SMAP_E_ARG;
-    if (o.precision == 1 && o.kind != SMAP_OP_CONV && o.kind != SMAP_OP_STEM && o.kind != SMAP_OP_MAXPOOL && o.kind != SMAP_OP_HEADSUM &&
-        o.kind != SMAP_OP_STEMPOOL && o.kind != SMAP_OP_TAPSUM)
-        return SMAP_E_ARG;                               // UPADD has no split-precision instance
-    switch (o.kind) {
-        case SMAP_OP_CONV: {
-            const TileRow* t = tile_find(o.tile);          // csrc/tiles.h: what the id's kernel is and which instances it has
-            if (!t || !tile_has(*t, o.precision == 1)) return SMAP_E_ARG;      // unknown id, or no instance in this precision
-            const int bm = t->bm, bn = t->bn;
-            if (o.Cin % 64 || o.Cin * 2 + 16 > SMAP_ZERO_PAGE || o.cout_pad % bn || o.cout_pad < o.Cout) return SMAP_E_ARG;
-            if (o.precision == 1) {
-                if (o.in_stride_c % 16 || (!o.out_fp32 && o.out_stride_c % 16)) return SMAP_E_ARG;
-                if (o.Cin * 2 + o.in_stride_c + 16 > SMAP_ZERO_PAGE || !(o.acc_scale > 0.f)) return SMAP_E_ARG;
-                if (o.in_c_off + o.Cin > o.in_stride_c / 2) return SMAP_E_ARG;
-            }
-            if (o.ksize != 1 && o.ksize != 3) return SMAP_E_ARG;
-            if (o.w_pairs != 0 && o.w_pairs != 1) return SMAP_E_ARG;
-            if (t->family == TF_HALO && (o.ksize != 3 || o.stride != 1 || o.pad != 1 || o.res_off >= 0 || o.add1_off >= 0 ||
-                                 o.add2_off >= 0 || o.aux_off[0] >= 0))
-                return SMAP_E_ARG;                       // halo-tiled kernel: plain 3x3 stride-1 convs only
-            if ((t->tail_bn > 0) != (o.tail_cout > 0)) return SMAP_E_ARG;
-            if ((t->family == TF_BLOCK) != (o.head_cin > 0)) return SMAP_E_ARG;
-            if (t->family == TF_BLOCK) {                 // whole Bottleneck (convb.hip / convc.hip): `planes` planes, 4 x planes output channels
-                const bool first = t->first;             // a layer's FIRST block: `planes` input channels, 1x1 shortcut conv instead of + x
-                if (o.ksize != 3 || o.stride != 1 || o.pad != 1 || o.out_fp32 || o.aux_off[0] >= 0) return SMAP_E_ARG;
-                const int planes = t->planes;
-                if (o.Cin != planes || o.Cout != planes || o.cout_pad != planes || o.head_cin != (first ? planes : 4 * planes) || o.tail_cout != 4 * planes ||
-                    o.tail_cout_pad != 4 * planes)
-                    return SMAP_E_ARG;
-                if (o.in_stride_c != 2 * o.head_cin || o.in_c_off != 0) return SMAP_E_ARG;
-                if (first ? (o.res_off >= 0 || o.add1_off >= 0 || o.add2_off >= 0 || o.short_w_off < 0 || !(o.short_acc_scale > 0.f))
-                          : (o.res_off != o.in_off || o.short_acc_scale != 0.f))     // identity block: the residual IS the input
-                    return SMAP_E_ARG;
-                if (o.head_w_off < 0 || o.head_bias_off < 0 || o.tail_w_off < 0 || o.tail_bias_off < 0) return SMAP_E_ARG;
-                if (!(o.head_acc_scale > 0.f) || !(o.tail_acc_scale > 0.f) || o.out_stride_c < o.tail_cout) return SMAP_E_ARG;
-                if ((int64_t)o.B * o.Ho * o.Wo * o.tail_cout * 2 >= ((int64_t)1 << 31)) return SMAP_E_ARG;
-            } else if (o.short_acc_scale != 0.f) return SMAP_E_ARG;      // (a zero-initialised op has no shortcut conv)
-            if (t->family == TF_TAIL) {                  // 3x3 + fused 1x1 tail: the op's Cout is the tile's whole N extent
-                const int bn2 = t->tail_bn;
-                if (o.ksize != 3 || o.stride != 1 || o.pad != 1 || o.out_fp32 || o.aux_off[0] >= 0 || o.Cout != bn || o.cout_pad != bn)
-                    return SMAP_E_ARG;
-                if (o.tail_cout % 8 || o.tail_cout_pad % bn2 || o.tail_cout_pad < o.tail_cout || o.tail_w_off < 0 || o.tail_bias_off < 0)
-                    return SMAP_E_ARG;
-                if (o.precision == 1 && !(o.tail_acc_scale > 0.f)) return SMAP_E_ARG;
-                if (o.out_stride_c < o.tail_cout) return SMAP_E_ARG;
-                if ((int64_t)o.B * o.Ho * o.Wo * o.tail_cout * (1 + o.precision) >= ((int64_t)1 << 31)) return SMAP_E_ARG;
-            }
-            if ((t->caps & TC_REGEPI) && (o.out_fp32 || o.aux_off[0] >= 0 || o.add1_off >= 0 || o.add2_off >= 0 || o.Cout % 8 || o.ksplit > 1))
-                return SMAP_E_ARG;                       // register-epilogue tiles of conv.hip: fp16 outputs, residual + ReLU only
-            if (t->family == TF_PERSIST && (o.out_fp32 || o.aux_off[0] >= 0 || o.Cout % 8 || o.cout_pad > 2048))
-                return SMAP_E_ARG;                       // persistent kernel: register epilogue, fp16 outputs, no fused bilinear add, bias table of 2048 channels in LDS
-            if (o.in_stride_c % 8 || o.in_c_off % 8 || o.out_stride_c % 8 || o.out_c_off % 8) return SMAP_E_ARG;
-            if (o.out_stride_c < ((o.Cout + 7) & ~7) && o.tap_n == 0) return SMAP_E_ARG;      // (tap-dot: `out` is the [M][16] tap tensor)
-            if ((o.res_off >= 0 || o.add1_off >= 0 || o.add2_off >= 0 || o.aux_off[0] >= 0) && o.Cout % 8) return SMAP_E_ARG;
-            if (o.aux_off[0] >= 0 && (o.aux_h[0] <= 0 || o.aux_w[0] <= 0)) return SMAP_E_ARG;
-            if (o.in_off < SMAP_ZERO_PAGE || o.out_off < SMAP_ZERO_PAGE || o.w_off < 0 || o.bias_off < 0) return SMAP_E_ARG;
-            {   // conv A-operand addresses are 32-bit byte offsets from the input's window base; no tensor of the op may lie on a
-                // reserved zero page
-                const int64_t in_bytes = (int64_t)o.B * o.H * o.W * o.in_stride_c * 2;
-                const int64_t M = (int64_t)o.B * o.Ho * o.Wo;
-                const int64_t out_bytes = M * o.out_stride_c * (o.out_fp32 ? 4 : 2);
-                const int64_t dense = M * ((o.tail_cout > 0 ? o.tail_cout : ((o.Cout + 7) & ~7))) * 2 * (1 + o.precision);
-                if (o.in_off - window_of(o.in_off) + in_bytes > ((int64_t)1 << 32)) return SMAP_E_ARG;
-                const int64_t up_bytes = o.aux_off[0] >= 0 ? (int64_t)o.B * o.aux_h[0] * o.aux_w[0] * ((o.Cout + 7) & ~7) * 2 * (1 + o.precision) : 0;
-                if (hits_zero_page(o.in_off, in_bytes) || hits_zero_page(o.out_off, out_bytes) || hits_zero_page(o.res_off, dense) ||
-                    hits_zero_page(o.add1_off, dense) || hits_zero_page(o.add2_off, dense) || hits_zero_page(o.aux_off[0], up_bytes))
-                    return SMAP_E_ARG;
-            }
-            if ((int64_t)o.cout_pad * o.ksize * o.ksize * o.Cin * 2 * (1 + o.precision) > ((int64_t)1 << 32)) return SMAP_E_ARG;
-            if (o.ksplit < 0 || o.ksplit > 16) return SMAP_E_ARG;
-            if (o.ksplit > 1) {                          // split K: conv.hip's tiles; scratch and tickets inside the arena, off the zero pages
-                const int bk = tile_bk(*t, o.precision == 1);
-                if (!(t->caps & TC_SPLITK) || o.ksplit > o.ksize * o.ksize * o.Cin / bk) return SMAP_E_ARG;
-                const int64_t tiles = (((int64_t)o.B * o.Ho * o.Wo + bm - 1) / bm) * (o.cout_pad / bn);
-                const int64_t pbytes = tiles * o.ksplit * bm * bn * 4, cbytes = tiles * 4;
-                if (o.kpart_off < SMAP_ZERO_PAGE || o.kcount_off < SMAP_ZERO_PAGE || o.kpart_off % 16 || o.kcount_off % 4) return SMAP_E_ARG;
-                if (hits_zero_page(o.kpart_off, pbytes) || hits_zero_page(o.kcount_off, cbytes)) return SMAP_E_ARG;
-            }
-            if (o.tap_n != 0) {                          // tap-dot epilogue: one N tile of 256 channels, t = fp32 [M][16]
-                if (o.tap_n != 9 || !(t->caps & TC_TAPDOT) || o.cout_pad != 256 || o.Cout != 256 || o.ksize != 1 || o.stride != 1 || !o.out_fp32 || o.out_stride_c != 16 ||
-                    o.out_c_off != 0 || o.res_off >= 0 || o.add1_off >= 0 || o.add2_off >= 0 || o.aux_off[0] >= 0 || o.seg_n[0] != 0 || o.ksplit > 1 || o.in2_C != 0 ||
-                    o.tap_w_off < 0 || !(o.tap_scale > 0.f))
-                    return SMAP_E_ARG;
-            }
-            if (o.in2_C < 0) return SMAP_E_ARG;
-            if (o.in2_C > 0) {                           // second input along K: 1x1 stride 1 on the first input, plain epilogue
-                if (!(t->caps & TC_DUAL) || o.ksize != 1 || o.stride != 1 || o.pad != 0 || o.ksplit > 1 || o.seg_n[0] != 0 || o.aux_off[0] >= 0 ||
-                    o.add1_off >= 0 || o.add2_off >= 0 || o.out_fp32 || o.in_c_off != 0)
-                    return SMAP_E_ARG;
-                if (o.in2_C % 64 || o.in2_stride < 1 || o.in2_stride > 2 || o.in2_H <= 0 || o.in2_W <= 0 || o.in2_off < SMAP_ZERO_PAGE) return SMAP_E_ARG;
-                if (o.Ho != (o.in2_H - 1) / o.in2_stride + 1 || o.Wo != (o.in2_W - 1) / o.in2_stride + 1) return SMAP_E_ARG;
-                if (o.in2_stride_c % 8 || o.in2_stride_c < o.in2_C * (1 + o.precision) || (o.precision == 1 && o.in2_stride_c % 16)) return SMAP_E_ARG;
-                if (o.in2_C * 2 + (o.precision ? o.in2_stride_c : 0) + 16 > SMAP_ZERO_PAGE) return SMAP_E_ARG;      // padding rows read the zero page (both planes)
-                const int64_t b2 = (int64_t)o.B * o.in2_H * o.in2_W * o.in2_stride_c * 2;
-                if (window_of(o.in2_off) != window_of(o.in_off) || o.in2_off - window_of(o.in_off) + b2 > ((int64_t)1 << 32) || hits_zero_page(o.in2_off, b2))
-                    return SMAP_E_ARG;
-                if ((int64_t)o.cout_pad * (o.Cin + o.in2_C) * 2 * (1 + o.precision) > ((int64_t)1 << 32)) return SMAP_E_ARG;
-                if (o.in2_mode != 0 && o.in2_mode != 1) return SMAP_E_ARG;
-                if (o.in2_mode == 1 && (!(t->caps & TC_RELUSUM) || o.in2_stride != 1 || o.res_off >= 0 || o.relu != 0 || o.in2_bias_off < 0 || (o.precision == 1 && !(o.in2_acc_scale > 0.f))))
-                    return SMAP_E_ARG;               // relu(W1 x + b1) + relu(W2 x2 + b2): its own activations, no residual
-            } else if (o.in2_mode != 0) return SMAP_E_ARG;
-            if (o.seg_n[0] == 0 && o.seg_n[1] != 0) return SMAP_E_ARG;
-            if (o.seg_n[0] != 0) {                       // N segments: conv.hip's tiles, 1x1, fp16 outputs; every segment starts on an N tile
-                if (t->family != TF_IGEMM || o.ksize != 1 || o.out_fp32 || o.out_c_off != 0) return SMAP_E_ARG;
-                int prev = 0;
-                for (int j = 0; j < 2 && o.seg_n[j] != 0; ++j) {
-                    if (o.seg_n[j] <= prev || o.seg_n[j] % bn || o.seg_n[j] >= o.cout_pad) return SMAP_E_ARG;
-                    const int end = (j == 0 && o.seg_n[1] != 0) ? o.seg_n[1] : o.cout_pad;
-                    if (o.seg_cout[j] <= 0 || o.seg_cout[j] % 8 || o.seg_n[j] + o.seg_cout[j] > end) return SMAP_E_ARG;
-                    if (o.seg_out_stride_c[j] % 8 || (o.precision == 1 && o.seg_out_stride_c[j] % 16)) return SMAP_E_ARG;
-                    if (o.seg_out_stride_c[j] < o.seg_cout[j] * (1 + o.precision)) return SMAP_E_ARG;
-                    if (o.precision == 1 && !(o.seg_acc_scale[j] > 0.f)) return SMAP_E_ARG;
-                    const int64_t sb = (int64_t)o.B * o.Ho * o.Wo * o.seg_out_stride_c[j];
-                    if (sb >= ((int64_t)1 << 31) || o.seg_out_off[j] < SMAP_ZERO_PAGE || hits_zero_page(o.seg_out_off[j], sb * 2)) return SMAP_E_ARG;
-                    prev = o.seg_n[j];
-                }
-                if (((o.Cout + 7) & ~7) > o.seg_n[0]) return SMAP_E_ARG;
-            }
-            // epilogues address outputs / residuals / addends / the low-res tensor with 32-bit ELEMENT offsets from their bases
-            if ((int64_t)o.B * o.Ho * o.Wo * o.out_stride_c >= ((int64_t)1 << 31)) return SMAP_E_ARG;
-            if ((int64_t)o.B * o.Ho * o.Wo * ((o.Cout + 7) & ~7) * (1 + o.precision) >= ((int64_t)1 << 31)) return SMAP_E_ARG;
-            if (o.Ho != (o.H + 2 * o.pad - o.ksize) / o.stride + 1) return SMAP_E_ARG;
-            if (o.Wo != (o.W + 2 * o.pad - o.ksize) / o.stride + 1) return SMAP_E_ARG;
-            return 0;
-        }
-        case SMAP_OP_STEM:
-            if (o.Cin != 3 || o.Cout != 64 || o.Ho != (o.H + 6 - 7) / 2 + 1 || o.Wo != (o.W + 6 - 7) / 2 + 1)
-                return SMAP_E_ARG;
-            if (o.flip_from < 0 || (o.flip_from > 0 && o.B != 2 * o.flip_from)) return SMAP_E_ARG;
-            return 0;
-        case SMAP_OP_STEMPOOL: {
-            const int hs = (o.H + 6 - 7) / 2 + 1, ws = (o.W + 6 - 7) / 2 + 1;
-            if (o.Cin != 3 || o.Cout != 64 || o.Ho != (hs + 2 - 3) / 2 + 1 || o.Wo != (ws + 2 - 3) / 2 + 1) return SMAP_E_ARG;
-            if (o.flip_from < 0 || (o.flip_from > 0 && o.B != 2 * o.flip_from)) return SMAP_E_ARG;
-            return 0;
-        }
-        case SMAP_OP_MAXPOOL:
-            if (o.Cin % 8 || o.Cin != o.Cout || o.Ho != (o.H + 2 - 3) / 2 + 1 || o.Wo != (o.W + 2 - 3) / 2 + 1)
-                return SMAP_E_ARG;
-            return 0;
-        case SMAP_OP_UPADD:
-            if (o.Cout % 8 || o.aux_off[0] < 0 || o.aux_h[0] <= 0 || o.aux_w[0] <= 0) return SMAP_E_ARG;
-            return 0;
-        case SMAP_OP_TAPSUM:
-            if (o.Cout != 1 || o.Cin < 9 || o.Cin % 4 || o.Ho != o.H || o.Wo != o.W || o.aux_off[0] < SMAP_ZERO_PAGE || o.ext_off < 0 || o.bias_off < 0) return SMAP_E_ARG;
-            if (o.status_off < 0 || o.status_off % 4 || hits_zero_page(o.aux_off[0], (int64_t)o.B * o.H * o.W * o.Cin * 4)) return SMAP_E_ARG;
-            return 0;
-        case SMAP_OP_HEADSUM:
-            if (o.n_aux < 1 || o.n_aux > 3 || o.Cout > 48 || o.Cin < o.Cout || o.ext_off < 0) return SMAP_E_ARG;
-            if (o.flip_from < 0 || (o.flip_from > 0 && (o.w_off < 0 || o.in_c_off < 0 || o.in_c_off > o.Cout))) return SMAP_E_ARG;
-            if (o.status_off < 0 || o.status_off % 4) return SMAP_E_ARG;
-            if ((o.scale_hms != 0 && o.scale_hms != 1) || (o.scale_hms && (o.in_c_off < 0 || o.in_c_off > o.Cout))) return SMAP_E_ARG;
-            return 0;
-        default:
-            return SMAP_E_ARG;
-    }
-}
 
 #ifdef SMAP_TIMELINE
 // Diagnostics build (tools/build_ablate.py --timeline): every conv launch gets a slice of a caller-provided buffer
@@ -774,84 +590,23 @@ extern "C" __attribute__((visibility("default"))) int smap_timeline_count(void) 
 
 extern "C" {
 
-int smap_sizeof_op(void) { return (int)sizeof(smap_op); }
-
+// The two constructors: the checker (csrc/plan_check.cpp) fills the plan or refuses the schedule; nothing here touches the GPU.
 int smap_plan_create(const smap_op* ops, int n_ops, smap_plan** plan)
 {
-    if (!ops || !plan || n_ops <= 0 || n_ops > 4096) return SMAP_E_ARG;
-    for (int i = 0; i < n_ops; ++i)
-        if (int rc = validate(ops[i])) return rc;
-    smap_plan* p = new (std::nothrow) smap_plan();
-    if (!p) return SMAP_E_ARG;
-    p->ops.assign(ops, ops + n_ops);
-    p->signalled.assign(n_ops, 0);
-    for (int i = 0; i < n_ops; ++i) {                    // lanes: every wait names an EARLIER op of ANOTHER lane
-        const smap_op& o = ops[i];
-        if (o.lane < 0 || o.lane >= SMAP_MAX_LANES || o.n_wait < 0 || o.n_wait > 4) { delete p; return SMAP_E_ARG; }
-        if (o.lane + 1 > p->n_lanes) p->n_lanes = o.lane + 1;
-        for (int k = 0; k < o.n_wait; ++k) {
-            const int w = o.wait_op[k];
-            if (w < 0 || w >= i || ops[w].lane == o.lane) { delete p; return SMAP_E_ARG; }
-            p->signalled[w] = 1;
-        }
-    }
-    p->windows.push_back(0);
-    for (int i = 0; i < n_ops; ++i)
-        if (ops[i].kind == SMAP_OP_CONV) {
-            const int64_t w = window_of(ops[i].in_off);
-            bool have = false;
-            for (int64_t x : p->windows) have = have || x == w;
-            if (!have) p->windows.push_back(w);
-            if (ops[i].ksplit > 1) {
-                int bm = 0, bn = 1;
-                smap_conv_tile_dims(ops[i].tile, &bm, &bn);
-                const int64_t tiles = (((int64_t)ops[i].B * ops[i].Ho * ops[i].Wo + bm - 1) / bm) * (ops[i].cout_pad / bn);
-                p->tickets.push_back({ops[i].kcount_off, tiles * 4, i});
-            }
-        }
-    // Split-K tickets: smap_plan_run zeroes EACH op's own slice (not a span from the lowest to the highest ticket: a foreign blob may put
-    // tensors in between), and a slice overlaps neither another op's slice nor any tensor / scratch range an op of the schedule touches --
-    // the tickets live for the whole schedule, whatever the packer reuses around them.
-    for (size_t t = 0; t < p->tickets.size(); ++t) {
-        const int64_t lo = p->tickets[t].off, hi = lo + p->tickets[t].bytes;
-        for (size_t u = 0; u < t; ++u)
-            if (lo < p->tickets[u].off + p->tickets[u].bytes && p->tickets[u].off < hi) { delete p; return SMAP_E_ARG; }
-        for (int i = 0; i < n_ops; ++i) {
-            const smap_op& o = ops[i];
-            if (o.kind != SMAP_OP_CONV && o.kind != SMAP_OP_STEM && o.kind != SMAP_OP_MAXPOOL && o.kind != SMAP_OP_UPADD && o.kind != SMAP_OP_STEMPOOL) continue;
-            const int64_t M = (int64_t)o.B * o.Ho * o.Wo, pl = 1 + o.precision;
-            const int64_t c8 = o.tail_cout > 0 ? o.tail_cout : ((o.Cout + 7) & ~7);
-            auto hit = [&](int64_t off, int64_t bytes) { return off >= 0 && bytes > 0 && off < hi && lo < off + bytes; };
-            bool bad = hit(o.out_off, M * (o.kind == SMAP_OP_CONV ? (int64_t)o.out_stride_c * (o.out_fp32 ? 4 : 2) : c8 * 2 * pl));
-            if (o.kind == SMAP_OP_CONV || o.kind == SMAP_OP_MAXPOOL || o.kind == SMAP_OP_UPADD)
-                bad = bad || hit(o.in_off, (int64_t)o.B * o.H * o.W * (o.kind == SMAP_OP_CONV ? (int64_t)o.in_stride_c * 2 : (int64_t)o.Cin * 2 * pl));
-            if (o.kind == SMAP_OP_CONV) {
-                bad = bad || hit(o.res_off, M * c8 * 2 * pl) || hit(o.add1_off, M * c8 * 2 * pl) || hit(o.add2_off, M * c8 * 2 * pl);
-                if (o.in2_C > 0) bad = bad || hit(o.in2_off, (int64_t)o.B * o.in2_H * o.in2_W * o.in2_stride_c * 2);
-                bad = bad || hit(o.aux_off[0], (int64_t)o.B * o.aux_h[0] * o.aux_w[0] * c8 * 2 * pl);
-                for (int j = 0; j < 2; ++j)
-                    if (o.seg_n[j] > 0) bad = bad || hit(o.seg_out_off[j], M * o.seg_out_stride_c[j] * 2);
-                if (o.ksplit > 1) {
-                    int bm = 0, bn = 1;
-                    smap_conv_tile_dims(o.tile, &bm, &bn);
-                    const int64_t tiles = ((M + bm - 1) / bm) * (o.cout_pad / bn);
-                    bad = bad || hit(o.kpart_off, tiles * o.ksplit * bm * bn * 4);
-                }
-            }
-            if (bad) { delete p; return SMAP_E_ARG; }
-        }
-    }
-    *plan = p;
+    std::unique_ptr<smap_plan> p(new (std::nothrow) smap_plan());
+    if (!plan || !p) return SMAP_E_ARG;
+    if (int rc = plan_check(ops, n_ops, p.get())) return rc;
+    *plan = p.release();
     return 0;
 }
 
-static void lanes_release(smap_plan* p);
-
-void smap_plan_destroy(smap_plan* plan)
+int smap_plan_create_from_blob(const void* blob, size_t blob_bytes, smap_plan** plan, smap_blob_info* info)
 {
-    if (!plan) return;
-    lanes_release(plan);
-    delete plan;
+    std::unique_ptr<smap_plan> p(new (std::nothrow) smap_plan());
+    if (!plan || !p) return SMAP_E_ARG;
+    if (int rc = plan_check_blob(blob, blob_bytes, p.get(), info)) return rc;
+    *plan = p.release();
+    return 0;
 }
 
 static void lanes_release(smap_plan* p)
@@ -862,6 +617,13 @@ static void lanes_release(smap_plan* p)
         if (p->side[l]) { (void)hipStreamDestroy(p->side[l]); p->side[l] = nullptr; }
     }
     p->lanes_ready = false;
+}
+
+void smap_plan_destroy(smap_plan* plan)
+{
+    if (!plan) return;
+    lanes_release(plan);
+    delete plan;
 }
 
 // side streams + events of a plan whose lanes are switched on (device = the current one).  All or nothing: a failure half way releases
@@ -891,6 +653,70 @@ int smap_plan_set_lanes(smap_plan* plan, int on)
         if (int rc = lanes_setup(plan)) return rc;
     plan->lanes_on = on != 0;
     return 0;
+}
+
+// a CONV op as the argument block of its launch
+static ConvArgs conv_args(const smap_op& o, char* ar, const char* wb)
+{
+    auto A = [&](int64_t off) -> _Float16* { return off < 0 ? nullptr : reinterpret_cast<_Float16*>(ar + off); };
+    const TileRow& t = *tile_find(o.tile);       // (a checked op names a tile)
+    ConvArgs a;
+    a.arena = ar + window_of(o.in_off);          // 64-bit base of the launch; lane offsets are 32-bit from here
+    a.in_off = o.in_off - window_of(o.in_off);
+    a.w = reinterpret_cast<const _Float16*>(wb + o.w_off);
+    a.bias = reinterpret_cast<const float*>(wb + o.bias_off);
+    a.out = ar + o.out_off;
+    a.res = A(o.res_off);
+    a.add1 = A(o.add1_off);
+    a.add2 = A(o.add2_off);
+    a.up = A(o.aux_off[0]);
+    a.up_h = o.aux_h[0];
+    a.up_w = o.aux_w[0];
+    a.H = o.H; a.W = o.W; a.Cin = o.Cin; a.in_stride_c = o.in_stride_c; a.in_c_off = o.in_c_off;
+    a.Ho = o.Ho; a.Wo = o.Wo; a.Cout8 = (o.Cout + 7) & ~7;
+    a.ksize = o.ksize; a.stride = o.stride; a.pad = o.pad; a.relu = o.relu;
+    a.out_stride_c = o.out_stride_c; a.out_c_off = o.out_c_off; a.out_fp32 = o.out_fp32;
+    a.M = o.B * o.Ho * o.Wo;
+    a.K = o.ksize * o.ksize * o.Cin + (o.in2_C > 0 ? o.in2_C : 0);      // (a second input extends K)
+    a.Cin2 = o.in2_C > 0 ? o.in2_C : 0;
+    a.in2_off = o.in2_C > 0 ? o.in2_off - window_of(o.in_off) : 0;       // same base as the first input (validate: same window)
+    a.H2 = o.in2_H; a.W2 = o.in2_W; a.in2_stride_c = o.in2_stride_c; a.stride2 = o.in2_stride; a.in2_lo = o.in2_stride_c / 2;
+    a.bias_b = (o.in2_C > 0 && o.in2_mode == 1) ? reinterpret_cast<const float*>(wb + o.in2_bias_off) : nullptr;
+    a.acc_scale_b = o.in2_acc_scale;
+    a.x3 = o.precision;
+    a.in_lo = o.in_stride_c / 2;
+    a.out_lo = o.out_stride_c / 2;
+    a.w_lo = (long long)o.cout_pad * a.K * 2;
+    a.acc_scale = o.acc_scale;
+    a.w_pairs = o.w_pairs;
+    a.w2 = o.tail_cout > 0 ? reinterpret_cast<const _Float16*>(wb + o.tail_w_off) : nullptr;
+    a.bias2 = o.tail_cout > 0 ? reinterpret_cast<const float*>(wb + o.tail_bias_off) : nullptr;
+    a.tail_cout8 = o.tail_cout;
+    a.tail_chunks = o.tail_cout > 0 ? o.tail_cout_pad / t.tail_bn : 0;
+    a.tail_acc_scale = o.tail_acc_scale;
+    a.w0 = o.head_cin > 0 ? reinterpret_cast<const _Float16*>(wb + o.head_w_off) : nullptr;
+    a.bias0 = o.head_cin > 0 ? reinterpret_cast<const float*>(wb + o.head_bias_off) : nullptr;
+    a.head_cin = o.head_cin;
+    a.acc_scale0 = o.head_acc_scale;
+    a.wd = o.head_cin > 0 && o.short_acc_scale > 0.f ? reinterpret_cast<const _Float16*>(wb + o.short_w_off) : nullptr;
+    a.acc_scale_d = o.short_acc_scale;
+    a.tap_n = o.tap_n;
+    a.tap_w = o.tap_n > 0 ? reinterpret_cast<const _Float16*>(wb + o.tap_w_off) : nullptr;
+    a.tap_scale = o.tap_scale;
+    a.ksplit = o.ksplit > 1 ? o.ksplit : 1;
+    a.kpart = o.ksplit > 1 ? reinterpret_cast<float*>(ar + o.kpart_off) : nullptr;
+    a.kcount = o.ksplit > 1 ? reinterpret_cast<unsigned*>(ar + o.kcount_off) : nullptr;
+    a.seg_n1 = o.seg_n[0] > 0 ? o.seg_n[0] : INT32_MAX;
+    a.seg_n2 = o.seg_n[1] > 0 ? o.seg_n[1] : INT32_MAX;
+    a.seg_out1 = o.seg_n[0] > 0 ? ar + o.seg_out_off[0] : nullptr;
+    a.seg_out2 = o.seg_n[1] > 0 ? ar + o.seg_out_off[1] : nullptr;
+    a.seg_cout8_1 = o.seg_cout[0]; a.seg_cout8_2 = o.seg_cout[1];
+    a.seg_stride1 = o.seg_out_stride_c[0]; a.seg_stride2 = o.seg_out_stride_c[1];
+    a.seg_relu1 = o.seg_relu[0]; a.seg_relu2 = o.seg_relu[1];
+    a.seg_scale1 = o.seg_acc_scale[0]; a.seg_scale2 = o.seg_acc_scale[1];
+    a.m_tiles = (a.M + t.bm - 1) / t.bm;
+    a.n_tiles = o.cout_pad / t.bn;
+    return a;
 }
 
 static int run_ops(const smap_plan* plan, int first, int count, const float* const* inputs, int n_inputs, void* arena,
@@ -953,18 +779,7 @@ static int run_ops(const smap_plan* plan, int first, int count, const float* con
         }
         switch (o.kind) {
             case SMAP_OP_CONV: {
-                ConvArgs a;
-                a.arena = ar + window_of(o.in_off);          // 64-bit base of the launch; lane offsets are 32-bit from here
-                a.in_off = o.in_off - window_of(o.in_off);
-                a.w = reinterpret_cast<const _Float16*>(wb + o.w_off);
-                a.bias = reinterpret_cast<const float*>(wb + o.bias_off);
-                a.out = ar + o.out_off;
-                a.res = A(o.res_off);
-                a.add1 = A(o.add1_off);
-                a.add2 = A(o.add2_off);
-                a.up = A(o.aux_off[0]);
-                a.up_h = o.aux_h[0];
-                a.up_w = o.aux_w[0];
+                ConvArgs a = conv_args(o, ar, wb);
 #ifdef SMAP_TIMELINE
                 a.tl = nullptr;
                 if (tl_base() && tl_next < tl_cap()) {
@@ -975,52 +790,6 @@ static int run_ops(const smap_plan* plan, int first, int count, const float* con
 #ifdef SMAP_TRACE
                 a.dbg = getenv("SMAP_TRACE_PTR") ? reinterpret_cast<long long*>(strtoull(getenv("SMAP_TRACE_PTR"), nullptr, 0)) : nullptr;
 #endif
-                a.H = o.H; a.W = o.W; a.Cin = o.Cin; a.in_stride_c = o.in_stride_c; a.in_c_off = o.in_c_off;
-                a.Ho = o.Ho; a.Wo = o.Wo; a.Cout8 = (o.Cout + 7) & ~7;
-                a.ksize = o.ksize; a.stride = o.stride; a.pad = o.pad; a.relu = o.relu;
-                a.out_stride_c = o.out_stride_c; a.out_c_off = o.out_c_off; a.out_fp32 = o.out_fp32;
-                a.M = o.B * o.Ho * o.Wo;
-                a.K = o.ksize * o.ksize * o.Cin + (o.in2_C > 0 ? o.in2_C : 0);      // (a second input extends K)
-                a.Cin2 = o.in2_C > 0 ? o.in2_C : 0;
-                a.in2_off = o.in2_C > 0 ? o.in2_off - window_of(o.in_off) : 0;       // same base as the first input (validate: same window)
-                a.H2 = o.in2_H; a.W2 = o.in2_W; a.in2_stride_c = o.in2_stride_c; a.stride2 = o.in2_stride; a.in2_lo = o.in2_stride_c / 2;
-                a.bias_b = (o.in2_C > 0 && o.in2_mode == 1) ? reinterpret_cast<const float*>(wb + o.in2_bias_off) : nullptr;
-                a.acc_scale_b = o.in2_acc_scale;
-                a.x3 = o.precision;
-                a.in_lo = o.in_stride_c / 2;
-                a.out_lo = o.out_stride_c / 2;
-                a.w_lo = (long long)o.cout_pad * a.K * 2;
-                a.acc_scale = o.acc_scale;
-                a.w_pairs = o.w_pairs;
-                a.w2 = o.tail_cout > 0 ? reinterpret_cast<const _Float16*>(wb + o.tail_w_off) : nullptr;
-                a.bias2 = o.tail_cout > 0 ? reinterpret_cast<const float*>(wb + o.tail_bias_off) : nullptr;
-                a.tail_cout8 = o.tail_cout;
-                a.tail_chunks = o.tail_cout > 0 ? o.tail_cout_pad / smap_conv_tile_tail_bn(o.tile) : 0;
-                a.tail_acc_scale = o.tail_acc_scale;
-                a.w0 = o.head_cin > 0 ? reinterpret_cast<const _Float16*>(wb + o.head_w_off) : nullptr;
-                a.bias0 = o.head_cin > 0 ? reinterpret_cast<const float*>(wb + o.head_bias_off) : nullptr;
-                a.head_cin = o.head_cin;
-                a.acc_scale0 = o.head_acc_scale;
-                a.wd = o.head_cin > 0 && o.short_acc_scale > 0.f ? reinterpret_cast<const _Float16*>(wb + o.short_w_off) : nullptr;
-                a.acc_scale_d = o.short_acc_scale;
-                a.tap_n = o.tap_n;
-                a.tap_w = o.tap_n > 0 ? reinterpret_cast<const _Float16*>(wb + o.tap_w_off) : nullptr;
-                a.tap_scale = o.tap_scale;
-                a.ksplit = o.ksplit > 1 ? o.ksplit : 1;
-                a.kpart = o.ksplit > 1 ? reinterpret_cast<float*>(ar + o.kpart_off) : nullptr;
-                a.kcount = o.ksplit > 1 ? reinterpret_cast<unsigned*>(ar + o.kcount_off) : nullptr;
-                a.seg_n1 = o.seg_n[0] > 0 ? o.seg_n[0] : INT32_MAX;
-                a.seg_n2 = o.seg_n[1] > 0 ? o.seg_n[1] : INT32_MAX;
-                a.seg_out1 = o.seg_n[0] > 0 ? ar + o.seg_out_off[0] : nullptr;
-                a.seg_out2 = o.seg_n[1] > 0 ? ar + o.seg_out_off[1] : nullptr;
-                a.seg_cout8_1 = o.seg_cout[0]; a.seg_cout8_2 = o.seg_cout[1];
-                a.seg_stride1 = o.seg_out_stride_c[0]; a.seg_stride2 = o.seg_out_stride_c[1];
-                a.seg_relu1 = o.seg_relu[0]; a.seg_relu2 = o.seg_relu[1];
-                a.seg_scale1 = o.seg_acc_scale[0]; a.seg_scale2 = o.seg_acc_scale[1];
-                int bm, bn;
-                smap_conv_tile_dims(o.tile, &bm, &bn);
-                a.m_tiles = (a.M + bm - 1) / bm;
-                a.n_tiles = o.cout_pad / bn;
                 e = smap_launch_conv(a, o.tile, st);
                 break;
             }
@@ -1124,108 +893,10 @@ static int run_ops(const smap_plan* plan, int first, int count, const float* con
     return 0;
 }
 
-// arena / output bytes the schedule touches, from the ops alone (a host that did not build the schedule sizes its buffers with it)
 int smap_workspace_bytes(const smap_plan* plan, int64_t* arena_bytes, int64_t* out_bytes)
 {
     if (!plan) return SMAP_E_ARG;
-    int64_t ar = SMAP_ZERO_PAGE, ob = 0;
-    auto up = [](int64_t& m, int64_t off, int64_t bytes) { if (off >= 0 && off + bytes > m) m = off + bytes; };
-    for (const smap_op& o : plan->ops) {
-        const int64_t M = (int64_t)o.B * o.Ho * o.Wo, pl = 1 + o.precision;
-        switch (o.kind) {
-            case SMAP_OP_CONV: {
-                const int64_t c8 = o.tail_cout > 0 ? o.tail_cout : ((o.Cout + 7) & ~7);
-                up(ar, o.in_off, (int64_t)o.B * o.H * o.W * o.in_stride_c * 2);
-                if (o.in2_C > 0) up(ar, o.in2_off, (int64_t)o.B * o.in2_H * o.in2_W * o.in2_stride_c * 2);
-                up(ar, o.out_off, M * o.out_stride_c * (o.out_fp32 ? 4 : 2));
-                up(ar, o.res_off, M * c8 * 2 * pl); up(ar, o.add1_off, M * c8 * 2 * pl); up(ar, o.add2_off, M * c8 * 2 * pl);
-                up(ar, o.aux_off[0], (int64_t)o.B * o.aux_h[0] * o.aux_w[0] * c8 * 2 * pl);
-                for (int j = 0; j < 2; ++j)
-                    if (o.seg_n[j] > 0) up(ar, o.seg_out_off[j], M * o.seg_out_stride_c[j] * 2);
-                if (o.ksplit > 1) {
-                    int bm = 0, bn = 1;
-                    smap_conv_tile_dims(o.tile, &bm, &bn);
-                    const int64_t tiles = ((M + bm - 1) / bm) * (o.cout_pad / bn);
-                    up(ar, o.kpart_off, tiles * o.ksplit * bm * bn * 4);
-                    up(ar, o.kcount_off, tiles * 4);
-                }
-                break;
-            }
-            case SMAP_OP_STEM: case SMAP_OP_STEMPOOL: up(ar, o.out_off, M * 64 * 2 * pl); break;
-            case SMAP_OP_MAXPOOL:
-                up(ar, o.in_off, (int64_t)o.B * o.H * o.W * o.Cin * 2 * pl); up(ar, o.out_off, M * o.Cout * 2 * pl); break;
-            case SMAP_OP_UPADD:
-                up(ar, o.in_off, M * o.Cout * 2); up(ar, o.out_off, M * o.Cout * 2);
-                up(ar, o.aux_off[0], (int64_t)o.B * o.aux_h[0] * o.aux_w[0] * o.Cout * 2); break;
-            case SMAP_OP_TAPSUM:
-                up(ar, o.aux_off[0], M * o.Cin * 4);
-                up(ob, o.ext_off, M * 4);
-                if (o.status_off > 0) up(ob, o.status_off, 4 * (int64_t)SMAP_STATUS_WORDS(o.B));
-                break;
-            case SMAP_OP_HEADSUM: {
-                const int64_t frames = o.flip_from > 0 ? 2 * (int64_t)o.B : o.B;        // the sources hold the mirrored half too
-                for (int k = 0; k < o.n_aux; ++k) up(ar, o.aux_off[k], frames * o.aux_h[k] * o.aux_w[k] * o.Cin * 4);
-                up(ob, o.ext_off, M * o.Cout * 4);
-                if (o.status_off > 0) up(ob, o.status_off, 4 * (int64_t)SMAP_STATUS_WORDS(o.B));
-                break;
-            }
-            default: break;
-        }
-    }
-    if (arena_bytes) *arena_bytes = ar;
-    if (out_bytes) *out_bytes = ob;
-    return 0;
-}
-
-// ---- serialised plans: include/smap_hip.h "plan blob"
-int smap_plan_create_from_blob(const void* blob, size_t blob_bytes, smap_plan** plan, smap_blob_info* info)
-{
-    if (!blob || !plan || blob_bytes < sizeof(smap_blob_header)) return SMAP_E_ARG;
-    smap_blob_header h;
-    memcpy(&h, blob, sizeof(h));
-    if (memcmp(h.magic, "SMAPPLN1", 8) || h.version != SMAP_BLOB_VERSION || h.sizeof_op != sizeof(smap_op) || h.header_bytes != sizeof(smap_blob_header))
-        return SMAP_E_ARG;
-    // every (offset, size) pair is checked as `off <= total - size` with total - size >= 0: no sum that could wrap
-    const int64_t total = (int64_t)blob_bytes;
-    auto inside = [](int64_t off, int64_t size, int64_t total_) { return off >= 0 && size >= 0 && size <= total_ && off <= total_ - size; };
-    if (h.n_ops <= 0 || h.n_ops > 4096 || h.ops_offset < (int64_t)sizeof(h)) return SMAP_E_ARG;
-    if (!inside(h.ops_offset, (int64_t)h.n_ops * (int64_t)sizeof(smap_op), total) || !inside(h.weights_offset, h.weights_bytes, total)) return SMAP_E_ARG;
-    std::vector<smap_op> ops(h.n_ops);
-    memcpy(ops.data(), static_cast<const char*>(blob) + h.ops_offset, (size_t)h.n_ops * sizeof(smap_op));
-    for (const smap_op& o : ops) {      // the blob's weight section must hold EVERY byte the ops point at (packed sizes: include/smap_hip.h)
-        const int64_t wb = h.weights_bytes, pl = o.precision == 1 ? 2 : 1;
-        bool ok = true;
-        if (o.kind == SMAP_OP_CONV) {
-            if (o.cout_pad <= 0 || o.Cin <= 0 || o.ksize <= 0 || o.ksize > 7) return SMAP_E_ARG;
-            if (o.in2_C < 0 || o.in2_C > (1 << 20)) return SMAP_E_ARG;
-            ok = inside(o.w_off, (int64_t)o.cout_pad * (o.ksize * o.ksize * o.Cin + o.in2_C) * 2 * pl, wb) && inside(o.bias_off, (int64_t)o.cout_pad * 4, wb);
-            if (o.tail_cout > 0)
-                ok = ok && o.tail_cout_pad > 0 && o.Cout > 0 && inside(o.tail_w_off, (int64_t)o.tail_cout_pad * o.Cout * 2 * pl, wb) &&
-                     inside(o.tail_bias_off, (int64_t)o.tail_cout_pad * 4, wb);
-            if (o.head_cin > 0) {
-                ok = ok && inside(o.head_w_off, (int64_t)o.head_cin * o.Cin * 2 * pl, wb) && inside(o.head_bias_off, (int64_t)o.Cin * 4, wb);
-                if (o.short_acc_scale > 0.f) ok = ok && o.tail_cout > 0 && inside(o.short_w_off, (int64_t)o.tail_cout * o.head_cin * 2 * pl, wb);
-            }
-        } else if (o.kind == SMAP_OP_STEM || o.kind == SMAP_OP_STEMPOOL) {
-            ok = inside(o.w_off, (int64_t)64 * ST_K * 2 * pl, wb) && inside(o.bias_off, 64 * 4, wb);
-        } else if (o.kind == SMAP_OP_HEADSUM && o.flip_from > 0) {
-            ok = o.Cout > 0 && inside(o.w_off, (int64_t)o.Cout * 4, wb);
-        } else if (o.kind == SMAP_OP_TAPSUM) {
-            ok = inside(o.bias_off, 4, wb);
-        }
-        if (o.kind == SMAP_OP_CONV && o.in2_C > 0 && o.in2_mode == 1) ok = ok && inside(o.in2_bias_off, (int64_t)o.cout_pad * 4, wb);
-        if (o.kind == SMAP_OP_CONV && o.tap_n > 0) ok = ok && inside(o.tap_w_off, (int64_t)(o.cout_pad / 32) * 2 * 64 * 8 * 2, wb);
-        if (!ok) return SMAP_E_ARG;
-    }
-    smap_plan* p = nullptr;
-    if (int rc = smap_plan_create(ops.data(), h.n_ops, &p)) return rc;
-    int64_t ar = 0, ob = 0;
-    smap_workspace_bytes(p, &ar, &ob);
-    // the sizes a host allocates from (header AND info) must cover what the ops touch
-    if (ar > h.arena_bytes || ob > h.out_bytes || ar > h.info.arena_bytes || ob > h.info.out_bytes ||
-        h.info.weights_offset != h.weights_offset || h.info.weights_bytes != h.weights_bytes) { smap_plan_destroy(p); return SMAP_E_ARG; }
-    if (info) *info = h.info;
-    *plan = p;
+    plan_workspace_bytes(plan->ops, arena_bytes, out_bytes);
     return 0;
 }
 

@@ -219,3 +219,53 @@ def test_status_words_follow_the_frame_count():
         ob = C.c_int64()
         assert lib.smap_workspace_bytes(plan, None, C.byref(ob)) == 0 and ob.value == info.out_bytes
         lib.smap_plan_destroy(plan)
+
+
+def _small_blobs():
+    """The two serialised 2x64x96 schedules of test_plan_blob_round_trip_and_workspace_bytes."""
+    from recipe import recipe_state_dict
+    from smap_amd.engine import Graph
+    from smap_amd.model.smap import SMAP
+    torch.manual_seed(0)
+    sd = recipe_state_dict(SMAP(make_cfg((16, 24))).state_dict())
+    for precision, flip in (("x3", None), ("f16", list(range(43)))):
+        g = Graph(sd, 2, 64, 96, precision=precision, flip_pair=flip)
+        g.allocate()
+        yield precision, g.blob()
+
+
+def test_plan_checker_under_sanitizers_and_sizes_beyond_int64(tmp_path):
+    """tests/c/plan_check_main.cpp + csrc/plan_check.cpp built for the CPU with -fsanitize=address,undefined: the blob itself, every
+    truncation of its header and ops section and every field of every op overwritten with -1, 0, 1, INT32_MAX, INT32_MIN (INT64_MAX,
+    2^32 - 8) -- no report, no crash, the intact blob accepted.  And through the library: a CONV whose input size does not fit int64
+    (B = H = W = in_stride_c = INT32_MAX, the rest as emitted) is refused by the blob loader."""
+    import ctypes as C
+    import subprocess
+    from smap_amd import lib as L
+    csrc = os.path.join(ROOT, "smap_amd", "csrc")
+    exe = tmp_path / "plan_check"
+    r = subprocess.run(["g++", "-g", "-O2", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                        "-I" + os.path.join(ROOT, "include"), "-I" + csrc, os.path.join(ROOT, "tests", "c", "plan_check_main.cpp"),
+                        os.path.join(csrc, "plan_check.cpp"), "-o", str(exe)], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-3000:]
+    procs = []
+    for precision, blob in _small_blobs():
+        p = tmp_path / (precision + ".blob")
+        p.write_bytes(blob)
+        procs.append((precision, subprocess.Popen([str(exe), str(p)], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True,
+                                                  env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0"))))
+        hdr = L.BlobHeader.from_buffer_copy(blob[:C.sizeof(L.BlobHeader)])
+        so = C.sizeof(L.SmapOp)
+        ops = (L.SmapOp * hdr.n_ops).from_buffer_copy(blob[hdr.ops_offset:hdr.ops_offset + hdr.n_ops * so])
+        i = next(k for k in range(hdr.n_ops) if ops[k].kind == 0 and ops[k].head_cin == 0)
+        ops[i].B = ops[i].H = ops[i].W = ops[i].in_stride_c = 2 ** 31 - 1
+        huge = blob[:hdr.ops_offset] + bytes(ops) + blob[hdr.ops_offset + hdr.n_ops * so:]
+        plan = C.c_void_p()
+        assert L.load().smap_plan_create_from_blob(huge, len(huge), C.byref(plan), None) == -1, precision
+        del huge
+    for precision, p in procs:
+        out, err = p.communicate(timeout=900)
+        assert p.returncode == 0 and "ERROR" not in err and "runtime error" not in err, (precision, err[-3000:])
+        lines = out.splitlines()
+        assert lines[0] == "blob accepted" and lines[-1].startswith("total accepted ") and len(lines) > 100000, (precision, lines[:2], lines[-1:])
+        assert all(ln.endswith((" accepted", " rejected")) for ln in lines[:-1])

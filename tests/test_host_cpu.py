@@ -193,7 +193,7 @@ def test_tile_geometry_tables_agree_with_the_library():
 
 
 def _capability_probe(tile, x3, variant):
-    """The smallest CONV op that csrc/plan.hip::validate can only refuse for what tile id `tile` is: laid out from the PYTHON table's row
+    """The smallest CONV op that csrc/plan_check.cpp::validate can only refuse for what tile id `tile` is: laid out from the PYTHON table's row
     (unknown ids: as a 1x1 on a 128 x 64 tile), 1 frame of 8 x 8 pixels, every tensor a MiB apart inside the first window.
     variant: "plain", "fp32out", "splitk" (ksplit = 2), "dual" (in2_C), "relusum" (in2_mode = 1), "segments" (two N segments), "tapdot"."""
     from smap_amd import lib as L
@@ -241,7 +241,7 @@ def _capability_probe(tile, x3, variant):
 def test_tile_capabilities_agree_with_what_the_plan_accepts():
     """The facts of a tile id that no ABI function exports -- which precisions it has an instance in, its kernel family, split K, second
     input, relu-sum, register epilogue, tap-dot, the planes / first-block flag of a whole-block tile -- compared through
-    csrc/plan.hip::validate: for every id 0..99 and both precisions, smap_plan_create accepts a minimal op that needs the fact exactly
+    csrc/plan_check.cpp::validate: for every id 0..99 and both precisions, smap_plan_create accepts a minimal op that needs the fact exactly
     when the Python table (smap_amd/engine.py TILE_TABLE) says the id has it.  Plan creation touches no GPU."""
     import ctypes as C
     from smap_amd import lib as L
@@ -707,3 +707,121 @@ def test_arena_without_reuse_keeps_two_input_launches_in_one_window(monkeypatch,
     h = C.c_void_p()
     assert L.load().smap_plan_create(g.emit(), len(g.ops), C.byref(h)) == 0
     L.load().smap_plan_destroy(h)
+
+
+# -- the host-side guard (csrc/plan_check.cpp): one rule for every arena range of every op kind ---------------------------------------------
+
+def _one_op_plan_rc(o, alter=None):
+    """smap_plan_create on a copy of `o` alone (lane 0, no waits), after alter(copy)."""
+    import ctypes as C
+    from smap_amd import lib as L
+    one = (L.SmapOp * 1)(o)
+    one[0].lane = one[0].n_wait = 0
+    if alter:
+        alter(one[0])
+    h = C.c_void_p()
+    rc = L.load().smap_plan_create(one, 1, C.byref(h))
+    if rc == 0:
+        L.load().smap_plan_destroy(h)
+    return rc
+
+
+BAD_ARENA_OFFSETS = (-1, 0, 16384 - 16, 2 ** 32 - 16)      # absent; on the zero page; its last 16 bytes; crossing into the next window's zero page
+
+
+@pytest.fixture(scope="module")
+def guard_schedules(small_sd):
+    """Two emitted 2x64x96 schedules that between them hold every op kind: split precision with split K forced on and round 6's launches
+    (second input, tap-dot + TAPSUM); fp16 with one launch per conv, the unfused UPADD and the fused stem + pool."""
+    from smap_amd.engine import Graph
+    out = {}
+    for name, precision, env in (("x3", "x3", dict(SMAP_SPLITK="2", SMAP_CAT="1", SMAP_SKIPSUM="1", SMAP_TAPHEAD="1")),
+                                 ("f16", "f16", dict(SMAP_MERGE_1X1="0", SMAP_NO_UPADD_FUSION="1", SMAP_STEMPOOL="1"))):
+        with pytest.MonkeyPatch.context() as mp:
+            for k, v in env.items():
+                mp.setenv(k, v)
+            g = Graph(small_sd, 2, 64, 96, precision=precision)
+            g.allocate()
+            out[name] = g.emit()
+    return out
+
+
+def test_every_required_arena_offset_of_every_op_kind_is_checked(guard_schedules):
+    """One op of each kind out of emitted 2x64x96 schedules, as a one-op plan: accepted as emitted, refused with any REQUIRED arena offset
+    absent (-1), on a reserved zero page (0, SMAP_ZERO_PAGE - 16) or crossing into the next window (2^32 - 16).  (Before the ranges of
+    every kind went through one walk, the MAXPOOL, UPADD, STEM, STEMPOOL and HEADSUM rows were accepted.)"""
+    from smap_amd.engine import OP_CONV, OP_HEADSUM, OP_MAXPOOL, OP_STEM, OP_STEMPOOL, OP_TAPSUM, OP_UPADD
+    x3, f16 = guard_schedules["x3"], guard_schedules["f16"]
+    first = lambda ops, pred: next(o for o in ops if pred(o))
+    rows = [     # kind, the op, its required arena offsets as (field, index or None)
+        ("CONV", first(x3, lambda o: o.kind == OP_CONV and o.head_cin == 0 and o.ksplit <= 1), [("in_off", None), ("out_off", None)]),
+        ("CONV split K", first(x3, lambda o: o.kind == OP_CONV and o.ksplit > 1), [("kpart_off", None), ("kcount_off", None)]),
+        ("CONV second input", first(x3, lambda o: o.kind == OP_CONV and o.in2_C > 0), [("in2_off", None)]),
+        ("CONV segments", first(x3, lambda o: o.kind == OP_CONV and o.seg_n[0] > 0), [("seg_out_off", 0)]),
+        ("STEM", first(x3, lambda o: o.kind == OP_STEM), [("out_off", None)]),
+        ("STEMPOOL", first(f16, lambda o: o.kind == OP_STEMPOOL), [("out_off", None)]),
+        ("MAXPOOL", first(x3, lambda o: o.kind == OP_MAXPOOL), [("in_off", None), ("out_off", None)]),
+        ("UPADD", first(f16, lambda o: o.kind == OP_UPADD), [("in_off", None), ("out_off", None), ("aux_off", 0)]),
+        ("HEADSUM", first(x3, lambda o: o.kind == OP_HEADSUM and o.n_aux == 3), [("aux_off", 0), ("aux_off", 1), ("aux_off", 2)]),
+        ("TAPSUM", first(x3, lambda o: o.kind == OP_TAPSUM), [("aux_off", 0)]),
+    ]
+    for kind, o, fields in rows:
+        assert _one_op_plan_rc(o) == 0, kind
+        for field, idx in fields:
+            for val in BAD_ARENA_OFFSETS:
+                def alter(c, field=field, idx=idx, val=val):
+                    if idx is None:
+                        setattr(c, field, val)
+                    else:
+                        getattr(c, field)[idx] = val
+                assert _one_op_plan_rc(o, alter) != 0, (kind, field, idx, val)
+
+
+def test_split_k_tickets_may_not_lie_on_a_head_sum_or_tap_sum_source(guard_schedules):
+    """A ticket slice overlaps no arena range of any op: the fp32 sources of HEADSUM and TAPSUM included."""
+    import ctypes as C
+    from smap_amd import lib as L
+    from smap_amd.engine import OP_CONV, OP_HEADSUM, OP_TAPSUM
+    ops = guard_schedules["x3"]
+    n, h = len(ops), C.c_void_p()
+    assert L.load().smap_plan_create(ops, n, C.byref(h)) == 0
+    L.load().smap_plan_destroy(h)
+    i = next(k for k in range(n) if ops[k].kind == OP_CONV and ops[k].ksplit > 1)
+    for kind in (OP_HEADSUM, OP_TAPSUM):
+        src = next(o for o in ops if o.kind == kind)
+        bad = (L.SmapOp * n)()
+        C.memmove(bad, ops, C.sizeof(bad))
+        bad[i].kcount_off = src.aux_off[0]
+        assert L.load().smap_plan_create(bad, n, C.byref(h)) != 0, kind
+
+
+def test_sizes_beyond_int64_are_refused(guard_schedules):
+    """B = H = W = in_stride_c = INT32_MAX on an otherwise valid CONV: the byte count of its input does not fit int64."""
+    from smap_amd.engine import OP_CONV
+    o = next(o for o in guard_schedules["x3"] if o.kind == OP_CONV and o.head_cin == 0)
+
+    def huge(c):
+        c.B = c.H = c.W = c.in_stride_c = 2 ** 31 - 1
+    assert _one_op_plan_rc(o) == 0 and _one_op_plan_rc(o, huge) != 0
+
+
+# smap_workspace_bytes (arena, output) of the library built from the parent of the commit that introduced csrc/plan_check.cpp
+WORKSPACE_BEFORE_THE_SPLIT = {("x3", 2): (4735232, 178180), ("f16 flip", 2): (5718784, 178180),
+                              ("x3", 8): (1308639232, 49414148), ("x3", 16): (2617262080, 98828292)}
+
+
+def test_workspace_bytes_did_not_drift(small_sd):
+    import ctypes as C
+    from smap_amd import lib as L
+    from smap_amd.engine import Graph
+    lib = L.load()
+    full = _full_size_sd()
+    for (name, B), want in WORKSPACE_BEFORE_THE_SPLIT.items():
+        g = Graph(small_sd, 2, 64, 96, precision=name[:3].strip(), flip_pair=list(range(43)) if "flip" in name else None) if B == 2 else \
+            Graph(full, B, 512, 832, precision="x3")
+        g.allocate()
+        h, ar, ob = C.c_void_p(), C.c_int64(), C.c_int64()
+        assert lib.smap_plan_create(g.emit(), len(g.ops), C.byref(h)) == 0
+        assert lib.smap_workspace_bytes(h, C.byref(ar), C.byref(ob)) == 0
+        lib.smap_plan_destroy(h)
+        assert (ar.value, ob.value) == want, (name, B)
