@@ -67,12 +67,18 @@ class DevicePreprocLoader:
     device_decode (`--device_decode 1`): the pool threads read the file bytes, parse the JPEG markers and Huffman-decode the coefficients
     into page-locked memory (native code, no interpreter lock); the consumer uploads them and the GPU finishes the decode (smap_amd/jpeg.py),
     bit for bit PIL's frame.  Whatever the native decoder does not take (progressive, PNG, damaged files ...) is decoded with PIL as before;
-    the count is logged at the end of the run.  Worker processes (SMAP_DECODE_PROCS) are not used then."""
+    the count is logged at the end of the run.  Worker processes (SMAP_DECODE_PROCS) are not used then.
+    `--device_decode 2`: the Huffman decode runs on the GPU too (smap_amd/csrc/jpeg_huff.hip).  The pool threads only read the file, parse
+    its markers and pack the scan's tables with the file bytes into one page-locked buffer; the consumer uploads it, launches the decode of
+    every frame of the batch, waits ONCE per batch and reads the status words.  A frame the device decoder does not vouch for (status != 0)
+    is decoded again by the host decoder, then by PIL, exactly as mode 1 would have decoded it; both counts are logged at the end."""
 
     def __init__(self, dataset, indices, batch_size, cfg, device, device_decode=False):
         self.ds, self.idx, self.bs, self.cfg, self.device = dataset, list(indices), batch_size, cfg, device
         self.device_decode = bool(device_decode)
+        self.device_huffman = int(device_decode) == 2        # --device_decode 2: the entropy decode on the GPU as well
         self.pil_frames = 0                                  # device_decode: frames that fell back to PIL
+        self.host_frames = 0                                 # device_huffman: frames the host decoder redid
         try:
             allowed = len(os.sched_getaffinity(0))
         except AttributeError:
@@ -91,15 +97,20 @@ class DevicePreprocLoader:
 
     def __iter__(self):
         yield from self._batches()
-        if self.device_decode:
+        if self.device_huffman:
+            logging.getLogger(self.cfg.DATASET.NAME).info("device decode: {} of {} frames were redone on the host, {} fell back to PIL".format(
+                self.host_frames, len(self.idx), self.pil_frames))
+        elif self.device_decode:
             logging.getLogger(self.cfg.DATASET.NAME).info("device decode: {} of {} frames fell back to PIL".format(self.pil_frames, len(self.idx)))
 
     def _batches(self):
         from smap_amd.preprocess import preprocess_batch
-        self.pil_frames = 0
+        self.pil_frames = self.host_frames = 0
         if self.threads <= 1:
             for s in range(0, len(self.idx), self.bs):
-                if self.device_decode:
+                if self.device_huffman:
+                    raws, names = zip(*self._device_frames([self._coefficients(i, lambda img: img) for i in self.idx[s:s + self.bs]]))
+                elif self.device_decode:
                     raws, names = zip(*[self._device_frame(self._coefficients(i, lambda img: img)) for i in self.idx[s:s + self.bs]])
                 else:
                     raws, names = zip(*[self.ds.raw(i) for i in self.idx[s:s + self.bs]])
@@ -141,7 +152,9 @@ class DevicePreprocLoader:
                 n = min(self.bs, len(futs))
                 got = [futs.popleft().result() for _ in range(n)]       # in submission order: frame order is kept
                 fill()
-                if self.device_decode:
+                if self.device_huffman:
+                    got = self._device_frames(got)
+                elif self.device_decode:
                     got = [self._device_frame(g) for g in got]
                 raws, names = zip(*got)
                 imgs, scales = preprocess_batch(raws, self.cfg.INPUT.MEANS, self.cfg.INPUT.STDS, self.device)
@@ -156,7 +169,11 @@ class DevicePreprocLoader:
             with open(path, "rb") as f:
                 data = f.read()
             info = J.probe(data)
-            coeffs = J.decode_coefficients(data, info) if info is not None else None
+            if self.device_huffman:
+                frame = J.pack_frame(data, info) if info is not None else None
+                if frame is not None:
+                    return ("huff", frame, info, i), path.replace(self.ds.dataset_path, "").lstrip("/")
+            coeffs = J.decode_coefficients(data, info) if info is not None and not self.device_huffman else None
             if coeffs is not None:
                 return ("jpeg", coeffs, info), path.replace(self.ds.dataset_path, "").lstrip("/")
         img, name = self.ds.raw(i)
@@ -171,6 +188,30 @@ class DevicePreprocLoader:
         if not name.endswith(".npy"):
             self.pil_frames += 1
         return img, name
+
+    def _device_frames(self, items):
+        """device_huffman, in the consumer: upload every frame of the batch and launch its Huffman decode, wait once, read the status
+        words; redo what the device does not vouch for as mode 1 does (host decoder, then PIL); finish the decode on the GPU."""
+        from smap_amd import jpeg as J
+        launched = [(k, J.decode_coefficients_device(img[1], img[2], None, self.device))
+                    for k, (img, _) in enumerate(items) if isinstance(img, tuple)]
+        status = torch.cat([st for _, (_, st) in launched]).cpu().tolist() if launched else []     # the one wait of the batch
+        coeffs = {k: co for (k, (co, _)), st in zip(launched, status) if st == 0}
+        out = []
+        for k, (img, name) in enumerate(items):
+            if isinstance(img, tuple) and k not in coeffs:
+                self.host_frames += 1
+                co = J.decode_coefficients(J.frame_bytes(img[1]), img[2])
+                if co is None:
+                    raw, name = self.ds.raw(img[3])
+                    out.append(self._device_frame((raw, name)))
+                    continue
+                coeffs[k] = co
+            if isinstance(img, tuple):
+                out.append((J.reconstruct(coeffs[k], img[2], self.device), name))
+            else:
+                out.append(self._device_frame((img, name)))
+        return out
 
     def _process_decoders(self, stack, pinned):
         """Start SMAP_DECODE_PROCS workers (dataset/decode.py) over one shared-memory block; -> decode(i) for the pool threads.  A pool
@@ -396,13 +437,16 @@ def main():
                         help="(addition) 1: resize/pad/normalise on the GPU (smap_preprocess) instead of in the dataset")
     parser.add_argument("--device_decode", type=int, default=0,
                         help="(addition) 1: baseline JPEGs are Huffman-decoded on the host and finished on the GPU (smap_amd/jpeg.py), "
-                             "bit for bit the PIL frame; other files are decoded with PIL.  Requires --device_preprocess 1")
+                             "bit for bit the PIL frame; other files are decoded with PIL.  2: the Huffman decode runs on the GPU too "
+                             "(verified there; a frame it does not vouch for is redone on the host).  Requires --device_preprocess 1")
     parser.add_argument("--eval_3d", type=int, default=0, choices=[0, 1],
                         help="(addition) 1, with -t generate_result: score the run on the GPU (MPJPE, PCK, recall, reverse rate: "
                              "lib/eval/test_util_panoptic.py eval_3d) and write the `error` dict into the result file")
     args = parser.parse_args()
+    if args.device_decode not in (0, 1, 2):
+        parser.error("--device_decode is 0, 1 or 2")
     if args.device_decode and not args.device_preprocess:
-        parser.error("--device_decode 1 requires --device_preprocess 1")
+        parser.error("--device_decode {} requires --device_preprocess 1".format(args.device_decode))
     if args.eval_3d and args.test_mode != "generate_result":
         parser.error("--eval_3d 1 requires -t generate_result")
     if args.eval_3d and args.dry_run:

@@ -422,6 +422,61 @@ int64_t smap_jpeg_workspace_bytes(const smap_jpeg_info* info);
  * bgr: DEVICE uint8 [H'][W'][3], the orientation applied (orientations 5-8 swap width and height).  Two launches on `stream`. */
 int smap_jpeg_reconstruct(const int16_t* coeffs, const smap_jpeg_info* info, uint8_t* planes, uint8_t* bgr, void* stream);
 
+/* ---- Huffman decode on the device (csrc/jpeg_huff.h, csrc/jpeg_huff.hip; DESIGN.md "JPEG decode", "Huffman decode on the GPU") ----
+ * The host parses the markers and packs the scan's Huffman tables (microseconds); the GPU decodes the entropy-coded segment into the
+ * coefficients smap_jpeg_decode_coefficients writes: subsequences of the segment are decoded speculatively, one per lane, their decoder
+ * states are propagated to a fixed point, and a last EXACT pass re-decodes from those states, repeats every check of the host decoder
+ * and verifies that the chain of states closes.  Only that pass is trusted: status 0 means its output is the host decoder's. */
+#define SMAP_JPEG_DEV_E_DATA 1            /* the exact pass met what smap_jpeg_decode_coefficients calls SMAP_JPEG_E_DATA          */
+#define SMAP_JPEG_DEV_NOT_CONVERGED 2     /* the chain of decoder states did not close (more rounds, or the host decoder)         */
+#define SMAP_JPEG_SUBSEQ_BYTES 128        /* shipped defaults of subseq_bytes and rounds (DESIGN.md has the runs behind them)     */
+#define SMAP_JPEG_ROUNDS 8
+#define SMAP_JPEG_MAX_MCU_BLOCKS 6        /* 2x2 luma + Cb + Cr                                                                    */
+
+/* One Huffman table in decoding form: a 9-bit lookahead, then jdhuff.c's maxcode / valoff / vals for the longer codes. */
+typedef struct smap_jpeg_huff {
+    uint16_t look[512];                 /* (code length << 8) | symbol; 0 = longer than 9 bits, or no such code              */
+    int32_t maxcode[18];                /* largest code of each length, -1 = none; [17] = INT32_MAX                          */
+    int32_t valoff[18];                 /* index into vals of the first code of each length, minus that code                */
+    uint8_t vals[256];
+} smap_jpeg_huff;
+
+typedef struct smap_jpeg_scan {
+    smap_jpeg_huff table[6];            /* [2 * c] = DC table of scan component c, [2 * c + 1] = its AC table                */
+    int32_t ncomp;
+    int32_t blocks_per_mcu;
+    int32_t block_comp[SMAP_JPEG_MAX_MCU_BLOCKS];   /* of each block of the MCU, in scan order: its component ...            */
+    int32_t block_v[SMAP_JPEG_MAX_MCU_BLOCKS];      /* ... and its (v, h) inside the component's part of the MCU             */
+    int32_t block_h[SMAP_JPEG_MAX_MCU_BLOCKS];
+    int32_t restart_interval;
+    int32_t reserved;
+    int64_t scan_offset;                /* as smap_jpeg_info                                                                */
+    int64_t file_bytes;
+    int64_t total_blocks;               /* every block of the MCU grid, all components                                      */
+} smap_jpeg_scan;
+
+/* sizeof(smap_jpeg_scan) as compiled (binding check). */
+int smap_sizeof_jpeg_scan(void);
+
+/* data / info / scan: HOST.  Fills `scan` for these bytes; the refusals of smap_jpeg_decode_coefficients at the marker level (info is
+ * not this file's: SMAP_E_ARG; an undefined table, an over-long code set, a DC category above 15: SMAP_JPEG_E_DATA).  No allocation,
+ * no global state, callable from many threads. */
+int smap_jpeg_scan_tables(const uint8_t* data, size_t n, const smap_jpeg_info* info, smap_jpeg_scan* scan);
+
+/* Device scratch of smap_jpeg_decode_coefficients_device (bytes; 0 = bad arguments).  subseq_bytes: 0 = SMAP_JPEG_SUBSEQ_BYTES, else a
+ * multiple of 4 in 8..128.  info: HOST. */
+int64_t smap_jpeg_huff_workspace_bytes(const smap_jpeg_info* info, size_t file_bytes, int subseq_bytes);
+
+/* d_file: DEVICE copy of the whole file; info: HOST, what smap_jpeg_probe returned for it; d_scan: DEVICE copy of what
+ * smap_jpeg_scan_tables filled (8-byte aligned); rounds: cross-workgroup propagation launches, 0 = SMAP_JPEG_ROUNDS, at most the number
+ * of workgroups = ceil(ceil((file_bytes - scan_offset) / subseq_bytes) / 256), which is provably enough for any valid file; workspace:
+ * DEVICE, 8-byte aligned.  d_coeffs: DEVICE, info->coef_bytes, the layout of smap_jpeg_decode_coefficients.  *d_status (DEVICE) is
+ * 0 -- d_coeffs is bit for bit what smap_jpeg_decode_coefficients writes for these bytes -- or an OR of SMAP_JPEG_DEV_E_DATA and
+ * SMAP_JPEG_DEV_NOT_CONVERGED: the caller then uses the host decoder.  A fixed sequence of launches on `stream`, no read-back. */
+int smap_jpeg_decode_coefficients_device(const uint8_t* d_file, size_t file_bytes, const smap_jpeg_info* info,
+                                         const smap_jpeg_scan* d_scan, int subseq_bytes, int rounds, void* workspace,
+                                         int64_t workspace_bytes, int16_t* d_coeffs, int32_t* d_status, void* stream);
+
 /* ---- scoring: lib/eval/test_util_panoptic.py eval_3d (:273-307), initialization (:332-355) on the device ----
  * The accumulator is SMAP_EVAL_ACC_DOUBLES f64 on the device, kept across calls:
  *   real_error[15] | root_error[15] | count_point[15] | real_PCK[15] | root_PCK[15] |

@@ -29,6 +29,7 @@ SOURCES = [
     ("plan_check.cpp", []),       # host-only C++: which schedules and plan blobs the library runs (also built alone under sanitizers)
     ("jpeg.hip", []),
     ("jpeg_host.cpp", []),        # host-only C++ (marker parse + Huffman decode); no fast-math anywhere in this library
+    ("jpeg_huff.hip", []),        # the Huffman decode on the device; its algorithm is csrc/jpeg_huff.h (also built alone for the CPU)
 ]
 # -fvisibility=hidden: the .so exports exactly what include/smap_hip.h declares (its visibility push / pop), nothing of the internals
 COMMON = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden", "-I" + os.path.join(ROOT, "include"),

@@ -1,5 +1,6 @@
 // jpeg_host.cpp -- the host half of the JPEG decode (include/smap_hip.h "JPEG decode"): marker parsing and Huffman entropy decoding
 // into quantised coefficients.  The per-pixel half (dequantisation, IDCT, upsampling, colour, orientation) is csrc/jpeg.hip.
+// smap_jpeg_scan_tables hands the scan's decoding tables to the Huffman decode on the device (csrc/jpeg_huff.h, csrc/jpeg_huff.hip).
 //
 // Plain C++ with no HIP include, so that a test can build it alone for the CPU under AddressSanitizer (tests/c/jpeg_asan_main.cpp).
 // No allocation, no global state: every call keeps its tables on its own stack, and the entry points are called from many pool threads
@@ -20,13 +21,10 @@ constexpr uint8_t kNatural[64] = {
     0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6,  7,  14, 21, 28,
     35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
 
-struct Huff {
-    uint16_t look[1 << kLook];               // (code length << 8) | symbol; 0 = the code is longer than kLook bits (or invalid)
-    int32_t maxcode[18];                     // largest code of each length, -1 = none
-    int32_t valoff[18];                      // index into vals of the first code of each length, minus that code
-    uint8_t vals[256];
+struct Huff : smap_jpeg_huff {               // the decoding tables in the form the device kernels also read (include/smap_hip.h)
     bool defined;
 };
+static_assert(sizeof(((smap_jpeg_huff*)0)->look) == sizeof(uint16_t) << kLook, "smap_jpeg_huff::look is the kLook-bit lookahead");
 
 struct Parsed {
     smap_jpeg_info info;
@@ -39,6 +37,7 @@ inline uint32_t be16(const uint8_t* p) { return (uint32_t(p[0]) << 8) | p[1]; }
 // DHT table -> decoding tables (jdhuff.c jpeg_make_d_derived_tbl: canonical codes, an over-long code set is an error)
 int build_huff(const uint8_t* counts, const uint8_t* vals, int nvals, bool is_dc, Huff* h) {
     memset(h->look, 0, sizeof(h->look));
+    memset(h->vals, 0, sizeof(h->vals));                         // (the tables are also handed out whole: smap_jpeg_scan_tables)
     memcpy(h->vals, vals, size_t(nvals));
     uint32_t code = 0;
     int k = 0;
@@ -408,5 +407,36 @@ int smap_jpeg_decode_coefficients(const uint8_t* data, size_t n, const smap_jpeg
 }
 
 int64_t smap_jpeg_workspace_bytes(const smap_jpeg_info* info) { return info ? info->coef_bytes / 2 : 0; }
+
+int smap_sizeof_jpeg_scan(void) { return int(sizeof(smap_jpeg_scan)); }
+
+int smap_jpeg_scan_tables(const uint8_t* data, size_t n, const smap_jpeg_info* info, smap_jpeg_scan* scan) {
+    if (!data || !info || !scan) return SMAP_E_ARG;
+    Parsed p;
+    int rc = parse(data, n, &p, true);
+    if (rc != kOk) return rc;
+    if (memcmp(&p.info, info, sizeof(smap_jpeg_info)) != 0) return SMAP_E_ARG;
+    const smap_jpeg_info& I = p.info;
+    memset(scan, 0, sizeof(*scan));
+    scan->ncomp = I.ncomp;
+    int nb = 0;
+    for (int c = 0; c < I.ncomp; ++c) {
+        scan->table[2 * c] = p.dc[p.comp_dc[c]];                   // (slices the `defined` flag off)
+        scan->table[2 * c + 1] = p.ac[p.comp_ac[c]];
+        for (int v = 0; v < I.v_samp[c]; ++v)
+            for (int h = 0; h < I.h_samp[c]; ++h, ++nb) {
+                if (nb >= SMAP_JPEG_MAX_MCU_BLOCKS) return SMAP_E_ARG;   // (parse admits 1x1, 2x1, 2x2 luma only: cannot happen)
+                scan->block_comp[nb] = c;
+                scan->block_v[nb] = v;
+                scan->block_h[nb] = h;
+            }
+    }
+    scan->blocks_per_mcu = nb;
+    scan->restart_interval = I.restart_interval;
+    scan->scan_offset = I.scan_offset;
+    scan->file_bytes = int64_t(n);
+    scan->total_blocks = I.coef_bytes / 128;
+    return kOk;
+}
 
 }  // extern "C"

@@ -22,6 +22,7 @@ SYMBOLS = [
     "smap_nms_workspace_bytes", "smap_nms_ws",
     "smap_eval3d_acc_init", "smap_eval3d_terms", "smap_eval3d_fold", "smap_eval3d_update",
     "smap_sizeof_jpeg_info", "smap_jpeg_probe", "smap_jpeg_decode_coefficients", "smap_jpeg_workspace_bytes", "smap_jpeg_reconstruct",
+    "smap_sizeof_jpeg_scan", "smap_jpeg_scan_tables", "smap_jpeg_huff_workspace_bytes", "smap_jpeg_decode_coefficients_device",
 ]
 MAX_INPUTS = 8                         # SMAP_MAX_INPUTS
 
@@ -82,8 +83,25 @@ class JpegInfo(C.Structure):
                 ("scan_offset", C.c_int64), ("restart_interval", C.c_int32), ("reserved", C.c_int32)]
 
 
+class JpegHuff(C.Structure):
+    """Mirror of `struct smap_jpeg_huff`."""
+    _fields_ = [("look", C.c_uint16 * 512), ("maxcode", C.c_int32 * 18), ("valoff", C.c_int32 * 18), ("vals", C.c_uint8 * 256)]
+
+
+class JpegScan(C.Structure):
+    """Mirror of `struct smap_jpeg_scan`."""
+    _fields_ = [("table", JpegHuff * 6), ("ncomp", C.c_int32), ("blocks_per_mcu", C.c_int32), ("block_comp", C.c_int32 * 6),
+                ("block_v", C.c_int32 * 6), ("block_h", C.c_int32 * 6), ("restart_interval", C.c_int32), ("reserved", C.c_int32),
+                ("scan_offset", C.c_int64), ("file_bytes", C.c_int64), ("total_blocks", C.c_int64)]
+
+
 JPEG_UNSUPPORTED = 1      # SMAP_JPEG_UNSUPPORTED
 JPEG_E_DATA = -2          # SMAP_JPEG_E_DATA
+JPEG_DEV_E_DATA = 1       # SMAP_JPEG_DEV_E_DATA
+JPEG_DEV_NOT_CONVERGED = 2   # SMAP_JPEG_DEV_NOT_CONVERGED
+JPEG_SUBSEQ_BYTES = 128   # SMAP_JPEG_SUBSEQ_BYTES
+JPEG_ROUNDS = 8           # SMAP_JPEG_ROUNDS
+JPEG_HUFF_LANES = 256     # subsequences per workgroup (csrc/jpeg_huff.h kLanes)
 
 _lib = None
 
@@ -136,19 +154,26 @@ def load():
     lib.smap_jpeg_decode_coefficients.argtypes = [vp, C.c_size_t, C.POINTER(JpegInfo), vp]
     lib.smap_jpeg_workspace_bytes.argtypes = [C.POINTER(JpegInfo)]
     lib.smap_jpeg_reconstruct.argtypes = [vp, C.POINTER(JpegInfo), vp, vp, vp]
+    lib.smap_jpeg_scan_tables.argtypes = [vp, C.c_size_t, C.POINTER(JpegInfo), vp]
+    lib.smap_jpeg_huff_workspace_bytes.argtypes = [C.POINTER(JpegInfo), C.c_size_t, ip]
+    lib.smap_jpeg_decode_coefficients_device.argtypes = [vp, C.c_size_t, C.POINTER(JpegInfo), vp, ip, ip, vp, C.c_int64, vp, vp, vp]
     lib.smap_eval3d_acc_init.argtypes = [vp, vp]
     lib.smap_eval3d_terms.argtypes = [vp, vp, vp, ip, ip, vp, vp]
     lib.smap_eval3d_fold.argtypes = [vp, vp, ip, ip, vp, vp]
     lib.smap_eval3d_update.argtypes = [vp, vp, vp, ip, ip, vp, vp, vp]
     for s in SYMBOLS:
-        if s not in ("smap_version", "smap_plan_destroy", "smap_nms_workspace_bytes", "smap_jpeg_workspace_bytes"):  # everything else returns int
+        if s not in ("smap_version", "smap_plan_destroy", "smap_nms_workspace_bytes", "smap_jpeg_workspace_bytes",
+                     "smap_jpeg_huff_workspace_bytes"):  # everything else returns int
             getattr(lib, s).restype = ip
     lib.smap_nms_workspace_bytes.restype = C.c_int64
     lib.smap_jpeg_workspace_bytes.restype = C.c_int64
+    lib.smap_jpeg_huff_workspace_bytes.restype = C.c_int64
     if lib.smap_sizeof_op() != C.sizeof(SmapOp):
         raise ImportError(f"smap_op layout mismatch: C {lib.smap_sizeof_op()} vs ctypes {C.sizeof(SmapOp)}")
     if lib.smap_sizeof_jpeg_info() != C.sizeof(JpegInfo):
         raise ImportError(f"smap_jpeg_info layout mismatch: C {lib.smap_sizeof_jpeg_info()} vs ctypes {C.sizeof(JpegInfo)}")
+    if lib.smap_sizeof_jpeg_scan() != C.sizeof(JpegScan):
+        raise ImportError(f"smap_jpeg_scan layout mismatch: C {lib.smap_sizeof_jpeg_scan()} vs ctypes {C.sizeof(JpegScan)}")
     _lib = lib
     return lib
 

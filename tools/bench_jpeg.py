@@ -7,6 +7,12 @@ Two sets: the 8 JPEGs tools/cli_e2e.py writes (the bench's frames pixel-doubled,
 gradients with mild noise, quality 90, 4:2:0).
 
     python tools/bench_jpeg.py [--reps 5] [--threads 16] [--out file.json]
+
+`--device_huffman 1` (needs the GPU) measures `--device_decode 2` on the same two sets instead: the host's share per frame (marker parse
++ smap_jpeg_scan_tables + the copy into one page-locked buffer, process time of one thread), the bytes a frame uploads in either mode,
+and the GPU time per frame of smap_jpeg_decode_coefficients_device between two stream events for every `--subseq` x `--rounds` asked
+for, with the status words (a configuration that does not converge on every frame says so).  `--trace_only 1` only runs the shipped
+defaults once per frame after a warm-up: the run to put under `rocprofv3 --kernel-trace --stats` for per-kernel times.
 """
 import argparse
 import io
@@ -63,14 +69,76 @@ def timed(fn, frames, reps, threads):
     return 1e3 * (time.perf_counter() - t0) / len(work)
 
 
+def device_huffman(args, sets):
+    import torch
+    from smap_amd import jpeg as J
+    dev = torch.device("cuda:0")
+    res = {"subseq": args.subseq, "rounds": args.rounds, "reps": args.reps, "sets": {}}
+    for name, frames in sets:
+        infos = [J.probe(f) for f in frames]
+        t0 = time.process_time()
+        for _ in range(args.reps):
+            packed = [J.pack_frame(f, i) for f, i in zip(frames, infos)]
+        r = {"mean_file_KB": float(np.mean([len(f) for f in frames])) / 1e3,
+             "host_probe_tables_pack_ms": 1e3 * (time.process_time() - t0) / (args.reps * len(frames)) + 1e3 * _probe_s(J, frames),
+             "h2d_bytes_mode1": float(np.mean([i.coef_bytes for i in infos])),
+             "h2d_bytes_mode2": float(np.mean([p.numel() for p in packed])), "runs": []}
+        want = [J.decode_coefficients(f, i, pin=False) for f, i in zip(frames, infos)]
+        if args.trace_only:
+            for _ in range(2):
+                for p, i in zip(packed, infos):
+                    J.decode_coefficients_device(p, i, None, dev)
+                torch.cuda.synchronize()
+            res["sets"][name] = r
+            continue
+        for subseq in args.subseq:
+            for rounds in args.rounds:
+                outs = [J.decode_coefficients_device(p, i, None, dev, subseq, rounds) for p, i in zip(packed, infos)]    # warm-up + check
+                status = [int(st.item()) for _, st in outs]
+                equal = all(torch.equal(co.cpu(), w) for (co, _), w, st in zip(outs, want, status) if st == 0)
+                ups = [p.to(dev) for p in packed]
+                torch.cuda.synchronize()
+                ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+                ev[0].record()
+                for _ in range(args.reps):
+                    for p, i in zip(ups, infos):                                  # (already on the device: the launches alone)
+                        J.decode_coefficients_device(p, i, None, dev, subseq, rounds)
+                ev[1].record()
+                torch.cuda.synchronize()
+                run = {"subseq_bytes": subseq, "rounds": rounds, "status": status, "equal_where_status_0": bool(equal),
+                       "gpu_ms_per_frame": ev[0].elapsed_time(ev[1]) / (args.reps * len(frames))}
+                r["runs"].append(run)
+                print(name, json.dumps(run), flush=True)
+        res["sets"][name] = r
+        print(name, json.dumps({k: v for k, v in r.items() if k != "runs"}), flush=True)
+    return res
+
+
+def _probe_s(J, frames):
+    t0 = time.process_time()
+    for f in frames:
+        J.probe(f)
+    return (time.process_time() - t0) / len(frames)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--device_huffman", type=int, default=0)
+    ap.add_argument("--trace_only", type=int, default=0)
+    ap.add_argument("--subseq", type=int, nargs="+", default=[0])
+    ap.add_argument("--rounds", type=int, nargs="+", default=[0])
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--threads", type=int, default=16)
     ap.add_argument("--out", default="")
     args = ap.parse_args()
     from dataset.decode import read_bgr
     from smap_amd import jpeg as J
+    if args.device_huffman:
+        res = device_huffman(args, (("cli_e2e 1664x1024 q98 4:4:4", cli_e2e_frames()), ("photo-like 1664x1024 q90 4:2:0", photo_like_frames())))
+        if args.out:
+            os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+            json.dump(res, open(args.out, "w"), indent=1)
+        return
 
     def pil(data):
         return read_bgr(io.BytesIO(data))

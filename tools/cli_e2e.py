@@ -9,10 +9,12 @@ resolutions -- the bench's 8 frames as 832x512 PNGs and as 1664x1024 JPEGs (ever
 the frame back) -- so that the network sees the workload the bench line is quoted on (~20 skeletons per frame: association, lifting
 and record building do real work); a second folder holds the same pictures as .npy (no decoder).
 
-    python tools/cli_e2e.py [--images 256] [--out profiles/r5_cli_e2e.json] [--only jpeg]
+    python tools/cli_e2e.py [--images 256] [--out profiles/r5_cli_e2e.json] [--only jpeg | --only huffman [--pairs 3]]
 
 A third folder holds only the 1664x1024 JPEGs: there the PIL decoders (16 threads, 16 processes) run against `--device_decode 1`
-(Huffman decode on the host, the rest of the decode on the GPU) and the .npy frames.  --only jpeg runs those four legs alone.
+(Huffman decode on the host, the rest of the decode on the GPU) and the .npy frames.  --only jpeg runs those four legs alone.  --only huffman runs, on that folder, `--device_decode 1` against
+`--device_decode 2` (the Huffman decode on the GPU as well) alternating, `--pairs` times each at SMAP_DECODE_THREADS = 16 and = 2 after one
+uncounted run that builds the plan cache, and adds a summary with the mean and the spread (min .. max) of every leg.
 """
 import argparse
 import json
@@ -42,7 +44,8 @@ def main():
     ap.add_argument("--images", type=int, default=1024)
     ap.add_argument("--batch", type=int, default=8)
     ap.add_argument("--out", default=os.path.join(ROOT, "gpurun_out", "cli_e2e.json"))
-    ap.add_argument("--only", choices=["", "jpeg"], default="")
+    ap.add_argument("--only", choices=["", "jpeg", "huffman"], default="")
+    ap.add_argument("--pairs", type=int, default=3)
     args = ap.parse_args()
     from PIL import Image
     from benchkit.workload import make_cfg, people_state_dict
@@ -95,6 +98,13 @@ def main():
                   ("1664x1024 JPEG only, --device_decode 1 (host Huffman decode, default threads; IDCT / colour on the GPU)", jpg, dd, {}),
                   (".npy frames (no decoder), GPU pre-processing", raw, ["--device_preprocess", "1"], {})]
     cases = jpeg_cases if args.only == "jpeg" else cases + jpeg_cases[:3]
+    if args.only == "huffman":
+        cases = [("warm-up (builds the plan cache; not counted)", jpg, dd, {"SMAP_DECODE_THREADS": "16"})]
+        for threads in ("16", "2"):
+            for _ in range(args.pairs):
+                for mode in ("1", "2"):
+                    cases.append((f"1664x1024 JPEG only, --device_decode {mode}, {threads} decode threads", jpg,
+                                  ["--device_preprocess", "1", "--device_decode", mode], {"SMAP_DECODE_THREADS": threads}))
     os.makedirs(enc + "_few")
     for n in sorted(os.listdir(enc)):
         if n.startswith("im") and int(n[2:7]) < 128:
@@ -124,6 +134,13 @@ def main():
     out = {"images": args.images, "batch_size": args.batch, "sources": "the bench's 8 frames: 832x512 PNG and 1664x1024 JPEG q98 4:4:4 (pixel-doubled), alternating in groups of 8",
            "mean_file_KB": float(np.mean(sizes)) / 1e3, "generation_s": gen_s, "host_cpus_allowed": len(os.sched_getaffinity(0)),
            "gpu": torch.cuda.get_device_name(0) if torch.cuda.is_available() else None, "runs": runs}
+    if args.only == "huffman":
+        legs = {}
+        for rec in runs[1:]:
+            if rec.get("frames_per_s_after_engine_build"):
+                legs.setdefault(rec["case"], []).append(rec["frames_per_s_after_engine_build"])
+        out["summary_frames_per_s"] = {k: {"mean": float(np.mean(v)), "min": min(v), "max": max(v), "runs": v} for k, v in legs.items()}
+        print(json.dumps(out["summary_frames_per_s"], indent=1))
     os.makedirs(os.path.dirname(args.out), exist_ok=True)
     json.dump(out, open(args.out, "w"), indent=1)
     print("wrote", args.out)
