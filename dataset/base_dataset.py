@@ -82,6 +82,15 @@ class JointDataset(Dataset):
         bodys[:, :, 3][out] = 0
         return bodys, scale, size, (left, top)
 
+    def _padded(self, bodys):
+        padded = np.zeros((self.max_people, self.keypoint_num, bodys.shape[2]), np.float64)
+        padded[:len(bodys)] = bodys
+        return torch.from_numpy(padded).float()
+
+    def _meta(self, d, scale):
+        return {"scale": scale, "img_width": int(d["img_width"]), "img_height": int(d["img_height"]),
+                "net_width": self.crop_x, "net_height": self.crop_y}
+
     def __getitem__(self, index):
         from smap_amd.preprocess import resize_linear_u8
         d = self.data[index]
@@ -95,8 +104,33 @@ class JointDataset(Dataset):
         if x1 > x0 and y1 > y0:
             canvas[y0:y1, x0:x1] = r[y0 - top:y1 - top, x0 - left:x1 - left]
         t = torch.from_numpy(canvas).permute(2, 0, 1).float().div(255.0)
-        padded = np.zeros((self.max_people, self.keypoint_num, bodys.shape[2]), np.float64)
-        padded[:len(bodys)] = bodys
-        meta = {"scale": scale, "img_width": int(d["img_width"]), "img_height": int(d["img_height"]),
-                "net_width": self.crop_x, "net_height": self.crop_y}
-        return (t - self.mean) / self.std, torch.from_numpy(padded).float(), d["img_paths"], meta
+        return (t - self.mean) / self.std, self._padded(bodys), d["img_paths"], self._meta(d, scale)
+
+    # ---- what the device loader of exps/stage3_root2/test.py asks of a dataset (CustomDataset answers the same five) ----
+    def path(self, index):
+        """File of frame `index`."""
+        return self.image_path(self.data[index])
+
+    def name(self, index):
+        """What a record calls frame `index`: the annotation's img_paths, as __getitem__ returns it."""
+        return self.data[index]["img_paths"]
+
+    def geometry(self, index):
+        """(meta dict, (nh, nw, top, left), fx, fy) for smap_amd.preprocess.preprocess_batch: the window of __getitem__, from the
+        ANNOTATION's img_width / img_height.  The stored frame's own size only clamps the taps (the kernel takes it from the frame),
+        as resize_linear_u8 does in __getitem__ when the two disagree."""
+        d = self.data[index]
+        scale, (nh, nw), (left, top) = croppad_geometry(int(d["img_width"]), int(d["img_height"]), self.crop_x, self.crop_y)
+        return self._meta(d, scale), (nh, nw, top, left), scale, scale
+
+    def extras(self, index):
+        """(annotations [MAX_PEOPLE,15,C] fp32 zero padded, meta dict) of frame `index`, without touching its file."""
+        d = self.data[index]
+        bodys, scale, _, _ = self.annotate(d)
+        return self._padded(bodys), self._meta(d, scale)
+
+    def raw(self, index):
+        """__getitem__ without the pre-processing: (decoded frame as it is: uint8 HxWx3 BGR, annotations, img_paths, meta dict,
+        geometry)."""
+        ann, meta = self.extras(index)
+        return CustomDataset._read_bgr(self.path(index)), ann, self.name(index), meta, self.geometry(index)

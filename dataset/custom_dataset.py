@@ -60,5 +60,21 @@ class CustomDataset(Dataset):
 
     def raw(self, index):
         """(uint8 HxWx3 BGR image, image name) for the device pre-processing path (smap_amd/preprocess.py)."""
-        image_path = self.image_list[index].rstrip()
-        return self._read_bgr(image_path), image_path.replace(self.dataset_path, "").lstrip("/")
+        return self._read_bgr(self.path(index)), self.name(index)
+
+    # ---- what the device loader of exps/stage3_root2/test.py asks of a dataset besides raw() (JointDataset answers the same) ----
+    def path(self, index):
+        """File of frame `index`."""
+        return self.image_list[index].rstrip()
+
+    def name(self, index):
+        """What a record calls frame `index`: its path below the folder."""
+        return self.path(index).replace(self.dataset_path, "").lstrip("/")
+
+    def geometry(self, index):
+        """None: the letter-box of the frame's own size (smap_amd.preprocess.letterbox_geometry)."""
+        return None
+
+    def extras(self, index):
+        """Nothing rides along with a frame of an image folder."""
+        return None

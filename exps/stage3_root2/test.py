@@ -20,7 +20,10 @@ one record per matched person, the RefineNet training pairs (dataset/p2p_dataset
 
 `-t generate_result --eval_3d 1` (addition) scores the run while it runs: MPJPE, root-relative error, PCK, point / person recall
 and the depth-order reverse rate of lib/eval/test_util_panoptic.py (eval_3d, calculate_and_log), accumulated on the GPU
-(smap_amd/evaluate.py) and written as `error` into the result file, as the reference's Panoptic test does."""
+(smap_amd/evaluate.py) and written as `error` into the result file, as the reference's Panoptic test does.
+
+`--device_preprocess 1 [--device_decode 1|2]` (addition) acts in all three modes: the frames are decoded ahead of the consumer and resized /
+padded / normalised on the GPU, one launch per batch (DevicePreprocLoader below); the result file is the same."""
 import argparse
 import json
 import logging
@@ -56,7 +59,7 @@ def get_logger(name, log_dir, filename):
 
 class DevicePreprocLoader:
     """Batches of (imgs on the device, names, scales) with decode on the host and resize / pad /
-    normalise in one HIP kernel per image (smap_amd/preprocess.py).  The decodes run AHEAD of the consumer on a small thread pool
+    normalise in one HIP launch per batch of up to 16 frames (smap_amd/preprocess.py: smap_preprocess_batch).  The decodes run AHEAD of the consumer on a small thread pool
     (PIL's decoders and numpy's file reads release the GIL): at ~800 frames/s of engine, one thread decoding a 1080p JPEG in ~10 ms
     would be the whole run (profiles/r5_cli_e2e.json: 62 frames/s with one thread, 333 with 8, 461 with 32).  SMAP_DECODE_THREADS
     (default: up to 16 of the allowed CPUs; 1 = decode in the consumer's thread, the round-4 behaviour).
@@ -71,7 +74,11 @@ class DevicePreprocLoader:
     `--device_decode 2`: the Huffman decode runs on the GPU too (smap_amd/csrc/jpeg_huff.hip).  The pool threads only read the file, parse
     its markers and pack the scan's tables with the file bytes into one page-locked buffer; the consumer uploads it, launches the decode of
     every frame of the batch, waits ONCE per batch and reads the status words.  A frame the device decoder does not vouch for (status != 0)
-    is decoded again by the host decoder, then by PIL, exactly as mode 1 would have decoded it; both counts are logged at the end."""
+    is decoded again by the host decoder, then by PIL, exactly as mode 1 would have decoded it; both counts are logged at the end.
+    The dataset is asked path(i), name(i), geometry(i) (None: letter-box) and extras(i) (CustomDataset and JointDataset answer them, next
+    to raw(i) for callers that want a frame with everything that belongs to it); the loader decodes path(i) itself, by whichever variant, and
+    asks for geometry and extras in the same pool thread, ahead of the consumer.  For an annotated set (the ground-truth modes) a batch is what
+    lib/utils/dataloader.py::collate_test yields: (imgs on the device, annotations [B,MAX_PEOPLE,15,C] fp32, tuple of paths, tuple of meta dicts)."""
 
     def __init__(self, dataset, indices, batch_size, cfg, device, device_decode=False):
         self.ds, self.idx, self.bs, self.cfg, self.device = dataset, list(indices), batch_size, cfg, device
@@ -104,18 +111,17 @@ class DevicePreprocLoader:
             logging.getLogger(self.cfg.DATASET.NAME).info("device decode: {} of {} frames fell back to PIL".format(self.pil_frames, len(self.idx)))
 
     def _batches(self):
-        from smap_amd.preprocess import preprocess_batch
         self.pil_frames = self.host_frames = 0
         if self.threads <= 1:
             for s in range(0, len(self.idx), self.bs):
+                idx = self.idx[s:s + self.bs]
                 if self.device_huffman:
-                    raws, names = zip(*self._device_frames([self._coefficients(i, lambda img: img) for i in self.idx[s:s + self.bs]]))
+                    got = self._device_frames([self._coefficients(i, lambda img: img) for i in idx])
                 elif self.device_decode:
-                    raws, names = zip(*[self._device_frame(self._coefficients(i, lambda img: img)) for i in self.idx[s:s + self.bs]])
+                    got = [self._device_frame(self._coefficients(i, lambda img: img)) for i in idx]
                 else:
-                    raws, names = zip(*[self.ds.raw(i) for i in self.idx[s:s + self.bs]])
-                imgs, scales = preprocess_batch(raws, self.cfg.INPUT.MEANS, self.cfg.INPUT.STDS, self.device)
-                yield imgs, list(names), scales
+                    got = [self._frame(i) for i in idx]
+                yield self._batch(got, [self._rides_along(i) for i in idx])
             return
         import collections
         import contextlib
@@ -130,7 +136,7 @@ class DevicePreprocLoader:
             return buf
 
         def decode(i):
-            img, name = self.ds.raw(i)
+            img, name = self._frame(i)
             return pinned(img), name
         workers = contextlib.ExitStack()
         if self.device_decode:
@@ -144,27 +150,62 @@ class DevicePreprocLoader:
             def fill():
                 while len(futs) < ahead:
                     try:
-                        futs.append(ex.submit(decode, next(todo)))
+                        i = next(todo)
                     except StopIteration:
                         return
+                    futs.append(ex.submit(lambda i=i: (decode(i), self._rides_along(i))))
             fill()
             while futs:
                 n = min(self.bs, len(futs))
-                got = [futs.popleft().result() for _ in range(n)]       # in submission order: frame order is kept
+                got, along = zip(*[futs.popleft().result() for _ in range(n)])     # in submission order: frame order is kept
+                got = list(got)
                 fill()
                 if self.device_huffman:
                     got = self._device_frames(got)
                 elif self.device_decode:
                     got = [self._device_frame(g) for g in got]
-                raws, names = zip(*got)
-                imgs, scales = preprocess_batch(raws, self.cfg.INPUT.MEANS, self.cfg.INPUT.STDS, self.device)
-                yield imgs, list(names), scales
+                yield self._batch(got, along)
 
+    def _where(self, i):
+        """(file, name in the records) of frame i: the dataset's path(i) and name(i).  The second branch serves ONE caller: a bare file list
+        (image_list below dataset_path, no methods) handed to _process_decoders alone, as tests/test_entry_cpu.py does; nothing that yields
+        batches works on such an object (geometry(i) and extras(i) are asked without a fallback)."""
+        if hasattr(self.ds, "path"):
+            return self.ds.path(i), self.ds.name(i)
+        path = self.ds.image_list[i].rstrip()
+        return path, path.replace(self.ds.dataset_path, "").lstrip("/")
+
+    def _frame(self, i):
+        """(frame i decoded in this thread, its name in the records): only the file is read, nothing of the annotations."""
+        from dataset.decode import read_bgr
+        path, name = self._where(i)
+        return read_bgr(path), name
+
+    def _rides_along(self, i):
+        """(geometry, extras) of frame i: no file is touched; in the pool thread that decodes the frame."""
+        return self.ds.geometry(i), self.ds.extras(i)
+
+    def _batch(self, got, along):
+        """Frames decoded as `got` = [(frame, name)] with `along` = [(geometry, extras)], as the batch the dataset's host loader would yield:
+        one pre-processing launch (smap_amd/preprocess.py) on the dataset's geometry, then (imgs, names, scales) for an image folder (the
+        default collate of CustomDataset's items) or (imgs, annotations, paths, metas) for an annotated set
+        (lib/utils/dataloader.py::collate_test)."""
+        from smap_amd.preprocess import preprocess_batch
+        raws, names = zip(*got)
+        geoms, extras = zip(*along)
+        kw = {}
+        if geoms[0] is not None:
+            kw = dict(geometries=list(geoms), net_w=geoms[0][0]["net_width"], net_h=geoms[0][0]["net_height"])
+        imgs, scales = preprocess_batch(raws, self.cfg.INPUT.MEANS, self.cfg.INPUT.STDS, self.device, **kw)
+        if extras[0] is None:
+            return imgs, list(names), scales
+        annotations, metas = zip(*extras)
+        return imgs, torch.stack(annotations, 0), tuple(names), tuple(metas)
 
     def _coefficients(self, i, pinned):
         """device_decode, in a pool thread: (("jpeg", coefficients in page-locked memory, info) or a PIL frame, name)."""
         from smap_amd import jpeg as J
-        path = self.ds.image_list[i].rstrip()
+        path, name = self._where(i)
         if not path.endswith(".npy"):
             with open(path, "rb") as f:
                 data = f.read()
@@ -172,12 +213,11 @@ class DevicePreprocLoader:
             if self.device_huffman:
                 frame = J.pack_frame(data, info) if info is not None else None
                 if frame is not None:
-                    return ("huff", frame, info, i), path.replace(self.ds.dataset_path, "").lstrip("/")
+                    return ("huff", frame, info, i), name
             coeffs = J.decode_coefficients(data, info) if info is not None and not self.device_huffman else None
             if coeffs is not None:
-                return ("jpeg", coeffs, info), path.replace(self.ds.dataset_path, "").lstrip("/")
-        img, name = self.ds.raw(i)
-        return pinned(img), name
+                return ("jpeg", coeffs, info), name
+        return pinned(self._frame(i)[0]), name
 
     def _device_frame(self, item):
         """device_decode, in the consumer: upload the coefficients and finish the decode on the GPU (current stream)."""
@@ -203,8 +243,7 @@ class DevicePreprocLoader:
                 self.host_frames += 1
                 co = J.decode_coefficients(J.frame_bytes(img[1]), img[2])
                 if co is None:
-                    raw, name = self.ds.raw(img[3])
-                    out.append(self._device_frame((raw, name)))
+                    out.append(self._device_frame(self._frame(img[3])))
                     continue
                 coeffs[k] = co
             if isinstance(img, tuple):
@@ -252,8 +291,8 @@ class DevicePreprocLoader:
             k = free.get()                                   # a worker and its slot, for this frame (as many pool threads as workers: no wait)
             try:
                 p = procs[k]
-                path = self.ds.image_list[i].rstrip()
-                name = path.replace(self.ds.dataset_path, "").lstrip("/")
+                path, name = self._where(i)
+                path = os.path.abspath(path)                 # the workers run in another directory
                 p.stdin.write(f"{k}\t{path}\n")
                 p.stdin.flush()
                 ans = p.stdout.readline().split(None, 3)
@@ -261,7 +300,7 @@ class DevicePreprocLoader:
                     raise RuntimeError(f"decode worker {k} died on {path}")
                 h, w = int(ans[1]), int(ans[2])
                 if h == -1:                                  # larger than a slot: here, in this thread
-                    return pinned(self.ds.raw(i)[0]), name
+                    return pinned(self._frame(i)[0]), name
                 if h < 0:
                     raise RuntimeError(f"decode worker: {path}: {ans[3] if len(ans) > 3 else 'failed'}")
                 n = h * w * 3
@@ -434,7 +473,8 @@ def main():
                         help="1: rehearse the run without a GPU or a checkpoint (stand-in pipeline, gloo gather): what a "
                              "multi-rank launch does around the device work -- split, ragged batches, gather, result file")
     parser.add_argument("--device_preprocess", type=int, default=0,
-                        help="(addition) 1: resize/pad/normalise on the GPU (smap_preprocess) instead of in the dataset")
+                        help="(addition) 1: resize/pad/normalise on the GPU (smap_preprocess_batch) instead of in the dataset, decodes ahead of "
+                             "the consumer on a thread pool; in all three test modes")
     parser.add_argument("--device_decode", type=int, default=0,
                         help="(addition) 1: baseline JPEGs are Huffman-decoded on the host and finished on the GPU (smap_amd/jpeg.py), "
                              "bit for bit the PIL frame; other files are decoded with PIL.  2: the Huffman decode runs on the GPU too "
@@ -479,7 +519,16 @@ def main():
         if args.precision:
             model.precision = args.precision
 
-    if args.test_mode != "run_inference":
+    if args.test_mode != "run_inference" and args.device_preprocess and dry:
+        logger.info("--dry_run 1: the ground-truth modes are rehearsed on the host loader (--device_preprocess needs the GPU)")
+    if args.test_mode != "run_inference" and args.device_preprocess and not dry:
+        from dataset.base_dataset import JointDataset
+        from lib.utils.dataloader import rank_block
+        if cfg.DATASET.NAME != "MIX":                          # get_test_loader's check
+            raise NameError("Dataset is not defined!", cfg.DATASET.NAME)
+        dataset = JointDataset(cfg, args.data_mode)
+        indices = range(*rank_block(len(dataset), world, dist.get_rank() if world > 1 else 0))      # get_test_loader's split
+    elif args.test_mode != "run_inference":
         from lib.utils.dataloader import get_test_loader
         data_loader = get_test_loader(cfg, num_gpu=world, local_rank=dist.get_rank() if world > 1 else 0,
                                       stage=args.data_mode)

@@ -126,6 +126,25 @@ int smap_refine_mlp(const float* x, int N, const float* const* wt, const float* 
 int smap_preprocess(const unsigned char* src, int h, int w, int nh, int nw, int top, int left, float* dst,
                     int net_h, int net_w, const float* mean3, const float* std3, double fx, double fy, void* stream);
 
+/* smap_preprocess for a batch whose frames lie in SEPARATE device buffers (no gather copy): frame b of `frames` (a HOST array of B
+ * descriptors, copied into the kernel arguments) is written to dst[b] of dst: fp32 [B][3][net_h][net_w], bit for bit what
+ * smap_preprocess writes for the same arguments (both run one per-pixel function).  One launch takes SMAP_PREP_MAX_FRAMES frames, a larger
+ * B is split into launches of that many on the same stream.  The window may stick out of the canvas on any side -- top / left negative,
+ * top + nh > net_h, left + nw > net_w: the crop-and-pad of the annotated sets (dataset/base_dataset.py::croppad_geometry centres it
+ * on int((w / 2) * scale), so odd sizes overhang on the right / bottom) -- and is clipped as the host paste clips it; a window wholly off
+ * the canvas gives a frame of padding.  h, w are the stored frame's own size: the taps are clamped to it, whatever size nh, nw, fx, fy
+ * were derived from.  SMAP_E_ARG: null pointers, B <= 0, non-positive sizes, nh / nw <= 0, fx / fy not positive. */
+#define SMAP_PREP_MAX_FRAMES 16
+struct smap_prep_frame {
+    const unsigned char* src;           /* uint8 [h][w][3] BGR, device */
+    int32_t h, w;                       /* stored frame */
+    int32_t nh, nw, top, left;          /* resized size and where it sits in the canvas */
+    double fx, fy;                      /* the factors given to cv2.resize */
+};
+int smap_sizeof_prep_frame(void);
+int smap_preprocess_batch(const struct smap_prep_frame* frames, int B, float* dst, int net_h, int net_w, const float* mean3,
+                          const float* std3, void* stream);
+
 /* ---- backbone: replaces model/smap.py SMAP.forward (eval) ------------------ */
 
 /* One op of the static inference schedule.  Offsets are BYTE offsets into the

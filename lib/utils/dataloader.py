@@ -17,14 +17,19 @@ def collate_test(batch):
     return torch.stack(images, 0), torch.stack(meta, 0), tuple(paths), tuple(scales)
 
 
+def rank_block(n, num_gpu, rank):
+    """[start, end) of rank `rank`: contiguous blocks of ceil(n / num_gpu) frames (dataloader.py:80-85); the last ranks may get fewer
+    frames, or none (start == end)."""
+    per = math.ceil(n / num_gpu)
+    st = min(n, rank * per)
+    return st, min(n, st + per)
+
+
 def get_test_loader(cfg, num_gpu, local_rank, stage, use_augmentation=False, with_mds=False):
     if cfg.DATASET.NAME != "MIX":
         raise NameError("Dataset is not defined!", cfg.DATASET.NAME)
     dataset = JointDataset(cfg, stage, None, use_augmentation, with_mds)
-    n = len(dataset)
-    per = math.ceil(n / num_gpu)
-    st = local_rank * per
-    ed = min(n, st + per)
+    st, ed = rank_block(len(dataset), num_gpu, local_rank)
     workers = int(cfg.get("DATALOADER", {}).get("NUM_WORKERS", 0)) if hasattr(cfg, "get") else 0
     return DataLoader(Subset(dataset, range(st, ed)), batch_size=cfg.TEST.IMG_PER_GPU, shuffle=False, drop_last=False,
                       num_workers=workers, collate_fn=collate_test)

@@ -805,12 +805,15 @@ __global__ void flip_merge_kernel(float* __restrict__ hms, const float* __restri
 }
 
 // ------------------------------------------------------------ preprocess --
-// dataset/custom_dataset.py:41-68 (aug_croppad) + ToTensor + Normalize on the device: bilinear
-// resize (half-pixel centres, no anti-aliasing -- the sampling rule of cv2.INTER_LINEAR and of
-// F.interpolate(align_corners=False)), round to uint8, centre into the net_h x net_w canvas padded
-// with 128, /255, (x - mean) / std.  One thread per canvas pixel, 3 channels; fp32 arithmetic in
-// ATen's operation order so that it matches the host path bit for bit.
-struct PrepArgs { int h, w, nh, nw, top, left, net_h, net_w; float mean[3], stdv[3]; double scale_x, scale_y; };
+// dataset/custom_dataset.py:41-68 (aug_croppad) and dataset/base_dataset.py (the annotated sets' crop-and-pad) + ToTensor + Normalize on
+// the device: OpenCV's 8-bit INTER_LINEAR resize, paste into the net_h x net_w canvas padded with 128, /255, (x - mean) / std, in ATen's
+// operation order so that it matches the host path bit for bit.  ONE per-pixel function (prep_pixel + prep_norm) behind both entry
+// points: smap_preprocess (one frame, one thread per canvas pixel) and smap_preprocess_batch (up to SMAP_PREP_MAX_FRAMES frames of
+// separate buffers per launch, four pixels and one 16-byte store per channel plane and thread).
+// One frame: the stored image, the window (nh x nw at (top, left), which may stick out of the canvas on any side) and 1 / fx, 1 / fy.
+struct PrepFrame { const unsigned char* src; int h, w, nh, nw, top, left; double scale_x, scale_y; };
+struct PrepCanvas { int net_h, net_w; float mean[3], stdv[3]; };
+struct PrepTable { PrepFrame f[SMAP_PREP_MAX_FRAMES]; };        // by value in the kernel arguments: 48 bytes per frame
 
 // One axis of OpenCV's 8-bit INTER_LINEAR (modules/imgproc/src/resize.cpp, cv::resize -> resizeGeneric_ set-up):
 //   fx = (float)((d + 0.5) * scale - 0.5) with scale = 1 / fx_arg (double); s = floor(fx); fx -= s;
@@ -831,41 +834,83 @@ __device__ __forceinline__ CvTap cv_tap(int d, double scale, int n)
     return t;
 }
 
-// dataset/custom_dataset.py:41-68 for one image: cv2.resize(img, (0,0), fx=s, fy=s) [INTER_LINEAR, 8-bit fixed point],
-// centre pad with 128, ToTensor, Normalize.  The resize follows OpenCV's published algorithm operation by operation:
-// horizontal pass in 11-bit fixed point (int32), vertical pass ((b0*(S0>>4))>>16) + ((b1*(S1>>4))>>16) + 2) >> 2
-// (VResizeLinear<uchar,int,short,FixedPtCast<int,uchar,22>>), and the exact 2x shrink as the 2x2 box mean
-// (cv::resize switches INTER_LINEAR to INTER_AREA there).  cv2 is not in this image: parity unpinned by execution.
-__global__ void preprocess_kernel(const unsigned char* __restrict__ src, float* __restrict__ dst, PrepArgs p)
+// ToTensor + Normalize of one 8-bit value, in that order.
+__device__ __forceinline__ float prep_norm(float v, float mean, float stdv) { return (v / 255.0f - mean) / stdv; }
+
+// Canvas pixel (x, y) of one frame as three 8-bit values: cv2.resize(img, (0,0), fx=s, fy=s) [INTER_LINEAR, 8-bit fixed point] where the
+// window covers the pixel, else false (padding).  The window test is the paste's clip: a pixel of the canvas is the resized image's
+// (y - top, x - left) if that exists, whatever the sign of top / left and however far the window overhangs (64-bit: no int overflow).
+// The resize follows OpenCV's published algorithm operation by operation: horizontal pass in 11-bit fixed point (int32), vertical pass
+// ((b0*(S0>>4))>>16) + ((b1*(S1>>4))>>16) + 2) >> 2 (VResizeLinear<uchar,int,short,FixedPtCast<int,uchar,22>>), and the exact 2x shrink
+// as the 2x2 box mean (cv::resize switches INTER_LINEAR to INTER_AREA there).  cv2 is not in this image: parity unpinned by execution.
+// Every tap is clamped to the STORED image (h, w), so no read leaves it even when nh / nw were derived from another size.
+__device__ __forceinline__ bool prep_pixel(const PrepFrame& p, int x, int y, float v[3])
 {
-    const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
-    if (x >= p.net_w) return;
-    float v[3] = {128.f, 128.f, 128.f};
-    const int ry = y - p.top, rx = x - p.left;
-    if ((unsigned)ry < (unsigned)p.nh && (unsigned)rx < (unsigned)p.nw) {
-        if (p.scale_x == 2.0 && p.scale_y == 2.0) {      // INTER_AREA fast path: (a + b + c + d + 2) >> 2
-            const int y0 = ry * 2 < p.h ? ry * 2 : p.h - 1, y1 = ry * 2 + 1 < p.h ? ry * 2 + 1 : p.h - 1;
-            const int x0 = rx * 2 < p.w ? rx * 2 : p.w - 1, x1 = rx * 2 + 1 < p.w ? rx * 2 + 1 : p.w - 1;
+    const long long ry64 = (long long)y - p.top, rx64 = (long long)x - p.left;
+    if (ry64 < 0 || ry64 >= p.nh || rx64 < 0 || rx64 >= p.nw) return false;
+    const int ry = (int)ry64, rx = (int)rx64;
+    const unsigned char* __restrict__ src = p.src;
+    if (p.scale_x == 2.0 && p.scale_y == 2.0) {          // INTER_AREA fast path: (a + b + c + d + 2) >> 2
+        const int y0 = ry * 2 < p.h ? ry * 2 : p.h - 1, y1 = ry * 2 + 1 < p.h ? ry * 2 + 1 : p.h - 1;
+        const int x0 = rx * 2 < p.w ? rx * 2 : p.w - 1, x1 = rx * 2 + 1 < p.w ? rx * 2 + 1 : p.w - 1;
 #pragma unroll
-            for (int c = 0; c < 3; ++c)
-                v[c] = (float)((src[((size_t)y0 * p.w + x0) * 3 + c] + src[((size_t)y0 * p.w + x1) * 3 + c] +
-                                src[((size_t)y1 * p.w + x0) * 3 + c] + src[((size_t)y1 * p.w + x1) * 3 + c] + 2) >> 2);
-        } else {
-            const CvTap ty = cv_tap(ry, p.scale_y, p.h), tx = cv_tap(rx, p.scale_x, p.w);
-            const unsigned char* r0 = src + ((size_t)ty.s0 * p.w) * 3;
-            const unsigned char* r1 = src + ((size_t)ty.s1 * p.w) * 3;
+        for (int c = 0; c < 3; ++c)
+            v[c] = (float)((src[((size_t)y0 * p.w + x0) * 3 + c] + src[((size_t)y0 * p.w + x1) * 3 + c] +
+                            src[((size_t)y1 * p.w + x0) * 3 + c] + src[((size_t)y1 * p.w + x1) * 3 + c] + 2) >> 2);
+    } else {
+        const CvTap ty = cv_tap(ry, p.scale_y, p.h), tx = cv_tap(rx, p.scale_x, p.w);
+        const unsigned char* r0 = src + ((size_t)ty.s0 * p.w) * 3;
+        const unsigned char* r1 = src + ((size_t)ty.s1 * p.w) * 3;
 #pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                const int h0 = r0[tx.s0 * 3 + c] * tx.c0 + r0[tx.s1 * 3 + c] * tx.c1;
-                const int h1 = r1[tx.s0 * 3 + c] * tx.c0 + r1[tx.s1 * 3 + c] * tx.c1;
-                const int t = (((ty.c0 * (h0 >> 4)) >> 16) + ((ty.c1 * (h1 >> 4)) >> 16) + 2) >> 2;
-                v[c] = (float)(t < 0 ? 0 : (t > 255 ? 255 : t));
-            }
+        for (int c = 0; c < 3; ++c) {
+            const int h0 = r0[tx.s0 * 3 + c] * tx.c0 + r0[tx.s1 * 3 + c] * tx.c1;
+            const int h1 = r1[tx.s0 * 3 + c] * tx.c0 + r1[tx.s1 * 3 + c] * tx.c1;
+            const int t = (((ty.c0 * (h0 >> 4)) >> 16) + ((ty.c1 * (h1 >> 4)) >> 16) + 2) >> 2;
+            v[c] = (float)(t < 0 ? 0 : (t > 255 ? 255 : t));
         }
     }
+    return true;
+}
+
+// smap_preprocess: one frame, one thread per canvas pixel.
+__global__ void preprocess_kernel(PrepFrame f, float* __restrict__ dst, PrepCanvas cv)
+{
+    const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
+    if (x >= cv.net_w) return;
+    float v[3];
+    if (!prep_pixel(f, x, y, v)) v[0] = v[1] = v[2] = 128.f;
 #pragma unroll
     for (int c = 0; c < 3; ++c)
-        dst[((size_t)c * p.net_h + y) * p.net_w + x] = (v[c] / 255.0f - p.mean[c]) / p.stdv[c];
+        dst[((size_t)c * cv.net_h + y) * cv.net_w + x] = prep_norm(v[c], cv.mean[c], cv.stdv[c]);
+}
+
+// smap_preprocess_batch: grid (x tiles, rows, frames), frame blockIdx.z of the table into plane block blockIdx.z of dst.  A thread owns
+// PX adjacent x of one row; PX = 4 (net_w % 4 == 0, dst 16-byte aligned: x0 + 3 < net_w whenever x0 < net_w, and every row of every
+// plane starts 16-byte aligned) writes one 16-byte store per channel plane, PX = 1 is the scalar path for every other canvas.
+// The padding value goes through prep_norm once per channel and thread, not once per pixel.
+template <int PX>
+__global__ void __launch_bounds__(256) preprocess_batch_kernel(PrepTable t, float* __restrict__ dst, PrepCanvas cv)
+{
+    const int x0 = (blockIdx.x * blockDim.x + threadIdx.x) * PX, y = blockIdx.y;
+    if (x0 >= cv.net_w) return;
+    const PrepFrame& f = t.f[blockIdx.z];
+    float pad[3], o[3][PX];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) pad[c] = prep_norm(128.f, cv.mean[c], cv.stdv[c]);
+#pragma unroll
+    for (int i = 0; i < PX; ++i) {
+        float v[3];
+        const bool in = prep_pixel(f, x0 + i, y, v);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) o[c][i] = in ? prep_norm(v[c], cv.mean[c], cv.stdv[c]) : pad[c];
+    }
+    const size_t plane = (size_t)cv.net_h * cv.net_w;
+    float* row = dst + (size_t)blockIdx.z * 3 * plane + (size_t)y * cv.net_w + x0;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        if (PX == 4) *reinterpret_cast<float4*>(row + c * plane) = make_float4(o[c][0], o[c][1], o[c][2], o[c][3]);
+        else row[c * plane] = o[c][0];
+    }
 }
 
 }  // namespace
@@ -1038,9 +1083,41 @@ extern "C" int smap_preprocess(const unsigned char* src, int h, int w, int nh, i
 {
     if (!src || !dst || !mean3 || !std3 || h <= 0 || w <= 0 || nh <= 0 || nw <= 0 || net_h <= 0 || net_w <= 0 || !(fx > 0) || !(fy > 0))
         return SMAP_E_ARG;
-    PrepArgs p{h, w, nh, nw, top, left, net_h, net_w, {mean3[0], mean3[1], mean3[2]}, {std3[0], std3[1], std3[2]}, 1.0 / fx, 1.0 / fy};
-    hipLaunchKernelGGL(preprocess_kernel, dim3((net_w + 255) / 256, net_h), dim3(256), 0, (hipStream_t)stream, src, dst, p);
+    const PrepFrame f{src, h, w, nh, nw, top, left, 1.0 / fx, 1.0 / fy};
+    const PrepCanvas cv{net_h, net_w, {mean3[0], mean3[1], mean3[2]}, {std3[0], std3[1], std3[2]}};
+    hipLaunchKernelGGL(preprocess_kernel, dim3((net_w + 255) / 256, net_h), dim3(256), 0, (hipStream_t)stream, f, dst, cv);
     return hip_rc(hipGetLastError());
+}
+
+extern "C" int smap_sizeof_prep_frame(void) { return (int)sizeof(smap_prep_frame); }
+
+extern "C" int smap_preprocess_batch(const smap_prep_frame* frames, int B, float* dst, int net_h, int net_w, const float* mean3,
+                                     const float* std3, void* stream)
+{
+    if (!frames || !dst || !mean3 || !std3 || B <= 0 || net_h <= 0 || net_w <= 0) return SMAP_E_ARG;
+    for (int b = 0; b < B; ++b) {                        // every frame is checked before the first launch: all of the batch or nothing
+        const smap_prep_frame& s = frames[b];
+        if (!s.src || s.h <= 0 || s.w <= 0 || s.nh <= 0 || s.nw <= 0 || !(s.fx > 0) || !(s.fy > 0)) return SMAP_E_ARG;
+    }
+    const PrepCanvas cv{net_h, net_w, {mean3[0], mean3[1], mean3[2]}, {std3[0], std3[1], std3[2]}};
+    const bool vec = net_w % 4 == 0 && ((uintptr_t)dst & 15) == 0;
+    const int px = vec ? 4 : 1;
+    const size_t frame_floats = (size_t)3 * net_h * net_w;                 // (a multiple of 4 floats when vec: every frame stays aligned)
+    for (int b0 = 0; b0 < B; b0 += SMAP_PREP_MAX_FRAMES) {
+        const int n = B - b0 < SMAP_PREP_MAX_FRAMES ? B - b0 : SMAP_PREP_MAX_FRAMES;
+        PrepTable t;
+        for (int i = 0; i < SMAP_PREP_MAX_FRAMES; ++i) {                    // unused entries repeat the last frame: never read (grid.z = n)
+            const smap_prep_frame& s = frames[b0 + (i < n ? i : n - 1)];
+            t.f[i] = PrepFrame{s.src, s.h, s.w, s.nh, s.nw, s.top, s.left, 1.0 / s.fx, 1.0 / s.fy};
+        }
+        const dim3 grid((net_w + 256 * px - 1) / (256 * px), net_h, n);
+        float* out = dst + (size_t)b0 * frame_floats;
+        if (vec) hipLaunchKernelGGL(preprocess_batch_kernel<4>, grid, dim3(256), 0, (hipStream_t)stream, t, out, cv);
+        else hipLaunchKernelGGL(preprocess_batch_kernel<1>, grid, dim3(256), 0, (hipStream_t)stream, t, out, cv);
+        const int rc = hip_rc(hipGetLastError());
+        if (rc) return rc;
+    }
+    return 0;
 }
 
 extern "C" const char* smap_version(void) { return "smap_hip gfx950 r6 (assoc + backbone f16|x3 + flip-TTA + persistent conv + whole-Bottleneck launches + plan blob v2 + windowed arena + N segments + split K + lanes + two-input launches + tap-dot head + scaled head sum + two-launch peak search)"; }

@@ -23,6 +23,7 @@ SYMBOLS = [
     "smap_eval3d_acc_init", "smap_eval3d_terms", "smap_eval3d_fold", "smap_eval3d_update",
     "smap_sizeof_jpeg_info", "smap_jpeg_probe", "smap_jpeg_decode_coefficients", "smap_jpeg_workspace_bytes", "smap_jpeg_reconstruct",
     "smap_sizeof_jpeg_scan", "smap_jpeg_scan_tables", "smap_jpeg_huff_workspace_bytes", "smap_jpeg_decode_coefficients_device",
+    "smap_sizeof_prep_frame", "smap_preprocess_batch",
 ]
 MAX_INPUTS = 8                         # SMAP_MAX_INPUTS
 
@@ -95,6 +96,13 @@ class JpegScan(C.Structure):
                 ("scan_offset", C.c_int64), ("file_bytes", C.c_int64), ("total_blocks", C.c_int64)]
 
 
+class PrepFrame(C.Structure):
+    """Mirror of `struct smap_prep_frame`."""
+    _fields_ = [("src", C.c_void_p), ("h", C.c_int32), ("w", C.c_int32), ("nh", C.c_int32), ("nw", C.c_int32), ("top", C.c_int32),
+                ("left", C.c_int32), ("fx", C.c_double), ("fy", C.c_double)]
+
+
+PREP_MAX_FRAMES = 16      # SMAP_PREP_MAX_FRAMES
 JPEG_UNSUPPORTED = 1      # SMAP_JPEG_UNSUPPORTED
 JPEG_E_DATA = -2          # SMAP_JPEG_E_DATA
 JPEG_DEV_E_DATA = 1       # SMAP_JPEG_DEV_E_DATA
@@ -138,6 +146,7 @@ def load():
     lib.smap_lift_gt.argtypes = lib.smap_lift.argtypes
     lib.smap_refine_gt.argtypes = lib.smap_refine.argtypes
     lib.smap_preprocess.argtypes = [vp, ip, ip, ip, ip, ip, ip, vp, ip, ip, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_double, C.c_double, vp]
+    lib.smap_preprocess_batch.argtypes = [C.POINTER(PrepFrame), ip, vp, ip, ip, C.POINTER(C.c_float), C.POINTER(C.c_float), vp]
     lib.smap_conv_tile_dims.argtypes = [ip, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     lib.smap_conv_tile_bk.argtypes = [ip, ip]
     lib.smap_conv_tile_tail_bn.argtypes = [ip]
@@ -174,6 +183,8 @@ def load():
         raise ImportError(f"smap_jpeg_info layout mismatch: C {lib.smap_sizeof_jpeg_info()} vs ctypes {C.sizeof(JpegInfo)}")
     if lib.smap_sizeof_jpeg_scan() != C.sizeof(JpegScan):
         raise ImportError(f"smap_jpeg_scan layout mismatch: C {lib.smap_sizeof_jpeg_scan()} vs ctypes {C.sizeof(JpegScan)}")
+    if lib.smap_sizeof_prep_frame() != C.sizeof(PrepFrame):
+        raise ImportError(f"smap_prep_frame layout mismatch: C {lib.smap_sizeof_prep_frame()} vs ctypes {C.sizeof(PrepFrame)}")
     _lib = lib
     return lib
 

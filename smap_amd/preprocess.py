@@ -1,9 +1,10 @@
 """GPU pre-processing for `run_inference`: the reference decodes, resizes,
 pads and normalises every image on the host (dataset/custom_dataset.py:27-68); here only the
 decode stays on the host, the uint8 image is uploaded as is (3 B/pixel instead of 12) and one HIP
-kernel (`smap_preprocess`) writes the letter-boxed, normalised fp32 frame straight into the batch.
+launch per batch (`smap_preprocess_batch`) writes the letter-boxed, normalised fp32 frames straight into the batch.
 `letterbox_geometry` is shared with the host path (dataset/custom_dataset.py) so both agree on the
-resized size and the padding offsets."""
+resized size and the padding offsets.  The ground-truth modes hand in the crop-and-pad window of
+dataset/base_dataset.py instead (`geometries`): same kernel, a window that may overhang the canvas."""
 import ctypes as C
 
 import warnings
@@ -73,17 +74,25 @@ def resize_linear_u8(img, nh, nw, fx=None, fy=None):
     return np.clip(t, 0, 255).astype(np.uint8)
 
 
-def preprocess_batch(images, means, stds, device, net_w=832, net_h=512):
+def preprocess_batch(images, means, stds, device, net_w=832, net_h=512, geometries=None):
     """images: list of uint8 HxWx3 BGR arrays/tensors.  Returns (imgs [B,3,net_h,net_w] fp32 on `device`,
-    scales: dict of lists as the DataLoader would collate them)."""
+    scales: dict of lists as the DataLoader would collate them).
+    geometries: None = the letter-box of run_inference (letterbox_geometry of every image's own size), or one entry per image
+    (scales_entry, (nh, nw, top, left), fx, fy): the window of an annotated set's crop-and-pad (dataset/base_dataset.py), which may
+    overhang the canvas and may have been derived from another size than the stored frame's; the kernel clips and clamps.  An entry whose
+    window is empty (nh or nw == 0) gives a frame of padding, as the host paste does.
+    Every frame is uploaded from where it lies and the whole batch is written by smap_preprocess_batch (one launch per 16 frames)."""
     lib = _L.load()
     B = len(images)
+    if geometries is not None and len(geometries) != B:
+        raise ValueError("one geometry per image")
     out = torch.empty((B, 3, net_h, net_w), dtype=torch.float32, device=device)
     mean = (C.c_float * 3)(*means)
     std = (C.c_float * 3)(*stds)
     scales = {k: [] for k in ("scale", "img_width", "img_height", "net_width", "net_height")}
     st = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
     keep = []
+    table = (_L.PrepFrame * max(B, 1))()
     with torch.cuda.device(device):
         for i, im in enumerate(images):
             if isinstance(im, torch.Tensor):
@@ -95,12 +104,18 @@ def preprocess_batch(images, means, stds, device, net_w=832, net_h=512):
             if t.dtype != torch.uint8 or t.dim() != 3 or t.shape[2] != 3:
                 raise ValueError("images must be uint8 HxWx3 (BGR)")
             h0, w0 = int(t.shape[0]), int(t.shape[1])
-            scale, (nh, nw, top, left) = letterbox_geometry(w0, h0, net_w, net_h)
+            if geometries is None:
+                scale, (nh, nw, top, left) = letterbox_geometry(w0, h0, net_w, net_h)
+                fx = fy = scale["scale"]
+            else:
+                scale, (nh, nw, top, left), fx, fy = geometries[i]
+                if nh <= 0 or nw <= 0:                   # (a 1 x 1024 strip: nothing to paste, the host path leaves a frame of padding;
+                    nh, nw, top, left = 1, 1, net_h, net_w   #  the library refuses an empty window, so hand it one off the canvas)
             d = t.to(device, non_blocking=True)
             keep.append(d)
-            _L.check(lib.smap_preprocess(C.c_void_p(d.data_ptr()), h0, w0, nh, nw, top, left,
-                                         C.c_void_p(out[i].data_ptr()), net_h, net_w, mean, std, scale["scale"], scale["scale"], st),
-                     "smap_preprocess")
+            table[i] = _L.PrepFrame(d.data_ptr(), h0, w0, int(nh), int(nw), int(top), int(left), float(fx), float(fy))
             for k in scales:
                 scales[k].append(scale[k])
+        if B:
+            _L.check(lib.smap_preprocess_batch(table, B, C.c_void_p(out.data_ptr()), net_h, net_w, mean, std, st), "smap_preprocess_batch")
     return out, scales

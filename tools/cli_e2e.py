@@ -9,12 +9,16 @@ resolutions -- the bench's 8 frames as 832x512 PNGs and as 1664x1024 JPEGs (ever
 the frame back) -- so that the network sees the workload the bench line is quoted on (~20 skeletons per frame: association, lifting
 and record building do real work); a second folder holds the same pictures as .npy (no decoder).
 
-    python tools/cli_e2e.py [--images 256] [--out profiles/r5_cli_e2e.json] [--only jpeg | --only huffman [--pairs 3]]
+    python tools/cli_e2e.py [--images 256] [--out profiles/r5_cli_e2e.json] [--only jpeg | --only huffman [--pairs 3] | --only gt [--pairs 3]]
 
 A third folder holds only the 1664x1024 JPEGs: there the PIL decoders (16 threads, 16 processes) run against `--device_decode 1`
 (Huffman decode on the host, the rest of the decode on the GPU) and the .npy frames.  --only jpeg runs those four legs alone.  --only huffman runs, on that folder, `--device_decode 1` against
 `--device_decode 2` (the Huffman decode on the GPU as well) alternating, `--pairs` times each at SMAP_DECODE_THREADS = 16 and = 2 after one
 uncounted run that builds the plan cache, and adds a summary with the mean and the spread (min .. max) of every leg.
+--only gt measures the GROUND-TRUTH modes: an annotated folder (M3E_gt.json + the 1664x1024 JPEGs) run as
+`-t generate_result --eval_3d 1` on the host loader (lib/utils/dataloader.py), with `--device_preprocess 1`, and with `--device_decode 1` / `2`
+on top, `--pairs` times each, interleaved, after one uncounted run; and the pre-processing of 8 1080p frames alone, by device events over
+200 batches: 8 launches of smap_preprocess against one of smap_preprocess_batch.
 """
 import argparse
 import json
@@ -39,12 +43,125 @@ def bench_frames_as_images(cfg_means, cfg_stds):
     return ((x * std + mean) * 255.0).round().clamp(0, 255).to(torch.uint8).permute(0, 2, 3, 1).contiguous().numpy()     # [8,512,832,3]
 
 
+def preprocess_launch_ab(batches=200, frames=8, h=1080, w=1920):
+    """Per-batch device time of the pre-processing of `frames` h x w frames (crop-and-pad geometry, separate source buffers, one fp32
+    batch): `frames` launches of smap_preprocess against one launch of smap_preprocess_batch, by events around `batches` batches,
+    three times each, alternating."""
+    import ctypes as C
+    from dataset.base_dataset import croppad_geometry
+    from exps.stage3_root2.config import cfg as run_cfg
+    from smap_amd import lib as L
+    lib = L.load()
+    dev = torch.device("cuda:0")
+    scale, (nh, nw), (left, top) = croppad_geometry(w, h, 832, 512)
+    srcs = [torch.randint(0, 256, (h, w, 3), dtype=torch.uint8, generator=torch.Generator().manual_seed(i)).to(dev) for i in range(frames)]
+    out = torch.empty((frames, 3, 512, 832), dtype=torch.float32, device=dev)
+    mean, std = (C.c_float * 3)(*run_cfg.INPUT.MEANS), (C.c_float * 3)(*run_cfg.INPUT.STDS)
+    st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    table = (L.PrepFrame * frames)(*[L.PrepFrame(s.data_ptr(), h, w, nh, nw, top, left, scale, scale) for s in srcs])
+
+    def single():
+        for i, s in enumerate(srcs):
+            L.check(lib.smap_preprocess(C.c_void_p(s.data_ptr()), h, w, nh, nw, top, left, C.c_void_p(out[i].data_ptr()), 512, 832, mean, std,
+                                        scale, scale, st), "smap_preprocess")
+
+    def batched():
+        L.check(lib.smap_preprocess_batch(table, frames, C.c_void_p(out.data_ptr()), 512, 832, mean, std, st), "smap_preprocess_batch")
+
+    def timed(fn):
+        for _ in range(10):
+            fn()
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        a.record()
+        for _ in range(batches):
+            fn()
+        b.record()
+        torch.cuda.synchronize()
+        return a.elapsed_time(b) * 1e3 / batches                  # us per batch
+    res = {"single_launches_us_per_batch": [], "batched_launch_us_per_batch": []}
+    for _ in range(3):
+        res["single_launches_us_per_batch"].append(timed(single))
+        res["batched_launch_us_per_batch"].append(timed(batched))
+    single()
+    ref = out.clone()
+    out.zero_()
+    batched()
+    res.update(frames=frames, source=f"{w}x{h}", batches=batches, same_bits=bool(torch.equal(ref, out)))
+    return res
+
+
+def gt_leg(args, tmp, jpg):
+    """--only gt: see the module's docstring."""
+    rng = np.random.default_rng(7)
+    root = os.path.join(tmp, "MultiPersonTestSet")
+    os.makedirs(os.path.join(root, "TS1"))
+    entries = []
+    for i in range(args.images):                                  # the 1664x1024 JPEGs of the JPEG-only folder, annotated: 4 persons per frame
+        rel = f"TS1/img_{i:06d}.jpg"
+        os.symlink(os.path.realpath(os.path.join(jpg, f"im{i:05d}.jpg")), os.path.join(root, rel))
+        bodys = np.zeros((4, 15, 11))
+        bodys[:, :, 0] = rng.uniform(0, 1664, (4, 1)) + rng.normal(0, 60, (4, 15))
+        bodys[:, :, 1] = rng.uniform(0, 1024, (4, 1)) + rng.normal(0, 60, (4, 15))
+        bodys[:, :, 2] = rng.uniform(200, 500, (4, 15))
+        bodys[:, :, 3] = 2
+        bodys[:, :, 4:7] = rng.normal(0, 60, (4, 15, 3)) + np.array([0, 0, 300])
+        bodys[:, :, 7:11] = [1500.0, 1490.0, 832.0, 512.0]
+        entries.append({"dataset": "MUCO", "img_paths": rel, "img_width": 1664, "img_height": 1024, "isValidation": 1, "bodys": bodys.tolist()})
+    with open(os.path.join(root, "M3E_gt.json"), "w") as f:
+        json.dump({"root": entries}, f)
+    dp = ["--device_preprocess", "1"]
+    legs = [("host loader (get_test_loader: PIL + numpy resize in the consumer's thread, fp32 upload)", []),
+            ("--device_preprocess 1", dp), ("--device_preprocess 1 --device_decode 1", dp + ["--device_decode", "1"]),
+            ("--device_preprocess 1 --device_decode 2", dp + ["--device_decode", "2"])]
+    cases = [("warm-up (builds the plan cache; not counted)", dp)] + [leg for _ in range(args.pairs) for leg in legs]
+    runs, first = [], None
+    for name, extra in cases:
+        timing = os.path.join(tmp, "timing.json")
+        env = dict(os.environ, PROJECT_HOME=tmp, PYTHONPATH=ROOT + os.pathsep + os.environ.get("PYTHONPATH", ""), SMAP_CLI_TIMING=timing,
+                   SMAP_PLAN_CACHE=os.path.join(tmp, "plan_cache"), SMAP_TEST_ROOT=root)
+        t0 = time.perf_counter()
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "exps", "stage3_root2", "test.py"), "-p", os.path.join(tmp, "SMAP.pth"),
+                            "-t", "generate_result", "-d", "test", "--eval_3d", "1", "--batch_size", str(args.batch), "--json_name", "gt"] + extra,
+                           capture_output=True, text=True, env=env, cwd=tmp, timeout=1500)
+        rec = {"case": name, "returncode": r.returncode, "process_wall_s": time.perf_counter() - t0}
+        if r.returncode == 0 and os.path.exists(timing):
+            rec.update(json.load(open(timing)))
+            os.remove(timing)
+            res = json.load(open(os.path.join(tmp, "model_logs", "stage3_root2", "result", "stage3_root2_generate_result_test_gt.json")))
+            rec["records_in_result_file"] = len(res["3d_pairs"])
+            rec["error_keys"] = len(res.get("error", {}))
+            if first is None:
+                first = res
+            rec["same_result_file_as_first_run"] = res == first
+        else:
+            rec["stderr_tail"] = r.stderr[-1500:]
+        runs.append(rec)
+        print(json.dumps(rec), flush=True)
+    summary = {}
+    for rec in runs[1:]:
+        if rec.get("frames_per_s_after_engine_build"):
+            summary.setdefault(rec["case"], []).append(rec["frames_per_s_after_engine_build"])
+    out = {"images": args.images, "batch_size": args.batch, "mode": "-t generate_result -d test --eval_3d 1",
+           "sources": "the bench's 8 frames as 1664x1024 JPEG q98 4:4:4 (pixel-doubled), annotated with 4 persons each",
+           "host_cpus_allowed": len(os.sched_getaffinity(0)), "gpu": torch.cuda.get_device_name(0) if torch.cuda.is_available() else None,
+           "repetitions_interleaved": args.pairs, "runs": runs,
+           "summary_frames_per_s_after_engine_build": {k: {"mean": float(np.mean(v)), "min": min(v), "max": max(v), "runs": v}
+                                                       for k, v in summary.items()},
+           "preprocess_8_frames_1080p": preprocess_launch_ab()}
+    print(json.dumps(out["summary_frames_per_s_after_engine_build"], indent=1))
+    print(json.dumps(out["preprocess_8_frames_1080p"], indent=1))
+    os.makedirs(os.path.dirname(args.out), exist_ok=True)
+    json.dump(out, open(args.out, "w"), indent=1)
+    print("wrote", args.out)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--images", type=int, default=1024)
     ap.add_argument("--batch", type=int, default=8)
     ap.add_argument("--out", default=os.path.join(ROOT, "gpurun_out", "cli_e2e.json"))
-    ap.add_argument("--only", choices=["", "jpeg", "huffman"], default="")
+    ap.add_argument("--only", choices=["", "jpeg", "huffman", "gt"], default="")
     ap.add_argument("--pairs", type=int, default=3)
     args = ap.parse_args()
     from PIL import Image
@@ -83,6 +200,8 @@ def main():
     net = SMAP(make_cfg((128, 208))).eval()
     sd = people_state_dict(net.state_dict(), "smooth")
     torch.save({"model": sd}, os.path.join(tmp, "SMAP.pth"))
+    if args.only == "gt":
+        return gt_leg(args, tmp, jpg)
     runs = []
     cases = [("encoded jpg/png, GPU pre-processing, 16 decode threads (default)", enc, ["--device_preprocess", "1"], {}),
              ("encoded jpg/png, GPU pre-processing, 8 decode threads", enc, ["--device_preprocess", "1"], {"SMAP_DECODE_THREADS": "8"}),
