@@ -22,6 +22,10 @@ one record per matched person, the RefineNet training pairs (dataset/p2p_dataset
 and the depth-order reverse rate of lib/eval/test_util_panoptic.py (eval_3d, calculate_and_log), accumulated on the GPU
 (smap_amd/evaluate.py) and written as `error` into the result file, as the reference's Panoptic test does.
 
+`-t generate_result --eval_maps 1` (addition), with or without --eval_3d, scores the network's MAPS: head-size-normalised 2D keypoint error,
+keypoint recall and the per-bone relative-depth error / reverse count of that module's `eval` branch (eval_one_image, generate_rootZ),
+accumulated on the GPU next to the lifting kernel (smap_amd/evaluate.py EvalMaps); the six raw accumulators are added to `error`.
+
 `--device_preprocess 1 [--device_decode 1|2]` (addition) acts in all three modes: the frames are decoded ahead of the consumer and resized /
 padded / normalised on the GPU, one launch per batch (DevicePreprocLoader below); the result file is the same."""
 import argparse
@@ -332,7 +336,7 @@ class _DryRunPipeline:
         return out or None
 
 
-def generate_3d_point_pairs(model, refine_model, data_loader, cfg, logger, device, output_dir="", pipeline_cls=None, eval_3d=False):
+def generate_3d_point_pairs(model, refine_model, data_loader, cfg, logger, device, output_dir="", pipeline_cls=None, eval_3d=False, eval_maps=False):
     os.makedirs(output_dir, exist_ok=True)
     if pipeline_cls is None:       # batches of <= 8 frames share a backbone launch (smap_amd/pipeline.py::make_pipeline, SMAP_LAUNCH_FRAMES)
         pipeline_cls = lambda m, c, b, h, w, d, rw, **kw: make_pipeline(m, c, b, h, w, d, refine_weights=rw, **kw)
@@ -340,6 +344,10 @@ def generate_3d_point_pairs(model, refine_model, data_loader, cfg, logger, devic
     if eval_3d:                    # the reference's `error` dict, accumulated on the device by every batch's post-processing
         from smap_amd.evaluate import Eval3D
         evaluator = Eval3D(device, refine=refine_model is not None)
+    map_evaluator = None
+    if eval_maps:                  # the `eval` keys of that dict: 2D keypoint error / recall and bone depth error of the maps
+        from smap_amd.evaluate import EvalMaps
+        map_evaluator = EvalMaps(device)
     if model is not None:
         model.eval()
     refine_w = None
@@ -402,7 +410,8 @@ def generate_3d_point_pairs(model, refine_model, data_loader, cfg, logger, devic
             pipe = pipeline_cls(model, cfg, len(imgs), imgs.shape[-2], imgs.shape[-1], device, refine_w,
                                 do_flip=bool(cfg.DO_FLIP), record_mode=cfg.TEST_MODE, numpy_records=True,
                                 depth=int(os.environ.get("SMAP_PIPELINE_DEPTH", 2)),   # two backbones in flight (+19 %)
-                                **({} if evaluator is None else {"evaluator": evaluator}))
+                                **({} if evaluator is None else {"evaluator": evaluator}),
+                                **({} if map_evaluator is None else {"map_evaluator": map_evaluator}))
         with torch.no_grad():
             drain(pipe.submit(imgs, cams, list(img_path), annotations=annotations))
         clock["submit_s"] += time.perf_counter() - t_sub
@@ -440,6 +449,15 @@ def generate_3d_point_pairs(model, refine_model, data_loader, cfg, logger, devic
             for line in log_lines(raw):                                         # calculate_and_log's lines (test_util_panoptic.py:388-400)
                 logger.info(line)
             result["error"] = summarize(raw)
+    if map_evaluator is not None:
+        from smap_amd.evaluate import MAPS_KEYS, log_lines_maps, merge_maps
+        raw = map_evaluator.raw()
+        if dist.is_initialized() and (dist.get_world_size() > 1 or os.environ.get("SMAP_FORCE_GATHER", "") == "1"):
+            raw = merge_maps(gather_records(raw, device))                       # rank order; evaluate.merge_maps says what that costs
+        if rank == 0:
+            for line in log_lines_maps(raw):                                    # calculate_and_log's `eval` lines (test_util_panoptic.py:374-378)
+                logger.info(line)
+            result.setdefault("error", {}).update({k: raw[k].tolist() for k in MAPS_KEYS})
     if rank == 0:
         dir_name = os.path.split(os.path.split(os.path.realpath(__file__))[0])[1]
         name = os.path.join(output_dir, "{}_{}_{}_{}.json".format(dir_name, cfg.TEST_MODE, cfg.DATA_MODE,
@@ -482,6 +500,10 @@ def main():
     parser.add_argument("--eval_3d", type=int, default=0, choices=[0, 1],
                         help="(addition) 1, with -t generate_result: score the run on the GPU (MPJPE, PCK, recall, reverse rate: "
                              "lib/eval/test_util_panoptic.py eval_3d) and write the `error` dict into the result file")
+    parser.add_argument("--eval_maps", type=int, default=0, choices=[0, 1],
+                        help="(addition) 1, with -t generate_result: score the network's maps on the GPU (2D keypoint error / recall, "
+                             "bone depth error: lib/eval/test_util_panoptic.py eval_one_image, generate_rootZ) and add the six raw "
+                             "accumulators to the `error` dict of the result file")
     args = parser.parse_args()
     if args.device_decode not in (0, 1, 2):
         parser.error("--device_decode is 0, 1 or 2")
@@ -491,6 +513,10 @@ def main():
         parser.error("--eval_3d 1 requires -t generate_result")
     if args.eval_3d and args.dry_run:
         parser.error("--eval_3d 1 scores on the GPU: not available with --dry_run 1")
+    if args.eval_maps and args.test_mode != "generate_result":
+        parser.error("--eval_maps 1 requires -t generate_result")
+    if args.eval_maps and args.dry_run:
+        parser.error("--eval_maps 1 scores on the GPU: not available with --dry_run 1")
     cfg.TEST_MODE = args.test_mode
     cfg.DATA_MODE = args.data_mode
     cfg.REFINE = len(args.RefineNet_path) > 0
@@ -565,7 +591,8 @@ def main():
                 logger.info("No such RefineNet checkpoint of {}".format(args.RefineNet_path))
                 return
         result = generate_3d_point_pairs(model, refine_model, data_loader, cfg, logger, device,
-                                         output_dir=os.path.join(cfg.OUTPUT_DIR, "result"), eval_3d=bool(args.eval_3d))
+                                         output_dir=os.path.join(cfg.OUTPUT_DIR, "result"), eval_3d=bool(args.eval_3d),
+                                         eval_maps=bool(args.eval_maps))
         if dist.is_initialized():
             dist.destroy_process_group()
         if result.get("dropped_frames"):

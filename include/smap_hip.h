@@ -110,6 +110,14 @@ int smap_lift_gt(const float* bodys, const int32_t* counts, const float* det_d, 
                  const double* cams, int B, int H, int W, double* pred_2d, double* pred_3d, double* root_z,
                  void* stream);
 
+/* smap_lift_gt that also hands out what the Z chain was built from, for the scorer of the maps (smap_evalmaps_update):
+ * depth_v: [B,127,14] f64 out, the mean of the ten clamped PAF-Z samples of every sampled limb (generate_relZ's depth_v), 0 elsewhere;
+ * bone_mask: [B,127] int32 out, bit k = limb k of the row was sampled (root score > 0 and both of the limb's joints found) -- a
+ * sampled depth may be exactly 0.0.  Rows >= counts[b]: zeros, empty mask.  pred_2d / pred_3d / root_z: smap_lift_gt's, bit for bit. */
+int smap_lift_gt_bones(const float* bodys, const int32_t* counts, const float* det_d, const float* root_d,
+                       const double* cams, int B, int H, int W, double* pred_2d, double* pred_3d, double* root_z,
+                       double* depth_v, int32_t* bone_mask, void* stream);
+
 /* smap_refine on the f64 pred_2d of smap_lift_gt. */
 int smap_refine_gt(const double* pred_2d, const double* pred_3d, const int32_t* counts, int B,
                    const float* const* wt, const float* const* bs, double* refined, void* stream);
@@ -524,6 +532,26 @@ int smap_eval3d_fold(const double* terms, const int32_t* counts, int B, int G, d
  * smap_eval3d_terms followed by smap_eval3d_fold.  Same bits either way.  terms: caller's scratch [B,G,SMAP_EVAL_TERM_DOUBLES]. */
 int smap_eval3d_update(const double* pred_3d, const int32_t* counts, const double* gt, int B, int G, double* terms, double* acc,
                        void* stream);
+
+/* ---- scoring the maps: eval_one_image (:88-113) and the `eval` part of generate_rootZ (:145-156) on the device ----
+ * The accumulator is SMAP_EVALMAPS_ACC_DOUBLES f64, kept across calls:
+ *   count_gt[15] | count_pred[15] | distance_e[15] | distance_d[14] | reverse_count[14] | count_pred_bone[14];
+ * a person's term row has the same layout. */
+#define SMAP_EVALMAPS_ACC_DOUBLES 87
+
+/* acc = zeros. */
+int smap_evalmaps_acc_init(double* acc, void* stream);
+
+/* pred_2d: [B,127,15,4] f64 and depth_v [B,127,14] f64 / bone_mask [B,127] int32 as smap_lift_gt_bones wrote them (row g registered to
+ * kept annotation g, smap_register_gt); counts: [B] int32 = smap_register_gt's matched_counts (clamped to 0..G); gt_2d: [B,G,15,4] f64 =
+ * columns 0:4 (x, y, Z, score) of the kept annotations, 1 <= G <= SMAP_EVAL_MAXG; terms: scratch [B,G,SMAP_EVALMAPS_ACC_DOUBLES] f64.
+ * Rows >= counts[b] are not read.  2D part: for a row whose predicted root has x > 0 and y > 0, every joint with gt score > 1 counts in
+ * count_gt, and in count_pred / distance_e (+= dis / head) when dis = |gt - pred| < head = |gt head - gt neck| / 3, strictly.  Bone part:
+ * for every sampled limb k (bone_mask), real = gt Z[dst] - gt Z[src]: distance_d += |depth_v - real|, count_pred_bone += 1,
+ * reverse_count += 1 when depth_v * real < -1.  A frame's persons are summed into a zero partial first, the partial is then added to
+ * acc -- the reference's association.  ONE launch of one workgroup while B * G <= 1024, two launches otherwise; same bits. */
+int smap_evalmaps_update(const double* pred_2d, const double* depth_v, const int32_t* bone_mask, const int32_t* counts,
+                         const double* gt_2d, int B, int G, double* terms, double* acc, void* stream);
 
 #if defined(__GNUC__)
 #pragma GCC visibility pop

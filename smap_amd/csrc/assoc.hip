@@ -534,7 +534,9 @@ __device__ __forceinline__ double np_lerp(double a, double b, double t)
 // back a FLOAT64 person array (test_util.py:37): the Z column, the un-letter-boxed x / y and the absolute depth
 // are never rounded to fp32, pred_2d is f64, and the root depth is an all-fp32 product (np.float32 map value x
 // Python float scale x np.float32 focal length under numpy 2's weak-scalar promotion).
-template <bool GT>
+// BONES = true (smap_lift_gt_bones): the per-limb depths the Z chain is built from go out as well, for the scorer of the
+// maps (eval.hip): depth_v [B,127,14] f64 and one bit per sampled limb -- a sampled depth may be exactly 0.0.
+template <bool GT, bool BONES = false>
 __global__ __launch_bounds__(128) void lift_kernel(const float* __restrict__ bodys_all,
                                                    const int* __restrict__ counts,
                                                    const float* __restrict__ det_d_all,
@@ -542,7 +544,9 @@ __global__ __launch_bounds__(128) void lift_kernel(const float* __restrict__ bod
                                                    const double* __restrict__ cams, int H, int W,
                                                    typename std::conditional<GT, double, float>::type* __restrict__ pred_2d_all,
                                                    double* __restrict__ pred_3d_all,
-                                                   double* __restrict__ root_z_all)
+                                                   double* __restrict__ root_z_all,
+                                                   double* __restrict__ depth_v_all = nullptr,
+                                                   int* __restrict__ bone_mask_all = nullptr)
 {
     typedef typename std::conditional<GT, double, float>::type T2;
     constexpr int STRIDE = 4, NPTS = 10, root_n = 2;
@@ -554,6 +558,10 @@ __global__ __launch_bounds__(128) void lift_kernel(const float* __restrict__ bod
     if (i >= P) {
         for (int k = 0; k < NJ * 4; ++k) { p2[k] = (T2)0; o[k] = 0.0; }
         root_z_all[(size_t)b * MAXP + i] = 0.0;
+        if constexpr (BONES) {
+            for (int k = 0; k < NL; ++k) depth_v_all[((size_t)b * MAXP + i) * NL + k] = 0.0;
+            bone_mask_all[(size_t)b * MAXP + i] = 0;
+        }
         return;
     }
     const float* src = bodys_all + ((size_t)b * MAXP + i) * NJ * 4;
@@ -572,6 +580,7 @@ __global__ __launch_bounds__(128) void lift_kernel(const float* __restrict__ bod
     }
     double depth_v[NL];
     for (int k = 0; k < NL; ++k) depth_v[k] = 0.0;
+    int sampled = 0;                             // bit k: limb k was sampled (BONES)
     double rz = 0.0;
     if (bs[root_n] > 0) {
         const int ry = (int)by[root_n], rx = (int)bx[root_n];
@@ -610,6 +619,7 @@ __global__ __launch_bounds__(128) void lift_kernel(const float* __restrict__ bod
             r += v[8];
             r += v[9];
             depth_v[k] = (double)(r / (float)NPTS);
+            if constexpr (BONES) sampled |= 1 << k;
         }
         bz[2] = (T2)0;
         bz[0] = (T2)((double)bz[2] - depth_v[1]);
@@ -618,6 +628,10 @@ __global__ __launch_bounds__(128) void lift_kernel(const float* __restrict__ bod
             bz[c_pairs[2 * k + 1]] = (T2)((double)bz[c_pairs[2 * k]] + depth_v[k]);
     }
     root_z_all[(size_t)b * MAXP + i] = rz;
+    if constexpr (BONES) {
+        for (int k = 0; k < NL; ++k) depth_v_all[((size_t)b * MAXP + i) * NL + k] = depth_v[k];
+        bone_mask_all[(size_t)b * MAXP + i] = sampled;
+    }
     const bool live = bs[root_n] != 0;
     for (int j = 0; j < NJ; ++j) {
         p2[4 * j] = bx[j]; p2[4 * j + 1] = by[j]; p2[4 * j + 2] = bz[j]; p2[4 * j + 3] = bs[j];
@@ -1001,6 +1015,17 @@ int smap_lift_gt(const float* bodys, const int32_t* counts, const float* det_d, 
         return SMAP_E_ARG;
     hipLaunchKernelGGL(lift_kernel<true>, dim3(B), dim3(128), 0, (hipStream_t)stream, bodys, counts, det_d, root_d,
                        cams, H, W, pred_2d, pred_3d, root_z);
+    return hip_rc(hipGetLastError());
+}
+
+int smap_lift_gt_bones(const float* bodys, const int32_t* counts, const float* det_d, const float* root_d,
+                       const double* cams, int B, int H, int W, double* pred_2d, double* pred_3d, double* root_z,
+                       double* depth_v, int32_t* bone_mask, void* stream)
+{
+    if (!bodys || !counts || !det_d || !root_d || !cams || !pred_2d || !pred_3d || !root_z || !depth_v || !bone_mask || B <= 0)
+        return SMAP_E_ARG;
+    hipLaunchKernelGGL((lift_kernel<true, true>), dim3(B), dim3(128), 0, (hipStream_t)stream, bodys, counts, det_d, root_d,
+                       cams, H, W, pred_2d, pred_3d, root_z, depth_v, bone_mask);
     return hip_rc(hipGetLastError());
 }
 

@@ -143,12 +143,16 @@ def register_gt_batch(bodys, counts, gt_roots, gt_counts):
     return matched, mcounts
 
 
-def lift_batch(bodys, counts, det_d, root_d, cams, gt_mode=False, out=None):
+def lift_batch(bodys, counts, det_d, root_d, cams, gt_mode=False, out=None, bones=False):
     """Batched 3D lifting (test.py:116-134, test_util.py:45-99, post_3d.py).
     det_d [B,14,H,W], root_d [B,H,W] or [B,1,H,W], cams [B,9] float64
     (scale,img_w,img_h,net_w,net_h,f_x,f_y,cx,cy).
     -> pred_2d [B,127,15,4] fp32, pred_3d [B,127,15,4] f64, root_z [B,127] f64 (device).
-    gt_mode: the float64 person array of the ground-truth modes (pred_2d comes back as f64)."""
+    gt_mode: the float64 person array of the ground-truth modes (pred_2d comes back as f64).
+    bones (gt_mode only): -> (pred_2d, pred_3d, root_z, depth_v [B,127,14] f64, bone_mask [B,127] int32): the per-limb relative depths
+    the Z chain is built from and, per row, which limbs were sampled (bit k = limb k) -- what smap_amd.evaluate.EvalMaps scores."""
+    if bones and not gt_mode:
+        raise ValueError("lift_batch(bones=True) needs gt_mode=True: the limb depths are scored against annotations")
     B = bodys.shape[0]
     if root_d.dim() == 4:
         root_d = root_d[:, 0]
@@ -171,6 +175,13 @@ def lift_batch(bodys, counts, det_d, root_d, cams, gt_mode=False, out=None):
         p2 = torch.empty((B, MAXP, NJ, 4), dtype=torch.float64 if gt_mode else torch.float32, device=dev)
         p3 = torch.empty((B, MAXP, NJ, 4), dtype=torch.float64, device=dev)
         rz = torch.empty((B, MAXP), dtype=torch.float64, device=dev)
+    if bones:
+        depth_v = torch.empty((B, MAXP, NL), dtype=torch.float64, device=dev)
+        mask = torch.empty((B, MAXP), dtype=torch.int32, device=dev)
+        with torch.cuda.device(dev):
+            _L.check(_L.load().smap_lift_gt_bones(_p(bodys), _p(counts), _p(det_d), _p(root_d), _p(cams), B, H, W, _p(p2), _p(p3), _p(rz),
+                                                  _p(depth_v), _p(mask), _stream()), "smap_lift_gt_bones")
+        return p2, p3, rz, depth_v, mask
     fn = _L.load().smap_lift_gt if gt_mode else _L.load().smap_lift
     with torch.cuda.device(dev):
         _L.check(fn(_p(bodys), _p(counts), _p(det_d), _p(root_d), _p(cams), B, H, W, _p(p2), _p(p3), _p(rz), _stream()),

@@ -8,9 +8,20 @@ smap_refine_gt), on the stream the caller is on, and nothing comes back to the h
 
 The 80 float64 accumulators (include/smap_hip.h, SMAP_EVAL_ACC_DOUBLES) live on the device across `update` calls and are
 the reference's running sums bit for bit: every person's terms are added one `+=` per field, frames then persons in
-order.  Not scored (out of scope): the 2D error / recall of `eval_one_image` and the per-bone depth error.
+order.
 
-    python -m smap_amd.evaluate RESULT.json [--refine 0|1] [--device cuda:0]
+`EvalMaps` scores the network's MAPS the same way -- the `eval` branch of that module: `eval_one_image` (:88-113, head-size-normalised
+2D keypoint error and keypoint recall), the `eval` part of `generate_rootZ` (:145-156, per limb |sampled relative depth - annotated
+relative depth| and a count of sign reversals) and the `eval` branch of `calculate_and_log` (:359-378).  Its 87 float64
+(SMAP_EVALMAPS_ACC_DOUBLES) are fed by `lift_batch(..., gt_mode=True, bones=True)`: the per-limb depth exists only inside the lifting
+kernel.  Those two functions sum a frame's persons into a zero vector first and add that to the running total; the device fold
+associates the same way, so the six counters and `distance_d` are the reference's bit for bit.  `distance_e` is not: the reference's
+`distance()` squares and roots with `**`, i.e. libm `pow`, which differs from multiply / correctly rounded `sqrt` in the last place
+for ~1 % of inputs (DESIGN section 10 has the bound).  Limb 0 is (0, 1) = cfg.DATASET.PAF.VECTOR, the table the lifting samples with;
+the panoptic module's own table has (1, 0) there.  Annotation depths are subtracted in float64 as they stand, where the reference,
+handed a float32 annotation array, would subtract in fp32.  Not scored: the MuPoTS MATLAB protocol.
+
+    python -m smap_amd.evaluate RESULT.json [--refine 0|1] [--maps 0|1] [--device cuda:0]
 
 scores an existing result file -- this project's or one written by the reference's test.py -- and prints the summary as
 JSON.  Annotations are fp32 (dataset/base_dataset.py), so a file holds exactly the ground truth the run saw; where the
@@ -127,6 +138,121 @@ def merge(raws):
     return unpack(acc, refine)
 
 
+# ---- the maps' scores: eval_one_image + generate_rootZ('eval') + calculate_and_log('eval') ----
+NL = 14
+MAPS_ACC_DOUBLES = MAPS_TERM_DOUBLES = 87
+# (key, length, integer in the reference) in accumulator order == the order of `initialization` (:338-343)
+MAPS_FIELDS = (("count_gt", NJ, True), ("count_pred", NJ, True), ("distance_e", NJ, False),
+               ("distance_d", NL, False), ("reverse_count", NL, False), ("count_pred_bone", NL, True))
+MAPS_KEYS = tuple(k for k, _, _ in MAPS_FIELDS)
+MAPS_2D_KEYS = MAPS_KEYS[:3]
+
+
+def unpack_maps(acc):
+    """[87] float64 in accumulator order -> the six `eval` keys of the reference's error dict with its dtypes: int64 arrays for
+    count_gt, count_pred and count_pred_bone, float64 for distance_e, distance_d and reverse_count."""
+    acc = np.asarray(acc, np.float64).reshape(MAPS_ACC_DOUBLES)
+    out, o = {}, 0
+    for key, n, is_int in MAPS_FIELDS:
+        out[key] = acc[o:o + n].astype(np.int64) if is_int else acc[o:o + n].copy()
+        o += n
+    return out
+
+
+def pack_maps(raw):
+    """The inverse of `unpack_maps`."""
+    return np.concatenate([np.asarray(raw[key], np.float64).reshape(n) for key, n, _ in MAPS_FIELDS])
+
+
+def summarize_maps(raw):
+    """The `eval` branch of calculate_and_log (:360-372) on a `raw()` dict: error_point = distance_e / count_pred, recall =
+    count_pred / count_gt, depth_e and depth_reverse_count over count_pred_bone, each where the divisor is > 0 and 0 elsewhere;
+    avg_error / avg_recall = np.average over the entries with a divisor (nan when there is none, as np.average of nothing is)."""
+    c_gt, c_pred, c_bone = (np.asarray(raw[k]) for k in ("count_gt", "count_pred", "count_pred_bone"))
+    d_e, d_d, rev = (np.asarray(raw[k], np.float64) for k in ("distance_e", "distance_d", "reverse_count"))
+    error_point, recall = np.zeros(NJ), np.zeros(NJ)
+    depth_e, depth_reverse_count = np.zeros(NL), np.zeros(NL)
+    mask, mask_bone = c_pred > 0, c_bone > 0
+    error_point[mask] = d_e[mask] / c_pred[mask]
+    depth_e[mask_bone] = d_d[mask_bone] / c_bone[mask_bone]
+    depth_reverse_count[mask_bone] = rev[mask_bone] / c_bone[mask_bone]
+    avg_error = np.average(error_point[mask]) if mask.any() else np.float64("nan")
+    mask = c_gt > 0
+    recall[mask] = c_pred[mask] / c_gt[mask]
+    avg_recall = np.average(recall[mask]) if mask.any() else np.float64("nan")
+    return {"error_point": error_point, "recall": recall, "depth_e": depth_e, "depth_reverse_count": depth_reverse_count,
+            "avg_error": avg_error, "avg_recall": avg_recall}
+
+
+def log_lines_maps(raw):
+    """The five result lines of calculate_and_log's `eval` branch (:374-378), same wording."""
+    s = summarize_maps(raw)
+    return ["keypoints error of validation dataset is {}".format(s["error_point"]),
+            "Keypoints recall of validation dataset is {}".format(s["recall"]),
+            "Bones depth distance is {}".format(s["depth_e"]),
+            "Bones reverse count is {}".format(s["depth_reverse_count"]),
+            "Average error is {}, average recall is {}".format(s["avg_error"], s["avg_recall"])]
+
+
+def merge_maps(raws):
+    """Per-rank `EvalMaps.raw()` dicts, in rank order -> the accumulators of the whole run.
+
+    The four counters are sums of ones: exact in any order.  distance_e and distance_d are float64 sums of non-negative terms; a
+    one-rank run adds one per-frame partial after the other, here per-rank subtotals are added, which re-associates them at the rank
+    boundaries.  As in `merge`: each way of summing n non-negative terms is within (n - 1) * 2^-53 of the exact sum, relatively, so
+    the two differ by at most n * 2^-52 relative, n = count_pred (count_pred_bone) of that field.  tests/test_eval_maps_cpu.py."""
+    raws = list(raws)
+    if not raws:
+        raise ValueError("merge_maps() needs at least one accumulator")
+    acc = np.zeros(MAPS_ACC_DOUBLES)
+    for r in raws:                                              # rank order; the counters are integers in float64: exact below 2^53
+        acc = acc + pack_maps(r)
+    return unpack_maps(acc)
+
+
+def gt2d_rows(annotations, gmax=None):
+    """B arrays [G_i,15,>=4] of KEPT annotations -> gt_2d [B,G,15,4] float64 = columns 0:4 (x, y, Z, score: network pixels and the
+    annotated depth), row for row, zero padded."""
+    rows = [np.asarray(a, np.float64) for a in annotations]
+    rows = [a if a.size else np.zeros((0, NJ, 4)) for a in rows]
+    G = max(1, max((len(a) for a in rows), default=1)) if gmax is None else int(gmax)
+    if G > MAXG or any(len(a) > G for a in rows):
+        raise ValueError("at most %d annotations per frame" % MAXG)
+    gt = np.zeros((len(rows), G, NJ, 4), np.float64)
+    for i, a in enumerate(rows):
+        if len(a):
+            gt[i, :len(a)] = a[:, :, 0:4]
+    return gt
+
+
+def check_maps_args(pred_2d, depth_v, bone_mask, counts, gt_2d):
+    """-> (B, G).  ValueError for anything smap_evalmaps_update must not be handed."""
+    named = (("pred_2d", pred_2d), ("depth_v", depth_v), ("bone_mask", bone_mask), ("counts", counts), ("gt_2d", gt_2d))
+    for name, t in named:
+        if not isinstance(t, torch.Tensor):
+            raise ValueError(f"{name} must be a torch.Tensor")
+        if not t.is_cuda:
+            raise ValueError(f"{name} must live on the GPU (there is no host scorer)")
+        if not t.is_contiguous():
+            raise ValueError(f"{name} must be contiguous")
+    if pred_2d.dim() != 4 or tuple(pred_2d.shape[1:]) != (MAXP, NJ, 4) or pred_2d.dtype != torch.float64:
+        raise ValueError(f"pred_2d must be float64 [B,{MAXP},{NJ},4] (lift_batch(gt_mode=True)), got {pred_2d.dtype} {tuple(pred_2d.shape)}")
+    B = pred_2d.shape[0]
+    if B < 1:
+        raise ValueError("an empty batch")
+    if tuple(depth_v.shape) != (B, MAXP, NL) or depth_v.dtype != torch.float64:
+        raise ValueError(f"depth_v must be float64 [B,{MAXP},{NL}], got {depth_v.dtype} {tuple(depth_v.shape)}")
+    if tuple(bone_mask.shape) != (B, MAXP) or bone_mask.dtype != torch.int32:
+        raise ValueError(f"bone_mask must be int32 [B,{MAXP}], got {bone_mask.dtype} {tuple(bone_mask.shape)}")
+    if gt_2d.dim() != 4 or gt_2d.shape[0] != B or tuple(gt_2d.shape[2:]) != (NJ, 4) or gt_2d.dtype != torch.float64 or not 1 <= gt_2d.shape[1] <= MAXG:
+        raise ValueError(f"gt_2d must be float64 [B,G,{NJ},4] with 1 <= G <= {MAXG}, got {gt_2d.dtype} {tuple(gt_2d.shape)}")
+    if tuple(counts.shape) != (B,) or counts.dtype != torch.int32:
+        raise ValueError(f"counts must be int32 [B], got {counts.dtype} {tuple(counts.shape)}")
+    if len({t.device for _, t in named}) != 1:
+        raise ValueError("pred_2d, depth_v, bone_mask, counts and gt_2d must be on one device")
+    return B, gt_2d.shape[1]
+
+
 def gt_rows(annotations, gmax=None):
     """B annotation arrays [G_i,15,>=7] -> (gt [B,G,15,4] float64 = (X,Y,Z,score) = columns 4:7 and 3, row for row, zero padded;
     counts [B]).  No row is dropped: row g stays the annotation the registration kernel calls g."""
@@ -235,6 +361,111 @@ class Eval3D:
         return summarize(self.raw())
 
 
+class EvalMaps:
+    """The six `eval` accumulators of the reference's error dict (count_gt, count_pred, distance_e, distance_d, reverse_count,
+    count_pred_bone) as 87 float64 on `device`.  Same contract as Eval3D: update() runs on the caller's current stream and returns at
+    once, calls are ordered after one another on the device by an event chain, raw() / summary() are the only host synchronisation."""
+
+    def __init__(self, device):
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise ValueError("EvalMaps scores on the GPU: device must be a cuda device (there is no host scorer)")
+        self._lib = _L.load()
+        self.acc = torch.empty((MAPS_ACC_DOUBLES,), dtype=torch.float64, device=self.device)
+        self._ev = torch.cuda.Event()
+        with torch.cuda.device(self.device):
+            _L.check(self._lib.smap_evalmaps_acc_init(_p(self.acc), _stream(self.device)), "smap_evalmaps_acc_init")
+            self._ev.record()
+
+    def update(self, pred_2d, depth_v, bone_mask, counts, gt_2d):
+        """pred_2d [B,127,15,4] f64, depth_v [B,127,14] f64, bone_mask [B,127] int32: lift_batch(gt_mode=True, bones=True) on the rows
+        register_gt_batch matched; counts [B] int32 = its matched_counts; gt_2d [B,G,15,4] f64 = columns 0:4 of the kept annotations
+        (gt2d_rows).  Device tensors; rows >= counts[b] are not read."""
+        B, G = check_maps_args(pred_2d, depth_v, bone_mask, counts, gt_2d)
+        if pred_2d.device != self.device:
+            raise ValueError(f"this evaluator lives on {self.device}, the tensors on {pred_2d.device}")
+        with torch.cuda.device(self.device):
+            cur = torch.cuda.current_stream(self.device)
+            cur.wait_event(self._ev)                            # after the previous update (or the initialisation), on whatever stream it ran
+            terms = torch.empty((B, G, MAPS_TERM_DOUBLES), dtype=torch.float64, device=self.device)
+            _L.check(self._lib.smap_evalmaps_update(_p(pred_2d), _p(depth_v), _p(bone_mask), _p(counts), _p(gt_2d), B, G, _p(terms),
+                                                    _p(self.acc), _stream(self.device)), "smap_evalmaps_update")
+            self._ev.record()
+
+    def update_from_annotations(self, pred_2d, depth_v, bone_mask, counts, annotations, root_idx=2):
+        """update() with gt_2d built from B annotation arrays [G_i,15,>=4] (rows with root score > 1 are kept, as the pipeline does)
+        and uploaded on the current stream."""
+        kept = []
+        for a in annotations:
+            a = np.asarray(a, np.float64)
+            kept.append(a[a[:, root_idx, 3] > 1] if a.size else a)
+        self.update(pred_2d, depth_v, bone_mask, counts, torch.from_numpy(gt2d_rows(kept)).to(self.device, non_blocking=True))
+
+    def raw(self):
+        """The reference's six `eval` keys BEFORE calculate_and_log's divisions, with its dtypes (unpack_maps)."""
+        with torch.cuda.device(self.device):
+            torch.cuda.current_stream(self.device).wait_event(self._ev)
+            host = self.acc.cpu().numpy()
+        return unpack_maps(host)
+
+    def summary(self):
+        """summarize_maps(raw()): error_point, recall, depth_e, depth_reverse_count, avg_error, avg_recall."""
+        return summarize_maps(self.raw())
+
+
+BONES_REFUSAL = ("the bone depth error cannot be scored from a result file: the per-limb depth `depth_v` is not in it (it exists only "
+                 "inside the lifting kernel); score it while the run runs, `test.py -t generate_result --eval_maps 1`")
+
+
+def _parse_records_maps(records, path):
+    """Frame records -> [(pred_2d [P,15,4], gt_2d [P,15,4])]; ValueError for anything whose 2D part cannot be scored."""
+    if not records:
+        raise ValueError(f"{path}: no records to score")
+    frames = []
+    for n, r in enumerate(records):
+        if not isinstance(r, dict) or "pred_2d" not in r:
+            raise ValueError(f"{path}: record {n} has no pred_2d: not a result file of test.py")
+        pred = np.asarray(r["pred_2d"], np.float64)
+        if pred.ndim != 3 or pred.shape[1:] != (NJ, 4):
+            raise ValueError(f"{path}: record {n} holds one person, not a frame: a generate_train file cannot be scored")
+        if "gt_2d" not in r or len(r["gt_2d"]) == 0:
+            raise ValueError(f"{path}: record {n} has no gt_2d (a run_inference file?): score a `-t generate_result` run")
+        g2 = np.asarray(r["gt_2d"], np.float64)
+        if g2.ndim != 3 or g2.shape[:2] != (len(pred), NJ) or g2.shape[2] < 4:
+            raise ValueError(f"{path}: record {n}: gt_2d does not match the {len(pred)} persons of pred_2d")
+        if len(pred) > MAXG:
+            raise ValueError(f"{path}: record {n} has {len(pred)} persons, at most {MAXG} are scored per frame")
+        frames.append((pred, g2[:, :, 0:4]))
+    return frames
+
+
+def score_records_maps(records, device, path="<records>", frames_per_call=256):
+    """The 2D part (count_gt, count_pred, distance_e) of `3d_pairs` frame records (pred_2d, gt_2d per frame) -> EvalMaps, frames in
+    order.  The bone part stays zero: BONES_REFUSAL."""
+    frames = _parse_records_maps(records, path)                # refusals first: they need no GPU
+    ev = EvalMaps(device)
+    for s in range(0, len(frames), frames_per_call):
+        part = frames[s:s + frames_per_call]
+        pred = np.zeros((len(part), MAXP, NJ, 4), np.float64)
+        for i, (p, _) in enumerate(part):
+            pred[i, :len(p)] = p
+        up = lambda a: torch.from_numpy(a).to(ev.device)
+        ev.update(up(pred), torch.zeros((len(part), MAXP, NL), dtype=torch.float64, device=ev.device),
+                  torch.zeros((len(part), MAXP), dtype=torch.int32, device=ev.device),
+                  up(np.asarray([len(p) for p, _ in part], np.int32)), up(gt2d_rows([g for _, g in part])))
+    return ev
+
+
+def score_file_maps(path, device="cuda:0", frames_per_call=256):
+    """Score the 2D part of a generate_result file on the GPU -> the three 2D keys of `EvalMaps.raw()`."""
+    with open(path) as f:
+        doc = json.load(f)
+    if not isinstance(doc, dict) or "3d_pairs" not in doc:
+        raise ValueError(f"{path}: no `3d_pairs` list: not a result file of test.py")
+    raw = score_records_maps(doc["3d_pairs"], device, path=path, frames_per_call=frames_per_call).raw()
+    return {k: raw[k] for k in MAPS_2D_KEYS}
+
+
 def _parse_records(records, path):
     """Frame records -> [(pred [P,15,4], gt xyz [P,15,3], gt score [P,15])]; ValueError for anything that cannot be scored."""
     if not records:
@@ -297,9 +528,23 @@ def main(argv=None):
     ap = argparse.ArgumentParser(prog="python -m smap_amd.evaluate", description="Score a `test.py -t generate_result` file on the GPU.")
     ap.add_argument("result", help="result JSON (`3d_pairs` with pred_3d, gt_3d, gt_2d per frame)")
     ap.add_argument("--refine", type=int, default=0, choices=[0, 1], help="1: the run used RefineNet (keys carry _after_refine)")
+    ap.add_argument("--maps", type=int, default=0, choices=[0, 1],
+                    help="1: score the 2D part of the maps' metrics instead (keypoint error / recall from pred_2d and gt_2d)")
+    ap.add_argument("--bones", type=int, default=0, choices=[0, 1], help="refused: " + BONES_REFUSAL)
     ap.add_argument("--device", default="cuda:0")
     args = ap.parse_args(argv)
+    if args.bones:
+        print(f"smap_amd.evaluate: {BONES_REFUSAL}", file=sys.stderr)
+        return 2
     try:
+        if args.maps:
+            raw = score_file_maps(args.result, args.device)
+            s = summarize_maps(dict(raw, distance_d=np.zeros(NL), reverse_count=np.zeros(NL), count_pred_bone=np.zeros(NL, np.int64)))
+            out = {k: np.asarray(v).tolist() for k, v in raw.items()}
+            out.update({k: np.asarray(s[k]).tolist() for k in ("error_point", "recall", "avg_error", "avg_recall")})
+            print(f"smap_amd.evaluate: {BONES_REFUSAL}", file=sys.stderr)
+            print(json.dumps(out))
+            return 0
         raw = score_file(args.result, args.device, bool(args.refine))
     except (ValueError, OSError) as exc:
         print(f"smap_amd.evaluate: {exc}", file=sys.stderr)

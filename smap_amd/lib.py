@@ -17,10 +17,11 @@ SO_PATH = os.environ.get("SMAP_HIP_LIB") or os.path.join(HERE, "libsmap_hip.so")
 # every symbol include/smap_hip.h declares
 SYMBOLS = [
     "smap_version", "smap_scale_hms", "smap_flip_merge", "smap_nms", "smap_paf_score", "smap_group", "smap_lift",
-    "smap_refine", "smap_register_gt", "smap_lift_gt", "smap_refine_gt", "smap_refine_mlp", "smap_preprocess", "smap_sizeof_op", "smap_conv_tile_dims", "smap_conv_tile_bk", "smap_conv_tile_tail_bn", "smap_plan_create", "smap_plan_destroy", "smap_plan_run", "smap_plan_run_range",
+    "smap_refine", "smap_register_gt", "smap_lift_gt", "smap_lift_gt_bones", "smap_refine_gt", "smap_refine_mlp", "smap_preprocess", "smap_sizeof_op", "smap_conv_tile_dims", "smap_conv_tile_bk", "smap_conv_tile_tail_bn", "smap_plan_create", "smap_plan_destroy", "smap_plan_run", "smap_plan_run_range",
     "smap_plan_run_inputs", "smap_workspace_bytes", "smap_plan_create_from_blob", "smap_plan_set_lanes",
     "smap_nms_workspace_bytes", "smap_nms_ws",
     "smap_eval3d_acc_init", "smap_eval3d_terms", "smap_eval3d_fold", "smap_eval3d_update",
+    "smap_evalmaps_acc_init", "smap_evalmaps_update",
     "smap_sizeof_jpeg_info", "smap_jpeg_probe", "smap_jpeg_decode_coefficients", "smap_jpeg_workspace_bytes", "smap_jpeg_reconstruct",
     "smap_sizeof_jpeg_scan", "smap_jpeg_scan_tables", "smap_jpeg_huff_workspace_bytes", "smap_jpeg_decode_coefficients_device",
     "smap_sizeof_prep_frame", "smap_preprocess_batch",
@@ -144,6 +145,7 @@ def load():
     lib.smap_refine_mlp.argtypes = [vp, ip, C.POINTER(vp), C.POINTER(vp), vp, vp]
     lib.smap_register_gt.argtypes = [vp, vp, vp, vp, ip, ip, vp, vp, vp]
     lib.smap_lift_gt.argtypes = lib.smap_lift.argtypes
+    lib.smap_lift_gt_bones.argtypes = [vp, vp, vp, vp, vp, ip, ip, ip, vp, vp, vp, vp, vp, vp]
     lib.smap_refine_gt.argtypes = lib.smap_refine.argtypes
     lib.smap_preprocess.argtypes = [vp, ip, ip, ip, ip, ip, ip, vp, ip, ip, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_double, C.c_double, vp]
     lib.smap_preprocess_batch.argtypes = [C.POINTER(PrepFrame), ip, vp, ip, ip, C.POINTER(C.c_float), C.POINTER(C.c_float), vp]
@@ -170,6 +172,8 @@ def load():
     lib.smap_eval3d_terms.argtypes = [vp, vp, vp, ip, ip, vp, vp]
     lib.smap_eval3d_fold.argtypes = [vp, vp, ip, ip, vp, vp]
     lib.smap_eval3d_update.argtypes = [vp, vp, vp, ip, ip, vp, vp, vp]
+    lib.smap_evalmaps_acc_init.argtypes = [vp, vp]
+    lib.smap_evalmaps_update.argtypes = [vp, vp, vp, vp, vp, ip, ip, vp, vp, vp]
     for s in SYMBOLS:
         if s not in ("smap_version", "smap_plan_destroy", "smap_nms_workspace_bytes", "smap_jpeg_workspace_bytes",
                      "smap_jpeg_huff_workspace_bytes"):  # everything else returns int

@@ -75,17 +75,22 @@ class _Slot:
 
 class PosePipeline:
     def __init__(self, model, cfg, batch, H, W, device, refine_weights=None, n_extra=0, do_flip=False, depth=1,
-                 record_mode="run_inference", numpy_records=False, max_frames_per_launch=None, strict_nonfinite=None, evaluator=None):
+                 record_mode="run_inference", numpy_records=False, max_frames_per_launch=None, strict_nonfinite=None, evaluator=None,
+                 map_evaluator=None):
         """record_mode: test.py's -t: "run_inference" (no ground truth), "generate_result" (one record per frame
         with the annotations attached) or "generate_train" (one record per matched person); the last two need
         `annotations=` in submit().
         evaluator: a smap_amd.evaluate.Eval3D (ground-truth modes only): every submitted batch is scored on the post stream, on the
-        tensor that is recorded as pred_3d; nothing is read back before its raw() / summary().  None: nothing changes."""
+        tensor that is recorded as pred_3d; nothing is read back before its raw() / summary().  None: nothing changes.
+        map_evaluator: a smap_amd.evaluate.EvalMaps (ground-truth modes only): the lifting also hands out its per-limb depths
+        (smap_lift_gt_bones) and every batch's registered rows are scored against the annotations' 2D columns on the post stream.
+        None: nothing changes."""
         assert record_mode in ("run_inference", "generate_result", "generate_train")
-        if evaluator is not None and record_mode == "run_inference":
-            raise ValueError("evaluator= needs a ground-truth record_mode: run_inference has nothing to score against")
+        if (evaluator is not None or map_evaluator is not None) and record_mode == "run_inference":
+            raise ValueError("evaluator= / map_evaluator= need a ground-truth record_mode: run_inference has nothing to score against")
         self.record_mode = record_mode
         self.evaluator = evaluator
+        self.map_evaluator = map_evaluator
         # frames whose maps came out non-finite (fp16 range exceeded): dropped with a RuntimeWarning and listed in
         # `dropped_frames` by default; strict_nonfinite=True (env SMAP_STRICT_NONFINITE=1) raises at collection instead
         self.strict_nonfinite = bool(int(os.environ.get("SMAP_STRICT_NONFINITE", "0"))) if strict_nonfinite is None else bool(strict_nonfinite)
@@ -141,9 +146,10 @@ class PosePipeline:
     def _post(self, slot, idx, hms, det_d, root_d, cams, scale, gt=None, row0=0):
         """Association + lifting of one set of maps on the post stream; results -> pinned memory (rows row0.. of result set idx:
         a coalesced launch hands its callers' extra maps over batch by batch, where they lie).
-        gt = (gt_roots [B,G,2], gt_counts [B][, gt_xyzs [B,G,15,4] f64]) on the device: register the persons to the annotations first
-        (test_util.py:18-42) and lift in the f64 flavour of the ground-truth modes; with the third tensor the evaluator scores
-        what is recorded as pred_3d against it (smap_amd/evaluate.py)."""
+        gt = (gt_roots [B,G,2], gt_counts [B][, gt_xyzs [B,G,15,4] f64 or None[, gt_2d [B,G,15,4] f64]]) on the device: register the
+        persons to the annotations first (test_util.py:18-42) and lift in the f64 flavour of the ground-truth modes; with the third
+        tensor the evaluator scores what is recorded as pred_3d against it, with the fourth the map evaluator scores the registered
+        rows and their limb depths (smap_amd/evaluate.py)."""
         if scale:
             dapalib.scale_hms_(hms)                                             # test.py:111-112
         n = hms.shape[0]
@@ -161,10 +167,14 @@ class PosePipeline:
         bodys, counts = dapalib.connect_batch(hms, root_d, self.cfg.DATASET.ROOT_IDX, True)
         if gt is not None:
             bodys, counts = dapalib.register_gt_batch(bodys, counts, gt[0], gt[1])
-        p2, p3, rz = dapalib.lift_batch(bodys, counts, det_d, root_d, cams, gt_mode=gt is not None)
+        if gt is not None and len(gt) > 3:
+            p2, p3, rz, depth_v, bone_mask = dapalib.lift_batch(bodys, counts, det_d, root_d, cams, gt_mode=True, bones=True)
+            self.map_evaluator.update(p2, depth_v, bone_mask, counts, gt[3])
+        else:
+            p2, p3, rz = dapalib.lift_batch(bodys, counts, det_d, root_d, cams, gt_mode=gt is not None)
         if self.refine is not None:
             p3 = dapalib.refine_batch(p2, p3, counts, *self.refine)
-        if gt is not None and len(gt) > 2:
+        if gt is not None and len(gt) > 2 and gt[2] is not None:
             self.evaluator.update(p3, counts, gt[2])
         h = slot.host[idx]
         if gt is not None:
@@ -197,7 +207,7 @@ class PosePipeline:
                 if len(a):
                     roots[i, :len(a)] = np.asarray(a)[:, self.cfg.DATASET.ROOT_IDX, :2]
             n_ann = [len(a) for a in annotations]
-            if self.evaluator is not None:
+            if self.evaluator is not None or self.map_evaluator is not None:
                 # a padding frame of a ragged last batch (tag None) repeats a real frame and has no record: no annotations, so no score either
                 n_ann = [0 if t is None else n for t, n in zip(tags, n_ann)]
             gt = (torch.from_numpy(roots).to(self.device, non_blocking=True),
@@ -205,6 +215,9 @@ class PosePipeline:
             if self.evaluator is not None:
                 from .evaluate import gt_rows
                 gt += (torch.from_numpy(gt_rows(annotations, gmax)[0]).to(self.device, non_blocking=True),)
+            if self.map_evaluator is not None:
+                from .evaluate import gt2d_rows
+                gt = gt[:3] + (None,) * (3 - len(gt)) + (torch.from_numpy(gt2d_rows(annotations, gmax)).to(self.device, non_blocking=True),)
         slot = self.slots[self.k % self.nslots]
         eng, s_bb = self.engines[self.k % self.depth], self.s_bbs[self.k % self.depth]
         ready = self._collect(slot) if slot.busy else None       # the batch submitted nslots calls ago ...
@@ -221,7 +234,8 @@ class PosePipeline:
         cams_d.record_stream(self.s_post)
         if gt is not None:
             for t in gt:
-                t.record_stream(self.s_post)
+                if t is not None:
+                    t.record_stream(self.s_post)
         as_parts = lambda t: list(t) if isinstance(t, (list, tuple)) else [t]
         for _, e_hms, e_rd, e_dd in extra:               # the caller may drop its references
             for t in (e_hms, e_rd, e_dd):

@@ -19,6 +19,10 @@ uncounted run that builds the plan cache, and adds a summary with the mean and t
 `-t generate_result --eval_3d 1` on the host loader (lib/utils/dataloader.py), with `--device_preprocess 1`, and with `--device_decode 1` / `2`
 on top, `--pairs` times each, interleaved, after one uncounted run; and the pre-processing of 8 1080p frames alone, by device events over
 200 batches: 8 launches of smap_preprocess against one of smap_preprocess_batch.
+--only maps measures what `--eval_maps 1` costs: on the same annotated folder, `-t generate_result --eval_3d 1 --device_preprocess 1
+--device_decode 1` without and with `--eval_maps 1`, `--pairs` times each, interleaved, after one uncounted run -- and, with `--parent DIR` (a
+built checkout of the parent commit), that checkout's run of the command without the flag as a third interleaved leg; then the device-event
+time of smap_evalmaps_update alone, back to back, at a step's shapes.
 """
 import argparse
 import json
@@ -91,8 +95,36 @@ def preprocess_launch_ab(batches=200, frames=8, h=1080, w=1920):
     return res
 
 
+def evalmaps_update_us(shapes=((8, 4), (8, 20), (16, 20), (8, 64), (17, 64)), iters=200):
+    """Device-event time of smap_evalmaps_update alone, back to back, per call, for (B, G): every annotation matched to a full person."""
+    from smap_amd.evaluate import EvalMaps
+    dev = torch.device("cuda:0")
+    out = {}
+    for B, G in shapes:
+        g = torch.Generator().manual_seed(B * 100 + G)
+        p2 = torch.zeros((B, 127, 15, 4), dtype=torch.float64)
+        p2[:, :G] = torch.rand((B, G, 15, 4), generator=g, dtype=torch.float64) * 400 + 1
+        gt = p2[:, :G].clone() + torch.randn((B, G, 15, 4), generator=g, dtype=torch.float64) * 3
+        gt[..., 3] = 2
+        dv = torch.randn((B, 127, 14), generator=g, dtype=torch.float64)
+        a = [p2.to(dev), dv.to(dev), torch.full((B, 127), (1 << 14) - 1, dtype=torch.int32, device=dev),
+             torch.full((B,), G, dtype=torch.int32, device=dev), gt.contiguous().to(dev)]
+        ev = EvalMaps(dev)
+        for _ in range(10):
+            ev.update(*a)
+        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        t0.record()
+        for _ in range(iters):
+            ev.update(*a)
+        t1.record()
+        torch.cuda.synchronize()
+        out[f"B={B},G={G}"] = {"us_per_update": t0.elapsed_time(t1) * 1e3 / iters, "launches": 2 if B * G > 1024 else 1}
+    return out
+
+
 def gt_leg(args, tmp, jpg):
-    """--only gt: see the module's docstring."""
+    """--only gt and --only maps: see the module's docstring."""
     rng = np.random.default_rng(7)
     root = os.path.join(tmp, "MultiPersonTestSet")
     os.makedirs(os.path.join(root, "TS1"))
@@ -115,13 +147,22 @@ def gt_leg(args, tmp, jpg):
             ("--device_preprocess 1", dp), ("--device_preprocess 1 --device_decode 1", dp + ["--device_decode", "1"]),
             ("--device_preprocess 1 --device_decode 2", dp + ["--device_decode", "2"])]
     cases = [("warm-up (builds the plan cache; not counted)", dp)] + [leg for _ in range(args.pairs) for leg in legs]
+    trees = {}
+    if args.only == "maps":
+        dd = dp + ["--device_decode", "1"]
+        legs = [("--eval_3d 1", dd), ("--eval_3d 1 --eval_maps 1", dd + ["--eval_maps", "1"])]
+        if args.parent:
+            legs.append(("parent commit, --eval_3d 1", dd))
+            trees["parent commit, --eval_3d 1"] = os.path.abspath(args.parent)
+        cases = [("warm-up (builds the plan cache; not counted)", dd)] + [leg for _ in range(args.pairs) for leg in legs]
     runs, first = [], None
     for name, extra in cases:
+        tree = trees.get(name, ROOT)
         timing = os.path.join(tmp, "timing.json")
-        env = dict(os.environ, PROJECT_HOME=tmp, PYTHONPATH=ROOT + os.pathsep + os.environ.get("PYTHONPATH", ""), SMAP_CLI_TIMING=timing,
+        env = dict(os.environ, PROJECT_HOME=tmp, PYTHONPATH=tree + os.pathsep + os.environ.get("PYTHONPATH", ""), SMAP_CLI_TIMING=timing,
                    SMAP_PLAN_CACHE=os.path.join(tmp, "plan_cache"), SMAP_TEST_ROOT=root)
         t0 = time.perf_counter()
-        r = subprocess.run([sys.executable, os.path.join(ROOT, "exps", "stage3_root2", "test.py"), "-p", os.path.join(tmp, "SMAP.pth"),
+        r = subprocess.run([sys.executable, os.path.join(tree, "exps", "stage3_root2", "test.py"), "-p", os.path.join(tmp, "SMAP.pth"),
                             "-t", "generate_result", "-d", "test", "--eval_3d", "1", "--batch_size", str(args.batch), "--json_name", "gt"] + extra,
                            capture_output=True, text=True, env=env, cwd=tmp, timeout=1500)
         rec = {"case": name, "returncode": r.returncode, "process_wall_s": time.perf_counter() - t0}
@@ -131,6 +172,8 @@ def gt_leg(args, tmp, jpg):
             res = json.load(open(os.path.join(tmp, "model_logs", "stage3_root2", "result", "stage3_root2_generate_result_test_gt.json")))
             rec["records_in_result_file"] = len(res["3d_pairs"])
             rec["error_keys"] = len(res.get("error", {}))
+            for k in ("count_gt", "count_pred", "distance_e", "distance_d", "reverse_count", "count_pred_bone"):
+                res.get("error", {}).pop(k, None)                 # (--only maps: the flag adds these six keys and nothing else)
             if first is None:
                 first = res
             rec["same_result_file_as_first_run"] = res == first
@@ -142,6 +185,20 @@ def gt_leg(args, tmp, jpg):
     for rec in runs[1:]:
         if rec.get("frames_per_s_after_engine_build"):
             summary.setdefault(rec["case"], []).append(rec["frames_per_s_after_engine_build"])
+    if args.only == "maps":
+        out = {"images": args.images, "batch_size": args.batch, "mode": "-t generate_result -d test --eval_3d 1 --device_preprocess 1 --device_decode 1",
+               "sources": "the bench's 8 frames as 1664x1024 JPEG q98 4:4:4 (pixel-doubled), annotated with 4 persons each",
+               "host_cpus_allowed": len(os.sched_getaffinity(0)), "gpu": torch.cuda.get_device_name(0) if torch.cuda.is_available() else None,
+               "repetitions_interleaved": args.pairs, "runs": runs,
+               "summary_frames_per_s_after_engine_build": {k: {"mean": float(np.mean(v)), "min": min(v), "max": max(v), "runs": v}
+                                                           for k, v in summary.items()},
+               "smap_evalmaps_update_device_events": evalmaps_update_us()}
+        print(json.dumps(out["summary_frames_per_s_after_engine_build"], indent=1))
+        print(json.dumps(out["smap_evalmaps_update_device_events"], indent=1))
+        os.makedirs(os.path.dirname(args.out), exist_ok=True)
+        json.dump(out, open(args.out, "w"), indent=1)
+        print("wrote", args.out)
+        return
     out = {"images": args.images, "batch_size": args.batch, "mode": "-t generate_result -d test --eval_3d 1",
            "sources": "the bench's 8 frames as 1664x1024 JPEG q98 4:4:4 (pixel-doubled), annotated with 4 persons each",
            "host_cpus_allowed": len(os.sched_getaffinity(0)), "gpu": torch.cuda.get_device_name(0) if torch.cuda.is_available() else None,
@@ -161,8 +218,9 @@ def main():
     ap.add_argument("--images", type=int, default=1024)
     ap.add_argument("--batch", type=int, default=8)
     ap.add_argument("--out", default=os.path.join(ROOT, "gpurun_out", "cli_e2e.json"))
-    ap.add_argument("--only", choices=["", "jpeg", "huffman", "gt"], default="")
+    ap.add_argument("--only", choices=["", "jpeg", "huffman", "gt", "maps"], default="")
     ap.add_argument("--pairs", type=int, default=3)
+    ap.add_argument("--parent", default="", help="--only maps: a built checkout of the parent commit, run as a third leg")
     args = ap.parse_args()
     from PIL import Image
     from benchkit.workload import make_cfg, people_state_dict
@@ -200,7 +258,7 @@ def main():
     net = SMAP(make_cfg((128, 208))).eval()
     sd = people_state_dict(net.state_dict(), "smooth")
     torch.save({"model": sd}, os.path.join(tmp, "SMAP.pth"))
-    if args.only == "gt":
+    if args.only in ("gt", "maps"):
         return gt_leg(args, tmp, jpg)
     runs = []
     cases = [("encoded jpg/png, GPU pre-processing, 16 decode threads (default)", enc, ["--device_preprocess", "1"], {}),
