@@ -340,14 +340,13 @@ def generate_3d_point_pairs(model, refine_model, data_loader, cfg, logger, devic
     os.makedirs(output_dir, exist_ok=True)
     if pipeline_cls is None:       # batches of <= 8 frames share a backbone launch (smap_amd/pipeline.py::make_pipeline, SMAP_LAUNCH_FRAMES)
         pipeline_cls = lambda m, c, b, h, w, d, rw, **kw: make_pipeline(m, c, b, h, w, d, refine_weights=rw, **kw)
-    evaluator = None
+    evaluators = {}                # pipeline argument -> evaluator, 3D first: the order of the log lines and of result["error"]
     if eval_3d:                    # the reference's `error` dict, accumulated on the device by every batch's post-processing
         from smap_amd.evaluate import Eval3D
-        evaluator = Eval3D(device, refine=refine_model is not None)
-    map_evaluator = None
+        evaluators["evaluator"] = Eval3D(device, refine=refine_model is not None)
     if eval_maps:                  # the `eval` keys of that dict: 2D keypoint error / recall and bone depth error of the maps
         from smap_amd.evaluate import EvalMaps
-        map_evaluator = EvalMaps(device)
+        evaluators["map_evaluator"] = EvalMaps(device)
     if model is not None:
         model.eval()
     refine_w = None
@@ -410,8 +409,7 @@ def generate_3d_point_pairs(model, refine_model, data_loader, cfg, logger, devic
             pipe = pipeline_cls(model, cfg, len(imgs), imgs.shape[-2], imgs.shape[-1], device, refine_w,
                                 do_flip=bool(cfg.DO_FLIP), record_mode=cfg.TEST_MODE, numpy_records=True,
                                 depth=int(os.environ.get("SMAP_PIPELINE_DEPTH", 2)),   # two backbones in flight (+19 %)
-                                **({} if evaluator is None else {"evaluator": evaluator}),
-                                **({} if map_evaluator is None else {"map_evaluator": map_evaluator}))
+                                **evaluators)
         with torch.no_grad():
             drain(pipe.submit(imgs, cams, list(img_path), annotations=annotations))
         clock["submit_s"] += time.perf_counter() - t_sub
@@ -440,24 +438,14 @@ def generate_3d_point_pairs(model, refine_model, data_loader, cfg, logger, devic
         result["dropped_frames"] = list(dropped)
         logger.warning("{} frame(s) have no result (non-finite maps: an activation exceeded the fp16 range, INTEGRATION.md section 5): {}".format(
             len(dropped), dropped[:20]))
-    if evaluator is not None:
-        from smap_amd.evaluate import log_lines, merge, summarize
-        raw = evaluator.raw()                                                   # the run's only read-back of the scores
+    for ev in evaluators.values():
+        raw = ev.raw()                                                          # the run's only read-back of the scores
         if dist.is_initialized() and (dist.get_world_size() > 1 or os.environ.get("SMAP_FORCE_GATHER", "") == "1"):
-            raw = merge(gather_records(raw, device))                            # rank order; evaluate.merge says what that costs
+            raw = ev.merge_raws(gather_records(raw, device))                    # rank order; evaluate.merge / merge_maps say what that costs
         if rank == 0:
-            for line in log_lines(raw):                                         # calculate_and_log's lines (test_util_panoptic.py:388-400)
+            for line in ev.log_lines(raw):                                      # calculate_and_log's lines (test_util_panoptic.py:388-400, :374-378)
                 logger.info(line)
-            result["error"] = summarize(raw)
-    if map_evaluator is not None:
-        from smap_amd.evaluate import MAPS_KEYS, log_lines_maps, merge_maps
-        raw = map_evaluator.raw()
-        if dist.is_initialized() and (dist.get_world_size() > 1 or os.environ.get("SMAP_FORCE_GATHER", "") == "1"):
-            raw = merge_maps(gather_records(raw, device))                       # rank order; evaluate.merge_maps says what that costs
-        if rank == 0:
-            for line in log_lines_maps(raw):                                    # calculate_and_log's `eval` lines (test_util_panoptic.py:374-378)
-                logger.info(line)
-            result.setdefault("error", {}).update({k: raw[k].tolist() for k in MAPS_KEYS})
+            result.setdefault("error", {}).update(ev.result_entry(raw))
     if rank == 0:
         dir_name = os.path.split(os.path.split(os.path.realpath(__file__))[0])[1]
         name = os.path.join(output_dir, "{}_{}_{}_{}.json".format(dir_name, cfg.TEST_MODE, cfg.DATA_MODE,

@@ -210,24 +210,46 @@ def merge_maps(raws):
     return unpack_maps(acc)
 
 
-def gt2d_rows(annotations, gmax=None):
-    """B arrays [G_i,15,>=4] of KEPT annotations -> gt_2d [B,G,15,4] float64 = columns 0:4 (x, y, Z, score: network pixels and the
-    annotated depth), row for row, zero padded."""
+def _padded(annotations, gmax, columns):
+    """B arrays [G_i,15,C] -> ([B,G,15,4] float64 = columns(a), row for row, zero padded; counts [B])."""
     rows = [np.asarray(a, np.float64) for a in annotations]
-    rows = [a if a.size else np.zeros((0, NJ, 4)) for a in rows]
+    rows = [a if a.size else np.zeros((0, NJ, 4)) for a in rows]                 # an empty list arrives as a 1-D array
     G = max(1, max((len(a) for a in rows), default=1)) if gmax is None else int(gmax)
     if G > MAXG or any(len(a) > G for a in rows):
         raise ValueError("at most %d annotations per frame" % MAXG)
     gt = np.zeros((len(rows), G, NJ, 4), np.float64)
     for i, a in enumerate(rows):
         if len(a):
-            gt[i, :len(a)] = a[:, :, 0:4]
-    return gt
+            gt[i, :len(a)] = columns(a)
+    return gt, np.asarray([len(a) for a in rows], np.int32)
 
 
-def check_maps_args(pred_2d, depth_v, bone_mask, counts, gt_2d):
-    """-> (B, G).  ValueError for anything smap_evalmaps_update must not be handed."""
-    named = (("pred_2d", pred_2d), ("depth_v", depth_v), ("bone_mask", bone_mask), ("counts", counts), ("gt_2d", gt_2d))
+def gt2d_rows(annotations, gmax=None):
+    """B arrays [G_i,15,>=4] of KEPT annotations -> gt_2d [B,G,15,4] float64 = columns 0:4 (x, y, Z, score: network pixels and the
+    annotated depth), row for row, zero padded."""
+    return _padded(annotations, gmax, lambda a: a[:, :, 0:4])[0]
+
+
+def gt_rows(annotations, gmax=None):
+    """B annotation arrays [G_i,15,>=7] -> (gt [B,G,15,4] float64 = (X,Y,Z,score) = columns 4:7 and 3, row for row, zero padded;
+    counts [B]).  No row is dropped: row g stays the annotation the registration kernel calls g."""
+    return _padded(annotations, gmax, lambda a: a[:, :, (4, 5, 6, 3)])
+
+
+def _kept(annotations, root_idx):
+    """The pipeline's filter (records.kept_annotations, test.py:76-80) on each frame: the annotations whose root score is > 1."""
+    from .records import kept_annotations
+    rows = [np.asarray(a, np.float64) for a in annotations]
+    return [kept_annotations(a, root_idx) if a.size else a for a in rows]
+
+
+def gt_from_annotations(annotations, root_idx=2):
+    """gt_rows of the annotations whose root score is > 1 -- the pipeline's filter (records.kept_annotations, test.py:76-80)."""
+    return gt_rows(_kept(annotations, root_idx))
+
+
+def _check_tensors(named):
+    """Every (name, t): a contiguous torch.Tensor on a GPU, or ValueError."""
     for name, t in named:
         if not isinstance(t, torch.Tensor):
             raise ValueError(f"{name} must be a torch.Tensor")
@@ -235,69 +257,55 @@ def check_maps_args(pred_2d, depth_v, bone_mask, counts, gt_2d):
             raise ValueError(f"{name} must live on the GPU (there is no host scorer)")
         if not t.is_contiguous():
             raise ValueError(f"{name} must be contiguous")
-    if pred_2d.dim() != 4 or tuple(pred_2d.shape[1:]) != (MAXP, NJ, 4) or pred_2d.dtype != torch.float64:
-        raise ValueError(f"pred_2d must be float64 [B,{MAXP},{NJ},4] (lift_batch(gt_mode=True)), got {pred_2d.dtype} {tuple(pred_2d.shape)}")
+
+
+def _check_one_device(named):
+    if len({t.device for _, t in named}) != 1:
+        names = [name for name, _ in named]
+        raise ValueError("%s and %s must be on one device" % (", ".join(names[:-1]), names[-1]))
+
+
+_PRED_SHAPE, _GT_SHAPE = f"float64 [B,{MAXP},{NJ},4]", f"float64 [B,G,{NJ},4] with 1 <= G <= {MAXG}"
+
+
+def _need(ok, name, t, what):
+    """`ok` -- t has the dtype and the shape -- or ValueError: name must be what, got ..."""
+    if not ok:
+        raise ValueError(f"{name} must be {what}, got {t.dtype} {tuple(t.shape)}")
+
+
+def _need_gt_counts(B, name, gt, counts):
+    _need(gt.dtype == torch.float64 and gt.dim() == 4 and gt.shape[0] == B and 1 <= gt.shape[1] <= MAXG and tuple(gt.shape[2:]) == (NJ, 4),
+          name, gt, _GT_SHAPE)
+    _need(counts.dtype == torch.int32 and tuple(counts.shape) == (B,), "counts", counts, "int32 [B]")
+
+
+def check_maps_args(pred_2d, depth_v, bone_mask, counts, gt_2d):
+    """-> (B, G).  ValueError for anything smap_evalmaps_update must not be handed."""
+    named = (("pred_2d", pred_2d), ("depth_v", depth_v), ("bone_mask", bone_mask), ("counts", counts), ("gt_2d", gt_2d))
+    _check_tensors(named)
+    _need(pred_2d.dtype == torch.float64 and pred_2d.dim() == 4 and tuple(pred_2d.shape[1:]) == (MAXP, NJ, 4), "pred_2d", pred_2d,
+          _PRED_SHAPE + " (lift_batch(gt_mode=True))")
     B = pred_2d.shape[0]
     if B < 1:
         raise ValueError("an empty batch")
-    if tuple(depth_v.shape) != (B, MAXP, NL) or depth_v.dtype != torch.float64:
-        raise ValueError(f"depth_v must be float64 [B,{MAXP},{NL}], got {depth_v.dtype} {tuple(depth_v.shape)}")
-    if tuple(bone_mask.shape) != (B, MAXP) or bone_mask.dtype != torch.int32:
-        raise ValueError(f"bone_mask must be int32 [B,{MAXP}], got {bone_mask.dtype} {tuple(bone_mask.shape)}")
-    if gt_2d.dim() != 4 or gt_2d.shape[0] != B or tuple(gt_2d.shape[2:]) != (NJ, 4) or gt_2d.dtype != torch.float64 or not 1 <= gt_2d.shape[1] <= MAXG:
-        raise ValueError(f"gt_2d must be float64 [B,G,{NJ},4] with 1 <= G <= {MAXG}, got {gt_2d.dtype} {tuple(gt_2d.shape)}")
-    if tuple(counts.shape) != (B,) or counts.dtype != torch.int32:
-        raise ValueError(f"counts must be int32 [B], got {counts.dtype} {tuple(counts.shape)}")
-    if len({t.device for _, t in named}) != 1:
-        raise ValueError("pred_2d, depth_v, bone_mask, counts and gt_2d must be on one device")
+    _need(depth_v.dtype == torch.float64 and tuple(depth_v.shape) == (B, MAXP, NL), "depth_v", depth_v, f"float64 [B,{MAXP},{NL}]")
+    _need(bone_mask.dtype == torch.int32 and tuple(bone_mask.shape) == (B, MAXP), "bone_mask", bone_mask, f"int32 [B,{MAXP}]")
+    _need_gt_counts(B, "gt_2d", gt_2d, counts)
+    _check_one_device(named)
     return B, gt_2d.shape[1]
-
-
-def gt_rows(annotations, gmax=None):
-    """B annotation arrays [G_i,15,>=7] -> (gt [B,G,15,4] float64 = (X,Y,Z,score) = columns 4:7 and 3, row for row, zero padded;
-    counts [B]).  No row is dropped: row g stays the annotation the registration kernel calls g."""
-    rows = [np.asarray(a, np.float64) for a in annotations]
-    rows = [a if a.size else np.zeros((0, NJ, 11)) for a in rows]
-    G = max(1, max((len(a) for a in rows), default=1)) if gmax is None else int(gmax)
-    if G > MAXG or any(len(a) > G for a in rows):
-        raise ValueError("at most %d annotations per frame" % MAXG)
-    gt = np.zeros((len(rows), G, NJ, 4), np.float64)
-    for i, a in enumerate(rows):
-        if len(a):
-            gt[i, :len(a), :, :3] = a[:, :, 4:7]
-            gt[i, :len(a), :, 3] = a[:, :, 3]
-    return gt, np.asarray([len(a) for a in rows], np.int32)
-
-
-def gt_from_annotations(annotations, root_idx=2):
-    """gt_rows of the annotations whose root score is > 1 -- the pipeline's filter (records.kept_annotations, test.py:76-80)."""
-    kept = []
-    for a in annotations:
-        a = np.asarray(a, np.float64)
-        kept.append(a[a[:, root_idx, 3] > 1] if a.size else a)
-    return gt_rows(kept)
 
 
 def check_update_args(pred_3d, counts, gt):
     """-> (B, G).  ValueError for anything smap_eval3d_update must not be handed."""
-    for name, t in (("pred_3d", pred_3d), ("counts", counts), ("gt", gt)):
-        if not isinstance(t, torch.Tensor):
-            raise ValueError(f"{name} must be a torch.Tensor")
-        if not t.is_cuda:
-            raise ValueError(f"{name} must live on the GPU (there is no host scorer)")
-        if not t.is_contiguous():
-            raise ValueError(f"{name} must be contiguous")
-    if pred_3d.dim() != 4 or tuple(pred_3d.shape[1:]) != (MAXP, NJ, 4) or pred_3d.dtype != torch.float64:
-        raise ValueError(f"pred_3d must be float64 [B,{MAXP},{NJ},4], got {pred_3d.dtype} {tuple(pred_3d.shape)}")
+    named = (("pred_3d", pred_3d), ("counts", counts), ("gt", gt))
+    _check_tensors(named)
+    _need(pred_3d.dtype == torch.float64 and pred_3d.dim() == 4 and tuple(pred_3d.shape[1:]) == (MAXP, NJ, 4), "pred_3d", pred_3d, _PRED_SHAPE)
     B = pred_3d.shape[0]
-    if gt.dim() != 4 or gt.shape[0] != B or tuple(gt.shape[2:]) != (NJ, 4) or gt.dtype != torch.float64 or not 1 <= gt.shape[1] <= MAXG:
-        raise ValueError(f"gt must be float64 [B,G,{NJ},4] with 1 <= G <= {MAXG}, got {gt.dtype} {tuple(gt.shape)}")
-    if tuple(counts.shape) != (B,) or counts.dtype != torch.int32:
-        raise ValueError(f"counts must be int32 [B], got {counts.dtype} {tuple(counts.shape)}")
+    _need_gt_counts(B, "gt", gt, counts)
     if B < 1:
         raise ValueError("an empty batch")
-    if not (pred_3d.device == counts.device == gt.device):
-        raise ValueError("pred_3d, counts and gt must be on one device")
+    _check_one_device(named)
     return B, gt.shape[1]
 
 
@@ -309,38 +317,70 @@ def _stream(device):
     return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
 
 
-class Eval3D:
-    """The reference's `error` dict of a generate_result run as 80 float64 on `device`.
+class _DeviceAccumulator:
+    """WIDTH float64 on `device`, updated in order by the library's INIT and UPDATE entry points.
 
     update() runs on the caller's current stream and returns at once; calls are ordered after one another on the device
     whatever streams they come from (an event chain, no host wait), because the sums are ordered.  raw() / summary() read the
-    accumulators back -- the only host synchronisation."""
+    accumulators back -- the only host synchronisation.  A metric set supplies WIDTH, INIT, UPDATE, _check (the inputs of update()
+    -> (B, G) or ValueError), _unpack (the accumulators on the host -> the raw() dict), _summarize, and merge_raws / log_lines /
+    result_entry, with which test.py treats every evaluator alike."""
 
-    def __init__(self, device, refine=False):
+    def __init__(self, device):
         self.device = torch.device(device)
         if self.device.type != "cuda":
-            raise ValueError("Eval3D scores on the GPU: device must be a cuda device (there is no host scorer)")
-        self.refine = bool(refine)
+            raise ValueError(f"{type(self).__name__} scores on the GPU: device must be a cuda device (there is no host scorer)")
         self._lib = _L.load()
-        self.acc = torch.empty((ACC_DOUBLES,), dtype=torch.float64, device=self.device)
+        self.acc = torch.empty((self.WIDTH,), dtype=torch.float64, device=self.device)
         self._ev = torch.cuda.Event()
+        self._launch = getattr(self._lib, self.UPDATE)
         with torch.cuda.device(self.device):
-            _L.check(self._lib.smap_eval3d_acc_init(_p(self.acc), _stream(self.device)), "smap_eval3d_acc_init")
+            _L.check(getattr(self._lib, self.INIT)(_p(self.acc), _stream(self.device)), self.INIT)
             self._ev.record()
+
+    def _update(self, *tensors):
+        """The inputs in the order UPDATE takes them."""
+        B, G = self._check(*tensors)
+        if tensors[0].device != self.device:
+            raise ValueError(f"this evaluator lives on {self.device}, the tensors on {tensors[0].device}")
+        with torch.cuda.device(self.device):
+            cur = torch.cuda.current_stream(self.device)
+            cur.wait_event(self._ev)                            # after the previous update (or the initialisation), on whatever stream it ran
+            terms = torch.empty((B, G, self.WIDTH), dtype=torch.float64, device=self.device)
+            _L.check(self._launch(*map(_p, tensors), B, G, _p(terms), _p(self.acc), _stream(self.device)), self.UPDATE)
+            self._ev.record()
+
+    def raw(self):
+        """The reference's error dict BEFORE calculate_and_log's divisions, with its keys and types (unpack / unpack_maps)."""
+        with torch.cuda.device(self.device):
+            torch.cuda.current_stream(self.device).wait_event(self._ev)
+            host = self.acc.cpu().numpy()
+        return self._unpack(host)
+
+    def summary(self):
+        """What calculate_and_log makes of raw() (summarize / summarize_maps)."""
+        return self._summarize(self.raw())
+
+
+class Eval3D(_DeviceAccumulator):
+    """The reference's `error` dict of a generate_result run as 80 float64 on `device`: its keys carry `_after_refine` when refine is
+    set.  summary() is what the reference's calculate_and_log leaves in result['error'] in generate_result mode."""
+    WIDTH, INIT, UPDATE = ACC_DOUBLES, "smap_eval3d_acc_init", "smap_eval3d_update"
+    _check, _summarize = staticmethod(check_update_args), staticmethod(summarize)
+    # the module's functions under the names test.py calls on every evaluator (the right-hand `log_lines` is the module's)
+    merge_raws, log_lines, result_entry = staticmethod(merge), staticmethod(log_lines), staticmethod(summarize)
+
+    def __init__(self, device, refine=False):
+        self.refine = bool(refine)
+        super().__init__(device)
+
+    def _unpack(self, host):
+        return unpack(host, self.refine)
 
     def update(self, pred_3d, counts, gt):
         """pred_3d [B,127,15,4] f64 (lift_batch(gt_mode=True) / refine_batch), counts [B] int32 (persons = kept annotations of each
         frame, register_gt_batch's matched_counts), gt [B,G,15,4] f64 (X,Y,Z,score): device tensors.  Rows >= counts[b] are not read."""
-        B, G = check_update_args(pred_3d, counts, gt)
-        if pred_3d.device != self.device:
-            raise ValueError(f"this evaluator lives on {self.device}, the tensors on {pred_3d.device}")
-        with torch.cuda.device(self.device):
-            cur = torch.cuda.current_stream(self.device)
-            cur.wait_event(self._ev)                            # after the previous update (or the initialisation), on whatever stream it ran
-            terms = torch.empty((B, G, TERM_DOUBLES), dtype=torch.float64, device=self.device)
-            _L.check(self._lib.smap_eval3d_update(_p(pred_3d), _p(counts), _p(gt), B, G, _p(terms), _p(self.acc), _stream(self.device)),
-                     "smap_eval3d_update")
-            self._ev.record()
+        self._update(pred_3d, counts, gt)
 
     def update_from_annotations(self, pred_3d, counts, annotations, root_idx=2):
         """update() with the ground truth built from B annotation arrays [G_i,15,11] (rows with root score > 1 are kept, as the
@@ -348,135 +388,71 @@ class Eval3D:
         gt, _ = gt_from_annotations(annotations, root_idx)
         self.update(pred_3d, counts, torch.from_numpy(gt).to(self.device, non_blocking=True))
 
-    def raw(self):
-        """The reference's error dict BEFORE calculate_and_log's divisions: its keys (with `_after_refine` when refine is set), ndarray
-        float64 [15] / int / float values."""
-        with torch.cuda.device(self.device):
-            torch.cuda.current_stream(self.device).wait_event(self._ev)
-            host = self.acc.cpu().numpy()
-        return unpack(host, self.refine)
 
-    def summary(self):
-        """What the reference's calculate_and_log leaves in result['error'] in generate_result mode."""
-        return summarize(self.raw())
-
-
-class EvalMaps:
+class EvalMaps(_DeviceAccumulator):
     """The six `eval` accumulators of the reference's error dict (count_gt, count_pred, distance_e, distance_d, reverse_count,
-    count_pred_bone) as 87 float64 on `device`.  Same contract as Eval3D: update() runs on the caller's current stream and returns at
-    once, calls are ordered after one another on the device by an event chain, raw() / summary() are the only host synchronisation."""
+    count_pred_bone) as 87 float64 on `device`.  summary(): error_point, recall, depth_e, depth_reverse_count, avg_error, avg_recall."""
+    WIDTH, INIT, UPDATE = MAPS_ACC_DOUBLES, "smap_evalmaps_acc_init", "smap_evalmaps_update"
+    _check, _unpack, _summarize = staticmethod(check_maps_args), staticmethod(unpack_maps), staticmethod(summarize_maps)
+    merge_raws, log_lines = staticmethod(merge_maps), staticmethod(log_lines_maps)
 
-    def __init__(self, device):
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise ValueError("EvalMaps scores on the GPU: device must be a cuda device (there is no host scorer)")
-        self._lib = _L.load()
-        self.acc = torch.empty((MAPS_ACC_DOUBLES,), dtype=torch.float64, device=self.device)
-        self._ev = torch.cuda.Event()
-        with torch.cuda.device(self.device):
-            _L.check(self._lib.smap_evalmaps_acc_init(_p(self.acc), _stream(self.device)), "smap_evalmaps_acc_init")
-            self._ev.record()
+    @staticmethod
+    def result_entry(raw):
+        return {k: raw[k].tolist() for k in MAPS_KEYS}
 
     def update(self, pred_2d, depth_v, bone_mask, counts, gt_2d):
         """pred_2d [B,127,15,4] f64, depth_v [B,127,14] f64, bone_mask [B,127] int32: lift_batch(gt_mode=True, bones=True) on the rows
         register_gt_batch matched; counts [B] int32 = its matched_counts; gt_2d [B,G,15,4] f64 = columns 0:4 of the kept annotations
         (gt2d_rows).  Device tensors; rows >= counts[b] are not read."""
-        B, G = check_maps_args(pred_2d, depth_v, bone_mask, counts, gt_2d)
-        if pred_2d.device != self.device:
-            raise ValueError(f"this evaluator lives on {self.device}, the tensors on {pred_2d.device}")
-        with torch.cuda.device(self.device):
-            cur = torch.cuda.current_stream(self.device)
-            cur.wait_event(self._ev)                            # after the previous update (or the initialisation), on whatever stream it ran
-            terms = torch.empty((B, G, MAPS_TERM_DOUBLES), dtype=torch.float64, device=self.device)
-            _L.check(self._lib.smap_evalmaps_update(_p(pred_2d), _p(depth_v), _p(bone_mask), _p(counts), _p(gt_2d), B, G, _p(terms),
-                                                    _p(self.acc), _stream(self.device)), "smap_evalmaps_update")
-            self._ev.record()
+        self._update(pred_2d, depth_v, bone_mask, counts, gt_2d)
 
     def update_from_annotations(self, pred_2d, depth_v, bone_mask, counts, annotations, root_idx=2):
         """update() with gt_2d built from B annotation arrays [G_i,15,>=4] (rows with root score > 1 are kept, as the pipeline does)
         and uploaded on the current stream."""
-        kept = []
-        for a in annotations:
-            a = np.asarray(a, np.float64)
-            kept.append(a[a[:, root_idx, 3] > 1] if a.size else a)
-        self.update(pred_2d, depth_v, bone_mask, counts, torch.from_numpy(gt2d_rows(kept)).to(self.device, non_blocking=True))
-
-    def raw(self):
-        """The reference's six `eval` keys BEFORE calculate_and_log's divisions, with its dtypes (unpack_maps)."""
-        with torch.cuda.device(self.device):
-            torch.cuda.current_stream(self.device).wait_event(self._ev)
-            host = self.acc.cpu().numpy()
-        return unpack_maps(host)
-
-    def summary(self):
-        """summarize_maps(raw()): error_point, recall, depth_e, depth_reverse_count, avg_error, avg_recall."""
-        return summarize_maps(self.raw())
+        gt_2d = gt2d_rows(_kept(annotations, root_idx))
+        self.update(pred_2d, depth_v, bone_mask, counts, torch.from_numpy(gt_2d).to(self.device, non_blocking=True))
 
 
 BONES_REFUSAL = ("the bone depth error cannot be scored from a result file: the per-limb depth `depth_v` is not in it (it exists only "
                  "inside the lifting kernel); score it while the run runs, `test.py -t generate_result --eval_maps 1`")
 
 
-def _parse_records_maps(records, path):
-    """Frame records -> [(pred_2d [P,15,4], gt_2d [P,15,4])]; ValueError for anything whose 2D part cannot be scored."""
+def _frame_preds(records, path, key):
+    """What both parsers refuse first -> (n, record n, its `key` as [P,15,4]) of every record."""
     if not records:
         raise ValueError(f"{path}: no records to score")
-    frames = []
     for n, r in enumerate(records):
-        if not isinstance(r, dict) or "pred_2d" not in r:
-            raise ValueError(f"{path}: record {n} has no pred_2d: not a result file of test.py")
-        pred = np.asarray(r["pred_2d"], np.float64)
+        if not isinstance(r, dict) or key not in r:
+            raise ValueError(f"{path}: record {n} has no {key}: not a result file of test.py")
+        pred = np.asarray(r[key], np.float64)
         if pred.ndim != 3 or pred.shape[1:] != (NJ, 4):
             raise ValueError(f"{path}: record {n} holds one person, not a frame: a generate_train file cannot be scored")
+        yield n, r, pred
+
+
+def _refuse_crowd(path, n, pred):
+    if len(pred) > MAXG:
+        raise ValueError(f"{path}: record {n} has {len(pred)} persons, at most {MAXG} are scored per frame")
+
+
+def _parse_records_maps(records, path):
+    """Frame records -> [(pred_2d [P,15,4], gt_2d [P,15,4])]; ValueError for anything whose 2D part cannot be scored."""
+    frames = []
+    for n, r, pred in _frame_preds(records, path, "pred_2d"):
         if "gt_2d" not in r or len(r["gt_2d"]) == 0:
             raise ValueError(f"{path}: record {n} has no gt_2d (a run_inference file?): score a `-t generate_result` run")
         g2 = np.asarray(r["gt_2d"], np.float64)
         if g2.ndim != 3 or g2.shape[:2] != (len(pred), NJ) or g2.shape[2] < 4:
             raise ValueError(f"{path}: record {n}: gt_2d does not match the {len(pred)} persons of pred_2d")
-        if len(pred) > MAXG:
-            raise ValueError(f"{path}: record {n} has {len(pred)} persons, at most {MAXG} are scored per frame")
+        _refuse_crowd(path, n, pred)
         frames.append((pred, g2[:, :, 0:4]))
     return frames
 
 
-def score_records_maps(records, device, path="<records>", frames_per_call=256):
-    """The 2D part (count_gt, count_pred, distance_e) of `3d_pairs` frame records (pred_2d, gt_2d per frame) -> EvalMaps, frames in
-    order.  The bone part stays zero: BONES_REFUSAL."""
-    frames = _parse_records_maps(records, path)                # refusals first: they need no GPU
-    ev = EvalMaps(device)
-    for s in range(0, len(frames), frames_per_call):
-        part = frames[s:s + frames_per_call]
-        pred = np.zeros((len(part), MAXP, NJ, 4), np.float64)
-        for i, (p, _) in enumerate(part):
-            pred[i, :len(p)] = p
-        up = lambda a: torch.from_numpy(a).to(ev.device)
-        ev.update(up(pred), torch.zeros((len(part), MAXP, NL), dtype=torch.float64, device=ev.device),
-                  torch.zeros((len(part), MAXP), dtype=torch.int32, device=ev.device),
-                  up(np.asarray([len(p) for p, _ in part], np.int32)), up(gt2d_rows([g for _, g in part])))
-    return ev
-
-
-def score_file_maps(path, device="cuda:0", frames_per_call=256):
-    """Score the 2D part of a generate_result file on the GPU -> the three 2D keys of `EvalMaps.raw()`."""
-    with open(path) as f:
-        doc = json.load(f)
-    if not isinstance(doc, dict) or "3d_pairs" not in doc:
-        raise ValueError(f"{path}: no `3d_pairs` list: not a result file of test.py")
-    raw = score_records_maps(doc["3d_pairs"], device, path=path, frames_per_call=frames_per_call).raw()
-    return {k: raw[k] for k in MAPS_2D_KEYS}
-
-
 def _parse_records(records, path):
     """Frame records -> [(pred [P,15,4], gt xyz [P,15,3], gt score [P,15])]; ValueError for anything that cannot be scored."""
-    if not records:
-        raise ValueError(f"{path}: no records to score")
     frames = []
-    for n, r in enumerate(records):
-        if not isinstance(r, dict) or "pred_3d" not in r:
-            raise ValueError(f"{path}: record {n} has no pred_3d: not a result file of test.py")
-        pred = np.asarray(r["pred_3d"], np.float64)
-        if pred.ndim != 3 or pred.shape[1:] != (NJ, 4):
-            raise ValueError(f"{path}: record {n} holds one person, not a frame: a generate_train file cannot be scored")
+    for n, r, pred in _frame_preds(records, path, "pred_3d"):
         if "gt_3d" not in r or "gt_2d" not in r:
             raise ValueError(f"{path}: record {n} has no gt_3d / gt_2d: not a generate_result file")
         if len(r["gt_3d"]) == 0 or len(r["gt_2d"]) == 0:
@@ -484,24 +460,42 @@ def _parse_records(records, path):
         g3, g2 = np.asarray(r["gt_3d"], np.float64), np.asarray(r["gt_2d"], np.float64)
         if g3.ndim != 3 or g2.ndim != 3 or g3.shape[:2] != (len(pred), NJ) or g2.shape[:2] != (len(pred), NJ) or g3.shape[2] < 3 or g2.shape[2] < 4:
             raise ValueError(f"{path}: record {n}: gt_3d / gt_2d do not match the {len(pred)} persons of pred_3d")
-        if len(pred) > MAXG:
-            raise ValueError(f"{path}: record {n} has {len(pred)} persons, at most {MAXG} are scored per frame")
+        _refuse_crowd(path, n, pred)
         frames.append((pred, g3[:, :, 0:3], g2[:, :, 3]))
     return frames
 
 
-def _batches(frames, frames_per_call):
-    """-> (pred [B,127,15,4], counts [B], gt [B,G,15,4]) of at most frames_per_call frames each, in order."""
+def _pred_batches(frames, frames_per_call):
+    """Parsed frames (the prediction first) -> (the frames of a call, pred [B,127,15,4], counts [B]) of at most frames_per_call frames
+    each, in order."""
     for s in range(0, len(frames), frames_per_call):
         part = frames[s:s + frames_per_call]
-        G = max(len(p) for p, _, _ in part)
         pred = np.zeros((len(part), MAXP, NJ, 4), np.float64)
-        gt = np.zeros((len(part), G, NJ, 4), np.float64)
+        for i, fr in enumerate(part):
+            pred[i, :len(fr[0])] = fr[0]
+        yield part, pred, np.asarray([len(fr[0]) for fr in part], np.int32)
+
+
+def _batches(frames, frames_per_call):
+    """-> (pred [B,127,15,4], counts [B], gt [B,G,15,4]) of at most frames_per_call frames each, in order."""
+    for part, pred, counts in _pred_batches(frames, frames_per_call):
+        gt = np.zeros((len(part), counts.max(), NJ, 4), np.float64)
         for i, (p, xyz, score) in enumerate(part):
-            pred[i, :len(p)] = p
             gt[i, :len(p), :, :3] = xyz
             gt[i, :len(p), :, 3] = score
-        yield pred, np.asarray([len(p) for p, _, _ in part], np.int32), gt
+        yield pred, counts, gt
+
+
+def score_records_maps(records, device, path="<records>", frames_per_call=256):
+    """The 2D part (count_gt, count_pred, distance_e) of `3d_pairs` frame records (pred_2d, gt_2d per frame) -> EvalMaps, frames in
+    order.  The bone part stays zero: BONES_REFUSAL."""
+    frames = _parse_records_maps(records, path)                # refusals first: they need no GPU
+    ev = EvalMaps(device)
+    up = lambda a: torch.from_numpy(a).to(ev.device)
+    for part, pred, counts in _pred_batches(frames, frames_per_call):
+        ev.update(up(pred), torch.zeros((len(part), MAXP, NL), dtype=torch.float64, device=ev.device),
+                  torch.zeros((len(part), MAXP), dtype=torch.int32, device=ev.device), up(counts), up(gt2d_rows([g for _, g in part])))
+    return ev
 
 
 def score_records(records, device, refine=False, path="<records>", frames_per_call=256):
@@ -513,14 +507,25 @@ def score_records(records, device, refine=False, path="<records>", frames_per_ca
     return ev
 
 
-def score_file(path, device="cuda:0", refine=False, frames_per_call=256):
-    """Score a generate_result file on the GPU -> the `raw()` dict.  Reads pred_3d, gt_3d[:, :, 0:3] and gt_2d[:, :, 3] per record.
-    A file without ground truth (run_inference) or with per-person records (generate_train) is refused with ValueError."""
+def _load_pairs(path):
+    """The `3d_pairs` list of a result file, or ValueError."""
     with open(path) as f:
         doc = json.load(f)
     if not isinstance(doc, dict) or "3d_pairs" not in doc:
         raise ValueError(f"{path}: no `3d_pairs` list: not a result file of test.py")
-    return score_records(doc["3d_pairs"], device, refine, path=path, frames_per_call=frames_per_call).raw()
+    return doc["3d_pairs"]
+
+
+def score_file_maps(path, device="cuda:0", frames_per_call=256):
+    """Score the 2D part of a generate_result file on the GPU -> the three 2D keys of `EvalMaps.raw()`."""
+    raw = score_records_maps(_load_pairs(path), device, path=path, frames_per_call=frames_per_call).raw()
+    return {k: raw[k] for k in MAPS_2D_KEYS}
+
+
+def score_file(path, device="cuda:0", refine=False, frames_per_call=256):
+    """Score a generate_result file on the GPU -> the `raw()` dict.  Reads pred_3d, gt_3d[:, :, 0:3] and gt_2d[:, :, 3] per record.
+    A file without ground truth (run_inference) or with per-person records (generate_train) is refused with ValueError."""
+    return score_records(_load_pairs(path), device, refine, path=path, frames_per_call=frames_per_call).raw()
 
 
 def main(argv=None):

@@ -20,11 +20,13 @@ backbone launch of up to 16 frames (the 32x52 and 16x26 levels of the network ha
 to fill 256 CUs), same protocol, same records, same order.
 """
 import os
+from typing import NamedTuple, Optional
 
 import numpy as np
 import torch
 
 from . import dapalib
+from .evaluate import gt2d_rows, gt_rows
 from .records import frame_record, train_records
 
 NJ, MAXP = 15, 127
@@ -71,6 +73,15 @@ class _Slot:
         self.ev_post = torch.cuda.Event()       # the host waits on this one: PosePipeline._wait
         self.meta = None
         self.busy = False
+
+
+class GroundTruth(NamedTuple):
+    """A batch's annotations on the device: roots [B,G,2] f32 and counts [B] int32 for the registration; xyz [B,G,15,4] f64 when an
+    Eval3D scores the batch, xy [B,G,15,4] f64 when an EvalMaps does (evaluate.gt_rows / gt2d_rows)."""
+    roots: torch.Tensor
+    counts: torch.Tensor
+    xyz: Optional[torch.Tensor] = None
+    xy: Optional[torch.Tensor] = None
 
 
 class PosePipeline:
@@ -146,10 +157,9 @@ class PosePipeline:
     def _post(self, slot, idx, hms, det_d, root_d, cams, scale, gt=None, row0=0):
         """Association + lifting of one set of maps on the post stream; results -> pinned memory (rows row0.. of result set idx:
         a coalesced launch hands its callers' extra maps over batch by batch, where they lie).
-        gt = (gt_roots [B,G,2], gt_counts [B][, gt_xyzs [B,G,15,4] f64 or None[, gt_2d [B,G,15,4] f64]]) on the device: register the
-        persons to the annotations first (test_util.py:18-42) and lift in the f64 flavour of the ground-truth modes; with the third
-        tensor the evaluator scores what is recorded as pred_3d against it, with the fourth the map evaluator scores the registered
-        rows and their limb depths (smap_amd/evaluate.py)."""
+        gt: a GroundTruth on the device: register the persons to the annotations (roots, counts) first (test_util.py:18-42) and lift
+        in the f64 flavour of the ground-truth modes; with xyz the evaluator scores what is recorded as pred_3d against it, with xy
+        the map evaluator scores the registered rows and their limb depths (smap_amd/evaluate.py)."""
         if scale:
             dapalib.scale_hms_(hms)                                             # test.py:111-112
         n = hms.shape[0]
@@ -166,16 +176,16 @@ class PosePipeline:
             return
         bodys, counts = dapalib.connect_batch(hms, root_d, self.cfg.DATASET.ROOT_IDX, True)
         if gt is not None:
-            bodys, counts = dapalib.register_gt_batch(bodys, counts, gt[0], gt[1])
-        if gt is not None and len(gt) > 3:
+            bodys, counts = dapalib.register_gt_batch(bodys, counts, gt.roots, gt.counts)
+        if gt is not None and gt.xy is not None:
             p2, p3, rz, depth_v, bone_mask = dapalib.lift_batch(bodys, counts, det_d, root_d, cams, gt_mode=True, bones=True)
-            self.map_evaluator.update(p2, depth_v, bone_mask, counts, gt[3])
+            self.map_evaluator.update(p2, depth_v, bone_mask, counts, gt.xy)
         else:
             p2, p3, rz = dapalib.lift_batch(bodys, counts, det_d, root_d, cams, gt_mode=gt is not None)
         if self.refine is not None:
             p3 = dapalib.refine_batch(p2, p3, counts, *self.refine)
-        if gt is not None and len(gt) > 2 and gt[2] is not None:
-            self.evaluator.update(p3, counts, gt[2])
+        if gt is not None and gt.xyz is not None:
+            self.evaluator.update(p3, counts, gt.xyz)
         h = slot.host[idx]
         if gt is not None:
             if slot.p2_f64 is None:
@@ -210,14 +220,10 @@ class PosePipeline:
             if self.evaluator is not None or self.map_evaluator is not None:
                 # a padding frame of a ragged last batch (tag None) repeats a real frame and has no record: no annotations, so no score either
                 n_ann = [0 if t is None else n for t, n in zip(tags, n_ann)]
-            gt = (torch.from_numpy(roots).to(self.device, non_blocking=True),
-                  torch.tensor(n_ann, dtype=torch.int32).to(self.device, non_blocking=True))
-            if self.evaluator is not None:
-                from .evaluate import gt_rows
-                gt += (torch.from_numpy(gt_rows(annotations, gmax)[0]).to(self.device, non_blocking=True),)
-            if self.map_evaluator is not None:
-                from .evaluate import gt2d_rows
-                gt = gt[:3] + (None,) * (3 - len(gt)) + (torch.from_numpy(gt2d_rows(annotations, gmax)).to(self.device, non_blocking=True),)
+            up = lambda a: torch.from_numpy(a).to(self.device, non_blocking=True)
+            gt = GroundTruth(up(roots), torch.tensor(n_ann, dtype=torch.int32).to(self.device, non_blocking=True),
+                             None if self.evaluator is None else up(gt_rows(annotations, gmax)[0]),
+                             None if self.map_evaluator is None else up(gt2d_rows(annotations, gmax)))
         slot = self.slots[self.k % self.nslots]
         eng, s_bb = self.engines[self.k % self.depth], self.s_bbs[self.k % self.depth]
         ready = self._collect(slot) if slot.busy else None       # the batch submitted nslots calls ago ...
@@ -233,9 +239,8 @@ class PosePipeline:
             t.record_stream(s_bb)
         cams_d.record_stream(self.s_post)
         if gt is not None:
-            for t in gt:
-                if t is not None:
-                    t.record_stream(self.s_post)
+            for t in filter(lambda t: t is not None, gt):
+                t.record_stream(self.s_post)
         as_parts = lambda t: list(t) if isinstance(t, (list, tuple)) else [t]
         for _, e_hms, e_rd, e_dd in extra:               # the caller may drop its references
             for t in (e_hms, e_rd, e_dd):

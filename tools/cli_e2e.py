@@ -23,6 +23,8 @@ on top, `--pairs` times each, interleaved, after one uncounted run; and the pre-
 --device_decode 1` without and with `--eval_maps 1`, `--pairs` times each, interleaved, after one uncounted run -- and, with `--parent DIR` (a
 built checkout of the parent commit), that checkout's run of the command without the flag as a third interleaved leg; then the device-event
 time of smap_evalmaps_update alone, back to back, at a step's shapes.
+--only scorers measures that time for both scorers, smap_eval3d_update and smap_evalmaps_update, and with `--parent DIR` on that
+checkout's library as well: one process per tree and repeat, alternating, `--pairs` repeats each.
 """
 import argparse
 import json
@@ -95,9 +97,10 @@ def preprocess_launch_ab(batches=200, frames=8, h=1080, w=1920):
     return res
 
 
-def evalmaps_update_us(shapes=((8, 4), (8, 20), (16, 20), (8, 64), (17, 64)), iters=200):
-    """Device-event time of smap_evalmaps_update alone, back to back, per call, for (B, G): every annotation matched to a full person."""
-    from smap_amd.evaluate import EvalMaps
+def update_us(evaluator="maps", shapes=((8, 4), (8, 20), (16, 20), (8, 64), (17, 64)), iters=200):
+    """Device-event time of one scorer's update alone ("maps": smap_evalmaps_update, "3d": smap_eval3d_update), back to back, per
+    call, for (B, G): every annotation matched to a full person."""
+    from smap_amd.evaluate import Eval3D, EvalMaps
     dev = torch.device("cuda:0")
     out = {}
     for B, G in shapes:
@@ -107,9 +110,12 @@ def evalmaps_update_us(shapes=((8, 4), (8, 20), (16, 20), (8, 64), (17, 64)), it
         gt = p2[:, :G].clone() + torch.randn((B, G, 15, 4), generator=g, dtype=torch.float64) * 3
         gt[..., 3] = 2
         dv = torch.randn((B, 127, 14), generator=g, dtype=torch.float64)
-        a = [p2.to(dev), dv.to(dev), torch.full((B, 127), (1 << 14) - 1, dtype=torch.int32, device=dev),
-             torch.full((B,), G, dtype=torch.int32, device=dev), gt.contiguous().to(dev)]
-        ev = EvalMaps(dev)
+        counts = torch.full((B,), G, dtype=torch.int32, device=dev)
+        if evaluator == "maps":
+            ev, a = EvalMaps(dev), [p2.to(dev), dv.to(dev), torch.full((B, 127), (1 << 14) - 1, dtype=torch.int32, device=dev), counts,
+                                    gt.contiguous().to(dev)]
+        else:
+            ev, a = Eval3D(dev), [p2.to(dev), counts, gt.contiguous().to(dev)]
         for _ in range(10):
             ev.update(*a)
         t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -121,6 +127,39 @@ def evalmaps_update_us(shapes=((8, 4), (8, 20), (16, 20), (8, 64), (17, 64)), it
         torch.cuda.synchronize()
         out[f"B={B},G={G}"] = {"us_per_update": t0.elapsed_time(t1) * 1e3 / iters, "launches": 2 if B * G > 1024 else 1}
     return out
+
+
+def scorers_leg(args):
+    """--only scorers: update_us of both scorers on this tree and, with --parent, on that checkout's package: one process per tree and
+    repeat, alternating, `--pairs` repeats each.  A shape passes when this tree's median is at most the parent's median plus the
+    parent's own spread (max - min) over its repeats."""
+    trees = ([("parent", os.path.abspath(args.parent))] if args.parent else []) + [("this", ROOT)]
+    runs = {name: [] for name, _ in trees}
+    for _ in range(args.pairs):
+        for name, tree in trees:
+            r = subprocess.run([sys.executable, os.path.abspath(__file__), "--scorers_child", tree], capture_output=True, text=True, timeout=600)
+            if r.returncode:
+                sys.exit(f"{name}: update_us failed ({r.returncode}): {r.stderr[-1500:]}")
+            runs[name].append(json.loads(r.stdout.strip().splitlines()[-1]))
+    out = {"what": "Eval3D.update / EvalMaps.update alone, back to back, by device events: tools/cli_e2e.py --only scorers --pairs N --parent DIR",
+           "gpu": torch.cuda.get_device_name(0) if torch.cuda.is_available() else None, "repeats_alternating": args.pairs,
+           "rule": "this tree's median <= the parent's median + (the parent's max - min)", "shapes": {}}
+    for scorer in ("3d", "maps"):
+        for shape in runs["this"][0][scorer]:
+            us = {name: [rep[scorer][shape]["us_per_update"] for rep in reps] for name, reps in runs.items()}
+            rec = {f"{name}_us": v for name, v in us.items()}
+            rec.update({f"{name}_median_us": float(np.median(v)) for name, v in us.items()})
+            if args.parent:
+                rec["parent_spread_us"] = max(us["parent"]) - min(us["parent"])
+                rec["passes"] = bool(rec["this_median_us"] <= rec["parent_median_us"] + rec["parent_spread_us"])
+            out["shapes"][f"{scorer} {shape}"] = rec
+    if args.parent:
+        out["shapes_passing"], out["shapes_measured"] = sum(v["passes"] for v in out["shapes"].values()), len(out["shapes"])
+    print(json.dumps(out["shapes"], indent=1))
+    os.makedirs(os.path.dirname(args.out), exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(out, f, indent=1)
+    print("wrote", args.out)
 
 
 def gt_leg(args, tmp, jpg):
@@ -192,7 +231,7 @@ def gt_leg(args, tmp, jpg):
                "repetitions_interleaved": args.pairs, "runs": runs,
                "summary_frames_per_s_after_engine_build": {k: {"mean": float(np.mean(v)), "min": min(v), "max": max(v), "runs": v}
                                                            for k, v in summary.items()},
-               "smap_evalmaps_update_device_events": evalmaps_update_us()}
+               "smap_evalmaps_update_device_events": update_us("maps")}
         print(json.dumps(out["summary_frames_per_s_after_engine_build"], indent=1))
         print(json.dumps(out["smap_evalmaps_update_device_events"], indent=1))
         os.makedirs(os.path.dirname(args.out), exist_ok=True)
@@ -218,10 +257,19 @@ def main():
     ap.add_argument("--images", type=int, default=1024)
     ap.add_argument("--batch", type=int, default=8)
     ap.add_argument("--out", default=os.path.join(ROOT, "gpurun_out", "cli_e2e.json"))
-    ap.add_argument("--only", choices=["", "jpeg", "huffman", "gt", "maps"], default="")
+    ap.add_argument("--only", choices=["", "jpeg", "huffman", "gt", "maps", "scorers"], default="")
     ap.add_argument("--pairs", type=int, default=3)
-    ap.add_argument("--parent", default="", help="--only maps: a built checkout of the parent commit, run as a third leg")
+    ap.add_argument("--parent", default="", help="--only maps / scorers: a built checkout of the parent commit, run as a further leg")
+    ap.add_argument("--scorers_child", default="", help=argparse.SUPPRESS)       # one repeat of --only scorers on the package of that tree
     args = ap.parse_args()
+    if args.scorers_child:
+        sys.path.insert(0, args.scorers_child)
+        import smap_amd
+        assert os.path.realpath(os.path.dirname(os.path.dirname(smap_amd.__file__))) == os.path.realpath(args.scorers_child)
+        print(json.dumps({"3d": update_us("3d"), "maps": update_us("maps")}))
+        return
+    if args.only == "scorers":
+        return scorers_leg(args)
     from PIL import Image
     from benchkit.workload import make_cfg, people_state_dict
     from smap_amd.model.smap import SMAP
