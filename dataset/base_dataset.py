@@ -2,7 +2,8 @@
 
 Only the inference-side stages exist here -- `test` (the validation frames of cfg.TEST.JSON_PATH, images under
 cfg.TEST.ROOT_PATH) and `generation` (the training frames of the 3D datasets, the input of RefineNet training-pair
-export); stage `train` builds heat-map / PAF labels for training, which is outside this repository.
+export); stage `train` is the training loader (augmentation, label assembly), which is outside this repository -- the label maps
+themselves are rendered by smap_amd/labels.py (dataset/representation.py).
 
 A sample is what the reference returns for these stages (base_dataset.py:157-166):
     (normalised BGR CHW image, annotations [MAX_PEOPLE,15,C] fp32 zero padded, image path, scale dict)

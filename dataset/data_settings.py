@@ -46,6 +46,8 @@ def _build():
         d[name + "_ROOT_PATH"] = os.path.join(d.PREFIX, "data", folder)
         d[name + "_JSON_PATH"] = os.path.join(d[name + "_ROOT_PATH"], "annotations", ann + ".json")
     d.USED_3D_DATASETS = ["MUCO"]
+    # label rendering (data_settings.py:64): the blur size of each of the five label scales, coarse to fine; read by smap_amd/labels.py
+    d.TRAIN = AttrDict(GAUSSIAN_KERNELS=[(k, k) for k in (15, 11, 9, 7, 5)])
     return d
 
 

@@ -26,6 +26,11 @@ and the depth-order reverse rate of lib/eval/test_util_panoptic.py (eval_3d, cal
 keypoint recall and the per-bone relative-depth error / reverse count of that module's `eval` branch (eval_one_image, generate_rootZ),
 accumulated on the GPU next to the lifting kernel (smap_amd/evaluate.py EvalMaps); the six raw accumulators are added to `error`.
 
+`-t generate_result|generate_train --maps_from_gt 1` (addition): the maps of every batch are RENDERED from the frame's annotations on the
+GPU (smap_amd/labels.py: what a perfectly trained backbone would return) instead of coming from the backbone: no checkpoint, no engine,
+no image file; everything behind the maps is unchanged.  Checks an annotation file end to end and measures the ceiling of association +
+lifting on it.
+
 `--device_preprocess 1 [--device_decode 1|2]` (addition) acts in all three modes: the frames are decoded ahead of the consumer and resized /
 padded / normalised on the GPU, one launch per batch (DevicePreprocLoader below); the result file is the same."""
 import argparse
@@ -314,6 +319,24 @@ class DevicePreprocLoader:
         return decode
 
 
+class AnnotationLoader:
+    """`--maps_from_gt 1`: batches of an annotated set WITHOUT its images -- (None, annotations [B,MAX_PEOPLE,15,C] fp32, tuple of names,
+    tuple of meta dicts), the batch of lib/utils/dataloader.py::collate_test with no frames in it.  Only dataset.extras(i) and name(i)
+    are asked: no file is opened."""
+
+    def __init__(self, dataset, indices, batch_size):
+        self.ds, self.idx, self.bs = dataset, list(indices), batch_size
+
+    def __len__(self):
+        return (len(self.idx) + self.bs - 1) // self.bs
+
+    def __iter__(self):
+        for s in range(0, len(self.idx), self.bs):
+            idx = self.idx[s:s + self.bs]
+            annotations, metas = zip(*[self.ds.extras(i) for i in idx])
+            yield None, torch.stack(annotations, 0), tuple(self.ds.name(i) for i in idx), tuple(metas)
+
+
 class _DryRunPipeline:
     """Stand-in for PosePipeline in `--dry_run 1` (no GPU, no checkpoint): the same submit / flush contract -- records of
     the batch submitted `depth` calls earlier -- with one fake person per frame.  What the rehearsal exercises is everything
@@ -336,8 +359,13 @@ class _DryRunPipeline:
         return out or None
 
 
-def generate_3d_point_pairs(model, refine_model, data_loader, cfg, logger, device, output_dir="", pipeline_cls=None, eval_3d=False, eval_maps=False):
+def generate_3d_point_pairs(model, refine_model, data_loader, cfg, logger, device, output_dir="", pipeline_cls=None, eval_3d=False, eval_maps=False,
+                            maps_from_gt=False):
     os.makedirs(output_dir, exist_ok=True)
+    source = {}
+    if maps_from_gt:               # the batches carry no frames (AnnotationLoader): their maps are rendered from the annotations
+        from smap_amd.labels import GtMapsSource, label_spec
+        source["maps_source"] = GtMapsSource(label_spec(cfg), device)
     if pipeline_cls is None:       # batches of <= 8 frames share a backbone launch (smap_amd/pipeline.py::make_pipeline, SMAP_LAUNCH_FRAMES)
         pipeline_cls = lambda m, c, b, h, w, d, rw, **kw: make_pipeline(m, c, b, h, w, d, refine_weights=rw, **kw)
     evaluators = {}                # pipeline argument -> evaluator, 3D first: the order of the log lines and of result["error"]
@@ -394,9 +422,20 @@ def generate_3d_point_pairs(model, refine_model, data_loader, cfg, logger, devic
             imgs, meta_data, img_path, scales = batch
             annotations = [kept_annotations(m.numpy(), cfg.DATASET.ROOT_IDX) for m in meta_data]
             cams = [annotation_camera(a, s) if len(a) else [1.0] * 9 for a, s in zip(annotations, scales)]
-        imgs = imgs.to(device, non_blocking=True).float().contiguous()
         img_path = list(img_path)
-        if pipe is not None and len(imgs) < pipe.B:              # ragged last batch: pad with copies of its last frame and
+        map_inputs = None
+        if maps_from_gt:
+            n, pad = len(img_path), (pipe.B - len(img_path) if pipe is not None else 0)
+            all_annotations = list(meta_data) + [meta_data[-1]] * max(pad, 0)      # a ragged last batch repeats its last frame (tag None)
+            map_inputs = (all_annotations, list(scales) + [scales[-1]] * max(pad, 0))
+            if pad > 0:
+                cams = np.concatenate([np.asarray(cams, np.float64), np.repeat(np.asarray(cams, np.float64)[-1:], pad, 0)], 0)
+                img_path = img_path + [None] * pad
+                annotations = list(annotations) + [annotations[-1]] * pad
+            imgs = _NoFrames(len(img_path), cfg.dataset.INPUT_SHAPE)
+        else:
+            imgs = imgs.to(device, non_blocking=True).float().contiguous()
+        if not maps_from_gt and pipe is not None and len(imgs) < pipe.B:              # ragged last batch: pad with copies of its last frame and
             pad = pipe.B - len(imgs)                             # drop their records (tag None) -- no second engine / arena
             imgs = torch.cat([imgs, imgs[-1:].expand(pad, -1, -1, -1)], 0).contiguous()
             cams = np.concatenate([np.asarray(cams, np.float64), np.repeat(np.asarray(cams, np.float64)[-1:], pad, 0)], 0)
@@ -409,9 +448,12 @@ def generate_3d_point_pairs(model, refine_model, data_loader, cfg, logger, devic
             pipe = pipeline_cls(model, cfg, len(imgs), imgs.shape[-2], imgs.shape[-1], device, refine_w,
                                 do_flip=bool(cfg.DO_FLIP), record_mode=cfg.TEST_MODE, numpy_records=True,
                                 depth=int(os.environ.get("SMAP_PIPELINE_DEPTH", 2)),   # two backbones in flight (+19 %)
-                                **evaluators)
+                                **evaluators, **source)
         with torch.no_grad():
-            drain(pipe.submit(imgs, cams, list(img_path), annotations=annotations))
+            if maps_from_gt:
+                drain(pipe.submit(None, cams, list(img_path), annotations=annotations, map_inputs=map_inputs))
+            else:
+                drain(pipe.submit(imgs, cams, list(img_path), annotations=annotations))
         clock["submit_s"] += time.perf_counter() - t_sub
         if "first_submit_s" not in clock:                        # builds the engine (schedule, weight packing, plan, arenas): seconds, once
             clock["first_submit_s"] = time.perf_counter() - t_sub
@@ -457,6 +499,16 @@ def generate_3d_point_pairs(model, refine_model, data_loader, cfg, logger, devic
     return result
 
 
+class _NoFrames:
+    """What the loop reads of a batch of frames (its length and shape) when there are none (--maps_from_gt 1)."""
+
+    def __init__(self, n, input_shape):
+        self.shape = (n, 3, int(input_shape[0]), int(input_shape[1]))
+
+    def __len__(self):
+        return self.shape[0]
+
+
 def main():
     # the schedule of a (checkpoint, shape, arithmetic) is built once and kept on disk (smap_amd/engine.py plan cache): the second start of
     # this command loads it through smap_plan_create_from_blob instead of re-packing the weights (SMAP_PLAN_CACHE=0 switches it off)
@@ -492,7 +544,14 @@ def main():
                         help="(addition) 1, with -t generate_result: score the network's maps on the GPU (2D keypoint error / recall, "
                              "bone depth error: lib/eval/test_util_panoptic.py eval_one_image, generate_rootZ) and add the six raw "
                              "accumulators to the `error` dict of the result file")
+    parser.add_argument("--maps_from_gt", type=int, default=0, choices=[0, 1],
+                        help="(addition) 1, with -t generate_result or generate_train: render the maps of every frame from its annotations "
+                             "on the GPU (smap_amd/labels.py) instead of running the backbone: no checkpoint, no image file is read")
     args = parser.parse_args()
+    if args.maps_from_gt and args.test_mode == "run_inference":
+        parser.error("--maps_from_gt 1 renders the maps from annotations: -t run_inference has none (use -t generate_result or generate_train)")
+    if args.maps_from_gt and args.dry_run:
+        parser.error("--maps_from_gt 1 renders on the GPU: not available with --dry_run 1")
     if args.device_decode not in (0, 1, 2):
         parser.error("--device_decode is 0, 1 or 2")
     if args.device_decode and not args.device_preprocess:
@@ -527,7 +586,11 @@ def main():
 
     device = torch.device("cpu") if dry else torch.device(cfg.MODEL.DEVICE, local)
     model = None
-    if not dry:
+    if args.maps_from_gt:
+        if args.do_flip or args.precision:
+            logger.info("--maps_from_gt 1: no backbone runs, --do_flip and --precision are ignored")
+        cfg.DO_FLIP = 0
+    elif not dry:
         model = SMAP(cfg, run_efficient=cfg.RUN_EFFICIENT)
         model.to(device)
         if args.precision:
@@ -535,7 +598,17 @@ def main():
 
     if args.test_mode != "run_inference" and args.device_preprocess and dry:
         logger.info("--dry_run 1: the ground-truth modes are rehearsed on the host loader (--device_preprocess needs the GPU)")
-    if args.test_mode != "run_inference" and args.device_preprocess and not dry:
+    if args.maps_from_gt:
+        from dataset.base_dataset import JointDataset
+        from lib.utils.dataloader import rank_block
+        if cfg.DATASET.NAME != "MIX":                          # get_test_loader's check
+            raise NameError("Dataset is not defined!", cfg.DATASET.NAME)
+        dataset = JointDataset(cfg, args.data_mode)
+        if args.device_preprocess:
+            logger.info("--maps_from_gt 1: no frame is read, --device_preprocess / --device_decode are ignored")
+        data_loader = AnnotationLoader(dataset, range(*rank_block(len(dataset), world, dist.get_rank() if world > 1 else 0)), args.batch_size)
+        dataset = None
+    elif args.test_mode != "run_inference" and args.device_preprocess and not dry:
         from dataset.base_dataset import JointDataset
         from lib.utils.dataloader import rank_block
         if cfg.DATASET.NAME != "MIX":                          # get_test_loader's check
@@ -569,9 +642,10 @@ def main():
             dist.destroy_process_group()
         return
     refine_model = RefineNet().to(device) if cfg.REFINE else None
-    if os.path.exists(args.SMAP_path):
-        state_dict = torch.load(args.SMAP_path, map_location=lambda storage, loc: storage)
-        model.load_state_dict(state_dict["model"])
+    if args.maps_from_gt or os.path.exists(args.SMAP_path):
+        if not args.maps_from_gt:
+            state_dict = torch.load(args.SMAP_path, map_location=lambda storage, loc: storage)
+            model.load_state_dict(state_dict["model"])
         if refine_model is not None:
             if os.path.exists(args.RefineNet_path):
                 refine_model.load_state_dict(torch.load(args.RefineNet_path, map_location="cpu"))
@@ -580,7 +654,7 @@ def main():
                 return
         result = generate_3d_point_pairs(model, refine_model, data_loader, cfg, logger, device,
                                          output_dir=os.path.join(cfg.OUTPUT_DIR, "result"), eval_3d=bool(args.eval_3d),
-                                         eval_maps=bool(args.eval_maps))
+                                         eval_maps=bool(args.eval_maps), maps_from_gt=bool(args.maps_from_gt))
         if dist.is_initialized():
             dist.destroy_process_group()
         if result.get("dropped_frames"):

@@ -553,6 +553,28 @@ int smap_evalmaps_acc_init(double* acc, void* stream);
 int smap_evalmaps_update(const double* pred_2d, const double* depth_v, const int32_t* bone_mask, const int32_t* counts,
                          const double* gt_2d, int B, int G, double* terms, double* acc, void* stream);
 
+/* ---- label maps: dataset/representation.py generate_heatmap (:5-21) and generate_paf / putVecMaps3D (:36-113) on the device ----
+ * labels: [B, S, SMAP_LABEL_C, H, W] fp32 out, the layout of JointDataset.__getitem__ (dataset/base_dataset.py:177-185): per label
+ * scale 15 heat-maps (x 255), then per limb its x, y (x 127) and relative-depth channel.  Every value is written.
+ * 8 <= H, 8 <= W, H * W <= 32768; 1 <= S <= SMAP_LABEL_MAX_SCALES; 1 <= P <= SMAP_LABEL_MAX_PERSONS; B * S <= 65535.
+ * ksizes: HOST, [S][2] = (width, height) of every scale's blur kernel, as cv2.GaussianBlur takes them: odd, below SMAP_LABEL_MAX_TAPS.
+ * table: DEVICE, 8-byte aligned, table_bytes long, what the host computed in float64 with the reference's own expressions
+ * (smap_amd/labels.py pack_table); sections in this order, each starting on a multiple of 8 bytes, group = (b * S + s) * 14 + limb:
+ *   limb_f   f64 [B*S*14][P][6]   per valid person of the group, IN ORDER: centerA_x, centerA_y (/ stride), unit_x, unit_y, limb_z, thre
+ *   limb_box i32 [B*S*14][P][4]   min_x, max_x, min_y, max_y: the rounded box, half open, clipped to the map (:80-83)
+ *   limb_n   i32 [B*S*14]         valid persons of the group (invalid or shorter than one cell: not in the table, :41-45,74-75)
+ *   imp      i32 [B*15][P]        y * W + x of the distinct cells of joint j that hold an impulse (:10-14); other values are ignored
+ *   imp_n    i32 [B*15]
+ *   taps     f32 [S][2][SMAP_LABEL_MAX_TAPS]   the blur taps of every scale: [0] the row pass (along x), [1] the column pass
+ * Counts outside 0..P are clamped.  Two launches on `stream`: one grid over (pixels, limb, frame x scale) for the fields, one workgroup
+ * per (joint, frame x scale) for the heat-maps (blur, maximum, division).  DESIGN.md "Label maps" has the arithmetic. */
+#define SMAP_LABEL_C 57                   /* 15 + 3 * 14 */
+#define SMAP_LABEL_MAX_SCALES 8
+#define SMAP_LABEL_MAX_TAPS 16
+#define SMAP_LABEL_MAX_PERSONS 64
+int smap_render_labels(const void* table, int64_t table_bytes, const int32_t* ksizes, int B, int S, int P, int H, int W, float* labels,
+                       void* stream);
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif

@@ -15,10 +15,11 @@ CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "libsmap_hip.so")
 OBJ = os.path.join(CSRC, "obj")
 
-# (source, extra flags).  assoc.hip and eval.hip are bit-exact float work: contraction OFF.
+# (source, extra flags).  assoc.hip, eval.hip and labels.hip are bit-exact float work: contraction OFF.
 SOURCES = [
     ("assoc.hip", ["-ffp-contract=off"]),
     ("eval.hip", ["-ffp-contract=off"]),
+    ("labels.hip", ["-ffp-contract=off"]),       # label maps: held to the reference's bits as well
     ("conv.hip", []),
     ("conv3.hip", []),
     ("convp.hip", []),

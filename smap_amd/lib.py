@@ -25,6 +25,7 @@ SYMBOLS = [
     "smap_sizeof_jpeg_info", "smap_jpeg_probe", "smap_jpeg_decode_coefficients", "smap_jpeg_workspace_bytes", "smap_jpeg_reconstruct",
     "smap_sizeof_jpeg_scan", "smap_jpeg_scan_tables", "smap_jpeg_huff_workspace_bytes", "smap_jpeg_decode_coefficients_device",
     "smap_sizeof_prep_frame", "smap_preprocess_batch",
+    "smap_render_labels",
 ]
 MAX_INPUTS = 8                         # SMAP_MAX_INPUTS
 
@@ -103,6 +104,7 @@ class PrepFrame(C.Structure):
                 ("left", C.c_int32), ("fx", C.c_double), ("fy", C.c_double)]
 
 
+LABEL_C, LABEL_MAX_SCALES, LABEL_MAX_TAPS, LABEL_MAX_PERSONS = 57, 8, 16, 64      # SMAP_LABEL_*
 PREP_MAX_FRAMES = 16      # SMAP_PREP_MAX_FRAMES
 JPEG_UNSUPPORTED = 1      # SMAP_JPEG_UNSUPPORTED
 JPEG_E_DATA = -2          # SMAP_JPEG_E_DATA
@@ -174,6 +176,7 @@ def load():
     lib.smap_eval3d_update.argtypes = [vp, vp, vp, ip, ip, vp, vp, vp]
     lib.smap_evalmaps_acc_init.argtypes = [vp, vp]
     lib.smap_evalmaps_update.argtypes = [vp, vp, vp, vp, vp, ip, ip, vp, vp, vp]
+    lib.smap_render_labels.argtypes = [vp, C.c_int64, C.POINTER(C.c_int32), ip, ip, ip, ip, ip, vp, vp]
     for s in SYMBOLS:
         if s not in ("smap_version", "smap_plan_destroy", "smap_nms_workspace_bytes", "smap_jpeg_workspace_bytes",
                      "smap_jpeg_huff_workspace_bytes"):  # everything else returns int

@@ -47,7 +47,10 @@ def pack_views(buf, B):
 
 
 class _Slot:
-    def __init__(self, engine, device, n_extra, B):
+    def __init__(self, engine, device, n_extra, B, map_shape=None):
+        if engine is None:
+            self._init_maps_only(device, n_extra, B, map_shape)
+            return
         # one output buffer per backbone launch (engine.B frames each); with several launches per batch the maps of the
         # whole batch are gathered into B-frame tensors behind them
         self.outs = [engine.new_output() for _ in range(B // engine.B)]
@@ -68,6 +71,23 @@ class _Slot:
         self.status_words = engine.status_words
         # host copy of every launch's status words (word f // 31: bit 0 = non-finite maps, bit 1 + f % 31 = frame f of the launch)
         self.status_host = torch.zeros((len(self.outs), engine.status_words), dtype=torch.float32).pin_memory()
+        self._init_rest()
+
+    def _init_maps_only(self, device, n_extra, B, map_shape):
+        """A slot of a pipeline whose maps come from a maps_source: the three map tensors, no backbone output, no status words."""
+        h, w = map_shape
+        self.outs, self.out = [], None
+        self.hms = torch.empty((B, NJ + 2 * 14, h, w), dtype=torch.float32, device=device)
+        self.det_d = torch.empty((B, 14, h, w), dtype=torch.float32, device=device)
+        self.root_d = torch.empty((B, 1, h, w), dtype=torch.float32, device=device)
+        self.pack_bytes = pack_layout(B)[-1]
+        self.host_pack = [torch.empty((self.pack_bytes,), dtype=torch.uint8).pin_memory() for _ in range(1 + n_extra)]
+        self.host = [pack_views(hp, B) for hp in self.host_pack]
+        self.status, self.status_words = 0, 0
+        self.status_host = torch.zeros((0, 1), dtype=torch.float32)
+        self._init_rest()
+
+    def _init_rest(self):
         self.p2_f64 = None               # ground-truth modes: the f64 pred_2d (allocated on first use)
         self.ev_bb = torch.cuda.Event()
         self.ev_post = torch.cuda.Event()       # the host waits on this one: PosePipeline._wait
@@ -87,7 +107,7 @@ class GroundTruth(NamedTuple):
 class PosePipeline:
     def __init__(self, model, cfg, batch, H, W, device, refine_weights=None, n_extra=0, do_flip=False, depth=1,
                  record_mode="run_inference", numpy_records=False, max_frames_per_launch=None, strict_nonfinite=None, evaluator=None,
-                 map_evaluator=None):
+                 map_evaluator=None, maps_source=None):
         """record_mode: test.py's -t: "run_inference" (no ground truth), "generate_result" (one record per frame
         with the annotations attached) or "generate_train" (one record per matched person); the last two need
         `annotations=` in submit().
@@ -95,10 +115,17 @@ class PosePipeline:
         tensor that is recorded as pred_3d; nothing is read back before its raw() / summary().  None: nothing changes.
         map_evaluator: a smap_amd.evaluate.EvalMaps (ground-truth modes only): the lifting also hands out its per-limb depths
         (smap_lift_gt_bones) and every batch's registered rows are scored against the annotations' 2D columns on the post stream.
-        None: nothing changes."""
+        None: nothing changes.
+        maps_source: a callable (ground-truth modes only), e.g. smap_amd.labels.GtMapsSource: submit(map_inputs=x) fills the slot's maps
+        with maps_source(x) = (hms [B,43,h,w], det_d [B,14,h,w], root_d [B,1,h,w]) at the network's RAW scale, on the backbone stream,
+        INSTEAD of running the backbone; everything behind the maps is the same.  `model` may be None: no engine is built, no image is
+        read (imgs may be None), do_flip does not apply.  None: nothing changes."""
         assert record_mode in ("run_inference", "generate_result", "generate_train")
         if (evaluator is not None or map_evaluator is not None) and record_mode == "run_inference":
             raise ValueError("evaluator= / map_evaluator= need a ground-truth record_mode: run_inference has nothing to score against")
+        if maps_source is not None and record_mode == "run_inference":
+            raise ValueError("maps_source= needs a ground-truth record_mode: run_inference has no annotations to render maps from")
+        self.maps_source = maps_source
         self.record_mode = record_mode
         self.evaluator = evaluator
         self.map_evaluator = map_evaluator
@@ -114,6 +141,13 @@ class PosePipeline:
         # stem reads the mirrored image by index, the head sum merges the mirrored maps (no ATen cat/flip, no merge pass)
         kpt = cfg.DATASET.KEYPOINT.NUM
         self.flip_pair = list(cfg.DATASET.KEYPOINT.FLIP_ORDER) + [kpt + c for c in cfg.DATASET.PAF.FLIP_CHANNEL]
+        self.refine = refine_weights
+        self.depth = max(1, int(depth))
+        if maps_source is not None:                       # no backbone: no engine, no arena, no weights to go stale
+            self.engine, self.chunk, self.engines = None, batch, [None] * self.depth
+            self._model = self._generation = None
+            self._streams_and_slots(n_extra, batch, (H // cfg.dataset.STRIDE, W // cfg.dataset.STRIDE))
+            return
         # frames per backbone launch: the whole batch, or the largest divisor of it that the engine accepts (ArenaTooLarge: one tensor
         # beyond a 4 GiB addressing window -- 53+ frames in split precision -- or an arena beyond the memory budget, SMAP_MAX_ARENA_BYTES /
         # 90 % of the device memory shared by 4 arenas: every backbone in flight has its own)
@@ -136,9 +170,10 @@ class PosePipeline:
                                                       batch // parts, exc, parts + 1)
         self._model, self._generation = model, model.weights_generation      # a reload / .to() after this point makes the
                                                                              # pipeline stale: submit() refuses to run on old weights
-        self.refine = refine_weights
-        self.depth = max(1, int(depth))
         self.engines = [self.engine] + [self.engine.sibling() for _ in range(self.depth - 1)]
+        self._streams_and_slots(n_extra, batch)
+
+    def _streams_and_slots(self, n_extra, batch, map_shape=None):
         prio = [int(x) for x in os.environ.get("SMAP_BB_STREAM_PRIORITIES", "").split(",") if x.strip()]     # experiment hook
         self.s_bbs = [torch.cuda.Stream(self.device, priority=prio[i % len(prio)]) if prio else torch.cuda.Stream(self.device)
                       for i in range(self.depth)]
@@ -146,7 +181,7 @@ class PosePipeline:
         self.s_post = torch.cuda.Stream(self.device)
         self.s_comm = torch.cuda.Stream(self.device)      # result gather (RCCL) never queues behind compute
         self.nslots = self.depth + 1
-        self.slots = [_Slot(self.engine, self.device, n_extra, batch) for _ in range(self.nslots)]
+        self.slots = [_Slot(self.engine, self.device, n_extra, batch, map_shape) for _ in range(self.nslots)]
         self.frames_per_launch = self.chunk
         self.k = 0
         self.wait_s = 0.0                # host time spent WAITING for the GPU inside submit() / flush() (sleeping, not enqueueing)
@@ -196,14 +231,15 @@ class PosePipeline:
         for k, t in (("p3", p3), ("rz", rz), ("counts", counts)):
             h[k][row0:row0 + n].copy_(t, non_blocking=True)
 
-    def submit(self, imgs, cams, tags, extra=(), time_backbone=False, annotations=None):
+    def submit(self, imgs, cams, tags, extra=(), time_backbone=False, annotations=None, map_inputs=None):
         """imgs [B,3,H,W] fp32 on the device -- or a list of equally sized tensors that together hold the B frames (read where
         they are: smap_plan_run_inputs); cams [B,9] float64 (host array); tags: B image names.
         extra: tuples (tag_prefix, hms, root_d, det_d) of already-scaled maps to associate as well (bench only); each of the three
         may be a list of tensors covering the B frames in order (associated part by part, no concatenation).  annotations (ground-truth modes): B arrays [G_i,15,C] of the KEPT annotations of each
         frame (records.kept_annotations; G_i may be 0 -- the frame is skipped, test.py:81-82).
+        map_inputs (with maps_source= only): what the source renders this batch's maps from; imgs is not read then.
         Returns the record list of the previous batch or None."""
-        if self._model.weights_generation != self._generation:
+        if self.maps_source is None and self._model.weights_generation != self._generation:
             raise RuntimeError("the model's weights were reloaded or moved after this PosePipeline was built; build a new one")
         gt = None
         if self.record_mode != "run_inference":
@@ -231,7 +267,7 @@ class PosePipeline:
         cur = torch.cuda.current_stream(self.device)
         s_bb.wait_stream(cur)                          # imgs were produced on the caller's stream
         self.s_post.wait_stream(cur)
-        img_parts = list(imgs) if isinstance(imgs, (list, tuple)) else [imgs]
+        img_parts = [] if self.maps_source is not None else list(imgs) if isinstance(imgs, (list, tuple)) else [imgs]
         if len(img_parts) > 1 and (len(img_parts) > 8 or len({tuple(t.shape) for t in img_parts}) > 1 or
                                    (len(slot.outs) > 1 and len(img_parts) % len(slot.outs))):
             img_parts = [torch.cat(img_parts)]         # shapes the stem's buffer table cannot express: gather (never on the bench path)
@@ -251,7 +287,10 @@ class PosePipeline:
             if time_backbone:
                 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                 e0.record()
-            if len(slot.outs) == 1:
+            if self.maps_source is not None:          # the maps a perfectly trained backbone would return for this batch
+                for dst, src in zip((slot.hms, slot.det_d, slot.root_d), self.maps_source(map_inputs)):
+                    dst.copy_(src, non_blocking=True)
+            elif len(slot.outs) == 1:
                 eng.run(img_parts if len(img_parts) > 1 else img_parts[0], out=slot.out)
             else:                                      # the batch in engine-sized launches, one after the other on this stream
                 c = eng.B
@@ -278,7 +317,8 @@ class PosePipeline:
                 self.post_events.append((tag if isinstance(tag, str) else "+".join(sorted(set(tag))), p0, p1))
             for j, o in enumerate(slot.outs):
                 slot.status_host[j].copy_(o[slot.status:slot.status + slot.status_words], non_blocking=True)
-            timed_post("network", slot, 0, slot.hms, slot.det_d, slot.root_d, cams_d, scale=False, gt=gt)   # (scaled by the head sum)
+            # (the backbone's maps are scaled by its head sum; a maps_source hands over raw maps: test.py:111-112 here)
+            timed_post("network", slot, 0, slot.hms, slot.det_d, slot.root_d, cams_d, scale=self.maps_source is not None, gt=gt)
             for j, (tag, hms, rd, dd) in enumerate(extra):
                 row = 0
                 hp, rp = as_parts(hms), as_parts(rd)
