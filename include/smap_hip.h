@@ -575,6 +575,51 @@ int smap_evalmaps_update(const double* pred_2d, const double* depth_v, const int
 int smap_render_labels(const void* table, int64_t table_bytes, const int32_t* ksizes, int B, int S, int P, int H, int W, float* labels,
                        void* stream);
 
+/* ---- training loss: SMAP._calculate_loss (model/smap.py:355-401) with JointsL2Loss / DepthLoss (lib/utils/loss_h.py), value and
+ * gradient ----
+ * heads: HOST array of 3 * n_heads DEVICE pointers, n_heads = 4 * stage_num, head h = 4 * stage + scale:
+ *   heads[3 * h + 0] heatmap_2d [B, 43, H, W], heads[3 * h + 1] det_d [B, 14, H, W], heads[3 * h + 2] root_d [B, 1, H, W], fp32, dense.
+ * labels [B, S, 57, H, W] fp32 as smap_render_labels writes them; head (stage i, scale j) is compared with label scale
+ *   j + (i == stage_num - 1 && ctf).  2D channel c < 15 reads label channel c, c >= 15 reads 15 + 3 * ((c - 15) / 2) + (c - 15) % 2;
+ *   det_d channel c reads 15 + 3 * c + 2.
+ * valids [B, 57] fp32 in OUTPUT order (43 2D channels, then 14 det_d channels); a channel weighs 1 where valids > 0, else 0.
+ * rdepth [B, R, 3] fp32 rows (y, x, Z); a row counts where Z > 0 and is read at cell (int(y), int(x)), truncated toward zero.
+ * Per channel m = mean((out - label)^2) * weight, the difference in fp32, the sum in double in a fixed order (the same bits run to
+ * run).  Per head: mean of m over (B, channels); with ohkm, on the finest head (j == 3) the `topk` largest of the 15 key-point channels
+ * and the 2 * topk largest of the 28 PAF channels of every frame (mean + mean), and the topk largest of the 14 det_d channels; ties go
+ * to the LOWER channel index.  Root: sum |root_d[cell] - Z| / count over the whole batch, 0 when no row counts.
+ * total = sum over heads of (0.1 * 2D + 5 * depth + 10 * root), / 4 where j < 3.
+ * result [8] fp32: total, 2D, bone, root (the three: finest heads summed over the stages), bad_rows, 0, 0, 0.  A counted row outside
+ * [0, H) x [0, W) is never dereferenced; it is counted in bad_rows, and total is NaN then.
+ * single != 0: ONE head (n_heads = 1, stage_num = 1, ctf = 0, label scale 0, S >= 1), treated as a finest head, all weights 1; any of
+ *   its three tensors may be null and is left out then (labels / valids may be null when both maps are).
+ * workspace: smap_loss_workspace_bytes(n_heads, B, R) bytes, 8-byte aligned; smap_loss_forward fills it (sums f64 [n_heads][B][57] at
+ *   offset 0; csrc/loss_core.h workspace_layout has the rest) and smap_loss_backward reads it.
+ * smap_loss_forward: two launches (reduce: one workgroup per (channel, frame, head); finish: one workgroup).
+ * smap_loss_backward: one launch; upstream: DEVICE fp32 scalar, d L / d total.  grad: per head [B, 43, H, W] | [B, 14, H, W] |
+ *   [B, 1, H, W], head after head (58 * B * H * W floats each); every element of a given tensor is written once,
+ *   (out - label) * fp32(coef * upstream), root_d's from the root table.
+ * 16-byte loads where H * W % 4 == 0 and every tensor is 16-byte aligned, 4-byte loads otherwise.
+ * SMAP_E_ARG: null pointers, stage_num outside 1..4, S < 4 + ctf, topk outside 1..14 with ohkm, H * W outside 1..2^24, B or R outside
+ * 1..65535, a workspace that is too small or misaligned.
+ * smap_loss_finish_host: everything behind the reduction (csrc/loss_core.h, the text the device runs) on the HOST, all pointers
+ * HOST: sums [n_heads][B][57], rd_at_rows [n_heads][B][R] = root_d at the rows' cells (anything for rows that do not count); out:
+ * result [8], m / sel / coef [n_heads][B][57] (the per-channel loss, the 0 / 1 selection, the gradient factor),
+ * root_cell [n_heads][B][R] (y * W + x, -1 for a row that does not count, -2 for one outside the map), root_fac [n_heads][B][R]
+ * (10 * head factor * sign(out - Z) / count), part [n_heads][B][6] (per frame the sums of the kept m of the key-point | 2D, PAF and
+ * depth groups, then of its rows: sum |root_d - Z|, rows counted, rows outside).
+ * Needs no GPU. */
+int64_t smap_loss_workspace_bytes(int n_heads, int B, int R);
+int smap_loss_forward(const void* const* heads, const float* labels, const float* valids, const float* rdepth, int stage_num, int ohkm,
+                      int topk, int ctf, int single, int B, int S, int R, int H, int W, void* workspace, int64_t workspace_bytes,
+                      float* result, void* stream);
+int smap_loss_backward(const void* const* heads, const float* labels, int stage_num, int ohkm, int topk, int ctf, int single, int B, int S,
+                       int R, int H, int W, const void* workspace, int64_t workspace_bytes, const float* upstream, float* grad,
+                       void* stream);
+int smap_loss_finish_host(const double* sums, const float* valids, const float* rdepth, const float* rd_at_rows, int stage_num, int ohkm,
+                          int topk, int ctf, int single, int B, int R, int H, int W, double* result, double* m, double* sel, double* coef,
+                          int32_t* root_cell, double* root_fac, double* part);
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif

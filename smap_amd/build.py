@@ -15,11 +15,12 @@ CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "libsmap_hip.so")
 OBJ = os.path.join(CSRC, "obj")
 
-# (source, extra flags).  assoc.hip, eval.hip and labels.hip are bit-exact float work: contraction OFF.
+# (source, extra flags).  assoc.hip, eval.hip, labels.hip and loss.hip are bit-exact float work: contraction OFF.
 SOURCES = [
     ("assoc.hip", ["-ffp-contract=off"]),
     ("eval.hip", ["-ffp-contract=off"]),
     ("labels.hip", ["-ffp-contract=off"]),       # label maps: held to the reference's bits as well
+    ("loss.hip", ["-ffp-contract=off"]),         # training loss: fixed-order double sums; its finish is csrc/loss_core.h (also built alone for the CPU)
     ("conv.hip", []),
     ("conv3.hip", []),
     ("convp.hip", []),

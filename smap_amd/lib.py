@@ -26,6 +26,7 @@ SYMBOLS = [
     "smap_sizeof_jpeg_scan", "smap_jpeg_scan_tables", "smap_jpeg_huff_workspace_bytes", "smap_jpeg_decode_coefficients_device",
     "smap_sizeof_prep_frame", "smap_preprocess_batch",
     "smap_render_labels",
+    "smap_loss_workspace_bytes", "smap_loss_forward", "smap_loss_backward", "smap_loss_finish_host",
 ]
 MAX_INPUTS = 8                         # SMAP_MAX_INPUTS
 
@@ -177,13 +178,19 @@ def load():
     lib.smap_evalmaps_acc_init.argtypes = [vp, vp]
     lib.smap_evalmaps_update.argtypes = [vp, vp, vp, vp, vp, ip, ip, vp, vp, vp]
     lib.smap_render_labels.argtypes = [vp, C.c_int64, C.POINTER(C.c_int32), ip, ip, ip, ip, ip, vp, vp]
+    i64 = C.c_int64
+    lib.smap_loss_workspace_bytes.argtypes = [ip, ip, ip]
+    lib.smap_loss_forward.argtypes = [C.POINTER(vp), vp, vp, vp, ip, ip, ip, ip, ip, ip, ip, ip, ip, ip, vp, i64, vp, vp]
+    lib.smap_loss_backward.argtypes = [C.POINTER(vp), vp, ip, ip, ip, ip, ip, ip, ip, ip, ip, ip, vp, i64, vp, vp, vp]
+    lib.smap_loss_finish_host.argtypes = [vp, vp, vp, vp, ip, ip, ip, ip, ip, ip, ip, ip, ip, vp, vp, vp, vp, vp, vp, vp]
     for s in SYMBOLS:
         if s not in ("smap_version", "smap_plan_destroy", "smap_nms_workspace_bytes", "smap_jpeg_workspace_bytes",
-                     "smap_jpeg_huff_workspace_bytes"):  # everything else returns int
+                     "smap_jpeg_huff_workspace_bytes", "smap_loss_workspace_bytes"):  # everything else returns int
             getattr(lib, s).restype = ip
     lib.smap_nms_workspace_bytes.restype = C.c_int64
     lib.smap_jpeg_workspace_bytes.restype = C.c_int64
     lib.smap_jpeg_huff_workspace_bytes.restype = C.c_int64
+    lib.smap_loss_workspace_bytes.restype = C.c_int64
     if lib.smap_sizeof_op() != C.sizeof(SmapOp):
         raise ImportError(f"smap_op layout mismatch: C {lib.smap_sizeof_op()} vs ctypes {C.sizeof(SmapOp)}")
     if lib.smap_sizeof_jpeg_info() != C.sizeof(JpegInfo):

@@ -1,0 +1,230 @@
+"""The training loss of the network on the GPU (reference: model/smap.py:355-401 SMAP._calculate_loss, lib/utils/loss_h.py).
+
+`SMAPLoss` takes what the reference's loss takes -- the outputs of all 4 * stage_num heads, `valids`, `labels` (as `render_labels`
+returns them) and `rdepth` -- and returns the reference's dict.  The value is two launches (smap_loss_forward: a fixed-order
+reduction per (channel, frame, head), then one workgroup that selects, averages and weighs), the gradient one launch
+(smap_loss_backward), with no host synchronisation in either: csrc/loss.hip, csrc/loss_core.h, DESIGN.md section 13.
+
+Differences from the reference, on purpose:
+  * only `total_loss` is differentiable.  `loss_2d`, `loss_bone` and `loss_root` are detached logging values; the reference's carry
+    graphs too, and nothing backpropagates them.
+  * hard-keypoint mining breaks ties towards the LOWER channel index; torch.topk leaves them unspecified.
+  * a root-depth row with Z > 0 whose cell lies outside the map makes `total_loss` NaN (result[4] counts such rows; `strict=True`
+    reads it -- one synchronisation -- and raises); the reference wraps around or raises an IndexError there.
+  * there is no CPU path and no fallback: the tensors live on the GPU.
+"""
+import ctypes as C
+
+import numpy as np
+import torch
+from torch.autograd.function import once_differentiable
+
+from . import lib as L
+
+NKP, N2D, NDD, NC, MAX_HEADS, GRAD_C = 15, 43, 14, 57, 16, 58
+# label channel of every output channel: the 43 2D channels (key points, then the x, y of every limb), then the 14 depth channels
+LABEL_CHANNEL = tuple(list(range(NKP)) + [NKP + 3 * (c // 2) + c % 2 for c in range(N2D - NKP)] + [NKP + 3 * c + 2 for c in range(NDD)])
+
+
+def workspace_layout(n_heads, B, R):
+    """Byte offsets of the workspace's sections and its size (csrc/loss_core.h workspace_layout)."""
+    n, rows = n_heads * B * NC, n_heads * B * R
+    w = {"sums": 0}
+    w["m"] = w["sums"] + n * 8
+    w["part"] = w["m"] + n * 8
+    w["headloss"] = w["part"] + n_heads * B * 6 * 8
+    w["coef"] = w["headloss"] + MAX_HEADS * 5 * 8
+    w["sel"] = w["coef"] + n * 4
+    w["rd_at"] = w["sel"] + n * 4
+    w["root_fac"] = w["rd_at"] + rows * 4
+    w["root_cell"] = w["root_fac"] + rows * 4
+    w["bytes"] = (w["root_cell"] + rows * 4 + 7) // 8 * 8
+    return w
+
+
+def workspace_views(ws, n_heads, B, R):
+    """dict of typed views of a workspace tensor (uint8 [bytes], device or host)."""
+    w = workspace_layout(n_heads, B, R)
+    v = lambda key, dtype, shape: ws[w[key]:w[key] + int(np.prod(shape)) * torch.empty((), dtype=dtype).element_size()].view(dtype).view(shape)
+    return dict(sums=v("sums", torch.float64, (n_heads, B, NC)), m=v("m", torch.float64, (n_heads, B, NC)),
+                part=v("part", torch.float64, (n_heads, B, 6)), headloss=v("headloss", torch.float64, (MAX_HEADS, 5)), coef=v("coef", torch.float32, (n_heads, B, NC)),
+                sel=v("sel", torch.float32, (n_heads, B, NC)), rd_at=v("rd_at", torch.float32, (n_heads, B, R)),
+                root_fac=v("root_fac", torch.float32, (n_heads, B, R)), root_cell=v("root_cell", torch.int32, (n_heads, B, R)))
+
+
+class _Config:
+    """The integers every entry point takes."""
+
+    def __init__(self, stage_num, ohkm, topk, ctf, single, B, S, R, H, W):
+        self.stage_num, self.ohkm, self.topk, self.ctf, self.single = int(stage_num), int(bool(ohkm)), int(topk), int(bool(ctf)), int(bool(single))
+        self.B, self.S, self.R, self.H, self.W = int(B), int(S), int(R), int(H), int(W)
+        self.n_heads = 1 if self.single else 4 * self.stage_num
+
+    def head_args(self):
+        return (self.stage_num, self.ohkm, self.topk, self.ctf, self.single)
+
+
+def _ptr(t):
+    return None if t is None else t.data_ptr()
+
+
+def _head_array(tensors):
+    return (C.c_void_p * len(tensors))(*[_ptr(t) for t in tensors])
+
+
+def forward_raw(cfg, tensors, labels, valids, rdepth):
+    """smap_loss_forward on the current stream: (result [8] fp32, workspace uint8).  tensors: 3 * n_heads checked device tensors (or
+    None in single-head mode).  No synchronisation."""
+    dev = rdepth.device
+    bytes_ = workspace_layout(cfg.n_heads, cfg.B, cfg.R)["bytes"]
+    ws = torch.empty((bytes_,), dtype=torch.uint8, device=dev)
+    result = torch.empty((8,), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        L.check(L.load().smap_loss_forward(_head_array(tensors), _ptr(labels), _ptr(valids), _ptr(rdepth), *cfg.head_args(), cfg.B, cfg.S,
+                                           cfg.R, cfg.H, cfg.W, ws.data_ptr(), bytes_, result.data_ptr(),
+                                           torch.cuda.current_stream(dev).cuda_stream), "smap_loss_forward")
+    return result, ws
+
+
+def backward_raw(cfg, tensors, labels, ws, upstream):
+    """smap_loss_backward on the current stream: one buffer [n_heads, 58 * B * H * W] fp32 and its 3 * n_heads views, in the order of
+    `tensors` (None where the tensor was).  upstream: device fp32 tensor, its first element is d L / d total."""
+    dev = ws.device
+    HW = cfg.H * cfg.W
+    grad = torch.empty((cfg.n_heads, GRAD_C * cfg.B * HW), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        L.check(L.load().smap_loss_backward(_head_array(tensors), _ptr(labels), *cfg.head_args(), cfg.B, cfg.S, cfg.R, cfg.H, cfg.W,
+                                            ws.data_ptr(), ws.numel(), upstream.data_ptr(), grad.data_ptr(),
+                                            torch.cuda.current_stream(dev).cuda_stream), "smap_loss_backward")
+    views = []
+    for h in range(cfg.n_heads):
+        cut = (0, N2D * cfg.B * HW, NC * cfg.B * HW, GRAD_C * cfg.B * HW)
+        for k, ch in enumerate((N2D, NDD, 1)):
+            views.append(None if tensors[3 * h + k] is None else grad[h, cut[k]:cut[k + 1]].view(cfg.B, ch, cfg.H, cfg.W))
+    return grad, views
+
+
+class _LossFunction(torch.autograd.Function):
+    """result [8] of smap_loss_forward as a function of the head tensors; the gradient flows from result[0] alone."""
+
+    @staticmethod
+    def forward(ctx, cfg, labels, valids, rdepth, *tensors):
+        result, ws = forward_raw(cfg, tensors, labels, valids, rdepth)
+        ctx.cfg, ctx.present, ctx.ws = cfg, [t is not None for t in tensors], ws     # ws: neither input nor output, kept on ctx
+        ctx.save_for_backward(labels, *[t for t in tensors if t is not None])
+        return result
+
+    @staticmethod
+    @once_differentiable                                     # the gradient is a constant to autograd: a double backward raises
+    def backward(ctx, grad_result):
+        labels, *given = ctx.saved_tensors
+        ws = ctx.ws
+        given = iter(given)
+        tensors = [next(given) if here else None for here in ctx.present]
+        _, views = backward_raw(ctx.cfg, tensors, labels, ws, grad_result.contiguous())
+        return (None, None, None, None) + tuple(views)
+
+
+def _device_fp32(t, what, shape=None):
+    """A dense fp32 device tensor, or the error the input rules ask for."""
+    if not isinstance(t, torch.Tensor):
+        raise TypeError("%s: expected a torch.Tensor, got %s" % (what, type(t).__name__))
+    if t.dtype != torch.float32:
+        raise TypeError("%s: expected float32, got %s" % (what, t.dtype))
+    if t.device.type != "cuda":
+        raise ValueError("%s: the loss runs on the GPU (smap_amd has no CPU path), got device %s" % (what, t.device))
+    if shape is not None and tuple(t.shape) != tuple(shape):
+        raise ValueError("%s: expected shape %s, got %s" % (what, tuple(shape), tuple(t.shape)))
+    return t.contiguous()
+
+
+def _valids_2d(valids, B, what="valids"):
+    if isinstance(valids, torch.Tensor) and valids.dim() == 3 and valids.shape[2] == 1:
+        valids = valids[:, :, 0]
+    return _device_fp32(valids, what, (B, NC))
+
+
+class SMAPLoss:
+    """SMAP._calculate_loss on the GPU.
+
+        criterion = SMAPLoss.from_cfg(cfg)               # or SMAPLoss(stage_num=3, ohkm=True, topk=8, ctf=True)
+        losses = criterion(outputs, valids, labels, rdepth)
+        losses["total_loss"].backward()
+
+    outputs: dict with 'heatmap_2d', 'det_d', 'root_d', each a list of stage_num lists of 4 tensors [B, 43 | 14 | 1, H, W] (what
+    SMAP.forward collects); valids [B, 57, 1] or [B, 57]; labels [B, S, 57, H, W] with S >= 4 + ctf; rdepth [B, R, 3].  All fp32 on one
+    GPU.  Returns {'total_loss', 'loss_2d', 'loss_bone', 'loss_root'}: 0-d fp32 tensors, the last three detached."""
+
+    def __init__(self, stage_num=3, ohkm=True, topk=8, ctf=True, strict=False):
+        self.stage_num, self.ohkm, self.topk, self.ctf, self.strict = int(stage_num), bool(ohkm), int(topk), bool(ctf), bool(strict)
+        if not 1 <= self.stage_num <= 4:
+            raise ValueError("stage_num is 1 to 4, got %d" % self.stage_num)
+        if self.ohkm and not 1 <= self.topk <= NDD:
+            raise ValueError("topk is 1 to %d with ohkm, got %d" % (NDD, self.topk))
+
+    @classmethod
+    def from_cfg(cls, cfg, strict=False):
+        return cls(cfg.MODEL.STAGE_NUM, cfg.LOSS.OHKM, cfg.LOSS.TOPK, cfg.LOSS.COARSE_TO_FINE, strict)
+
+    def _check(self, outputs, valids, labels, rdepth):
+        labels = _device_fp32(labels, "labels")
+        if labels.dim() != 5 or labels.shape[2] != NC or labels.shape[1] < 4 + int(self.ctf):
+            raise ValueError("labels: expected [B, S >= %d, 57, H, W], got %s" % (4 + int(self.ctf), tuple(labels.shape)))
+        B, S, _, H, W = labels.shape
+        valids = _valids_2d(valids, B)
+        rdepth = _device_fp32(rdepth, "rdepth")
+        if rdepth.dim() != 3 or rdepth.shape[0] != B or rdepth.shape[2] != 3 or rdepth.shape[1] < 1:
+            raise ValueError("rdepth: expected [%d, R >= 1, 3], got %s" % (B, tuple(rdepth.shape)))
+        tensors = []
+        for i in range(self.stage_num):
+            for j in range(4):
+                for key, ch in (("heatmap_2d", N2D), ("det_d", NDD), ("root_d", 1)):
+                    what = "outputs['%s'][%d][%d]" % (key, i, j)
+                    try:
+                        t = outputs[key][i][j]
+                    except (KeyError, IndexError, TypeError):
+                        raise ValueError("%s is missing: %d stages of 4 heads each" % (what, self.stage_num))
+                    tensors.append(_device_fp32(t, what, (B, ch, H, W)))
+        for t in tensors + [valids, rdepth]:
+            if t.device != labels.device:
+                raise ValueError("all tensors live on one GPU: labels on %s, another on %s" % (labels.device, t.device))
+        return _Config(self.stage_num, self.ohkm, self.topk, self.ctf, 0, B, S, rdepth.shape[1], H, W), tensors, labels, valids, rdepth
+
+    def __call__(self, outputs, valids, labels, rdepth):
+        cfg, tensors, labels, valids, rdepth = self._check(outputs, valids, labels, rdepth)
+        result = _LossFunction.apply(cfg, labels, valids, rdepth, *tensors)
+        if self.strict:
+            bad = int(result[4].item())                       # the one synchronisation of strict mode
+            if bad:
+                raise ValueError("rdepth: %d row(s) with Z > 0 lie outside the %d x %d map" % (bad, cfg.H, cfg.W))
+        logged = result.detach()
+        return dict(total_loss=result[0], loss_2d=logged[1], loss_bone=logged[2], loss_root=logged[3])
+
+    forward = __call__
+
+
+def single_head_loss(hm=None, dd=None, rd=None, labels=None, valids=None, rdepth=None, ohkm=False, topk=8):
+    """ONE head with unit weights (smap_loss_forward's single mode), for lib/utils/loss_h.py: result [8] = (2D + depth + root, 2D,
+    depth, root, bad_rows, ...), differentiable through its first element.  labels [B, S >= 1, 57, H, W] (scale 0 is read), valids
+    [B, 57] in output order; either may be None when hm and dd are."""
+    given = [t for t in (hm, dd, rd) if t is not None]
+    if not given:
+        raise ValueError("at least one of hm, dd, rd")
+    B, _, H, W = given[0].shape
+    tensors = [None if t is None else _device_fp32(t, name, (B, ch, H, W)) for t, name, ch in ((hm, "hm", N2D), (dd, "dd", NDD), (rd, "rd", 1))]
+    S = 1
+    if hm is not None or dd is not None:
+        labels = _device_fp32(labels, "labels")
+        if labels.dim() != 5 or tuple(labels.shape[2:]) != (NC, H, W) or labels.shape[0] != B:
+            raise ValueError("labels: expected [%d, S, 57, %d, %d], got %s" % (B, H, W, tuple(labels.shape)))
+        S = labels.shape[1]
+        valids = _valids_2d(valids, B)
+    else:
+        labels = valids = None
+    if rdepth is None:
+        rdepth = torch.zeros((B, 1, 3), dtype=torch.float32, device=given[0].device)
+    rdepth = _device_fp32(rdepth, "rdepth")
+    if rdepth.dim() != 3 or rdepth.shape[0] != B or rdepth.shape[2] != 3 or rdepth.shape[1] < 1:
+        raise ValueError("rdepth: expected [%d, R >= 1, 3], got %s" % (B, tuple(rdepth.shape)))
+    cfg = _Config(1, ohkm, topk, False, 1, B, S, rdepth.shape[1], H, W)
+    return _LossFunction.apply(cfg, labels, valids, rdepth, *tensors)
