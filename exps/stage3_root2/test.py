@@ -360,7 +360,7 @@ class _DryRunPipeline:
 
 
 def generate_3d_point_pairs(model, refine_model, data_loader, cfg, logger, device, output_dir="", pipeline_cls=None, eval_3d=False, eval_maps=False,
-                            maps_from_gt=False):
+                            maps_from_gt=False, eval_loss=False):
     os.makedirs(output_dir, exist_ok=True)
     source = {}
     if maps_from_gt:               # the batches carry no frames (AnnotationLoader): their maps are rendered from the annotations
@@ -377,6 +377,10 @@ def generate_3d_point_pairs(model, refine_model, data_loader, cfg, logger, devic
         evaluators["map_evaluator"] = EvalMaps(device)
     if model is not None:
         model.eval()
+    val_loss = None
+    if eval_loss:                  # the validation loss: SMAP.forward(imgs, valids, labels, rdepth) on every batch's own frames
+        from smap_amd.loss import ValidationLoss
+        val_loss = ValidationLoss(model, cfg, device)
     refine_w = None
     if refine_model is not None:
         refine_model.eval()
@@ -435,6 +439,8 @@ def generate_3d_point_pairs(model, refine_model, data_loader, cfg, logger, devic
             imgs = _NoFrames(len(img_path), cfg.dataset.INPUT_SHAPE)
         else:
             imgs = imgs.to(device, non_blocking=True).float().contiguous()
+        if val_loss is not None:                                 # before the padding: the batch's real frames, unmirrored, a forward of its own
+            val_loss.update(imgs, meta_data, scales)
         if not maps_from_gt and pipe is not None and len(imgs) < pipe.B:              # ragged last batch: pad with copies of its last frame and
             pad = pipe.B - len(imgs)                             # drop their records (tag None) -- no second engine / arena
             imgs = torch.cat([imgs, imgs[-1:].expand(pad, -1, -1, -1)], 0).contiguous()
@@ -488,6 +494,15 @@ def generate_3d_point_pairs(model, refine_model, data_loader, cfg, logger, devic
             for line in ev.log_lines(raw):                                      # calculate_and_log's lines (test_util_panoptic.py:388-400, :374-378)
                 logger.info(line)
             result.setdefault("error", {}).update(ev.result_entry(raw))
+    if val_loss is not None:
+        raw = val_loss.raw()                                                    # one read-back
+        if dist.is_initialized() and (dist.get_world_size() > 1 or os.environ.get("SMAP_FORCE_GATHER", "") == "1"):
+            raw = val_loss.merge_raws(gather_records(raw, device))
+        if rank == 0:
+            entry = val_loss.result_entry(raw)
+            logger.info("validation loss over {frames} frames in {batches} batches: total {total_loss:.6g}  2d {loss_2d:.6g}  bone {loss_bone:.6g}  "
+                        "root {loss_root:.6g}".format(**entry["loss"]))
+            result.setdefault("error", {}).update(entry)
     if rank == 0:
         dir_name = os.path.split(os.path.split(os.path.realpath(__file__))[0])[1]
         name = os.path.join(output_dir, "{}_{}_{}_{}.json".format(dir_name, cfg.TEST_MODE, cfg.DATA_MODE,
@@ -547,7 +562,17 @@ def main():
     parser.add_argument("--maps_from_gt", type=int, default=0, choices=[0, 1],
                         help="(addition) 1, with -t generate_result or generate_train: render the maps of every frame from its annotations "
                              "on the GPU (smap_amd/labels.py) instead of running the backbone: no checkpoint, no image file is read")
+    parser.add_argument("--eval_loss", type=int, default=0, choices=[0, 1],
+                        help="(addition) 1, with -t generate_result: the validation loss of the checkpoint (SMAP.forward with labels rendered "
+                             "from every batch's annotations) as frame-weighted means into error['loss'] of the result file.  One more "
+                             "forward per batch; the value depends on --batch_size, as the training log's does")
     args = parser.parse_args()
+    if args.eval_loss and args.test_mode != "generate_result":
+        parser.error("--eval_loss 1 requires -t generate_result")
+    if args.eval_loss and args.dry_run:
+        parser.error("--eval_loss 1 runs on the GPU: not available with --dry_run 1")
+    if args.eval_loss and args.maps_from_gt:
+        parser.error("--eval_loss 1 needs the network's heads: not available with --maps_from_gt 1")
     if args.maps_from_gt and args.test_mode == "run_inference":
         parser.error("--maps_from_gt 1 renders the maps from annotations: -t run_inference has none (use -t generate_result or generate_train)")
     if args.maps_from_gt and args.dry_run:
@@ -654,7 +679,7 @@ def main():
                 return
         result = generate_3d_point_pairs(model, refine_model, data_loader, cfg, logger, device,
                                          output_dir=os.path.join(cfg.OUTPUT_DIR, "result"), eval_3d=bool(args.eval_3d),
-                                         eval_maps=bool(args.eval_maps), maps_from_gt=bool(args.maps_from_gt))
+                                         eval_maps=bool(args.eval_maps), maps_from_gt=bool(args.maps_from_gt), eval_loss=bool(args.eval_loss))
         if dist.is_initialized():
             dist.destroy_process_group()
         if result.get("dropped_frames"):

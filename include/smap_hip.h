@@ -620,6 +620,38 @@ int smap_loss_finish_host(const double* sums, const float* valids, const float* 
                           int topk, int ctf, int single, int B, int R, int H, int W, double* result, double* m, double* sel, double* coef,
                           int32_t* root_cell, double* root_fac, double* part);
 
+/* ---- the same loss, forward only, from the heads WHERE THE ENGINE LEAVES THEM (validation loss: SMAP.forward with labels) ----
+ * An all-heads schedule (smap_amd/engine.py Graph(all_heads=True)) keeps the 36 head tensors at their units' own resolutions; the
+ * reference upsamples each to H x W (bilinear, align_corners) before it compares it with the labels.  smap_loss_forward_src does that
+ * interpolation inside the reduction: no upsampled map is written or read back.
+ * sources: HOST array of 3 * n_heads descriptors (n_heads = 4 * stage_num, no single-head mode), [3 * h + 0 / 1 / 2] = heatmap_2d (c = 43),
+ *   det_d (c = 14), root_d (c = 1) of head h.  Element (frame b, pixel y, x, channel ch) of a source is the fp32 number at
+ *   ptr[b * frame_stride + (y * w + x) * pix_stride + ch * ch_stride] (strides in floats): NHWC with a padded pixel
+ *   (ch_stride = 1, pix_stride >= c) or NCHW (pix_stride = 1, ch_stride >= h * w).  h <= H and w <= W; a source of height or width 1 is
+ *   legal, all its taps are index 0; a source of H x W is read as it is.  Frames 0 .. B - 1 are read, whatever lies behind them.
+ * Value at an output pixel: ATen's align-corners index rule in fp32 and l0y * (l0x * v00 + l1x * v01) + l1y * (l0x * v10 + l1x * v11),
+ *   every operation rounded once -- the expression of the engine's head sum.  root_d is read the same way at the rows' cells.
+ * Everything else (labels, valids, rdepth, the integers, result) as smap_loss_forward.  The workspace begins with smap_loss_forward's
+ *   layout (sums, ..., rd_at, root_cell: what the shared finish launch reads and writes) followed by the per-chunk partial sums
+ *   f64 [n_heads][B][ceil(H * W / 256)][57]; smap_loss_src_workspace_bytes has its size.  It does not feed smap_loss_backward: no gradient.
+ * Three launches on `stream` (reduce: one workgroup per (256 output pixels, frame, head) over all 57 channels; fold: the chunks in
+ *   order; finish), no atomics: the same bits run to run, and a frame's sums depend on that frame only.  No allocation, no
+ *   synchronisation.
+ * SMAP_E_ARG: as smap_loss_forward, and: a null or misaligned source pointer, c other than 43 / 14 / 1, a size below 1 or above H x W,
+ *   strides that are neither of the two orders. */
+struct smap_head_src {
+    const float* ptr;
+    int32_t h, w, c;
+    int32_t pix_stride, ch_stride;
+    int32_t reserved;
+    int64_t frame_stride;
+};
+int smap_sizeof_head_src(void);
+int64_t smap_loss_src_workspace_bytes(int n_heads, int B, int R, int H, int W);
+int smap_loss_forward_src(const struct smap_head_src* sources, const float* labels, const float* valids, const float* rdepth, int stage_num,
+                          int ohkm, int topk, int ctf, int B, int S, int R, int H, int W, void* workspace, int64_t workspace_bytes,
+                          float* result, void* stream);
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif

@@ -10,12 +10,22 @@
 //             zero is written as zeros without reading anything.  The root_d plane is zeroed, then ONE thread adds its frame's rows in
 //             order, so two persons on one cell add up the same way every time.
 // The 3 * n_heads tensor pointers travel by value in the kernel arguments (HeadPtrs), as smap_preprocess_batch passes its frames.
+//
+// smap_loss_forward_src: the same value with every head read where the engine left it (SrcTable: pointer, size and strides per tensor, by
+// value too), at its own resolution, interpolated to H x W on the fly -- three launches:
+//   reduce_src  one workgroup per (chunk of 256 output pixels, frame, head), all 57 channels: 64 pixels at a time, the source values (16-byte
+//               reads of four channels where the source is pixel-major, the tap expression of plan.hip's head_source4) go through an LDS
+//               transpose, then wave w owns channels w, w + 4, ... and lane l pixel l, so a label row is read 256 bytes at a time; fifteen
+//               double accumulators per lane, folded over the lanes once at the end -> partial [head][frame][chunk][57].
+//   fold_src    one workgroup per (frame, head): the chunks' partials added in chunk order -> sums; root_d at the frame's rows.
+//   finish      as above.
 // Compiled with -ffp-contract=off: every operation rounds once, in the order written.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "smap_hip.h"
 #include "hip_rc.h"
 #include "loss_core.h"
+#include "plan.h"            // lerp_index: the bilinear align-corners index rule the engine's kernels use
 
 namespace {
 
@@ -88,6 +98,132 @@ __global__ __launch_bounds__(NT) void loss_reduce_kernel(HeadPtrs hp, const floa
     if ((t & 63) == 0) s_part[t >> 6] = acc;
     __syncthreads();
     if (t == 0) sums[((int64_t)h * p.B + b) * NC + c] = ((s_part[0] + s_part[1]) + s_part[2]) + s_part[3];
+}
+
+// ---- the reduction from head sources ---------------------------------------------------------------------------------------------
+struct Src {
+    const float* p;          // element (frame b, pixel y, x, channel c) = p[b * frame + (y * w + x) * pix + c * ch]
+    int h, w, pix, ch;
+    long long frame;
+};
+struct SrcTable { Src s[3 * MAX_HEADS]; };      // [3 * h + 0 / 1 / 2] = heatmap_2d, det_d, root_d of head h
+
+constexpr int SRC_SUB = 64, SRC_CHUNK = 256, SRC_ROWS = (NC + 3) / 4, SRC_LD = SRC_SUB + 1;
+
+// 16-byte reads of four channels: channel-contiguous, every pixel 16-byte aligned, the pixel wide enough for the last group
+__device__ __forceinline__ bool src_vec(const Src& s, int c)
+{
+    return s.ch == 1 && !(s.pix & 3) && s.pix >= ((c + 3) & ~3) && !(s.frame & 3) && !((uintptr_t)s.p & 15);
+}
+
+// the source's bilinear (align_corners) image at output pixel (y, x), channel c: ATen's index rule (lerp_index) and the tap expression of
+// head_source4 (csrc/plan.hip); a source at the output's size is read as it is, one of height or width 1 has all its taps at index 0
+__device__ __forceinline__ float src_value1(const Src& s, int b, int y, int x, int c, int H, int W)
+{
+    const float* base = s.p + (int64_t)b * s.frame + (int64_t)c * s.ch;
+    if (s.h == H && s.w == W) return base[((int64_t)y * W + x) * s.pix];
+    const Lerp ly = lerp_index(y, s.h, H), lx = lerp_index(x, s.w, W);
+    const float v00 = base[((int64_t)ly.i0 * s.w + lx.i0) * s.pix], v01 = base[((int64_t)ly.i0 * s.w + lx.i1) * s.pix];
+    const float v10 = base[((int64_t)ly.i1 * s.w + lx.i0) * s.pix], v11 = base[((int64_t)ly.i1 * s.w + lx.i1) * s.pix];
+    return ly.l0 * (lx.l0 * v00 + lx.l1 * v01) + ly.l1 * (lx.l0 * v10 + lx.l1 * v11);
+}
+__device__ __forceinline__ float4 src_value4(const Src& s, int b, int y, int x, int c, int H, int W)
+{
+    const float* base = s.p + (int64_t)b * s.frame + c;
+    if (s.h == H && s.w == W) return *reinterpret_cast<const float4*>(base + ((int64_t)y * W + x) * s.pix);
+    const Lerp ly = lerp_index(y, s.h, H), lx = lerp_index(x, s.w, W);
+    const float4 v00 = *reinterpret_cast<const float4*>(base + ((int64_t)ly.i0 * s.w + lx.i0) * s.pix);
+    const float4 v01 = *reinterpret_cast<const float4*>(base + ((int64_t)ly.i0 * s.w + lx.i1) * s.pix);
+    const float4 v10 = *reinterpret_cast<const float4*>(base + ((int64_t)ly.i1 * s.w + lx.i0) * s.pix);
+    const float4 v11 = *reinterpret_cast<const float4*>(base + ((int64_t)ly.i1 * s.w + lx.i1) * s.pix);
+    float4 up;
+    up.x = ly.l0 * (lx.l0 * v00.x + lx.l1 * v01.x) + ly.l1 * (lx.l0 * v10.x + lx.l1 * v11.x);
+    up.y = ly.l0 * (lx.l0 * v00.y + lx.l1 * v01.y) + ly.l1 * (lx.l0 * v10.y + lx.l1 * v11.y);
+    up.z = ly.l0 * (lx.l0 * v00.z + lx.l1 * v01.z) + ly.l1 * (lx.l0 * v10.z + lx.l1 * v11.z);
+    up.w = ly.l0 * (lx.l0 * v00.w + lx.l1 * v01.w) + ly.l1 * (lx.l0 * v10.w + lx.l1 * v11.w);
+    return up;
+}
+
+// grid (chunks, B, n_heads).  partial [n_heads][B][chunks][57].  acc[] is indexed by unrolled loops only: registers, no private array
+// with a run-time index (EXPERIMENTS R3.6).
+__global__ __launch_bounds__(NT) void loss_reduce_src_kernel(SrcTable tab, const float* __restrict__ labels, Params p,
+                                                              double* __restrict__ partial)
+{
+    __shared__ float tile[NC * SRC_LD];
+    const int chunk = blockIdx.x, chunks = gridDim.x, b = blockIdx.y, h = blockIdx.z, t = threadIdx.x, wave = t >> 6, lane = t & 63;
+    const int HW = p.H * p.W;
+    const Src s2 = tab.s[3 * h], sd = tab.s[3 * h + 1];
+    const bool vec = src_vec(s2, N2D) && src_vec(sd, NDD);                       // uniform over the workgroup
+    const float* lab = labels + ((int64_t)b * p.S + head_scale(p, h)) * NC * HW;
+    double acc[SRC_ROWS];
+#pragma unroll
+    for (int k = 0; k < SRC_ROWS; ++k) acc[k] = 0.0;
+    const int last = min(HW, (chunk + 1) * SRC_CHUNK);
+    for (int pix0 = chunk * SRC_CHUNK; pix0 < last; pix0 += SRC_SUB) {
+        if (vec) {                                                               // item = (pixel, group of four channels): 12 + 4 groups
+            for (int idx = t; idx < SRC_SUB * 16; idx += NT) {
+                const int px = idx >> 4, g = idx & 15, pix = pix0 + px;
+                if (pix >= HW) continue;
+                const int y = pix / p.W, x = pix - y * p.W;
+                const bool flat = g < 12;
+                const int c = flat ? 4 * g : 4 * (g - 12), n = flat ? N2D : NDD, row = flat ? c : N2D + c;
+                if (c >= n) continue;                                            // (the twelfth group of the 43 channels)
+                const float4 v = flat ? src_value4(s2, b, y, x, c, p.H, p.W) : src_value4(sd, b, y, x, c, p.H, p.W);
+                tile[row * SRC_LD + px] = v.x;
+                if (c + 1 < n) tile[(row + 1) * SRC_LD + px] = v.y;
+                if (c + 2 < n) tile[(row + 2) * SRC_LD + px] = v.z;
+                if (c + 3 < n) tile[(row + 3) * SRC_LD + px] = v.w;
+            }
+        } else {                                                                 // item = (channel, pixel), pixels fastest
+            for (int idx = t; idx < NC * SRC_SUB; idx += NT) {
+                const int c = idx >> 6, px = idx & 63, pix = pix0 + px;
+                if (pix >= HW) continue;
+                const int y = pix / p.W, x = pix - y * p.W;
+                tile[c * SRC_LD + px] = c < N2D ? src_value1(s2, b, y, x, c, p.H, p.W) : src_value1(sd, b, y, x, c - N2D, p.H, p.W);
+            }
+        }
+        __syncthreads();
+        const int pix = pix0 + lane;
+        if (pix < HW) {
+#pragma unroll
+            for (int k = 0; k < SRC_ROWS; ++k) {
+                const int c = wave + 4 * k;
+                if (c < NC) {
+                    const float d = tile[c * SRC_LD + lane] - lab[(int64_t)label_channel(c) * HW + pix];
+                    acc[k] += (double)d * (double)d;
+                }
+            }
+        }
+        __syncthreads();
+    }
+#pragma unroll
+    for (int k = 0; k < SRC_ROWS; ++k) {
+        double a = acc[k];
+        for (int o = 32; o > 0; o >>= 1) a += __shfl_down(a, o, 64);
+        const int c = wave + 4 * k;
+        if (lane == 0 && c < NC) partial[((((int64_t)h * p.B + b) * chunks) + chunk) * NC + c] = a;
+    }
+}
+
+// grid (B, n_heads), 64 threads: the chunks in order; root_d at the frame's rows (a row outside the map is never dereferenced)
+__global__ __launch_bounds__(64) void loss_fold_src_kernel(SrcTable tab, const float* __restrict__ rdepth, Params p,
+                                                           const double* __restrict__ partial, int chunks, double* __restrict__ sums,
+                                                           float* __restrict__ rd_at, int32_t* __restrict__ root_cell)
+{
+    const int b = blockIdx.x, h = blockIdx.y, t = threadIdx.x;
+    const int64_t frame = (int64_t)h * p.B + b;
+    if (t < NC) {
+        const double* q = partial + frame * chunks * NC + t;
+        double s = 0.0;
+        for (int i = 0; i < chunks; ++i) s += q[(int64_t)i * NC];
+        sums[frame * NC + t] = s;
+    }
+    const Src sr = tab.s[3 * h + 2];
+    for (int r = t; r < p.R; r += 64) {
+        const int cell = root_row_cell(p, rdepth + ((int64_t)b * p.R + r) * 3);
+        rd_at[frame * p.R + r] = cell >= 0 ? src_value1(sr, b, cell / p.W, cell % p.W, 0, p.H, p.W) : 0.0f;
+        root_cell[frame * p.R + r] = cell;
+    }
 }
 
 // ---- finish: csrc/loss_core.h, one workgroup ---------------------------------------------------------------------------------------
@@ -213,6 +349,10 @@ int take_heads(const void* const* heads, Params& p, HeadPtrs& hp, const float* l
     return 0;
 }
 
+// smap_loss_forward_src's workspace: the layout above, then partial [n_heads][B][chunks][57] f64
+int src_chunks(int H, int W) { return (H * W + SRC_CHUNK - 1) / SRC_CHUNK; }
+int64_t src_partial_offset(int n_heads, int B, int R) { return workspace_layout(n_heads, B, R).bytes; }
+
 }  // namespace
 
 extern "C" {
@@ -243,6 +383,51 @@ int smap_loss_forward(const void* const* heads, const float* labels, const float
     else
         hipLaunchKernelGGL(loss_reduce_kernel<false>, grid, dim3(NT), 0, (hipStream_t)stream, hp, labels, rdepth, p, (double*)(ws + w.sums),
                            (float*)(ws + w.rd_at), (int32_t*)(ws + w.root_cell));
+    if (hipError_t e = hipGetLastError(); e != hipSuccess) return hip_rc(e);
+    hipLaunchKernelGGL(loss_finish_kernel, dim3(1), dim3(FINISH_NT), 0, (hipStream_t)stream, p, valids, rdepth, ws, result);
+    return hip_rc(hipGetLastError());
+}
+
+int smap_sizeof_head_src(void) { return (int)sizeof(smap_head_src); }
+
+int64_t smap_loss_src_workspace_bytes(int n_heads, int B, int R, int H, int W)
+{
+    if (n_heads < 1 || n_heads > MAX_HEADS || B < 1 || B > 65535 || R < 1 || R > 65535 || H < 1 || W < 1 || (int64_t)H * W > (1 << 24))
+        return SMAP_E_ARG;
+    return src_partial_offset(n_heads, B, R) + (int64_t)n_heads * B * src_chunks(H, W) * NC * 8;
+}
+
+int smap_loss_forward_src(const smap_head_src* sources, const float* labels, const float* valids, const float* rdepth, int stage_num,
+                          int ohkm, int topk, int ctf, int B, int S, int R, int H, int W, void* workspace, int64_t workspace_bytes,
+                          float* result, void* stream)
+{
+    Params p = make_params(stage_num, ohkm, topk, ctf, 0, B, S, R, H, W);
+    if (check_params(p) || !sources || !labels || !valids || !rdepth || !workspace || !result || ((uintptr_t)workspace & 7))
+        return SMAP_E_ARG;
+    SrcTable tab{};
+    for (int i = 0; i < 3 * p.n_heads; ++i) {
+        const smap_head_src& s = sources[i];
+        const int c = i % 3 == 0 ? N2D : (i % 3 == 1 ? NDD : 1);
+        if (!s.ptr || ((uintptr_t)s.ptr & 3) || s.h < 1 || s.w < 1 || s.h > H || s.w > W || s.c != c || s.pix_stride < 1 || s.ch_stride < 1 ||
+            s.frame_stride < 1)
+            return SMAP_E_ARG;
+        // the strides describe a tensor that does not fold onto itself: channel-minor (NHWC, padded or not) or pixel-minor (NCHW) order
+        const int64_t px = (int64_t)s.h * s.w;
+        const bool nhwc = s.ch_stride == 1 && s.pix_stride >= c && s.frame_stride >= px * s.pix_stride;
+        const bool nchw = s.pix_stride == 1 && s.ch_stride >= px && s.frame_stride >= (int64_t)c * s.ch_stride;
+        if (!nhwc && !nchw) return SMAP_E_ARG;
+        tab.s[i] = Src{s.ptr, s.h, s.w, s.pix_stride, s.ch_stride, (long long)s.frame_stride};
+    }
+    const Workspace w = workspace_layout(p.n_heads, B, R);
+    const int chunks = src_chunks(H, W);
+    if (workspace_bytes < smap_loss_src_workspace_bytes(p.n_heads, B, R, H, W)) return SMAP_E_ARG;
+    char* ws = (char*)workspace;
+    double* partial = (double*)(ws + src_partial_offset(p.n_heads, B, R));
+    hipLaunchKernelGGL(loss_reduce_src_kernel, dim3((unsigned)chunks, (unsigned)B, (unsigned)p.n_heads), dim3(NT), 0, (hipStream_t)stream, tab,
+                       labels, p, partial);
+    if (hipError_t e = hipGetLastError(); e != hipSuccess) return hip_rc(e);
+    hipLaunchKernelGGL(loss_fold_src_kernel, dim3((unsigned)B, (unsigned)p.n_heads), dim3(64), 0, (hipStream_t)stream, tab, rdepth, p, partial,
+                       chunks, (double*)(ws + w.sums), (float*)(ws + w.rd_at), (int32_t*)(ws + w.root_cell));
     if (hipError_t e = hipGetLastError(); e != hipSuccess) return hip_rc(e);
     hipLaunchKernelGGL(loss_finish_kernel, dim3(1), dim3(FINISH_NT), 0, (hipStream_t)stream, p, valids, rdepth, ws, result);
     return hip_rc(hipGetLastError());

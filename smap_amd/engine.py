@@ -9,7 +9,8 @@ What the schedule does differently from a layer-by-layer replay (all exact up to
 floating-point rounding):
   * eval-mode BatchNorm is folded into the conv weights / bias (smap.py:13-45);
   * heads that the inference branch never returns are not computed (smap.py:417-419 uses
-    only stage-2 res2..4, res_d4, res_rd4): 62 of the 268 convs;
+    only stage-2 res2..4, res_d4, res_rd4): 62 of the 268 convs -- unless the schedule is built with all_heads=True (the validation
+    loss, DESIGN.md section 14), which adds them and keeps all 36 head tensors;
   * `up_conv(bilinear_up(x))` (smap.py:214-215) is evaluated as `bilinear_up(up_conv(x))`:
     a 1x1 conv + per-channel affine commutes with the (convex, per-channel) bilinear
     resampling, which moves the 256->256 GEMM to the 4x smaller grid;
@@ -448,13 +449,17 @@ def arena_budget(device):
 
 class Graph:
     def __init__(self, sd, B, H, W, stage_num=3, chl=256, kpt_paf=43, paf=14, keep_ref=False, precision="f16",
-                 flip_pair=None, build=True, scaled_hms=False):
+                 flip_pair=None, build=True, scaled_hms=False, all_heads=False):
         """build=False: an EMPTY schedule with all the book-keeping in place (single-op harnesses of tests / tools append to it with
         Graph.tensor / conv / conv_seg and then allocate() / emit()).
         flip_pair (43 ints: KEYPOINT.FLIP_ORDER + [15 + c for c in PAF.FLIP_CHANNEL]) switches the flip-TTA of
         test.py:55-70 on INSIDE the schedule: B input frames run as a 2B batch whose second half the stem reads mirrored,
         and the head sum merges the mirrored maps back (no flipped copy of the images, no separate merge pass); the
-        depth heads, which the reference takes from the un-mirrored pass only, run on the first B frames."""
+        depth heads, which the reference takes from the un-mirrored pass only, run on the first B frames.
+        all_heads: every Upsample_unit of every stage also runs its three head chains (smap.py:221-229: res_conv1 -> res_conv2,
+        res_d_conv1 -> res_d_conv2, res_rd_conv1 -> res_rd_conv2) -- the 62 convs the inference schedule leaves out -- and keeps the 36
+        results as fp32 tensors at the unit's own resolution to the end of the schedule (Graph.head_tensors: what the validation loss
+        reads).  The launches the inference outputs come from are the default schedule's, unchanged."""
         assert precision in PRECISIONS, precision
         self.precision, self.x3 = precision, precision == "x3"
         self.keep_ref = keep_ref
@@ -462,6 +467,10 @@ class Graph:
         # scaled_hms: the head sum stores hms / 255 (key points) and / 127 (PAFs), i.e. the maps as test.py:111-112 hands them to the
         # association (smap_op.scale_hms) -- what the pipelines ask for; SMAP.forward keeps the raw maps of smap.py:417-419
         self.scaled_hms = bool(scaled_hms)
+        self.all_heads = bool(all_heads)
+        self.convs = []                       # state-dict prefix of every conv of the reference the schedule computes, in build order
+        self.head_tensors = {}                # all_heads: (stage, unit) -> {"heatmap_2d" | "det_d" | "root_d": Tensor, or None = the output buffer's map}
+        self.keep = []                        # tensors that stay allocated to the end of the schedule whoever reads them (allocate)
         self.frames = B                       # frames of the input / output
         if self.flip_pair is not None:
             assert len(self.flip_pair) == kpt_paf
@@ -483,6 +492,10 @@ class Graph:
             self._build()
 
     # -- helpers
+    def _fold(self, prefix):
+        self.convs.append(prefix)
+        return fold_conv_bn(self.sd, prefix)
+
     def tensor(self, name, H, W, C, esize=2):
         t = Tensor(name, self.B, H, W, C, esize, 2 if (self.x3 and esize == 2) else 1)
         self.tensors.append(t)
@@ -632,7 +645,7 @@ class Graph:
              in_c_off=0, cin=None, out_fp32=False, up=None, frames=None):
         """One conv launch; `prefixes` (list) are concatenated along Cout (shared input).  frames: run on the first
         `frames` frames of the batch only (flip-TTA: heads whose mirrored half nobody reads)."""
-        ws, bs = zip(*[fold_conv_bn(self.sd, p) for p in prefixes])
+        ws, bs = zip(*[self._fold(p) for p in prefixes])
         w, b = torch.cat(ws, 0), torch.cat(bs, 0)
         cout, cin_w = w.shape[0], w.shape[1]
         cin = cin or x.C
@@ -681,7 +694,7 @@ class Graph:
         """relu(conv1(x)) + relu(conv2(x2)) as ONE launch and ONE tensor (include/smap_hip.h smap_op.in2_mode = 1): the two inter-stage skips of an
         Upsample_unit, skip1 on the unit's input and skip2 on its output (smap.py:218-241), which the next stage only ever ADDS to its feature map
         (smap.py:142-153).  One write and one read of an in_planes-wide tensor less per level; each conv keeps its own power-of-two scale."""
-        (w1, b1), (w2, b2) = fold_conv_bn(self.sd, pre1), fold_conv_bn(self.sd, pre2)
+        (w1, b1), (w2, b2) = self._fold(pre1), self._fold(pre2)
         cout, c1, c2 = w1.shape[0], w1.shape[1], w2.shape[1]
         assert w2.shape[0] == cout and w1.shape[2] == 1 == w2.shape[2] and c1 == x.C and c2 == x2.C and cout % 8 == 0 and (x.H, x.W) == (x2.H, x2.W)
         M, K = self.B * x.H * x.W, c1 + c2
@@ -706,8 +719,8 @@ class Graph:
         res_rd_conv1 -> res_rd_conv2 -- with the per-pixel half of that 3x3 inside its epilogue (include/smap_hip.h smap_op.tap_n): the launch
         stores t[m][k] = <w3[k], y[m]>, nine fp32 numbers per pixel, instead of the 256-channel activation; Graph.tapsum finishes the conv.
         Returns (t tensor, bias of the 3x3)."""
-        w1, b1 = fold_conv_bn(self.sd, pre1)
-        w3, b3 = fold_conv_bn(self.sd, pre3)
+        w1, b1 = self._fold(pre1)
+        w3, b3 = self._fold(pre3)
         cout, cin = w1.shape[0], w1.shape[1]
         assert cout == 256 == w3.shape[1] and w3.shape[0] == 1 and w3.shape[2] == 3 and cin == x.C and w1.shape[2] == 1
         tile = tile_ids(cap="tapdot", x3=self.x3)[0]
@@ -742,7 +755,7 @@ class Graph:
         stride `stride2`) as ONE launch: out = act(W1 x + W2 x2 + b1 + b2) -- smap.py:60-77 adds the shortcut's output before the ReLU, no
         activation in between, so the two GEMMs share their accumulators when K is the concatenation of both inputs' channels
         (include/smap_hip.h smap_op.in2_*).  The shortcut tensor is never written or read back and its launch disappears."""
-        (w1, b1), (w2, b2) = fold_conv_bn(self.sd, pre1), fold_conv_bn(self.sd, pre2)
+        (w1, b1), (w2, b2) = self._fold(pre1), self._fold(pre2)
         cout, c1, c2 = w1.shape[0], w1.shape[1], w2.shape[1]
         assert w2.shape[0] == cout and w1.shape[2] == 1 == w2.shape[2] and c1 == x.C and c2 == x2.C and cout % 8 == 0
         Ho, Wo = x.H, x.W
@@ -770,7 +783,7 @@ class Graph:
         its own power-of-two scale in split precision, so every conv computes exactly what its own launch would.  Returns the
         output tensors in order."""
         assert 2 <= len(segs) <= 3
-        folded = [fold_conv_bn(self.sd, pre) for _, pre, _ in segs]
+        folded = [self._fold(pre) for _, pre, _ in segs]
         cin = x.C
         couts = [w.shape[0] for w, _ in folded]
         assert all(w.shape[1] == cin and w.shape[2] == 1 for w, _ in folded) and all(c % 8 == 0 for c in couts)
@@ -823,8 +836,8 @@ class Graph:
     def conv_tail(self, name, pre3, pre1, x, tile, res=None, add1=None, add2=None):
         """A Bottleneck's 3x3 stride-1 conv (prefix pre3, bias + ReLU) and the 1x1 behind it (prefix pre1, + res, ReLU, + add1,
         + add2) as ONE launch (csrc/convf.hip, the "tail" tile ids): the 3x3's output never leaves the CU."""
-        w3, b3 = fold_conv_bn(self.sd, pre3)
-        w1, b1 = fold_conv_bn(self.sd, pre1)
+        w3, b3 = self._fold(pre3)
+        w1, b1 = self._fold(pre1)
         P, cin = w3.shape[0], w3.shape[1]
         cout = w1.shape[0]
         bn2 = TAIL_BN[tile]
@@ -848,10 +861,10 @@ class Graph:
         """The FIRST Bottleneck of layer1 (smap.py:48-77 with the 1x1 shortcut conv of :124-129; 64 input channels, stride 1) as ONE
         launch (csrc/convb.hip, the "block" tile ids with first = True): relu(c3(c2(c1(x))) + downsample(x)); x is read once."""
         assert self.x3
-        w1, b1 = fold_conv_bn(self.sd, pre + ".conv_bn_relu1")
-        w3, b3 = fold_conv_bn(self.sd, pre + ".conv_bn_relu2")
-        wt, bt = fold_conv_bn(self.sd, pre + ".conv_bn_relu3")
-        wd, bd = fold_conv_bn(self.sd, pre + ".downsample")
+        w1, b1 = self._fold(pre + ".conv_bn_relu1")
+        w3, b3 = self._fold(pre + ".conv_bn_relu2")
+        wt, bt = self._fold(pre + ".conv_bn_relu3")
+        wd, bd = self._fold(pre + ".downsample")
         P, Cin = w1.shape[0], w1.shape[1]
         C = wt.shape[0]
         assert P == 64 == Cin == x.C and C == 256 and tuple(wd.shape[:2]) == (C, Cin) and wd.shape[2] == 1 and w3.shape[2] == 3
@@ -879,9 +892,9 @@ class Graph:
         ReLU, + add1, + add2) as ONE launch (csrc/convb.hip / convc.hip, the "block" tile ids, split precision): x is read once, the two
         intermediates and the residual never leave the CU."""
         assert self.x3, "the whole-block kernel has a split-precision instance only"
-        w1, b1 = fold_conv_bn(self.sd, pre + ".conv_bn_relu1")
-        w3, b3 = fold_conv_bn(self.sd, pre + ".conv_bn_relu2")
-        wt, bt = fold_conv_bn(self.sd, pre + ".conv_bn_relu3")
+        w1, b1 = self._fold(pre + ".conv_bn_relu1")
+        w3, b3 = self._fold(pre + ".conv_bn_relu2")
+        wt, bt = self._fold(pre + ".conv_bn_relu3")
         P, C = w1.shape[0], w1.shape[1]
         bn2 = TAIL_BN[tile]
         assert P == TILES[tile][1] and C == 4 * P == x.C == wt.shape[0] and w3.shape[:2] == (P, P) and w3.shape[2] == 3 and wt.shape[1] == P
@@ -922,7 +935,7 @@ class Graph:
     def _build(self):
         B, H, W, sd = self.B, self.H, self.W, self.sd
         # ResNet_top (smap.py:80-92)
-        w, b = fold_conv_bn(sd, "top.conv")
+        w, b = self._fold("top.conv")
         stem_scale = 1.0
         if self.x3:
             hi, lo, stem_scale = split_f16(w.permute(0, 2, 1, 3).reshape(64, 21, 7))
@@ -1075,6 +1088,7 @@ class Graph:
                     elif ind >= 1:
                         with self.on_lane(1):     # the 3x3 head of this unit runs beside the next unit's launches
                             head_t[f"res{ind + 1}"] = self.conv(u + ".res", [u + ".res_conv2"], got[u + ".res1"], 3, relu=False, out_fp32=True)
+                self._train_heads(s, ind, u, out, head_t if heads else {})
                 continue
             if ind == 0:
                 out = self.conv(u + ".out", [u + ".u_skip"], xin, relu=True)
@@ -1108,6 +1122,7 @@ class Graph:
                     m = self.conv(u + ".res1", [u + ".res_conv1"], out, relu=True)
                     head_t[f"res{ind + 1}"] = self.conv(u + ".res", [u + ".res_conv2"], m, 3, relu=False,
                                                         out_fp32=True)
+            self._train_heads(s, ind, u, out, head_t if heads else {})
         if heads:
             B, h, w = self.frames, self.out_h, self.out_w
             n_hms, n_d = self.kpt_paf, self.paf
@@ -1132,6 +1147,27 @@ class Graph:
                 else:
                     self.ops.append(Op(OP_HEADSUM, aux=[head_t["res_rd"]], p=dict(Cout=1, ext_off=self.out_layout["root_d"][0])))
         return cross, (s1 if gen_skip else None), (s2 if gen_skip else None)
+
+    def _train_heads(self, s, ind, u, out, head_t):
+        """all_heads: the head chains of unit `u` (stage s, up{ind + 1}) that the inference schedule does not run, on `out`, with the launches
+        the inference heads use: ONE 1x1 launch for the missing res_conv1 | res_d_conv1 | res_rd_conv1 (shared input, concatenated along
+        Cout), then a 3x3 per head on its channel slice, fp32 out at the unit's resolution.  head_t: what the unit has already (the last
+        stage's inference heads).  Flip-TTA: the first `frames` frames only, the loss never reads the mirrored half."""
+        if not self.all_heads:
+            return
+        have = {"heatmap_2d": head_t.get(f"res{ind + 1}"), "det_d": head_t.get("res_d") if ind == 3 else None,
+                "root_d": head_t.get("res_rd") if ind == 3 else None}
+        rd_in_output = ind == 3 and "res_rd_tap" in head_t       # tap-dot route: the map exists as the output buffer's NCHW block only
+        todo = [(key, nm) for key, nm in (("heatmap_2d", "res"), ("det_d", "res_d"), ("root_d", "res_rd"))
+                if have[key] is None and not (key == "root_d" and rd_in_output)]
+        if todo:
+            c = self.chl
+            m = self.conv(u + ".heads1x1", [f"{u}.{nm}_conv1" for _, nm in todo], out, relu=True, frames=self.frames)
+            for k, (key, nm) in enumerate(todo):
+                have[key] = self.conv(f"{u}.{nm}", [f"{u}.{nm}_conv2"], m, 3, relu=False, in_c_off=k * c, cin=c, out_fp32=True,
+                                      frames=self.frames)
+        self.head_tensors[(s, ind)] = have
+        self.keep += [t for t in have.values() if t is not None]
 
     # -- arena: liveness-based first-fit allocation
     def allocate(self, reuse=True):
@@ -1162,6 +1198,8 @@ class Graph:
                 t.last = n_last
         if self.kcount is not None:                                # the tickets of every split-K op: one region, alive for the whole schedule
             self.kcount.first, self.kcount.last = 0, len(self.ops) - 1
+        for t in self.keep:                                        # (all_heads: the loss reads the head tensors behind the schedule)
+            t.last = n_last
         every = self.tensors + self.scratch_tensors + ([self.kcount] if self.kcount is not None else [])
         # arena[k * WINDOW : k * WINDOW + ZERO_PAGE] are the conv kernels' zero pages (csrc/plan.hip): never allocated, so no
         # tensor crosses a window boundary and every conv input is within 32 bits of its window's base
@@ -1414,12 +1452,12 @@ def _schedule_env():
     return sorted((k, v) for k, v in os.environ.items() if k.startswith("SMAP_") and not k.startswith(skip))
 
 
-def plan_cache_key(sd, B, H, W, stage_num, chl, kpt_paf, paf, precision, flip_pair, scaled_hms):
+def plan_cache_key(sd, B, H, W, stage_num, chl, kpt_paf, paf, precision, flip_pair, scaled_hms, all_heads=False):
     import hashlib
     here = os.path.dirname(os.path.abspath(__file__))
     h = hashlib.blake2b(digest_size=16)
     h.update(repr((state_hash(sd), B, H, W, stage_num, chl, kpt_paf, paf, precision, tuple(flip_pair) if flip_pair is not None else None,
-                   bool(scaled_hms), _L.BLOB_VERSION, C.sizeof(_L.SmapOp), _L.version(), _schedule_env())).encode())
+                   bool(scaled_hms), _L.BLOB_VERSION, C.sizeof(_L.SmapOp), _L.version(), _schedule_env(), bool(all_heads))).encode())
     for f in ("engine.py", "tile_table.json", "tile_table_x3.json"):      # the schedule builder and its tables
         h.update(open(os.path.join(here, f), "rb").read())
     tt = os.environ.get("SMAP_TILE_TABLE_X3") or os.environ.get("SMAP_TILE_TABLE")
@@ -1428,19 +1466,42 @@ def plan_cache_key(sd, B, H, W, stage_num, chl, kpt_paf, paf, precision, flip_pa
     return h.hexdigest()
 
 
+HeadSource = namedtuple("HeadSource", "ptr h w c pix_stride ch_stride frame_stride")
+HEAD_KEYS = (("heatmap_2d", "kpt_paf"), ("det_d", "paf"), ("root_d", None))
+
+
+def graph_head_sources(g, arena_ptr=0, out_ptr=0):
+    """BackboneEngine.head_sources of an allocated all_heads Graph whose arena and output buffer start at these addresses."""
+    res = []
+    for s in range(g.stage_num):
+        for ind in range(4):
+            d = {}
+            for key, attr in HEAD_KEYS:
+                t, c = g.head_tensors[(s, ind)][key], (getattr(g, attr) if attr else 1)
+                if t is not None:            # fp32 NHWC in the arena
+                    assert t.esize == 4 and t.off >= 0 and t.C >= c
+                    d[key] = HeadSource(arena_ptr + t.off, t.H, t.W, c, t.C, 1, t.H * t.W * t.C)
+                else:                        # the [frames, 1, h, w] block of the output buffer
+                    hw = g.out_h * g.out_w
+                    d[key] = HeadSource(out_ptr + g.out_layout[key][0], g.out_h, g.out_w, c, 1, hw, c * hw)
+            res.append(d)
+    return res
+
+
 # ----------------------------------------------------------------------------- engine
 class BackboneEngine:
     """Device-resident schedule for one (B, H, W): weights, arena, output buffer, plan."""
 
     def __init__(self, state_dict, B, H, W, device, stage_num=3, chl=256, kpt_paf=43, paf=14, reuse=True,
-                 precision="f16", flip_pair=None, scaled_hms=False):
+                 precision="f16", flip_pair=None, scaled_hms=False, all_heads=False):
         self.lib = _L.load()          # fails loudly when libsmap_hip.so is missing
         self.precision = precision
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise RuntimeError("BackboneEngine needs a ROCm GPU device (no CPU path in smap_amd)")
         sd = {k: v.detach().cpu() for k, v in state_dict.items()}
-        self._graph_args = (sd, B, H, W, stage_num, chl, kpt_paf, paf, precision, flip_pair, scaled_hms, reuse)
+        self._graph_args = (sd, B, H, W, stage_num, chl, kpt_paf, paf, precision, flip_pair, scaled_hms, reuse, bool(all_heads))
+        self.all_heads, self.stage_num = bool(all_heads), stage_num
         self._graph = None
         self.B, self.H, self.W = B, H, W
         self.kpt_paf, self.paf = kpt_paf, paf
@@ -1448,7 +1509,7 @@ class BackboneEngine:
         cdir = plan_cache_dir() if reuse else None         # (reuse=False: debugging layouts, never cached)
         meta = None
         if cdir is not None:
-            self.cache_key = plan_cache_key(sd, B, H, W, stage_num, chl, kpt_paf, paf, precision, flip_pair, scaled_hms)
+            self.cache_key = plan_cache_key(sd, B, H, W, stage_num, chl, kpt_paf, paf, precision, flip_pair, scaled_hms, all_heads)
             meta = self._load_cached(cdir)
         if meta is None:
             g = self.graph                                 # builds and allocates the schedule
@@ -1486,8 +1547,9 @@ class BackboneEngine:
         """The schedule as Python objects (ops, tensors, weight chunks).  An engine loaded from the plan cache builds it only when somebody
         asks (profiling tools, tests, blob()): the launches themselves need the plan handle alone."""
         if self._graph is None:
-            sd, B, H, W, stage_num, chl, kpt_paf, paf, precision, flip_pair, scaled_hms, reuse = self._graph_args
-            g = Graph(sd, B, H, W, stage_num, chl, kpt_paf, paf, precision=precision, flip_pair=flip_pair, scaled_hms=scaled_hms)
+            sd, B, H, W, stage_num, chl, kpt_paf, paf, precision, flip_pair, scaled_hms, reuse, all_heads = self._graph_args
+            g = Graph(sd, B, H, W, stage_num, chl, kpt_paf, paf, precision=precision, flip_pair=flip_pair, scaled_hms=scaled_hms,
+                      all_heads=all_heads)
             g.allocate(reuse=reuse)
             self._graph = g
         return self._graph
@@ -1616,6 +1678,16 @@ class BackboneEngine:
                 _L.check(self.lib.smap_plan_run_inputs(self.handle, ptrs, n, C.c_void_p(self.arena.data_ptr()),
                                                        C.c_void_p(self.weights.data_ptr()), outp, st), "smap_plan_run_inputs")
         return (self.hms, self.det_d, self.root_d) if out is None else self.views(out)
+
+    def head_sources(self, out=None):
+        """all_heads engines: where the loss reads the 36 head tensors of the last run into `out` (default: the engine's own buffer).
+        A list over heads h = 4 * stage + j (j = 0: up1, the coarsest) of {"heatmap_2d" | "det_d" | "root_d": HeadSource}: device pointer,
+        source height and width, channels, and the pixel, channel and frame strides in floats.  The heads are fp32 NHWC with the padded
+        channel stride the convs leave (48 | 16 | 8); the last stage's finest root-depth map of the tap-dot route is the NCHW block of
+        the output buffer (never scaled).  Flip-TTA: 2B frames lie behind each pointer, the first B are the unmirrored ones."""
+        if not self.all_heads:
+            raise RuntimeError("head_sources() needs an engine built with all_heads=True")
+        return graph_head_sources(self.graph, self.arena.data_ptr(), (self.out if out is None else out).data_ptr())
 
     def blob(self):
         """The whole schedule as one relocatable byte image (Graph.blob): what a host without this Python builder loads with

@@ -27,6 +27,7 @@ SYMBOLS = [
     "smap_sizeof_prep_frame", "smap_preprocess_batch",
     "smap_render_labels",
     "smap_loss_workspace_bytes", "smap_loss_forward", "smap_loss_backward", "smap_loss_finish_host",
+    "smap_sizeof_head_src", "smap_loss_src_workspace_bytes", "smap_loss_forward_src",
 ]
 MAX_INPUTS = 8                         # SMAP_MAX_INPUTS
 
@@ -103,6 +104,12 @@ class PrepFrame(C.Structure):
     """Mirror of `struct smap_prep_frame`."""
     _fields_ = [("src", C.c_void_p), ("h", C.c_int32), ("w", C.c_int32), ("nh", C.c_int32), ("nw", C.c_int32), ("top", C.c_int32),
                 ("left", C.c_int32), ("fx", C.c_double), ("fy", C.c_double)]
+
+
+class HeadSrc(C.Structure):
+    """Mirror of `struct smap_head_src`."""
+    _fields_ = [("ptr", C.c_void_p), ("h", C.c_int32), ("w", C.c_int32), ("c", C.c_int32), ("pix_stride", C.c_int32),
+                ("ch_stride", C.c_int32), ("reserved", C.c_int32), ("frame_stride", C.c_int64)]
 
 
 LABEL_C, LABEL_MAX_SCALES, LABEL_MAX_TAPS, LABEL_MAX_PERSONS = 57, 8, 16, 64      # SMAP_LABEL_*
@@ -183,14 +190,17 @@ def load():
     lib.smap_loss_forward.argtypes = [C.POINTER(vp), vp, vp, vp, ip, ip, ip, ip, ip, ip, ip, ip, ip, ip, vp, i64, vp, vp]
     lib.smap_loss_backward.argtypes = [C.POINTER(vp), vp, ip, ip, ip, ip, ip, ip, ip, ip, ip, ip, vp, i64, vp, vp, vp]
     lib.smap_loss_finish_host.argtypes = [vp, vp, vp, vp, ip, ip, ip, ip, ip, ip, ip, ip, ip, vp, vp, vp, vp, vp, vp, vp]
+    lib.smap_loss_src_workspace_bytes.argtypes = [ip, ip, ip, ip, ip]
+    lib.smap_loss_forward_src.argtypes = [C.POINTER(HeadSrc), vp, vp, vp, ip, ip, ip, ip, ip, ip, ip, ip, ip, vp, i64, vp, vp]
     for s in SYMBOLS:
         if s not in ("smap_version", "smap_plan_destroy", "smap_nms_workspace_bytes", "smap_jpeg_workspace_bytes",
-                     "smap_jpeg_huff_workspace_bytes", "smap_loss_workspace_bytes"):  # everything else returns int
+                     "smap_jpeg_huff_workspace_bytes", "smap_loss_workspace_bytes", "smap_loss_src_workspace_bytes"):  # everything else returns int
             getattr(lib, s).restype = ip
     lib.smap_nms_workspace_bytes.restype = C.c_int64
     lib.smap_jpeg_workspace_bytes.restype = C.c_int64
     lib.smap_jpeg_huff_workspace_bytes.restype = C.c_int64
     lib.smap_loss_workspace_bytes.restype = C.c_int64
+    lib.smap_loss_src_workspace_bytes.restype = C.c_int64
     if lib.smap_sizeof_op() != C.sizeof(SmapOp):
         raise ImportError(f"smap_op layout mismatch: C {lib.smap_sizeof_op()} vs ctypes {C.sizeof(SmapOp)}")
     if lib.smap_sizeof_jpeg_info() != C.sizeof(JpegInfo):
@@ -199,6 +209,8 @@ def load():
         raise ImportError(f"smap_jpeg_scan layout mismatch: C {lib.smap_sizeof_jpeg_scan()} vs ctypes {C.sizeof(JpegScan)}")
     if lib.smap_sizeof_prep_frame() != C.sizeof(PrepFrame):
         raise ImportError(f"smap_prep_frame layout mismatch: C {lib.smap_sizeof_prep_frame()} vs ctypes {C.sizeof(PrepFrame)}")
+    if lib.smap_sizeof_head_src() != C.sizeof(HeadSrc):
+        raise ImportError(f"smap_head_src layout mismatch: C {lib.smap_sizeof_head_src()} vs ctypes {C.sizeof(HeadSrc)}")
     _lib = lib
     return lib
 

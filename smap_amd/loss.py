@@ -12,6 +12,10 @@ Differences from the reference, on purpose:
   * a root-depth row with Z > 0 whose cell lies outside the map makes `total_loss` NaN (result[4] counts such rows; `strict=True`
     reads it -- one synchronisation -- and raises); the reference wraps around or raises an IndexError there.
   * there is no CPU path and no fallback: the tensors live on the GPU.
+
+`EngineLoss` is the same value, forward only, for the validation loss: it reads the 36 head tensors where an all-heads engine
+(smap_amd/engine.py, BackboneEngine(all_heads=True).head_sources()) leaves them, at their own resolutions, and interpolates to H x W inside
+the reduction (smap_loss_forward_src).  Its values carry no graph.
 """
 import ctypes as C
 
@@ -83,6 +87,36 @@ def forward_raw(cfg, tensors, labels, valids, rdepth):
         L.check(L.load().smap_loss_forward(_head_array(tensors), _ptr(labels), _ptr(valids), _ptr(rdepth), *cfg.head_args(), cfg.B, cfg.S,
                                            cfg.R, cfg.H, cfg.W, ws.data_ptr(), bytes_, result.data_ptr(),
                                            torch.cuda.current_stream(dev).cuda_stream), "smap_loss_forward")
+    return result, ws
+
+
+SOURCE_KEYS = (("heatmap_2d", N2D), ("det_d", NDD), ("root_d", 1))
+
+
+def source_workspace_bytes(n_heads, B, R, H, W):
+    """Bytes of smap_loss_forward_src's workspace: workspace_layout, then the per-chunk partial sums (csrc/loss.hip)."""
+    return workspace_layout(n_heads, B, R)["bytes"] + n_heads * B * ((H * W + 255) // 256) * NC * 8
+
+
+def forward_from_sources(cfg, sources, labels, valids, rdepth):
+    """smap_loss_forward_src on the current stream: (result [8] fp32, workspace uint8).  sources: n_heads dicts
+    {"heatmap_2d", "det_d", "root_d": (ptr, h, w, c, pix_stride, ch_stride, frame_stride)} (engine.HeadSource), strides in floats;
+    labels, valids, rdepth: checked device tensors.  No synchronisation, no graph."""
+    dev = rdepth.device
+    if cfg.single or len(sources) != cfg.n_heads:
+        raise ValueError("sources: %d heads for %d stages of 4" % (len(sources), cfg.stage_num))
+    arr = (L.HeadSrc * (3 * cfg.n_heads))()
+    for h, d in enumerate(sources):
+        for k, (key, _) in enumerate(SOURCE_KEYS):
+            ptr, sh, sw, c, pix, ch, frame = d[key]
+            arr[3 * h + k] = L.HeadSrc(int(ptr), int(sh), int(sw), int(c), int(pix), int(ch), 0, int(frame))
+    bytes_ = source_workspace_bytes(cfg.n_heads, cfg.B, cfg.R, cfg.H, cfg.W)
+    ws = torch.empty((bytes_,), dtype=torch.uint8, device=dev)
+    result = torch.empty((8,), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        L.check(L.load().smap_loss_forward_src(arr, _ptr(labels), _ptr(valids), _ptr(rdepth), cfg.stage_num, cfg.ohkm, cfg.topk, cfg.ctf,
+                                               cfg.B, cfg.S, cfg.R, cfg.H, cfg.W, ws.data_ptr(), bytes_, result.data_ptr(),
+                                               torch.cuda.current_stream(dev).cuda_stream), "smap_loss_forward_src")
     return result, ws
 
 
@@ -201,6 +235,112 @@ class SMAPLoss:
         return dict(total_loss=result[0], loss_2d=logged[1], loss_bone=logged[2], loss_root=logged[3])
 
     forward = __call__
+
+
+class EngineLoss:
+    """SMAP._calculate_loss, forward only, on the heads of an all-heads engine (the validation loss).
+
+        eng = model.engine(B, H, W, device, all_heads=True)
+        eng.run(imgs, out=out)
+        losses = EngineLoss.from_cfg(cfg)(eng.head_sources(out), valids, labels, rdepth)
+
+    sources: BackboneEngine.head_sources() (or n_heads dicts of HeadSource tuples describing any fp32 device tensors); valids, labels,
+    rdepth as SMAPLoss takes them.  Returns {'total_loss', 'loss_2d', 'loss_bone', 'loss_root'}: 0-d fp32 device tensors without
+    grad_fn.  Runs on the current stream behind whatever wrote the sources; no synchronisation."""
+
+    def __init__(self, stage_num=3, ohkm=True, topk=8, ctf=True):
+        self._rules = SMAPLoss(stage_num, ohkm, topk, ctf)
+
+    @classmethod
+    def from_cfg(cls, cfg):
+        return cls(cfg.MODEL.STAGE_NUM, cfg.LOSS.OHKM, cfg.LOSS.TOPK, cfg.LOSS.COARSE_TO_FINE)
+
+    def check(self, valids, labels, rdepth):
+        """(_Config, labels, valids, rdepth) of checked inputs: SMAPLoss's rules."""
+        r = self._rules
+        labels = _device_fp32(labels, "labels")
+        if labels.dim() != 5 or labels.shape[2] != NC or labels.shape[1] < 4 + int(r.ctf):
+            raise ValueError("labels: expected [B, S >= %d, 57, H, W], got %s" % (4 + int(r.ctf), tuple(labels.shape)))
+        B, S, _, H, W = labels.shape
+        valids = _valids_2d(valids, B)
+        rdepth = _device_fp32(rdepth, "rdepth")
+        if rdepth.dim() != 3 or rdepth.shape[0] != B or rdepth.shape[2] != 3 or rdepth.shape[1] < 1:
+            raise ValueError("rdepth: expected [%d, R >= 1, 3], got %s" % (B, tuple(rdepth.shape)))
+        for t in (valids, rdepth):
+            if t.device != labels.device:
+                raise ValueError("all tensors live on one GPU: labels on %s, another on %s" % (labels.device, t.device))
+        return _Config(r.stage_num, r.ohkm, r.topk, r.ctf, 0, B, S, rdepth.shape[1], H, W), labels, valids, rdepth
+
+    def raw(self, sources, valids, labels, rdepth):
+        """(result [8], workspace): result[4] counts the rows with Z > 0 outside the map (total_loss is NaN then)."""
+        cfg, labels, valids, rdepth = self.check(valids, labels, rdepth)
+        return forward_from_sources(cfg, sources, labels, valids, rdepth)
+
+    def __call__(self, sources, valids, labels, rdepth):
+        with torch.no_grad():
+            result, _ = self.raw(sources, valids, labels, rdepth)
+        return dict(total_loss=result[0], loss_2d=result[1], loss_bone=result[2], loss_root=result[3])
+
+
+class ValidationLoss:
+    """The validation loss of a run (exps/stage3_root2/test.py --eval_loss 1): per loader batch the labels, channel mask and root rows
+    are rendered from the batch's annotations as the training set's sample does (smap_amd/labels.py: render_labels, valid_vector,
+    root_depth_labels), the loss is model(imgs, valids, labels, rdepth), and the four values are accumulated ON THE DEVICE weighted by
+    the batch's frames.  The value depends on the batch size, as the training log's does: the root term and the hard-keypoint mining
+    are normalised per batch.  raw() is the run's one read-back."""
+
+    KEYS = ("total_loss", "loss_2d", "loss_bone", "loss_root")
+
+    def __init__(self, model, cfg, device):
+        from .labels import label_spec, valid_vector
+        self.model, self.device = model, torch.device(device)
+        self.spec = label_spec(cfg)
+        self.valid = torch.from_numpy(valid_vector(cfg.DATASET.NAME)[:, 0].astype(np.float32))      # ("MIX": the annotated sets carry every channel)
+        self.sums = torch.zeros((4,), dtype=torch.float64, device=self.device)
+        self.frames = self.batches = 0
+
+    def inputs(self, annotations, metas):
+        """(valids [B, 57], labels [B, S, 57, H, W], rdepth [B, MAX_PEOPLE, 3]) on the device for a batch's annotations [B][P, 15, C >= 8]
+        in network pixels (zero rows = padding) and its per-frame dicts with 'scale'.  Visibilities of joints outside the map as held
+        are cleared first (JointDataset.remove_illegal_joint; GtMapsSource does the same)."""
+        from .labels import render_labels, root_depth_labels
+        H, W = self.spec.shape
+        frames = []
+        for a in annotations:
+            a = np.array(a.numpy() if isinstance(a, torch.Tensor) else a, np.float64)
+            off = (a[:, :, 0] >= W * self.spec.stride) | (a[:, :, 0] < 0) | (a[:, :, 1] >= H * self.spec.stride) | (a[:, :, 1] < 0)
+            a[:, :, 3][off] = 0
+            frames.append(a)
+        labels = render_labels(frames, self.spec, device=self.device)
+        scale = lambda m: float(np.asarray(m["scale"] if isinstance(m, dict) else m).reshape(-1)[0])
+        rdepth = np.stack([root_depth_labels(a, scale(m), self.spec) for a, m in zip(frames, metas)]).astype(np.float32)
+        valids = self.valid[None].repeat(len(frames), 1)
+        return valids.to(self.device), labels, torch.from_numpy(rdepth).to(self.device)
+
+    def update(self, imgs, annotations, metas):
+        """One batch: imgs [B, 3, H, W] on the device -- the batch's real, unmirrored frames."""
+        valids, labels, rdepth = self.inputs(annotations, metas)
+        losses = self.model(imgs, valids, labels, rdepth)
+        n = int(imgs.shape[0])
+        self.sums += torch.stack([losses[k] for k in self.KEYS]).double() * n
+        self.frames += n
+        self.batches += 1
+        return losses
+
+    def raw(self):
+        """[sum of frames * total, ... * 2d, ... * bone, ... * root, frames, batches] as floats (synchronises)."""
+        return [float(v) for v in self.sums.cpu()] + [float(self.frames), float(self.batches)]
+
+    @staticmethod
+    def merge_raws(raws):
+        return [sum(col) for col in zip(*raws)]
+
+    def result_entry(self, raw=None):
+        raw = self.raw() if raw is None else raw
+        frames = raw[4]
+        entry = {k: (raw[i] / frames if frames else float("nan")) for i, k in enumerate(self.KEYS)}
+        entry.update(frames=int(frames), batches=int(raw[5]))
+        return {"loss": entry}
 
 
 def single_head_loss(hm=None, dd=None, rd=None, labels=None, valids=None, rdepth=None, ohkm=False, topk=8):

@@ -6,7 +6,9 @@ The module tree exists to own the checkpoint: strict `load_state_dict` of a refe
 checkpoint works because every parameter / buffer carries the reference's key
 (`top.conv.{conv,bn}.*`, `stageK.downsample.layerL.i.conv_bn_reluJ.*`, `stageK.upsample.upU.<head>.*`).
 There is no PyTorch forward here: `forward` needs eval mode and a ROCm device and raises
-otherwise (training - smap.py:355-401 - is out of scope).
+otherwise.  `forward(imgs, valids, labels, rdepth)` returns the reference's loss dict (smap.py:355-401) as VALUES, in eval mode
+(folded BN): the validation loss of a checkpoint.  Batch-statistics BN, the backward pass and gradients of any kind are out of
+scope.
 """
 import os
 
@@ -138,29 +140,36 @@ class SMAP(nn.Module):
         self.invalidate_engine()
         return super()._apply(fn, *a, **k)
 
-    def engine(self, B, H, W, device, flip_pair=None, scaled_hms=False):
+    def engine(self, B, H, W, device, flip_pair=None, scaled_hms=False, all_heads=False):
         """flip_pair: 43 channel indices (FLIP_ORDER + 15 + PAF FLIP_CHANNEL) -> an engine that runs the flip-TTA of
         test.py:55-70 inside its schedule (B frames in, merged maps of B frames out).  scaled_hms: the engine writes hms / 255 | / 127,
-        the maps as test.py:111-112 hands them to dapalib (the pipelines); forward() keeps the raw maps the reference returns."""
-        key = (B, H, W, str(device), self.precision, tuple(flip_pair) if flip_pair is not None else None, bool(scaled_hms))
+        the maps as test.py:111-112 hands them to dapalib (the pipelines); forward() keeps the raw maps the reference returns.  all_heads: the
+        schedule also runs the 62 training-only head convs and keeps all 36 head tensors (BackboneEngine.head_sources: the loss)."""
+        key = (B, H, W, str(device), self.precision, tuple(flip_pair) if flip_pair is not None else None, bool(scaled_hms)) + ((True,) if all_heads else ())
         if key not in self._engines:
             if (H // 4, W // 4) != self.output_shape:
                 raise ValueError(f"input {H}x{W} does not match cfg.OUTPUT_SHAPE {self.output_shape} (stride 4)")
             self._engines[key] = BackboneEngine(self.state_dict(), B, H, W, device, self.stage_num,
                                                 self.upsample_chl_num, self.kpt_paf_num, self.paf_num,
-                                                precision=self.precision, flip_pair=flip_pair, scaled_hms=scaled_hms)
+                                                precision=self.precision, flip_pair=flip_pair, scaled_hms=scaled_hms, all_heads=all_heads)
         return self._engines[key]
 
     def forward(self, imgs, valids=None, labels=None, rdepth=None):
-        if valids is not None or labels is not None:
-            raise NotImplementedError("the training branch (smap.py:355-401) is out of scope of smap_amd")
+        with_loss = valids is not None or labels is not None or rdepth is not None
         if self.training:
+            if with_loss:
+                raise RuntimeError("smap_amd.SMAP evaluates the loss in eval mode only (folded BatchNorm, values without a graph): BatchNorm "
+                                   "with batch statistics and the backward pass are not implemented; call model.eval() first")
             raise RuntimeError("smap_amd.SMAP runs eval-mode inference only: call model.eval() first")
         if not imgs.is_cuda:
+            if with_loss:                      # (a RuntimeError too: the loss branch exists on the GPU alone)
+                raise NotImplementedError("smap_amd.SMAP evaluates the loss on a ROCm GPU only: images on %s, there is no CPU fallback" % imgs.device)
             raise RuntimeError("smap_amd.SMAP.forward needs the images on a ROCm GPU; there is no CPU fallback")
         if imgs.dim() != 4 or imgs.shape[1] != 3:
             raise ValueError(f"imgs must be [B,3,H,W], got {tuple(imgs.shape)}")
         B, _, H, W = imgs.shape
+        if with_loss:
+            return self._loss(imgs, valids, labels, rdepth)
         eng = self.engine(B, H, W, imgs.device)
         # a fresh output buffer per call (caching allocator: no device copy), so the caller owns what it gets back --
         # the reference returns new tensors too -- while the engine's arena is reused by the next forward
@@ -171,3 +180,25 @@ class SMAP(nn.Module):
         if os.environ.get("SMAP_CHECK_FINITE"):
             eng.raise_if_nonfinite(out)
         return res
+
+    def _loss(self, imgs, valids, labels, rdepth):
+        """The loss branch of the reference's forward (smap.py:355-401, :403-415) in eval mode: the all-heads schedule, then
+        smap_loss_forward_src on the heads where the engine left them -- both on the current stream, no synchronisation.  Returns
+        dict(total_loss, loss_2d, loss_bone, loss_root) of 0-d device tensors without grad_fn."""
+        from ..loss import EngineLoss
+        if valids is None or labels is None or rdepth is None:
+            raise ValueError("the loss needs valids [B,57(,1)], labels [B,S,57,H,W] and rdepth [B,R,3] (as smap_amd.loss.SMAPLoss takes them)")
+        B, _, H, W = imgs.shape
+        crit = EngineLoss(self.stage_num, self.ohkm, self.topk, self.ctf)
+        cfg, labels, valids, rdepth = crit.check(valids, labels, rdepth)
+        if (cfg.B, cfg.H, cfg.W) != (B, H // 4, W // 4) or labels.device != imgs.device:
+            raise ValueError(f"labels must be [{B},S,57,{H // 4},{W // 4}] on {imgs.device}, got {tuple(labels.shape)} on {labels.device}")
+        eng = self.engine(B, H, W, imgs.device, all_heads=True)
+        out = eng.new_output()                             # (the finest root-depth map may be read from it: kept until the loss has run)
+        eng.run(imgs.float(), out=out)
+        from ..loss import forward_from_sources
+        with torch.no_grad():
+            result, _ = forward_from_sources(cfg, eng.head_sources(out), labels, valids, rdepth)
+        if os.environ.get("SMAP_CHECK_FINITE"):
+            eng.raise_if_nonfinite(out)
+        return dict(total_loss=result[0], loss_2d=result[1], loss_bone=result[2], loss_root=result[3])
