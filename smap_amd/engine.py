@@ -29,7 +29,7 @@ bits) with three MFMAs per K step (csrc/conv.hip, template X3): ~1e-6 relative e
 import ctypes as C
 import os
 from collections import namedtuple
-from dataclasses import dataclass, field
+from dataclasses import dataclass, field, fields
 
 import torch
 
@@ -116,29 +116,110 @@ TAIL_BN = {t: r.tail_bn for t, r in TILE_TABLE.items() if r.tail_bn}          # 
 HALO_ROWS = ("halo", "tail", "block")     # families whose 3x3 weights are packed as 128-byte halo rows (pack_halo_rows)
 TAIL_DEFAULT = {}                          # Bottleneck planes -> fused tile id (empty: every block runs c2 and c3 as two launches)
 # Bottleneck planes -> tile id of the WHOLE-block launch (csrc/convb.hip) for stride-1 identity blocks in split precision; {} = off.
-# SMAP_BLOCK="64:91" overrides (A/B hook; "" = off).  BLOCK_FIRST_DEFAULT / SMAP_BLOCK_FIRST="64:93": the same for the first block of
-# layer1 (the one with a shortcut conv; 64 input channels).
+# BLOCK_FIRST_DEFAULT: the same for the first block of layer1 (the one with a shortcut conv; 64 input channels).
 # Measured in situ (profiles/r4_v4_ab_whole_block_first.log, same box, interleaved): 781 -> 800 (identity blocks, 8 x 16 tiles) -> 821
 # frames/s (+ first blocks); 4 x 16 tiles: 816.
 BLOCK_DEFAULT = {64: 91, 128: 94}       # layer1 (csrc/convb.hip) and layer2 (csrc/convc.hip) identity blocks
 BLOCK_FIRST_DEFAULT = {64: 93}
 
 
-def _planes_table(env, default):
-    """SMAP_BLOCK / SMAP_BLOCK_FIRST / SMAP_TAIL="64:91,128:94": Bottleneck planes -> tile id (A/B hooks, "" = none); unset: `default`."""
-    spec = os.environ.get(env)
-    return default if spec is None else {int(k): int(v) for k, v in (kv.split(":") for kv in spec.split(",") if ":" in kv)}
+# ----------------------------------------------------------------------------- schedule switches
+_HERE = os.path.dirname(os.path.abspath(__file__))
+_TABLE_FILES = {}       # (path, mtime, size) -> parsed tile table: SchedulePolicy.from_env runs once per Graph, hundreds of times in the tests
 
 
-def _tile_remap():
-    """SMAP_TILE_REMAP="0:5,1:6" swaps tile variants without touching the schedule (A/B runs)."""
-    out = {}
-    for kv in os.environ.get("SMAP_TILE_REMAP", "").split(","):
-        if ":" in kv:
-            a, b = kv.split(":")
-            assert TILES[int(a)] == TILES[int(b)], "remap must keep the tile shape"
-            out[int(a)] = int(b)
-    return out
+def _load_table(path):
+    """A measured tile table (json: shape key -> tile id or ranked list of ids) by path; {} when there is no such file."""
+    if not os.path.exists(path):
+        return {}
+    st = os.stat(path)
+    key = (path, st.st_mtime_ns, st.st_size)
+    if key not in _TABLE_FILES:
+        import json
+        _TABLE_FILES[key] = json.load(open(path))
+    return _TABLE_FILES[key]
+
+
+@dataclass(frozen=True)
+class SchedulePolicy:
+    """Every switch that changes what Graph builds, as one value: read from the SMAP_* environment variables ONCE (from_env, the only
+    place this file reads them), kept by the Graph built under it (Graph.policy) and hashed into the plan cache key (cache_token).  All
+    of them are A/B hooks and test handles; the defaults are the shipped schedule."""
+    block: tuple = None
+    """SMAP_BLOCK="64:91,128:94": (Bottleneck planes, tile id) of the whole-block launches; () = none; None (unset) = the rule of Graph.block_tile."""
+    block_first: tuple = None
+    """SMAP_BLOCK_FIRST="64:93": the same for layer1's first block; None (unset) = BLOCK_FIRST_DEFAULT, 92 for 93 in small schedules."""
+    tail: tuple = None
+    """SMAP_TAIL="64:80,128:82": (planes, tile id) pairs of the fused 3x3 + 1x1 launches (Graph.conv_tail); None (unset) = TAIL_DEFAULT."""
+    cat: bool = None
+    """SMAP_CAT=0|1: a Bottleneck's last 1x1 and its shortcut conv as one launch (Graph.conv_cat) never / in small schedules too; None = in all but those."""
+    skipsum: bool = None
+    """SMAP_SKIPSUM=0|1: skip1 + skip2 of an Upsample_unit as one launch and one tensor (Graph.conv_relusum), the same way."""
+    taphead: bool = None
+    """SMAP_TAPHEAD=0|1: the root-depth head as tap-dot launch + stencil (Graph.conv_tapdot / tapsum), the same way."""
+    merge_1x1: int = 1
+    """SMAP_MERGE_1X1: shared-input 1x1s of an Upsample_unit as one launch (Graph.conv_seg): 1 = the merges that pay, 2 = all of them, 0 = one launch per conv."""
+    splitk: str = ""
+    """SMAP_SPLITK: "" (unset or "1") = the measured rule of Graph.split_k, "0" = off, "<n>" = n parts wherever a launch qualifies, "t<n>" = aim at n workgroups."""
+    splitk_mink: int = 2048
+    """SMAP_SPLITK_MINK: shortest K loop the measured split-K rule shares out (re-measured with the release / acquire ticket: EXPERIMENTS R6.5)."""
+    deep_tile: bool = True
+    """SMAP_DEEP_TILE=0 switches Graph.deep_pipeline_tile (tile 2 -> 7 for launches of <= 256 workgroups, profiles/r5_v9_*) off."""
+    lanes: bool = False
+    """SMAP_LANES=1: the independent head chains on forked streams (use_lanes; profiles/r5_v3_ab_b1.log)."""
+    wpairs: int = None
+    """SMAP_WPAIRS=0|1 forces one layout of the packed 32-half weight tiles; None = pairs in small schedules (use_w_pairs; profiles/r3_ab_wpairs*.log)."""
+    x3_tile: int = None
+    """SMAP_X3_TILE: one split-precision tile id put before the table's candidates wherever it fits (Graph._pick)."""
+    cat_tile: int = None
+    """SMAP_CAT_TILE: tile id of every Graph.conv_cat launch."""
+    relusum_tile: int = None
+    """SMAP_RELUSUM_TILE: tile id of every Graph.conv_relusum launch (profiles/r6_v14_ab_two_input_tiles.log)."""
+    halo3: tuple = None
+    """SMAP_HALO3="16" | "32" [":64" | ":128"]: (pixel-tile width, BN or None) -- every plain 3x3 with Cout > 32 on that halo tile (csrc/conv3.hip)."""
+    halo3_deep: bool = False
+    """SMAP_HALO3_DEEP: ... on its variant with the deeper weight pipeline (tile id + 4)."""
+    tile_remap: tuple = ()
+    """SMAP_TILE_REMAP="0:5,1:6": (tile id, tile id) pairs that swap variants of one tile shape (other pipeline depth) without touching the schedule."""
+    tile_policy: str = ""
+    """SMAP_TILE_POLICY="traffic[:min blocks]": experiment of pick_tile -- fewest L2 -> LDS bytes subject to a minimum block count (fp16)."""
+    stempool: bool = False
+    """SMAP_STEMPOOL: ResNet_top as one kernel that writes the pooled tensor only (bit-identical, no faster inside the two-batch pipeline)."""
+    no_upadd_fusion: bool = False
+    """SMAP_NO_UPADD_FUSION: fp16 with SMAP_MERGE_1X1=0 -- the bilinear add as a launch of its own (SMAP_OP_UPADD) instead of the u_skip conv's epilogue."""
+    tile_table: dict = field(default_factory=dict, repr=False)
+    """The measured fp16 table (pick_tile): SMAP_TILE_TABLE=<json>, default smap_amd/tile_table.json; {} under SMAP_NO_TILE_TABLE."""
+    tile_table_x3: dict = field(default_factory=dict, repr=False)
+    """The measured split-precision table (pick_tile_x3): SMAP_TILE_TABLE_X3=<json>, default smap_amd/tile_table_x3.json; {} under SMAP_NO_TILE_TABLE."""
+
+    @classmethod
+    def from_env(cls, environ=os.environ):
+        """The policy that the SMAP_* variables of `environ` describe."""
+        get = lambda name, default="": environ.get("SMAP_" + name, default)
+        pairs = lambda spec: None if spec is None else tuple((int(a), int(b)) for a, b in (kv.split(":") for kv in spec.split(",") if ":" in kv))
+        tri = lambda name: {"0": False, "1": True}.get(get(name))
+        num = lambda name: int(get(name)) if get(name) else None
+        remap = pairs(get("TILE_REMAP"))
+        assert all(TILES[a] == TILES[b] for a, b in remap), "remap must keep the tile shape"
+        tw, _, bn = get("HALO3").partition(":")
+        table = lambda name, shipped: {} if get("NO_TILE_TABLE") else _load_table(get(name) or os.path.join(_HERE, shipped))
+        return cls(block=pairs(get("BLOCK", None)), block_first=pairs(get("BLOCK_FIRST", None)), tail=pairs(get("TAIL", None)),
+                   cat=tri("CAT"), skipsum=tri("SKIPSUM"), taphead=tri("TAPHEAD"), merge_1x1={"0": 0, "2": 2}.get(get("MERGE_1X1"), 1),
+                   splitk="" if get("SPLITK") == "1" else get("SPLITK"), splitk_mink=int(get("SPLITK_MINK", "2048")),
+                   deep_tile=get("DEEP_TILE") != "0", lanes=get("LANES") == "1", wpairs={"0": 0, "1": 1}.get(get("WPAIRS")),
+                   x3_tile=num("X3_TILE"), cat_tile=num("CAT_TILE"), relusum_tile=num("RELUSUM_TILE"),
+                   halo3=(int(tw), int(bn) if bn else None) if tw else None, halo3_deep=bool(get("HALO3_DEEP")), tile_remap=remap,
+                   tile_policy=get("TILE_POLICY"), stempool=bool(get("STEMPOOL")), no_upadd_fusion=bool(get("NO_UPADD_FUSION")),
+                   tile_table=table("TILE_TABLE", "tile_table.json"), tile_table_x3=table("TILE_TABLE_X3", "tile_table_x3.json"))
+
+    def cache_token(self):
+        """What the plan cache key hashes: every field in declaration order, the two tables as a digest of their parsed content."""
+        import hashlib
+        import json
+        digest = lambda t: hashlib.blake2b(json.dumps(t, sort_keys=True).encode(), digest_size=16).hexdigest()
+        return tuple((f.name, digest(v) if isinstance(v, dict) else v) for f in fields(self) for v in (getattr(self, f.name),))
+
+
 LAYERS = (3, 4, 6, 3)            # smap.py:299  resnet-50
 PLANES = (64, 128, 256, 512)
 ALIGN = 256
@@ -158,9 +239,6 @@ def split_f16(w, scaled=True):
     lo = (ws - hi.double()).to(torch.float16)
     assert torch.isfinite(hi).all()
     return hi, lo, 2.0 ** -s
-
-
-_TILE_TABLE_X3 = None
 
 
 def _table_entry(v):
@@ -185,26 +263,22 @@ def tile_legal(tile, *, cout, cout_pad=None, plain3=True, up=False, out_fp32=Fal
     return True
 
 
-def pick_tile_x3(M, cout, key=None):
+def pick_tile_x3(M, cout, key=None, policy=None):
     """Split precision: candidates in order of preference -- the measured table (tools/autotune.py --precision x3 ->
     smap_amd/tile_table_x3.json) when the shape is in it, then the largest BK = 32 tile that still gives >= 512
-    workgroups / the one with most workgroups."""
-    global _TILE_TABLE_X3
-    if _TILE_TABLE_X3 is None:
-        import json
-        path = os.environ.get("SMAP_TILE_TABLE_X3") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "tile_table_x3.json")
-        _TILE_TABLE_X3 = json.load(open(path)) if os.path.exists(path) and not os.environ.get("SMAP_NO_TILE_TABLE") else {}
+    workgroups / the one with most workgroups.  policy: whose table (None: the environment's)."""
+    table = (policy or SchedulePolicy.from_env()).tile_table_x3
     keys = [key] if isinstance(key, str) else list(key or [])          # several keys: most specific first
     # a batch size the table was not tuned for borrows the entries of the nearest tuned one (same layer shape, M within 2x-4x):
     # closer to the optimum than the block-count heuristic (tuned tables: +8 % at batch 8, +7 % at 16, +19 % at 1)
-    tuned = sorted({int(k.split(",")[0]) for k in _TILE_TABLE_X3})
+    tuned = sorted({int(k.split(",")[0]) for k in table})
     if keys and tuned:
         f = int(keys[0].split(",")[0])
         if f not in tuned:
             import math
             near = min(tuned, key=lambda b: abs(math.log(b / f)))
             keys = keys + [",".join([str(near)] + k.split(",")[1:]) for k in keys]
-    cands = [t for k in keys if k in _TILE_TABLE_X3 for t in _table_entry(_TILE_TABLE_X3[k])]
+    cands = [t for k in keys if k in table for t in _table_entry(table[k])]
     if cout <= 32:
         return cands + [3]
     best, best_blocks = None, -1
@@ -218,22 +292,22 @@ def pick_tile_x3(M, cout, key=None):
     return cands + [best]
 
 
+def use_lanes(frames, H, W, policy=None):
+    """Forked streams for the independent head chains (smap_op.lane).  OFF by default: measured at batch 1 (profiles/r5_v3_ab_b1.log) the
+    forward is SLOWER with them, launched kernel by kernel (3.619 -> 3.706 ms) and replayed from a graph (3.129 -> 3.436 ms): the head
+    chains are 6 of 170 launches, and every fork / join costs an event round trip on the critical path.  SchedulePolicy.lanes switches
+    them on (the mechanism stays tested: tests/test_backbone_gpu.py::test_lanes_fork_the_head_chains_and_change_nothing)."""
+    return int((policy or SchedulePolicy.from_env()).lanes)
+
+
 # 32-half K tiles of the packed weights are stored in PAIRS (128-byte rows [tile 2p | tile 2p+1]) for SMALL schedules (<= 2 frames of
 # 512x832 worth of pixels): every launch of those is latency-bound and lives on the L1 hit the second half of each fetched line
 # gives the next K tile (batch 1: 226 vs 195 frames/s); larger schedules are bandwidth-bound and prefer one contiguous block
 # per K tile (batch 8: 751 vs 738).  A per-launch rule (pairs for <= 512 workgroups) sits in between on both (226 / 745):
-# profiles/r3_ab_wpairs*.log.  SMAP_WPAIRS=0|1 forces one layout.
-def use_lanes(frames, H, W):
-    """Forked streams for the independent head chains (smap_op.lane).  OFF by default: measured at batch 1 (profiles/r5_v3_ab_b1.log) the
-    forward is SLOWER with them, launched kernel by kernel (3.619 -> 3.706 ms) and replayed from a graph (3.129 -> 3.436 ms): the head
-    chains are 6 of 170 launches, and every fork / join costs an event round trip on the critical path.  SMAP_LANES=1 switches them on
-    (the mechanism stays tested: tests/test_backbone_gpu.py::test_lanes_fork_the_head_chains_and_change_nothing)."""
-    return int(os.environ.get("SMAP_LANES", "0") == "1")
-
-
-def use_w_pairs(small):
-    forced = os.environ.get("SMAP_WPAIRS", "")
-    return int(forced) if forced in ("0", "1") else int(small)
+# profiles/r3_ab_wpairs*.log.  SchedulePolicy.wpairs forces one layout.
+def use_w_pairs(small, policy=None):
+    forced = (policy or SchedulePolicy.from_env()).wpairs
+    return int(small) if forced is None else forced
 
 
 def pack_conv_weights(w2, tile, x3, ksize, cin, pairs=True):
@@ -390,18 +464,11 @@ def pick_tile_heuristic(M, cout):
     return best
 
 
-_TILE_TABLE = None
-
-
-def pick_tile(M, cout, key=None):
+def pick_tile(M, cout, key=None, policy=None):
     """Measured table (tools/autotune.py -> smap_amd/tile_table.json, keyed "B,H,W,Cin,Cout,k,s")
-    when the shape is in it, else the block-count heuristic."""
-    global _TILE_TABLE
-    if _TILE_TABLE is None:
-        import json
-        path = os.environ.get("SMAP_TILE_TABLE") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "tile_table.json")
-        _TILE_TABLE = json.load(open(path)) if os.path.exists(path) and not os.environ.get("SMAP_NO_TILE_TABLE") else {}
-    pol = os.environ.get("SMAP_TILE_POLICY", "")
+    when the shape is in it, else the block-count heuristic.  policy: whose table and tile_policy (None: the environment's)."""
+    policy = policy or SchedulePolicy.from_env()
+    pol = policy.tile_policy
     if pol.startswith("traffic"):       # experiment: minimise L2->LDS bytes subject to a minimum block count
         min_blocks = int(pol.split(":")[1]) if ":" in pol else 256
         K = 1
@@ -420,8 +487,8 @@ def pick_tile(M, cout, key=None):
             if best is None or cost < best_cost:
                 best, best_cost = t, cost
         return best
-    if key is not None and key in _TILE_TABLE:
-        return _table_entry(_TILE_TABLE[key])[0]
+    if key is not None and key in policy.tile_table:
+        return _table_entry(policy.tile_table[key])[0]
     return pick_tile_heuristic(M, cout)
 
 
@@ -449,8 +516,10 @@ def arena_budget(device):
 
 class Graph:
     def __init__(self, sd, B, H, W, stage_num=3, chl=256, kpt_paf=43, paf=14, keep_ref=False, precision="f16",
-                 flip_pair=None, build=True, scaled_hms=False, all_heads=False):
-        """build=False: an EMPTY schedule with all the book-keeping in place (single-op harnesses of tests / tools append to it with
+                 flip_pair=None, build=True, scaled_hms=False, all_heads=False, policy=None):
+        """policy: the SchedulePolicy to build under (None: the environment's, read here) -- also what the emitters below consult when a
+        harness calls them.
+        build=False: an EMPTY schedule with all the book-keeping in place (single-op harnesses of tests / tools append to it with
         Graph.tensor / conv / conv_seg and then allocate() / emit()).
         flip_pair (43 ints: KEYPOINT.FLIP_ORDER + [15 + c for c in PAF.FLIP_CHANNEL]) switches the flip-TTA of
         test.py:55-70 on INSIDE the schedule: B input frames run as a 2B batch whose second half the stem reads mirrored,
@@ -462,6 +531,7 @@ class Graph:
         reads).  The launches the inference outputs come from are the default schedule's, unchanged."""
         assert precision in PRECISIONS, precision
         self.precision, self.x3 = precision, precision == "x3"
+        self.policy = policy or SchedulePolicy.from_env()
         self.keep_ref = keep_ref
         self.flip_pair = list(flip_pair) if flip_pair is not None else None
         # scaled_hms: the head sum stores hms / 255 (key points) and / 127 (PAFs), i.e. the maps as test.py:111-112 hands them to the
@@ -479,8 +549,8 @@ class Graph:
             B = 2 * B                         # frames of every activation tensor
         assert not build or (H % 32 == 0 and W % 32 == 0), "input must be a multiple of 32 (5 stride-2 levels)"
         self.sd, self.B, self.H, self.W = sd, B, H, W
-        self.w_pairs = use_w_pairs(self.small)               # layout of the packed 32-half weight tiles (whole schedule)
-        self.lanes = use_lanes(B, H, W)                      # head chains on forked streams (BackboneEngine switches the plan's lanes on)
+        self.w_pairs = use_w_pairs(self.small, self.policy)  # layout of the packed 32-half weight tiles (whole schedule)
+        self.lanes = use_lanes(B, H, W, self.policy)         # head chains on forked streams (BackboneEngine switches the plan's lanes on)
         self.cur_lane = 0                                    # lane of the ops being appended (Graph.on_lane)
         self.ops, self.tensors = [], []
         self.scratch_tensors, self.kcount, self.kcount_tiles = [], None, 0      # split K: partial-tile scratch per op, one ticket region per schedule
@@ -506,8 +576,8 @@ class Graph:
         128 KiB) for launches of at most 256 workgroups.  Such a launch leaves every CU to one workgroup anyway, so the second
         workgroup's worth of LDS buys prefetch depth instead: the K loops of these launches are bound by the latency of the ONE tile a
         two-stage pipeline keeps in flight (~1 us per K tile at batch 1).  Measured at batch 1 per shape (profiles/r5_v9_*): -6 .. -21 %
-        on launches of <= 256 workgroups, +31 .. +41 % on launches of 416 (one workgroup per CU instead of two).  SMAP_DEEP_TILE=0: off."""
-        if not self.x3 or tile != 2 or os.environ.get("SMAP_DEEP_TILE", "1") == "0":
+        on launches of <= 256 workgroups, +31 .. +41 % on launches of 416 (one workgroup per CU instead of two).  SchedulePolicy.deep_tile."""
+        if not self.x3 or tile != 2 or not self.policy.deep_tile:
             return tile
         bm, bn = TILES[2]
         wgs = -(-M // bm) * (cout_pad // bn) * self.split_k(2, M, cout_pad, K)
@@ -532,9 +602,9 @@ class Graph:
     def split_k(self, tile, M, cout_pad, K):
         """K parts per output tile for a conv.hip launch of this shape (include/smap_hip.h smap_op.ksplit), or 1.  Small schedules only
         (batch 1: configs[1]): a launch with fewer output tiles than half the CUs whose K loop is long enough to share out -- the 32x52
-        and 16x26 levels run 26-104 workgroups of 16-72 K tiles each there.  SMAP_SPLITK=0 switches it off, SMAP_SPLITK=<n> forces n
+        and 16x26 levels run 26-104 workgroups of 16-72 K tiles each there.  SchedulePolicy.splitk: "0" switches it off, "<n>" forces n
         parts wherever the tile allows."""
-        env = os.environ.get("SMAP_SPLITK", "")
+        env = self.policy.splitk
         if env == "0" or not tile_has(tile, "splitk", self.x3):
             return 1
         bm, bn = TILES[tile]
@@ -544,13 +614,13 @@ class Graph:
             return 1
         if env.startswith("t"):                          # "t384": aim at that many workgroups per launch, any K (A/B hook)
             s = min(8, int(env[1:]) // tiles, n_k // 4)
-        elif env and env != "1":                         # "3": that many parts wherever a launch qualifies (tests)
+        elif env:                                        # "3": that many parts wherever a launch qualifies (tests)
             s = min(int(env), 16, n_k)
         else:
             # Measured at batch 1 (profiles/r5_v3_*): a part costs ~9 us (partial tile to memory and back, ticket, late epilogue), so
             # only long K loops gain: K = 4608 with 4 parts 57.6 -> 33.0 us, K = 2304 with 2 parts 30.2 -> 25.1, K = 2048 with 4
             # parts 27.9 -> 25.8; K = 1024 with 2 parts LOSES (17.0 -> 19.0), and aiming at 384 / 512 workgroups instead of 256 loses too
-            if K < int(os.environ.get("SMAP_SPLITK_MINK", "2048")):      # (A/B hook; re-measured with the release / acquire ticket: R6.5)
+            if K < self.policy.splitk_mink:
                 return 1
             s = min(4, 256 // tiles, n_k // 8)
         return s if s >= 2 else 1
@@ -617,10 +687,32 @@ class Graph:
         """w_ref / b_ref of an op's p (sub-)dict: the folded f64 parameters under keep_ref (oracle/graph_interp.py, tests), else None."""
         return {k + "_ref": v if self.keep_ref else None for k, v in folded.items()}
 
-    def _forced_or_first(self, env, cands, cap):
-        """Tile of a two-input launch: the one the A/B hook `env` names, else the first candidate with an instance of `cap` in this precision."""
-        forced = os.environ.get(env, "")
-        return int(forced) if forced else next(t for t in cands if tile_has(t, cap, self.x3))
+    def _forced_or_first(self, forced, cands, cap):
+        """Tile of a two-input launch: the one an A/B hook of the policy names, else the first candidate with an instance of `cap` in this precision."""
+        return forced if forced is not None else next(t for t in cands if tile_has(t, cap, self.x3))
+
+    def _pick(self, keys, legal, M, cout, K, *, key16, deep_pad, remap, remap16, x3_tile_fits=lambda t: True, tile=None):
+        """Tile id of a conv.hip-style launch of M x cout x K.  Split precision: the first legal(t) among SchedulePolicy.x3_tile (where
+        x3_tile_fits), the measured table's entries under `keys` (most specific first) and the block-count rule.  fp16: the table's entry
+        under key16 -- the table is keyed by shape only, so the block-count heuristic stands in for an entry that is not legal(t).  Then
+        `remap` (fp16: before the legality check, and only with remap16) and the deep-pipeline rule for the 64 x 64 tile, whose N extent is
+        deep_pad.  tile: the caller names it -- it must be legal, the deep-pipeline rule still applies."""
+        pol = self.policy
+        if tile is not None:
+            assert legal(tile), tile
+        elif self.x3:
+            cands = pick_tile_x3(M, cout, keys, pol)
+            if pol.x3_tile is not None and x3_tile_fits(pol.x3_tile):
+                cands = [pol.x3_tile] + cands
+            tile = next(t for t in cands if legal(t))
+            tile = remap.get(tile, tile)
+        else:
+            tile = pick_tile(M, cout, key16, pol)
+            if remap16:
+                tile = remap.get(tile, tile)
+            if not legal(tile):
+                tile = pick_tile_heuristic(M, cout)
+        return self.deep_pipeline_tile(tile, M, deep_pad, K)
 
     def _conv_op(self, out, x, wk, bias, *, flops, alg_bytes, kinds, Cin, Cout, cout_pad, tile, acc_scale, ref, relu=1, ksize=1, stride=1,
                  in_c_off=0, out_fp32=0, frames=None, w_pairs=None, split_k=None, sub=None, **tensors):
@@ -659,26 +751,13 @@ class Graph:
         plain3 = ksize == 3 and stride == 1 and res is None and add1 is None and add2 is None and up is None
         legal = lambda t: tile_legal(t, cout=cout, plain3=plain3, up=up is not None, out_fp32=out_fp32,
                                      adds=add1 is not None or add2 is not None, x3=self.x3)
-        if self.x3:
-            # ops with the fused bilinear add have their own entries (the tap loads of the epilogue favour wider tiles)
-            cands = pick_tile_x3(M, cout, [key + ",up", key] if up is not None else key)
-            x3t = os.environ.get("SMAP_X3_TILE", "")         # A/B hook: force one split-precision tile where it fits
-            if x3t and cout > 32 and not (cout <= 64 and TILES[int(x3t)][1] > 64):
-                cands = [int(x3t)] + cands
-            tile = next(t for t in cands if legal(t))
-            tile = _tile_remap().get(tile, tile)             # A/B hook (SMAP_TILE_REMAP="2:7"): same tile shape, other pipeline depth
-        else:
-            tile = pick_tile(M, cout, key)
-            tile = _tile_remap().get(tile, tile)
-            if not legal(tile):                                 # the table is keyed by shape only
-                tile = pick_tile_heuristic(M, cout)
-        halo = os.environ.get("SMAP_HALO3", "")     # A/B hook: "16" / "32" = pixel-tile width, optional ":64" / ":128" = BN
-        if halo and plain3 and cout > 32:
-            tw, _, hbn = halo.partition(":")
-            hbn = int(hbn) if hbn else min(TILES[tile][1], 128 if cout > 64 else 64)
-            tile = {(16, 64): 30, (16, 128): 31, (32, 64): 32, (32, 128): 33}[(int(tw), max(hbn, 64))]
-            tile += 4 if os.environ.get("SMAP_HALO3_DEEP") else 0
-        tile = self.deep_pipeline_tile(tile, M, _rup(cout, TILES[tile][1]), K)
+        # ops with the fused bilinear add have their own table entries (the tap loads of the epilogue favour wider tiles)
+        tile = self._pick([key + ",up", key] if up is not None else [key], legal, M, cout, K, key16=key, deep_pad=_rup(cout, 64),
+                          remap=dict(self.policy.tile_remap), remap16=True, x3_tile_fits=lambda t: cout > 32 and not (cout <= 64 and TILES[t][1] > 64))
+        if self.policy.halo3 and plain3 and cout > 32:      # (a halo tile is never the 64 x 64 one: the deep-pipeline rule above has nothing to say)
+            tw, hbn = self.policy.halo3
+            hbn = hbn or min(TILES[tile][1], 128 if cout > 64 else 64)
+            tile = {(16, 64): 30, (16, 128): 31, (32, 64): 32, (32, 128): 33}[(tw, max(hbn, 64))] + (4 if self.policy.halo3_deep else 0)
         cout_pad = _rup(cout, TILES[tile][1])
         wk, acc_scale = self._weights(name, w.permute(0, 2, 3, 1).reshape(cout, K), cout_pad)
         wk = pack_conv_weights(wk, tile, self.x3, ksize, cin, pairs=self.w_pairs)   # one contiguous block per staged weight tile (pair)
@@ -702,7 +781,7 @@ class Graph:
             key = f"{self.B},{x.H},{x.W},{c1}+{c2}relusum,{cout},1,1"
             # measured in situ (profiles/r6_v14_ab_two_input_tiles.log): the 128 x 256 tile (both inputs' rows staged once per launch instead of once
             # per 128-channel N tile) 860-864 frames/s against 847 with the 128 x 128 tiles; the K-concatenated launches (conv_cat) do not care
-            tile = self._forced_or_first("SMAP_RELUSUM_TILE", (pick_tile_x3(M, cout, key) if self.x3 else []) + [54, 53, 50, 51], "relusum")
+            tile = self._forced_or_first(self.policy.relusum_tile, (pick_tile_x3(M, cout, key, self.policy) if self.x3 else []) + [54, 53, 50, 51], "relusum")
         assert tile_has(tile, "relusum", self.x3), tile
         cout_pad = _rup(cout, TILES[tile][1])
         wk1, sc1 = self._weights(name, w1.reshape(cout, c1), cout_pad)
@@ -763,7 +842,7 @@ class Graph:
         M, K = self.B * Ho * Wo, c1 + c2
         if tile is None:
             key = f"{self.B},{Ho},{Wo},{c1}+{c2}cat,{cout},1,1"
-            tile = self._forced_or_first("SMAP_CAT_TILE", (pick_tile_x3(M, cout, key) if self.x3 else []) + [50, 51, 20], "dual")
+            tile = self._forced_or_first(self.policy.cat_tile, (pick_tile_x3(M, cout, key, self.policy) if self.x3 else []) + [50, 51, 20], "dual")
         assert tile_has(tile, "dual", self.x3), tile
         cout_pad = _rup(cout, TILES[tile][1])
         # [cout][K = (x channels | x2 channels)] with ONE power-of-two scale: the two matrices share the accumulators
@@ -794,21 +873,10 @@ class Graph:
         wide = f"{self.B},{x.H},{x.W},{cin},{max(couts)},1,1"
         legal = lambda t: (tile_family(t) == "igemm" and tile_has(t, None, self.x3) and TILES[t][1] >= 64       # (not the Cout <= 32 tiles)
                            and (not tile_has(t, "regepi", True) or (self.x3 and up is None)))
-        if tile is not None:
-            assert legal(tile), tile
-        elif self.x3:
-            keys = ([key + ",up"] if up is not None else []) + [key] + ([wide + ",up"] if up is not None else []) + [wide]
-            cands = pick_tile_x3(M, sum(couts), keys)
-            x3t = os.environ.get("SMAP_X3_TILE", "")         # A/B hook, as in Graph.conv
-            if x3t:
-                cands = [int(x3t)] + cands
-            tile = _tile_remap().get(next(t for t in cands if legal(t)), None) or next(t for t in cands if legal(t))
-        else:
-            tile = pick_tile(M, sum(couts), key)
-            if not legal(tile):
-                tile = pick_tile_heuristic(M, sum(couts))
-        if tile == 2:                                            # (the deep-pipeline variant of the 64x64 tile for small launches)
-            tile = self.deep_pipeline_tile(2, M, sum(_rup(c, 64) for c in couts), cin)
+        keys = ([key + ",up"] if up is not None else []) + [key] + ([wide + ",up"] if up is not None else []) + [wide]
+        # (this emitter's own: every segment counts padded to 64 in the deep-pipeline rule; the remap does not apply in fp16, and never TO tile 0)
+        tile = self._pick(keys, legal, M, sum(couts), cin, key16=key, deep_pad=sum(_rup(c, 64) for c in couts),
+                          remap={a: b for a, b in self.policy.tile_remap if b}, remap16=False, tile=tile)
         bn = TILES[tile][1]
         starts, n = [], 0
         for c in couts:
@@ -921,15 +989,15 @@ class Graph:
 
     def block_tile(self, planes, stride, has_ds):
         """Tile id of the whole-block launch for this Bottleneck, or None.  Identity blocks (no shortcut conv) of stride 1 in
-        split precision only; SMAP_BLOCK="64:91" chooses per width (A/B hook), default BLOCK_DEFAULT -- in small schedules (<= 2 frames of
+        split precision only; SchedulePolicy.block chooses per width, default BLOCK_DEFAULT -- in small schedules (<= 2 frames of
         512x832) without layer2's entry (at batch 1 the 64x104 level has 52 tiles of the eight-wave kernel for 256 CUs, 55-57 us per block
         where the three launches take ~42: profiles/r5_v2_x3_layers_batch1.txt) and with layer1's on 4 x 16 pixel tiles (twice the
         workgroups: profiles/r5_v11_ab_b1_whole_block_tiles.log)."""
         if stride != 1 or has_ds or not self.x3:
             return None
-        if "SMAP_BLOCK" not in os.environ and self.small:
+        if self.policy.block is None and self.small:
             return {64: 90}.get(planes)  # 4 x 16 pixel tiles: 416 workgroups of half the work at batch 1 (2.91 -> 2.84 ms per frame)
-        return _planes_table("SMAP_BLOCK", BLOCK_DEFAULT).get(planes)
+        return dict(BLOCK_DEFAULT if self.policy.block is None else self.policy.block).get(planes)
 
     # -- the network (smap.py:313-353 structure, :403-419 data flow)
     def _build(self):
@@ -950,12 +1018,12 @@ class Graph:
         H4, W4 = (H2 + 2 - 3) // 2 + 1, (W2 + 2 - 3) // 2 + 1
         self.flops += 2 * B * H2 * W2 * 64 * 147
         stem_p = dict(w_off=self._add_w(wk), bias_off=self._add_w(b.to(torch.float32)), w_ref=w, b_ref=b, acc_scale=stem_scale)
-        if not os.environ.get("SMAP_STEMPOOL"):         # default: conv and max-pool as two kernels (the fused kernel below is
+        if not self.policy.stempool:                    # default: conv and max-pool as two kernels (the fused kernel below is
             t = self.tensor("top.conv", H2, W2, 64)     # bit-identical but no faster inside the two-batch pipeline)
             self.ops.append(Op(OP_STEM, out=t, p=stem_p))
             x = self.tensor("top.pool", H4, W4, 64)
             self.ops.append(Op(OP_MAXPOOL, out=x, inp=t))
-        else:                                           # SMAP_STEMPOOL=1: ResNet_top in one kernel, only the pooled tensor is written
+        else:                                           # ResNet_top in one kernel, only the pooled tensor is written
             x = self.tensor("top.pool", H4, W4, 64)
             self.ops.append(Op(OP_STEMPOOL, out=x, p=stem_p))
         self.out_h, self.out_w = H4, W4
@@ -969,19 +1037,18 @@ class Graph:
         blk = self.block_tile(planes, stride, has_ds)
         if blk is not None:         # c1 + c2 + c3 + residual in one launch (csrc/convb.hip)
             return self.conv_block(pre + ".c3", pre, x, blk, add1=add1, add2=add2)
-        first = _planes_table("SMAP_BLOCK_FIRST", BLOCK_FIRST_DEFAULT).get(planes)
-        if "SMAP_BLOCK_FIRST" not in os.environ and first == 93 and self.small:
+        first = dict(BLOCK_FIRST_DEFAULT if self.policy.block_first is None else self.policy.block_first).get(planes)
+        if self.policy.block_first is None and first == 93 and self.small:
             first = 92                   # small schedules: the 4 x 16 tiles here too
         if first is not None and self.x3 and has_ds and stride == 1 and x.C == 64 and planes == 64 and add1 is None and add2 is None:
             return self.conv_block_first(pre + ".c3", pre, x, first)
         # A block with a shortcut conv (the first of layer2 / 3 / 4; layer1's runs as a whole-block launch above): its last 1x1 and the shortcut
-        # as ONE GEMM over K = (planes | in_planes) -- the shortcut tensor is never stored (conv_cat).  SMAP_CAT=0: two launches, as round 5 ran.
+        # as ONE GEMM over K = (planes | in_planes) -- the shortcut tensor is never stored (conv_cat).  SchedulePolicy.cat = False: two launches, as round 5 ran.
         # (Not for arenas beyond one 4 GiB window: both inputs are addressed from one base.)
         # (Not in small schedules -- <= 2 frames of 512x832 --: their launches live on split K and the deep-pipeline 64 x 64 tile, which the
         #  two-input instances do not have: batch 1 measured 3.4 ms per frame with them against 2.9 without, profiles/r6_final_*.)
-        cat_env = os.environ.get("SMAP_CAT", "")
-        cat = (has_ds and add1 is None and add2 is None and cat_env != "0" and self.tail_tile(planes, stride) is None
-               and self.one_window and (cat_env == "1" or not self.small))
+        cat = (has_ds and add1 is None and add2 is None and self.policy.cat is not False and self.tail_tile(planes, stride) is None
+               and self.one_window and (self.policy.cat or not self.small))
         idn = x if (not has_ds or cat) else self.conv(pre + ".downsample", [pre + ".downsample"], x, 1, stride, relu=False)
         y = self.conv(pre + ".c1", [pre + ".conv_bn_relu1"], x, 1, 1, relu=True)
         if cat:
@@ -995,10 +1062,10 @@ class Graph:
 
     def tail_tile(self, planes, stride):
         """Tile id of the fused 3x3 + 1x1 launch for a Bottleneck of this width, or None = two launches.
-        SMAP_TAIL="64:80,128:82" chooses per width (A/B hook); default: see TAIL_DEFAULT."""
+        SchedulePolicy.tail chooses per width; default: see TAIL_DEFAULT."""
         if stride != 1:
             return None
-        return _planes_table("SMAP_TAIL", TAIL_DEFAULT).get(planes)
+        return dict(TAIL_DEFAULT if self.policy.tail is None else self.policy.tail).get(planes)
 
     def _stage(self, s, x, skip1, skip2, gen_skip, heads):
         pre = f"stage{s}."
@@ -1023,21 +1090,21 @@ class Graph:
         # launches on `out` (skip2 | cross_conv | res_conv1 | the next unit's up_conv) are 3-33 % faster merged than one by one at every
         # level; u_skip | skip1 on x is faster merged where u_skip has no fused bilinear add (up1: 228 vs 244 us at 16 frames) and SLOWER
         # where it has one (128x208: 712 vs 610 us; 32x52: 277 vs 256): one tile shape must then serve the bilinear epilogue (which wants
-        # the 256-wide tile) and the plain skip1 (which wants the eight-wave 128x128 one).  SMAP_MERGE_1X1: "1" (default) = the merges
-        # that pay, "2" = all of them, "0" = one launch per conv.
-        merge_mode = os.environ.get("SMAP_MERGE_1X1", "1")
-        merge = merge_mode != "0"
+        # the 256-wide tile) and the plain skip1 (which wants the eight-wave 128x128 one).  SchedulePolicy.merge_1x1: 1 (default) = the
+        # merges that pay, 2 = all of them, 0 = one launch per conv.
+        merge_mode = self.policy.merge_1x1
+        merge = merge_mode != 0
         tl = None                                                 # up_conv@low of the unit at hand (a segment of the previous unit's launch on `out`)
         for ind, xin in enumerate((x4, x3, x2, x1)):
             u = f"{pre}upsample.up{ind + 1}"
             un = f"{pre}upsample.up{ind + 2}"                     # the next unit: its up_conv reads this unit's `out` (commuted with the upsample)
             # The inter-stage skips as ONE tensor per level: skip1(x) + skip2(out) in one launch (conv_relusum); the next stage adds that one tensor.
-            # SMAP_SKIPSUM=0: round 5's two tensors (skip1 beside u_skip, skip2 as a segment of the launch on `out`).  Not beyond one 4 GiB window.
-            ss_env = os.environ.get("SMAP_SKIPSUM", "")
-            skipsum = gen_skip and merge and ss_env != "0" and self.one_window and (ss_env == "1" or not self.small)    # (small schedules: as conv_cat)
+            # SchedulePolicy.skipsum = False: round 5's two tensors (skip1 beside u_skip, skip2 as a segment of the launch on `out`).  Not beyond one 4 GiB window.
+            ss = self.policy.skipsum
+            skipsum = gen_skip and merge and ss is not False and self.one_window and (ss or not self.small)    # (small schedules: as conv_cat)
             if merge:
                 # launch 1, on x:   out = relu(u_skip(x) [+ bilinear(up_conv@low)])  |  skip1 = relu(skip1(x))
-                if gen_skip and not skipsum and (tl is None or merge_mode == "2"):
+                if gen_skip and not skipsum and (tl is None or merge_mode == 2):
                     out, s1[3 - ind] = self.conv_seg([(u + ".out", u + ".u_skip", True), (u + ".skip1", u + ".skip1", True)], xin, up=tl)
                 else:
                     out = self.conv(u + ".out", [u + ".u_skip"], xin, relu=True, up=tl)
@@ -1070,9 +1137,8 @@ class Graph:
                     if ind == 3:
                         # The root-depth head (res_rd_conv1 -> res_rd_conv2, a 3x3 with ONE output channel) as a 1x1 launch whose epilogue
                         # keeps nine dot products per pixel instead of the 256-channel activation, + a nine-term stencil (conv_tapdot / tapsum):
-                        # 0.87 GB per 16 frames and the N = 1 MFMA launch (8.9 TFLOP/s) gone.  SMAP_TAPHEAD=0: round 5's three-way 1x1 + 3x3.
-                        tap_env = os.environ.get("SMAP_TAPHEAD", "")
-                        tap = self.chl == 256 and tap_env != "0" and (tap_env == "1" or not self.small)
+                        # 0.87 GB per 16 frames and the N = 1 MFMA launch (8.9 TFLOP/s) gone.  SchedulePolicy.taphead = False: round 5's three-way 1x1 + 3x3.
+                        tap = self.chl == 256 and self.policy.taphead is not False and (self.policy.taphead or not self.small)
                         m = self.conv(u + ".heads1x1", [u + ".res_conv1", u + ".res_d_conv1"] + ([] if tap else [u + ".res_rd_conv1"]), out, relu=True)
                         c = self.chl
                         head_t["res4"] = self.conv(u + ".res", [u + ".res_conv2"], m, 3, relu=False, in_c_off=0, cin=c, out_fp32=True)
@@ -1094,7 +1160,7 @@ class Graph:
                 out = self.conv(u + ".out", [u + ".u_skip"], xin, relu=True)
             else:
                 tl = self.conv(u + ".up_conv@low", [u + ".up_conv"], out, relu=False)   # commuted with the upsample
-                if os.environ.get("SMAP_NO_UPADD_FUSION") and not self.x3:
+                if self.policy.no_upadd_fusion and not self.x3:
                     a = self.conv(u + ".u_skip", [u + ".u_skip"], xin, relu=False)
                     o = self.tensor(u + ".out", a.H, a.W, a.C)
                     self.ops.append(Op(OP_UPADD, out=o, inp=a, aux=[tl], p=dict(relu=1)))
@@ -1445,24 +1511,18 @@ def state_hash(sd):
     return h.hexdigest()
 
 
-def _schedule_env():
-    """The SMAP_* switches that change what Graph builds (tile overrides, merge policy, split K ...): part of the cache key."""
-    skip = ("SMAP_PLAN_CACHE", "SMAP_HIP_LIB", "SMAP_BENCH", "SMAP_CLI", "SMAP_DECODE", "SMAP_STRICT", "SMAP_CHECK", "SMAP_FORCE", "SMAP_GIT",
-            "SMAP_MAX_ARENA", "SMAP_MAX_FRAMES", "SMAP_BB_STREAM")
-    return sorted((k, v) for k, v in os.environ.items() if k.startswith("SMAP_") and not k.startswith(skip))
+# The schedule builder's source, hashed into the key: EVERY module the builder imports schedule logic from belongs in this tuple.
+BUILDER_SOURCES = ("engine.py",)
 
 
-def plan_cache_key(sd, B, H, W, stage_num, chl, kpt_paf, paf, precision, flip_pair, scaled_hms, all_heads=False):
+def plan_cache_key(sd, B, H, W, stage_num, chl, kpt_paf, paf, precision, flip_pair, scaled_hms, all_heads=False, policy=None):
     import hashlib
-    here = os.path.dirname(os.path.abspath(__file__))
+    policy = policy or SchedulePolicy.from_env()
     h = hashlib.blake2b(digest_size=16)
     h.update(repr((state_hash(sd), B, H, W, stage_num, chl, kpt_paf, paf, precision, tuple(flip_pair) if flip_pair is not None else None,
-                   bool(scaled_hms), _L.BLOB_VERSION, C.sizeof(_L.SmapOp), _L.version(), _schedule_env(), bool(all_heads))).encode())
-    for f in ("engine.py", "tile_table.json", "tile_table_x3.json"):      # the schedule builder and its tables
-        h.update(open(os.path.join(here, f), "rb").read())
-    tt = os.environ.get("SMAP_TILE_TABLE_X3") or os.environ.get("SMAP_TILE_TABLE")
-    if tt and os.path.exists(tt):
-        h.update(open(tt, "rb").read())
+                   bool(scaled_hms), _L.BLOB_VERSION, C.sizeof(_L.SmapOp), _L.version(), policy.cache_token(), bool(all_heads))).encode())
+    for f in BUILDER_SOURCES:
+        h.update(open(os.path.join(_HERE, f), "rb").read())
     return h.hexdigest()
 
 
@@ -1500,7 +1560,8 @@ class BackboneEngine:
         if self.device.type != "cuda":
             raise RuntimeError("BackboneEngine needs a ROCm GPU device (no CPU path in smap_amd)")
         sd = {k: v.detach().cpu() for k, v in state_dict.items()}
-        self._graph_args = (sd, B, H, W, stage_num, chl, kpt_paf, paf, precision, flip_pair, scaled_hms, reuse, bool(all_heads))
+        self.policy = SchedulePolicy.from_env()            # what the plan is made under: the cache key, and engine.graph whenever it is built
+        self._graph_args = (sd, B, H, W, stage_num, chl, kpt_paf, paf, precision, flip_pair, scaled_hms, reuse, bool(all_heads), self.policy)
         self.all_heads, self.stage_num = bool(all_heads), stage_num
         self._graph = None
         self.B, self.H, self.W = B, H, W
@@ -1509,7 +1570,7 @@ class BackboneEngine:
         cdir = plan_cache_dir() if reuse else None         # (reuse=False: debugging layouts, never cached)
         meta = None
         if cdir is not None:
-            self.cache_key = plan_cache_key(sd, B, H, W, stage_num, chl, kpt_paf, paf, precision, flip_pair, scaled_hms, all_heads)
+            self.cache_key = plan_cache_key(sd, B, H, W, stage_num, chl, kpt_paf, paf, precision, flip_pair, scaled_hms, all_heads, self.policy)
             meta = self._load_cached(cdir)
         if meta is None:
             g = self.graph                                 # builds and allocates the schedule
@@ -1547,9 +1608,9 @@ class BackboneEngine:
         """The schedule as Python objects (ops, tensors, weight chunks).  An engine loaded from the plan cache builds it only when somebody
         asks (profiling tools, tests, blob()): the launches themselves need the plan handle alone."""
         if self._graph is None:
-            sd, B, H, W, stage_num, chl, kpt_paf, paf, precision, flip_pair, scaled_hms, reuse, all_heads = self._graph_args
+            sd, B, H, W, stage_num, chl, kpt_paf, paf, precision, flip_pair, scaled_hms, reuse, all_heads, policy = self._graph_args
             g = Graph(sd, B, H, W, stage_num, chl, kpt_paf, paf, precision=precision, flip_pair=flip_pair, scaled_hms=scaled_hms,
-                      all_heads=all_heads)
+                      all_heads=all_heads, policy=policy)
             g.allocate(reuse=reuse)
             self._graph = g
         return self._graph

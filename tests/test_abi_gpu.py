@@ -138,12 +138,10 @@ def test_arena_beyond_4_gib_matches_smaller_launches():
     import smap_amd.engine as E
     from exps.stage3_root2.config import cfg
     from smap_amd.model.smap import SMAP
-    old = E._TILE_TABLE_X3
-    E._TILE_TABLE_X3 = {}
     # (the two-input launches -- conv_cat, conv_relusum -- address both inputs from ONE window and are left out of schedules beyond 4 GiB: the
     #  16-frame side is built without them too, so that both sides run the same launches)
-    saved = {k: os.environ.get(k) for k in ("SMAP_CAT", "SMAP_SKIPSUM")}
-    os.environ.update(SMAP_CAT="0", SMAP_SKIPSUM="0")
+    saved = {k: os.environ.get(k) for k in ("SMAP_CAT", "SMAP_SKIPSUM", "SMAP_NO_TILE_TABLE")}
+    os.environ.update(SMAP_CAT="0", SMAP_SKIPSUM="0", SMAP_NO_TILE_TABLE="1")
     try:
         torch.manual_seed(0)
         net = SMAP(make_cfg((128, 208))).eval()
@@ -169,6 +167,5 @@ def test_arena_beyond_4_gib_matches_smaller_launches():
                 err = (a - b).abs().max().item() / b.abs().max().item()
                 assert err <= 2e-6, (name, j, err)
     finally:
-        E._TILE_TABLE_X3 = old
         for k, v in saved.items():
             os.environ.pop(k, None) if v is None else os.environ.__setitem__(k, v)

@@ -36,9 +36,7 @@ def test_run_inference_cli_end_to_end(tmp_path, monkeypatch):
     # The CLI runs the flip-TTA inside ONE 4-frame schedule, the check below runs two 2-frame forwards: bit-equal results need the
     # same kernel family per layer on both sides (halo / im2col / persistent kernels sum in different orders), so both sides
     # take the batch-size-independent heuristic tiles instead of the measured table (whose entries are per batch size).
-    import smap_amd.engine as E
-    monkeypatch.setattr(E, "_TILE_TABLE_X3", {})
-    monkeypatch.setattr(E, "_TILE_TABLE", {})
+    monkeypatch.setenv("SMAP_NO_TILE_TABLE", "1")
     from model.smap import SMAP
     from model.refinenet import RefineNet
     from dataset.custom_dataset import CustomDataset
@@ -516,9 +514,7 @@ def test_ground_truth_modes_cli_end_to_end(tmp_path, monkeypatch, mode, data_mod
     from exps.stage3_root2.config import cfg
     from dataset.base_dataset import JointDataset
     from smap_amd.records import annotation_camera, frame_record, kept_annotations, train_records
-    import smap_amd.engine as E                           # batch 2 (CLI) vs batch 1 (below) must pick the same kernels: heuristic tiles
-    monkeypatch.setattr(E, "_TILE_TABLE_X3", {})
-    monkeypatch.setattr(E, "_TILE_TABLE", {})
+    monkeypatch.setenv("SMAP_NO_TILE_TABLE", "1")         # batch 2 (CLI) vs batch 1 (below) must pick the same kernels: heuristic tiles
     dev = "cuda:0"
     torch.manual_seed(0)
     net = SMAP(make_cfg((128, 208))).eval()

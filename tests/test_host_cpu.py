@@ -825,3 +825,106 @@ def test_workspace_bytes_did_not_drift(small_sd):
         assert lib.smap_workspace_bytes(h, C.byref(ar), C.byref(ob)) == 0
         lib.smap_plan_destroy(h)
         assert (ar.value, ob.value) == want, (name, B)
+
+
+# -- SchedulePolicy (smap_amd/engine.py): the SMAP_* schedule switches as one value
+# one setting per SchedulePolicy field that differs from what the tests run under (tests/conftest.py: CAT / SKIPSUM / TAPHEAD = 1); TABLE = a file
+POLICY_SETTINGS = {
+    "block": {"SMAP_BLOCK": ""}, "block_first": {"SMAP_BLOCK_FIRST": ""}, "tail": {"SMAP_TAIL": "64:80,128:82"},
+    "cat": {"SMAP_CAT": "0"}, "skipsum": {"SMAP_SKIPSUM": "0"}, "taphead": {"SMAP_TAPHEAD": "0"}, "merge_1x1": {"SMAP_MERGE_1X1": "0"},
+    "splitk": {"SMAP_SPLITK": "3"}, "splitk_mink": {"SMAP_SPLITK_MINK": "1024"}, "deep_tile": {"SMAP_DEEP_TILE": "0"},
+    "lanes": {"SMAP_LANES": "1"}, "wpairs": {"SMAP_WPAIRS": "0"}, "x3_tile": {"SMAP_X3_TILE": "2"}, "cat_tile": {"SMAP_CAT_TILE": "20"},
+    "relusum_tile": {"SMAP_RELUSUM_TILE": "53"}, "halo3": {"SMAP_HALO3": "16"}, "halo3_deep": {"SMAP_HALO3_DEEP": "1"},
+    "tile_remap": {"SMAP_TILE_REMAP": "2:7"}, "tile_policy": {"SMAP_TILE_POLICY": "traffic"}, "stempool": {"SMAP_STEMPOOL": "1"},
+    "no_upadd_fusion": {"SMAP_NO_UPADD_FUSION": "1"}, "tile_table": {"SMAP_TILE_TABLE": "TABLE"}, "tile_table_x3": {"SMAP_TILE_TABLE_X3": "TABLE"}}
+
+
+def _cache_key():
+    from smap_amd.engine import plan_cache_key
+    return plan_cache_key({"w": torch.arange(4.0)}, 2, 64, 96, 3, 256, 43, 14, "x3", None, False)
+
+
+def test_plan_cache_key_covers_every_policy_field_and_nothing_else(monkeypatch, tmp_path):
+    import dataclasses
+    from smap_amd.engine import SchedulePolicy
+    fields = [f.name for f in dataclasses.fields(SchedulePolicy)]
+    assert sorted(fields) == sorted(POLICY_SETTINGS), "a new SchedulePolicy field needs a setting in POLICY_SETTINGS"
+    table = tmp_path / "table.json"
+    table.write_text(json.dumps({"2,16,24,64,64,1,1": 21}))
+    base = _cache_key()
+    assert base == _cache_key()
+    for name in fields:
+        with monkeypatch.context() as mp:
+            for k, v in POLICY_SETTINGS[name].items():
+                mp.setenv(k, str(table) if v == "TABLE" else v)
+            assert getattr(SchedulePolicy.from_env(), name) != getattr(SchedulePolicy.from_env({"SMAP_CAT": "1", "SMAP_SKIPSUM": "1", "SMAP_TAPHEAD": "1"}), name), name
+            assert _cache_key() != base, name
+        assert _cache_key() == base, name
+    for k in ("SMAP_DECODE_THREADS", "SMAP_LAUNCH_FRAMES", "SMAP_TRACE_PTR", "SMAP_ARENAS_PER_DEVICE"):       # not schedule switches
+        monkeypatch.setenv(k, "3")
+    assert _cache_key() == base
+
+
+def test_plan_cache_key_covers_both_tile_tables(monkeypatch, tmp_path):
+    t16, tx3 = tmp_path / "t16.json", tmp_path / "tx3.json"
+    for t in (t16, tx3):
+        t.write_text(json.dumps({"2,16,24,64,64,1,1": 21}))
+    monkeypatch.setenv("SMAP_TILE_TABLE", str(t16))
+    monkeypatch.setenv("SMAP_TILE_TABLE_X3", str(tx3))
+    keys = [_cache_key()]
+    for t in (t16, tx3):
+        t.write_text(json.dumps({"2,16,24,64,64,1,1": 21, "2,16,24,64,256,1,1": 20}))
+        keys.append(_cache_key())
+    assert len(set(keys)) == 3, keys
+    monkeypatch.setenv("SMAP_NO_TILE_TABLE", "1")         # both tables empty, whatever the files say
+    assert _cache_key() not in keys
+
+
+def _plain_1x1(g):
+    """The first launch of Graph g that Graph.conv built from one 1x1 conv of 64 output channels: (op, its key in the tile tables)."""
+    from smap_amd.engine import OP_CONV
+    op = next(op for op in g.ops if op.kind == OP_CONV and op.p["ksize"] == 1 and op.p["Cout"] == 64 and op.p["kinds"] == "1x1"
+              and not ({"segs", "cat", "tap"} & set(op.p)) and not op.aux)
+    return op, f"{op.p['frames']},{op.inp.H},{op.inp.W},{op.p['Cin']},64,1,{op.p['stride']}"
+
+
+def test_every_graph_is_built_under_its_own_policy(small_sd, monkeypatch, tmp_path):
+    from smap_amd.engine import Graph, SchedulePolicy
+    monkeypatch.setenv("SMAP_BLOCK", "")                  # (layer by layer: layer1's 1x1 convs are launches of their own)
+    monkeypatch.setenv("SMAP_BLOCK_FIRST", "")
+    monkeypatch.setenv("SMAP_NO_TILE_TABLE", "1")
+    g1 = Graph(small_sd, 2, 64, 96, precision="x3")
+    op1, key = _plain_1x1(g1)
+    other = 21 if op1.p["tile"] != 21 else 22             # the two 32-half K tiles a 64-channel launch may run on
+    table = tmp_path / "tx3.json"
+    table.write_text(json.dumps({key: other}))
+    monkeypatch.setenv("SMAP_TILE_TABLE_X3", str(table))
+    assert _plain_1x1(Graph(small_sd, 2, 64, 96, precision="x3"))[0].p["tile"] == op1.p["tile"]       # SMAP_NO_TILE_TABLE still set
+    monkeypatch.delenv("SMAP_NO_TILE_TABLE")
+    g2 = Graph(small_sd, 2, 64, 96, precision="x3")       # same process, other table: honoured
+    assert g2.policy.tile_table_x3 == {key: other} and g1.policy.tile_table_x3 == {}
+    assert _plain_1x1(g2)[0].p["tile"] == other
+    g3 = Graph(small_sd, 2, 64, 96, precision="x3", policy=g1.policy)          # an explicit policy: the environment is not consulted
+    assert g3.policy is g1.policy and [op.p.get("tile") for op in g3.ops] == [op.p.get("tile") for op in g1.ops]
+    assert SchedulePolicy.from_env({"SMAP_NO_TILE_TABLE": "1", "SMAP_BLOCK": "", "SMAP_BLOCK_FIRST": "", "SMAP_CAT": "1", "SMAP_SKIPSUM": "1",
+                                    "SMAP_TAPHEAD": "1"}) == g1.policy
+
+
+def test_schedule_switches_are_read_in_from_env_only(small_sd, monkeypatch, tmp_path):
+    """Built twice under ONE policy object, with every switch variable of the environment changed in between: the same blob."""
+    from smap_amd.engine import Graph, SchedulePolicy
+    policy = SchedulePolicy.from_env()
+
+    def blob():
+        g = Graph(small_sd, 2, 64, 96, precision="x3", policy=policy)
+        g.allocate()
+        return g.blob()
+    want = blob()
+    table = tmp_path / "table.json"
+    table.write_text(json.dumps({"2,16,24,64,64,1,1": 21}))
+    for setting in POLICY_SETTINGS.values():
+        for k, v in setting.items():
+            monkeypatch.setenv(k, str(table) if v == "TABLE" else v)
+    monkeypatch.setenv("SMAP_NO_TILE_TABLE", "1")
+    assert SchedulePolicy.from_env() != policy
+    assert blob() == want

@@ -329,9 +329,7 @@ def test_cli_eval_loss_on_both_loaders(tmp_path, monkeypatch):
     from model.smap import SMAP
     from smap_amd.loss import ValidationLoss
     from test_entry_gpu import _annotated_set
-    import smap_amd.engine as E
-    monkeypatch.setattr(E, "_TILE_TABLE_X3", {})
-    monkeypatch.setattr(E, "_TILE_TABLE", {})
+    monkeypatch.setenv("SMAP_NO_TILE_TABLE", "1")
     torch.manual_seed(0)
     net = SMAP(make_cfg((128, 208))).eval()
     sd = recipe_state_dict(net.state_dict())
