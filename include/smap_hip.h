@@ -222,7 +222,9 @@ typedef struct smap_op {
                                        number of OUTPUT frames; when flip_from > 0 the summed maps of frame b + flip_from
                                        are merged into frame b: out[b,c,y,x] = v[b,c,y,x] + s_c * v[b+flip_from, pair[c], y,
                                        W-1-x], s_c = -1 on PAF-x channels (c >= in_c_off, (c - in_c_off) even), then
-                                       channels >= in_c_off are halved; pair = int32[Cout] at w_off in the weight blob. */
+                                       channels >= in_c_off are halved; pair = int32[Cout] at w_off in the weight blob.
+                                       HEADSUM: Cin (the sources' channel stride) is a multiple of 4, every aux_h / aux_w below n_aux
+                                       is >= 1, and flip_from is 0 or B. */
     int32_t w_pairs;                /* CONV, 32-half K tiles only: 1 = the weight blob stores them in pairs (see w_off), 0 = one
                                        contiguous block per K tile */
     int32_t status_off;             /* HEADSUM: byte offset (> 0) in the fp32 output buffer of SMAP_STATUS_WORDS(B) int32 STATUS words, or

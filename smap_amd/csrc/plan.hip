@@ -116,7 +116,7 @@ __global__ __launch_bounds__(256) void stem_kernel(const StemIn in, const _Float
             for (int t = 0; t < 2; ++t) {                      // 8 consecutive columns, 4-byte aligned: 4 x b32
                 const unsigned* q = reinterpret_cast<const unsigned*>(s_p + pl * 3 * ST_PH * ST_PW + pbase[t] + goff);
                 union { unsigned u[4]; half8 h; } cv;
-                cv.u[0] = q[0]; cv.u[1] = q[1]; cv.u[2] = q[2]; cv.u[3] = q[3];
+                cv.u[0] = q[0]; cv.u[1] = q[1]; cv.u[2] = q[2]; cv.u[3] = q[3] & 0xffffu;      // column 8 has weight 0: a NaN / inf there is not in the window
                 pf[pl][t] = cv.h;
             }
         }
@@ -268,7 +268,7 @@ __global__ __launch_bounds__(256) void stem_pool_kernel(const StemIn in, const _
             for (int t = 0; t < 2; ++t) {
                 const unsigned* q = reinterpret_cast<const unsigned*>(s_p + pl * 3 * SP_PH * SP_PW + pbase[t] + goff);
                 union { unsigned u[4]; half8 h; } cv;
-                cv.u[0] = q[0]; cv.u[1] = q[1]; cv.u[2] = q[2]; cv.u[3] = q[3];
+                cv.u[0] = q[0]; cv.u[1] = q[1]; cv.u[2] = q[2]; cv.u[3] = q[3] & 0xffffu;      // column 8 has weight 0: a NaN / inf there is not in the window
                 pf[pl][t] = cv.h;
             }
         }
@@ -342,7 +342,8 @@ __global__ __launch_bounds__(256) void stem_pool_kernel(const StemIn in, const _
 
 // --------------------------------------------------------------- maxpool --
 // NHWC fp16, 3x3 stride 2 pad 1 (padding never wins: only in-range taps are read).
-// X3: pixel = [hi(C) | lo(C)]; the maximum is taken over hi + lo (exact in fp32) and re-split (the same pair comes back).
+// X3: pixel = [hi(C) | lo(C)]; the maximum is taken over hi + lo (exact in fp32) and the winner's own pair is stored (re-splitting the
+// sum would turn (odd hi, lo = half an ulp of it) into (the even neighbour, -lo): the same value, another pair).
 template <bool X3>
 __global__ void maxpool_kernel(const _Float16* __restrict__ in, _Float16* __restrict__ out, int B, int H, int W,
                                int C, int Ho, int Wo)
@@ -358,8 +359,9 @@ __global__ void maxpool_kernel(const _Float16* __restrict__ in, _Float16* __rest
         pix /= Wo;
         const int oy = (int)(pix % Ho), b = (int)(pix / Ho);
         float m[8];
+        half8 h, l;                                            // X3: the winner's pair
 #pragma unroll
-        for (int e = 0; e < 8; ++e) m[e] = -INFINITY;
+        for (int e = 0; e < 8; ++e) { m[e] = -INFINITY; h[e] = (_Float16)-INFINITY; l[e] = (_Float16)0.f; }
         for (int dy = 0; dy < 3; ++dy) {
             const int iy = oy * 2 - 1 + dy;
             if ((unsigned)iy >= (unsigned)H) continue;
@@ -371,24 +373,26 @@ __global__ void maxpool_kernel(const _Float16* __restrict__ in, _Float16* __rest
                 if (X3) {
                     const half8 vl = *reinterpret_cast<const half8*>(ip + C);
 #pragma unroll
-                    for (int e = 0; e < 8; ++e) { const float x = (float)v[e] + (float)vl[e]; m[e] = (x > m[e] || x != x) ? x : m[e]; }   // ATen's rule: NaN sticks
+                    for (int e = 0; e < 8; ++e) {
+                        const float x = (float)v[e] + (float)vl[e];
+                        const bool take = x > m[e] || x != x;  // ATen's rule: NaN sticks
+                        m[e] = take ? x : m[e];
+                        h[e] = take ? v[e] : h[e];
+                        l[e] = take ? vl[e] : l[e];
+                    }
                 } else {
 #pragma unroll
                     for (int e = 0; e < 8; ++e) { const float x = (float)v[e]; m[e] = (x > m[e] || x != x) ? x : m[e]; }
                 }
             }
         }
-        half8 h;
+        if (!X3) {
 #pragma unroll
-        for (int e = 0; e < 8; ++e) h[e] = (_Float16)m[e];
+            for (int e = 0; e < 8; ++e) h[e] = (_Float16)m[e];
+        }
         _Float16* op = out + (((size_t)b * Ho + oy) * Wo + ox) * (NPL * C) + cg * 8;
         *reinterpret_cast<half8*>(op) = h;
-        if (X3) {
-            half8 l;
-#pragma unroll
-            for (int e = 0; e < 8; ++e) l[e] = (_Float16)(m[e] - (float)h[e]);
-            *reinterpret_cast<half8*>(op + C) = l;
-        }
+        if (X3) *reinterpret_cast<half8*>(op + C) = l;
     }
 }
 
@@ -493,7 +497,7 @@ __global__ __launch_bounds__(256) void headsum_kernel(HeadSrc s, float* __restri
     const int b = blockIdx.z, y = blockIdx.y, x0 = blockIdx.x * HS_PX, tid = threadIdx.x;
     const Lerp ly0 = lerp_index(y, s.h[0], Ho);
     const Lerp ly1 = lerp_index(y, s.n > 1 ? s.h[1] : Ho, Ho), ly2 = lerp_index(y, s.n > 2 ? s.h[2] : Ho, Ho);
-    // four channels per thread (16-byte loads; Cs is a multiple of 8)
+    // four channels per thread (16-byte loads; Cs is a multiple of 4: plan_check.cpp)
     const int G = Cs >> 2;
     for (int idx = tid; idx < HS_PX * G; idx += 256) {
         const int px = idx / G, c = (idx - px * G) * 4;

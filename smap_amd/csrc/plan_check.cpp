@@ -247,8 +247,11 @@ int geometry(const smap_op& o)
             if (o.status_off < 0 || o.status_off % 4) return SMAP_E_ARG;
             return 0;
         case SMAP_OP_HEADSUM:
-            if (o.n_aux < 1 || o.n_aux > 3 || o.Cout > 48 || o.Cin < o.Cout) return SMAP_E_ARG;
+            if (o.n_aux < 1 || o.n_aux > 3 || o.Cout > 48 || o.Cin < o.Cout || o.Cin % 4) return SMAP_E_ARG;      // (float4 loads of the sources)
+            for (int k = 0; k < o.n_aux; ++k)
+                if (o.aux_h[k] <= 0 || o.aux_w[k] <= 0) return SMAP_E_ARG;
             if (o.flip_from < 0 || (o.flip_from > 0 && (o.in_c_off < 0 || o.in_c_off > o.Cout))) return SMAP_E_ARG;
+            if (o.flip_from > 0 && o.flip_from != o.B) return SMAP_E_ARG;      // the mirrored frame of b is b + B: the sources hold 2 B frames
             if (o.status_off < 0 || o.status_off % 4) return SMAP_E_ARG;
             if ((o.scale_hms != 0 && o.scale_hms != 1) || (o.scale_hms && (o.in_c_off < 0 || o.in_c_off > o.Cout))) return SMAP_E_ARG;
             return 0;

@@ -241,6 +241,19 @@ def split_f16(w, scaled=True):
     return hi, lo, 2.0 ** -s
 
 
+def pack_stem_weights(w, x3):
+    """The stem's [64, 3, 7, 7] f64 weights -> (what SMAP_OP_STEM / STEMPOOL read at w_off, acc_scale): fp16 [64][22][8], K = (kh, c, kw
+    7->8) + one zero granule; split precision: the hi and the lo matrix of w * 2^s one behind the other, acc_scale = 2^-s."""
+    if x3:
+        hi, lo, scale = split_f16(w.permute(0, 2, 1, 3).reshape(64, 21, 7))
+        wk = torch.zeros((2, 64, 22, 8), dtype=torch.float16)
+        wk[0, :, :21, :7], wk[1, :, :21, :7] = hi, lo
+        return wk.reshape(2, 64, 176), scale
+    wk = torch.zeros((64, 22, 8), dtype=torch.float16)
+    wk[:, :21, :7] = w.permute(0, 2, 1, 3).reshape(64, 21, 7).to(torch.float16)
+    return wk.reshape(64, 176), 1.0
+
+
 def _table_entry(v):
     """A table value is one tile id or a ranked list of them (best first): the specialised kernels do not take every op of
     a shape (conv3.hip: plain 3x3 only; convp.hip: no fused bilinear add, no fp32 output), Graph.conv picks the first
@@ -1004,16 +1017,7 @@ class Graph:
         B, H, W, sd = self.B, self.H, self.W, self.sd
         # ResNet_top (smap.py:80-92)
         w, b = self._fold("top.conv")
-        stem_scale = 1.0
-        if self.x3:
-            hi, lo, stem_scale = split_f16(w.permute(0, 2, 1, 3).reshape(64, 21, 7))
-            wk = torch.zeros((2, 64, 22, 8), dtype=torch.float16)
-            wk[0, :, :21, :7], wk[1, :, :21, :7] = hi, lo
-            wk = wk.reshape(2, 64, 176)
-        else:
-            wk = torch.zeros((64, 22, 8), dtype=torch.float16)      # K = (kh, c, kw 7->8) + one zero granule
-            wk[:, :21, :7] = w.permute(0, 2, 1, 3).reshape(64, 21, 7).to(torch.float16)
-            wk = wk.reshape(64, 176)
+        wk, stem_scale = pack_stem_weights(w, self.x3)
         H2, W2 = (H + 6 - 7) // 2 + 1, (W + 6 - 7) // 2 + 1
         H4, W4 = (H2 + 2 - 3) // 2 + 1, (W2 + 2 - 3) // 2 + 1
         self.flops += 2 * B * H2 * W2 * 64 * 147

@@ -34,34 +34,43 @@ def weight_blob(chunks):
     return blob, offs
 
 
-def arena_of(tensors, *regions):
-    """Stored tensors (None: absent, offset -1), then zeroed regions of `regions` bytes, 256-aligned one behind the other behind the zero
-    page -> (uint8 host arena, the offsets of all of them)."""
+def arena_offsets(sizes):
+    """Byte sizes (None: absent, offset -1), 256-aligned one behind the other behind the zero page -> (their offsets, the arena's bytes)."""
     from smap_amd.engine import ZERO_PAGE
     offs, cur = [], ZERO_PAGE
-    for n in [None if t is None else t.numel() * t.element_size() for t in tensors] + list(regions):
+    for n in sizes:
         offs.append(-1 if n is None else cur)
         cur += _al(n or 0)
-    arena = torch.zeros(cur + 256, dtype=torch.uint8)
+    return offs, cur + 256
+
+
+def arena_of(tensors, *regions):
+    """Stored tensors (None: absent, offset -1), then zeroed regions of `regions` bytes, laid out by arena_offsets -> (uint8 host arena,
+    the offsets of all of them)."""
+    offs, total = arena_offsets([None if t is None else t.numel() * t.element_size() for t in tensors] + list(regions))
+    arena = torch.zeros(total, dtype=torch.uint8)
     for t, o in zip(tensors, offs):
         if t is not None:
             arena[o:o + t.numel() * t.element_size()] = raw8(t)
     return arena, offs
 
 
-def run_plan(ops, n, arena, blob, out=None):
+def run_plan(ops, n, arena, blob, out=None, inp=None):
     """A plan of the n smap_op in `ops` (one op or an array): create, run once on the current stream over arena / blob (copied to the device
-    unless they are there) [and the output buffer `out`], synchronise, destroy.  Returns the device arena."""
+    unless they are there) [, the output buffer `out` and the device images `inp` of a stem], synchronise, destroy.  Returns the device
+    arena."""
     from smap_amd import lib as L
     lib = L.load()
     h = C.c_void_p()
     L.check(lib.smap_plan_create(ops if isinstance(ops, C.Array) else C.byref(ops), n, C.byref(h)), "smap_plan_create")
     arena, blob = arena.to(DEV), blob.to(DEV)
     st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-    L.check(lib.smap_plan_run(h, None, C.c_void_p(arena.data_ptr()), C.c_void_p(blob.data_ptr()),
-                              C.c_void_p(out.data_ptr()) if out is not None else None, st), "run")
-    torch.cuda.synchronize()
-    lib.smap_plan_destroy(h)
+    try:
+        L.check(lib.smap_plan_run(h, C.c_void_p(inp.data_ptr()) if inp is not None else None, C.c_void_p(arena.data_ptr()),
+                                  C.c_void_p(blob.data_ptr()), C.c_void_p(out.data_ptr()) if out is not None else None, st), "run")
+        torch.cuda.synchronize()
+    finally:
+        lib.smap_plan_destroy(h)
     return arena
 
 
