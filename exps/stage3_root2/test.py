@@ -26,6 +26,10 @@ and the depth-order reverse rate of lib/eval/test_util_panoptic.py (eval_3d, cal
 keypoint recall and the per-bone relative-depth error / reverse count of that module's `eval` branch (eval_one_image, generate_rootZ),
 accumulated on the GPU next to the lifting kernel (smap_amd/evaluate.py EvalMaps); the six raw accumulators are added to `error`.
 
+`-t generate_result --eval_mupots ROOT` (addition) scores the finished run by the MuPoTS-3D protocol (lib/eval/mupots_smap.m: 3DPCK, AUC,
+MPJPE, ordinal rate; smap_amd/mupots.py on the GPU) against TS<k>/annot.mat and TS<k>/occlusion.mat under ROOT and writes the summary
+into error["mupots"] of the result file: lib/eval/convert.py and the MATLAB step in one.
+
 `-t generate_result|generate_train --maps_from_gt 1` (addition): the maps of every batch are RENDERED from the frame's annotations on the
 GPU (smap_amd/labels.py: what a perfectly trained backbone would return) instead of coming from the backbone: no checkpoint, no engine,
 no image file; everything behind the maps is unchanged.  Checks an annotation file end to end and measures the ceiling of association +
@@ -360,8 +364,12 @@ class _DryRunPipeline:
 
 
 def generate_3d_point_pairs(model, refine_model, data_loader, cfg, logger, device, output_dir="", pipeline_cls=None, eval_3d=False, eval_maps=False,
-                            maps_from_gt=False, eval_loss=False):
+                            maps_from_gt=False, eval_loss=False, eval_mupots=None):
     os.makedirs(output_dir, exist_ok=True)
+    mupots_ann = None
+    if eval_mupots:                # read before the run: a wrong root is refused at once
+        from smap_amd.mupots import load_annotations
+        mupots_ann = load_annotations(eval_mupots)
     source = {}
     if maps_from_gt:               # the batches carry no frames (AnnotationLoader): their maps are rendered from the annotations
         from smap_amd.labels import GtMapsSource, label_spec
@@ -508,9 +516,22 @@ def generate_3d_point_pairs(model, refine_model, data_loader, cfg, logger, devic
         name = os.path.join(output_dir, "{}_{}_{}_{}.json".format(dir_name, cfg.TEST_MODE, cfg.DATA_MODE,
                                                                   cfg.JSON_SUFFIX_NAME))
         result["3d_pairs"] = to_jsonable(result["3d_pairs"])          # ndarray -> nested lists, once, at the end of the run
+        mupots_refusal = None
+        if mupots_ann is not None:                                    # on the records as the file will hold them
+            from lib.eval.convert import convert_records
+            from smap_amd.mupots import MuPoTSScorer
+            try:
+                pose3d, pose2d, _ = convert_records(result["3d_pairs"])
+                summary = MuPoTSScorer(mupots_ann, device=device).score(pose2d, pose3d).summary()
+                logger.info("MuPoTS-3D: 3DPCK {mean_pck:.4g}  AUC {mean_auc:.4g}  MPJPE {mean_mpjpe:.6g} mm (means over the sequences)".format(**summary))
+                result.setdefault("error", {})["mupots"] = summary
+            except Exception as exc:                                  # refused or failed: the pairs are written all the same
+                mupots_refusal = exc
         with open(name, "w") as f:
             json.dump(result, f)
         logger.info("Pairs writed to {}".format(name))
+        if mupots_refusal is not None:
+            raise mupots_refusal
     return result
 
 
@@ -566,7 +587,15 @@ def main():
                         help="(addition) 1, with -t generate_result: the validation loss of the checkpoint (SMAP.forward with labels rendered "
                              "from every batch's annotations) as frame-weighted means into error['loss'] of the result file.  One more "
                              "forward per batch; the value depends on --batch_size, as the training log's does")
+    parser.add_argument("--eval_mupots", metavar="ROOT", default="",
+                        help="(addition) with -t generate_result: score the run by the MuPoTS-3D protocol on the GPU (3DPCK, AUC, MPJPE, "
+                             "ordinal rate: lib/eval/mupots_smap.m) against TS<k>/annot.mat + occlusion.mat under ROOT and write the "
+                             "summary into error['mupots'] of the result file")
     args = parser.parse_args()
+    if args.eval_mupots and args.test_mode != "generate_result":
+        parser.error("--eval_mupots requires -t generate_result")
+    if args.eval_mupots and args.dry_run:
+        parser.error("--eval_mupots scores on the GPU: not available with --dry_run 1")
     if args.eval_loss and args.test_mode != "generate_result":
         parser.error("--eval_loss 1 requires -t generate_result")
     if args.eval_loss and args.dry_run:
@@ -679,7 +708,8 @@ def main():
                 return
         result = generate_3d_point_pairs(model, refine_model, data_loader, cfg, logger, device,
                                          output_dir=os.path.join(cfg.OUTPUT_DIR, "result"), eval_3d=bool(args.eval_3d),
-                                         eval_maps=bool(args.eval_maps), maps_from_gt=bool(args.maps_from_gt), eval_loss=bool(args.eval_loss))
+                                         eval_maps=bool(args.eval_maps), maps_from_gt=bool(args.maps_from_gt), eval_loss=bool(args.eval_loss),
+                                         eval_mupots=args.eval_mupots or None)
         if dist.is_initialized():
             dist.destroy_process_group()
         if result.get("dropped_frames"):

@@ -555,6 +555,37 @@ int smap_evalmaps_acc_init(double* acc, void* stream);
 int smap_evalmaps_update(const double* pred_2d, const double* depth_v, const int32_t* bone_mask, const int32_t* counts,
                          const double* gt_2d, int B, int G, double* terms, double* acc, void* stream);
 
+/* ---- scoring MuPoTS-3D: lib/eval/mupots_smap.m and lib/eval/util_smap/ (3DPCK, AUC, MPJPE, ordinal rate) on the device ----
+ * Joints in the protocol's order (head top, neck, right arm, left arm, right leg, left leg, pelvis); the predictions arrive in SMAP's
+ * order (pose2d.mat / pose3d.mat) and are re-ordered where they are read.  F frames of S sequences, one after the other.
+ *   gt2d [F,G,15,2], gt3d [F,G,15,3], occ [F,G,15] f64: annot2, univ_annot3 and occlusion_labels (first 15 columns) of every frame's
+ *     VALID persons in annotation order; gt_count [F] int32 (clamped to 0..G), 1 <= G <= SMAP_MUPOTS_MAXG.
+ *   pred2d [sumP,15,2] (pixels), pred3d [sumP,15,4] (mm; column 3 is not read) f64; frame f owns rows pred_offset[f] .. pred_offset[f + 1] - 1
+ *     (int32 [F + 1]), at most SMAP_MUPOTS_MAXP of them; a range outside 0..sumP is read as no prediction.
+ *   relative: both sides minus their pelvis; use_skel: the matched prediction's bones scaled to the ground truth's lengths;
+ *     matched_only: EVALUATION_MODE 1, unmatched persons are not considered.
+ * smap_mupots_frames, one wavefront per frame: the greedy matching (ground-truth persons in order; score = joints 2..14 within 40 px on
+ * both axes, strictly, whose prediction is not at exactly (0, 0); the first prediction with the largest score > 0 wins and is not
+ * offered again), then per (person, joint) the error sqrt(((dx*dx) + (dy*dy)) + (dz*dz)); an unmatched person's prediction is 100000
+ * everywhere.  Rows out, written for g < gt_count[f] only: match [F,G] int32 (index inside the frame, -1 = unmatched), considered [F,G]
+ * int32, err [F,G,15] f64, rootz [F,G,2] f64 = (the prediction's, the ground truth's) pelvis depth as the ordinal test reads them.
+ * smap_mupots_fold, one thread per (sequence, field): acc [S, SMAP_MUPOTS_ACC_DOUBLES] f64 from the rows of frames seq_offset[s] ..
+ * seq_offset[s + 1] - 1 (int32 [S + 1], clamped to 0..F), frames then persons in order; no atomics, every field is written.  Counts are
+ * exact doubles.  Layout of a sequence's accumulator:
+ *   0 considered persons | 1 annotated (valid) persons | 2 undetected (unmatched) persons | 3 ordinal pairs correct | 4 ordinal pairs
+ *   (both 0 in relative mode) | 5 + 33 * j, j = 0..14: error sum, 31 counts of err < 0, 5, .. 150 (strict), count of err <= 150 |
+ *   500 + 45 * m + 3 * j, m = 0 visible (1 - occ) / 1 occluded (occ): mask sum, sum of (NaN -> 160) * mask, count of that > 150.
+ * float64 without contraction, correctly rounded square root and division (csrc/mupots_core.h is the text, for host and device). */
+#define SMAP_MUPOTS_MAXG 16
+#define SMAP_MUPOTS_MAXP 127
+#define SMAP_MUPOTS_ACC_DOUBLES 590
+int smap_mupots_frames(const double* gt2d, const double* gt3d, const int32_t* gt_count, const double* pred2d, const double* pred3d,
+                       const int32_t* pred_offset, int F, int G, int sumP, int relative, int use_skel, int matched_only, int32_t* match,
+                       int32_t* considered, double* err, double* rootz, void* stream);
+int smap_mupots_fold(const int32_t* seq_offset, int S, const int32_t* gt_count, int F, int G, const int32_t* match,
+                     const int32_t* considered, const double* err, const double* rootz, const double* occ, int relative, double* acc,
+                     void* stream);
+
 /* ---- label maps: dataset/representation.py generate_heatmap (:5-21) and generate_paf / putVecMaps3D (:36-113) on the device ----
  * labels: [B, S, SMAP_LABEL_C, H, W] fp32 out, the layout of JointDataset.__getitem__ (dataset/base_dataset.py:177-185): per label
  * scale 15 heat-maps (x 255), then per limb its x, y (x 127) and relative-depth channel.  Every value is written.

@@ -15,10 +15,11 @@ CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "libsmap_hip.so")
 OBJ = os.path.join(CSRC, "obj")
 
-# (source, extra flags).  assoc.hip, eval.hip, labels.hip and loss.hip are bit-exact float work: contraction OFF.
+# (source, extra flags).  assoc.hip, eval.hip, mupots.hip, labels.hip and loss.hip are bit-exact float work: contraction OFF.
 SOURCES = [
     ("assoc.hip", ["-ffp-contract=off"]),
     ("eval.hip", ["-ffp-contract=off"]),
+    ("mupots.hip", ["-ffp-contract=off"]),       # MuPoTS-3D protocol: float64 in a fixed order; its arithmetic is csrc/mupots_core.h (also built alone for the CPU)
     ("labels.hip", ["-ffp-contract=off"]),       # label maps: held to the reference's bits as well
     ("loss.hip", ["-ffp-contract=off"]),         # training loss: fixed-order double sums; its finish is csrc/loss_core.h (also built alone for the CPU)
     ("conv.hip", []),

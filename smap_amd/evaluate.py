@@ -19,9 +19,12 @@ associates the same way, so the six counters and `distance_d` are the reference'
 `distance()` squares and roots with `**`, i.e. libm `pow`, which differs from multiply / correctly rounded `sqrt` in the last place
 for ~1 % of inputs (DESIGN section 10 has the bound).  Limb 0 is (0, 1) = cfg.DATASET.PAF.VECTOR, the table the lifting samples with;
 the panoptic module's own table has (1, 0) there.  Annotation depths are subtracted in float64 as they stand, where the reference,
-handed a float32 annotation array, would subtract in fp32.  Not scored: the MuPoTS MATLAB protocol.
+handed a float32 annotation array, would subtract in fp32.  The MuPoTS-3D protocol (lib/eval/mupots_smap.m: 3DPCK, AUC, MPJPE,
+ordinal rate) is scored by smap_amd/mupots.py; `--mupots ROOT` below runs it.
 
     python -m smap_amd.evaluate RESULT.json [--refine 0|1] [--maps 0|1] [--device cuda:0]
+    python -m smap_amd.evaluate RESULT.json --mupots ROOT [--relative 0|1] [--matched_only 0|1] [--use_skel 0|1] [--out DIR]
+    python -m smap_amd.evaluate --pose3d pose3d.mat --pose2d pose2d.mat --mupots ROOT ...
 
 scores an existing result file -- this project's or one written by the reference's test.py -- and prints the summary as
 JSON.  Annotations are fp32 (dataset/base_dataset.py), so a file holds exactly the ground truth the run saw; where the
@@ -528,16 +531,52 @@ def score_file(path, device="cuda:0", refine=False, frames_per_call=256):
     return score_records(_load_pairs(path), device, refine, path=path, frames_per_call=frames_per_call).raw()
 
 
+def _main_mupots(ap, args):
+    """`--mupots ROOT`: convert (or read the two .mat files), score, print the summary as JSON.  Refusals: exit status 2."""
+    from . import mupots as M
+    if (args.pose3d is None) != (args.pose2d is None):
+        ap.error("--pose3d and --pose2d come together")
+    if (args.result is None) == (args.pose3d is None):
+        ap.error("--mupots scores either a result JSON or --pose3d / --pose2d")
+    try:
+        ann = M.load_annotations(args.mupots)
+        if args.result is not None:
+            from lib.eval.convert import convert_records
+            pose3d, pose2d, _ = convert_records(_load_pairs(args.result))
+        else:
+            pose2d, pose3d = M.load_pose_mats(args.pose3d, args.pose2d)
+        res = M.MuPoTSScorer(ann, bool(args.relative), bool(args.use_skel), bool(args.matched_only), args.device).score(pose2d, pose3d)
+        if args.out:
+            res.write_csv(args.out)
+    except (ValueError, OSError, KeyError, NotImplementedError) as exc:
+        print(f"smap_amd.evaluate: {exc}", file=sys.stderr)
+        return 2
+    print(json.dumps(res.summary()))
+    return 0
+
+
 def main(argv=None):
     import argparse
     ap = argparse.ArgumentParser(prog="python -m smap_amd.evaluate", description="Score a `test.py -t generate_result` file on the GPU.")
-    ap.add_argument("result", help="result JSON (`3d_pairs` with pred_3d, gt_3d, gt_2d per frame)")
+    ap.add_argument("result", nargs="?", help="result JSON (`3d_pairs` with pred_3d, gt_3d, gt_2d per frame)")
     ap.add_argument("--refine", type=int, default=0, choices=[0, 1], help="1: the run used RefineNet (keys carry _after_refine)")
     ap.add_argument("--maps", type=int, default=0, choices=[0, 1],
                     help="1: score the 2D part of the maps' metrics instead (keypoint error / recall from pred_2d and gt_2d)")
     ap.add_argument("--bones", type=int, default=0, choices=[0, 1], help="refused: " + BONES_REFUSAL)
     ap.add_argument("--device", default="cuda:0")
+    ap.add_argument("--mupots", metavar="ROOT", default=None,
+                    help="score the MuPoTS-3D protocol instead (lib/eval/mupots_smap.m): ROOT holds TS<k>/annot.mat and TS<k>/occlusion.mat")
+    ap.add_argument("--relative", type=int, default=1, choices=[0, 1], help="with --mupots: 1 root-relative (is_relative), 0 absolute + ordinal rate")
+    ap.add_argument("--matched_only", type=int, default=0, choices=[0, 1], help="with --mupots: EVALUATION_MODE, 1 = only matched annotations")
+    ap.add_argument("--use_skel", type=int, default=1, choices=[0, 1], help="with --mupots: map the predicted bones to the ground truth's lengths")
+    ap.add_argument("--out", metavar="DIR", default=None, help="with --mupots: also write the three sequence-wise CSV tables there")
+    ap.add_argument("--pose3d", default=None, help="with --mupots: pose3d.mat of lib/eval/convert.py in place of the result JSON")
+    ap.add_argument("--pose2d", default=None, help="with --mupots: pose2d.mat of lib/eval/convert.py")
     args = ap.parse_args(argv)
+    if args.mupots is not None:
+        return _main_mupots(ap, args)
+    if args.result is None:
+        ap.error("the following arguments are required: result")
     if args.bones:
         print(f"smap_amd.evaluate: {BONES_REFUSAL}", file=sys.stderr)
         return 2

@@ -22,6 +22,7 @@ SYMBOLS = [
     "smap_nms_workspace_bytes", "smap_nms_ws",
     "smap_eval3d_acc_init", "smap_eval3d_terms", "smap_eval3d_fold", "smap_eval3d_update",
     "smap_evalmaps_acc_init", "smap_evalmaps_update",
+    "smap_mupots_frames", "smap_mupots_fold",
     "smap_sizeof_jpeg_info", "smap_jpeg_probe", "smap_jpeg_decode_coefficients", "smap_jpeg_workspace_bytes", "smap_jpeg_reconstruct",
     "smap_sizeof_jpeg_scan", "smap_jpeg_scan_tables", "smap_jpeg_huff_workspace_bytes", "smap_jpeg_decode_coefficients_device",
     "smap_sizeof_prep_frame", "smap_preprocess_batch",
@@ -184,6 +185,8 @@ def load():
     lib.smap_eval3d_update.argtypes = [vp, vp, vp, ip, ip, vp, vp, vp]
     lib.smap_evalmaps_acc_init.argtypes = [vp, vp]
     lib.smap_evalmaps_update.argtypes = [vp, vp, vp, vp, vp, ip, ip, vp, vp, vp]
+    lib.smap_mupots_frames.argtypes = [vp, vp, vp, vp, vp, vp, ip, ip, ip, ip, ip, ip, vp, vp, vp, vp, vp]
+    lib.smap_mupots_fold.argtypes = [vp, ip, vp, ip, ip, vp, vp, vp, vp, vp, ip, vp, vp]
     lib.smap_render_labels.argtypes = [vp, C.c_int64, C.POINTER(C.c_int32), ip, ip, ip, ip, ip, vp, vp]
     i64 = C.c_int64
     lib.smap_loss_workspace_bytes.argtypes = [ip, ip, ip]
