@@ -24,7 +24,7 @@
 #include <stdint.h>
 #include "smap_hip.h"
 #include "plan.h"
-#include "conv_device.h"
+#include "block_device.h"       // the LDS write-back of y1 / y2 and the pixel-offset block, shared with convb.hip
 
 namespace {
 
@@ -34,20 +34,6 @@ namespace {
 #ifndef SMAP_CONVC_NRS
 #define SMAP_CONVC_NRS 2
 #endif
-#ifndef SMAP_CONVC_PIPE
-#define SMAP_CONVC_PIPE 1          // 0 = round 5's loops (fragments single-buffered, read -> wait -> multiply inside every K step)
-#endif
-
-// SMAP_CONVC_PIPE: the barrier whose wait hipcc's wait-count pass sees (conv_device.h says why); round 5's loops keep the inline-asm form
-__device__ __forceinline__ void lds_barrier()
-{
-#if SMAP_CONVC_PIPE
-    lds_barrier_builtin();
-#else
-    lds_barrier_asm();
-#endif
-}
-
 #ifndef SMAP_CONVC_ABLATE
 #define SMAP_CONVC_ABLATE 0        // diagnostics builds only (tools/build_ablate.py --one convc.hip SMAP_CONVC_ABLATE=N): 1 no x requests, 2 no MFMA,
 #endif                             // 4 no global stores, 8 no weight requests
@@ -162,7 +148,6 @@ __global__ __launch_bounds__(512, 2) void bottleneck128_kernel(const ConvArgs a,
     }
     const int fswz = (l31 >> 1) & 7;                            // (row >> 1) & 7 of every fragment row = multiple of 32 + l31
 
-#if SMAP_CONVC_PIPE
     // SOFTWARE PIPELINE (round 6).  Round 5's loops read a K step's fragments, waited for them and multiplied, step after step: hipcc
     // turns that into `ds_read x2-4, s_waitcnt lgkmcnt(0), mfma x1-4` groups -- an LDS round trip exposed five or six times per barrier
     // interval, in BOTH waves of a SIMD at once (they walk in step), which is where the tile's 105k non-MFMA cycles of 163k came from
@@ -197,7 +182,7 @@ __global__ __launch_bounds__(512, 2) void bottleneck128_kernel(const ConvArgs a,
     for (int ks = 0; ks < KS1; ++ks) {
         if (ks + NS1 - 1 <= KS1) wait_vm((NS1 - 2) * LPT1);     // stage ks has landed; younger stages stay in flight
         else wait_vm((KS1 - 1 - ks) * LPT1);
-        lds_barrier();
+        lds_barrier_builtin();
         if (ks + NS1 - 1 < KS1) issue1((ks + NS1 - 1) % NS1, ks + NS1 - 1);     // into the buffer stage ks-1 was read from
         rd1(ks, 0, w1a, x1a);
         if ((ks >> 2) < NRS && (ks & 3) == wn) {                // this wave's residual channels: nc*128 + wn*32 + .. = stage 4 nc + wn
@@ -223,47 +208,7 @@ __global__ __launch_bounds__(512, 2) void bottleneck128_kernel(const ConvArgs a,
         __builtin_amdgcn_sched_barrier(0);
     }
     mm1(w1b, x1b);
-#else
-#pragma unroll
-    for (int ks = 0; ks < KS1; ++ks) {
-        if (ks + NS1 - 1 <= KS1) wait_vm((NS1 - 2) * LPT1);     // stage ks has landed; younger stages stay in flight
-        else wait_vm((KS1 - 1 - ks) * LPT1);
-        lds_barrier();
-        if (ks + NS1 - 1 < KS1) issue1((ks + NS1 - 1) % NS1, ks + NS1 - 1);     // into the buffer stage ks-1 was read from
-        const char* sX = smem + (ks % NS1) * ST1;
-        const char* sW = sX + XS;
-        if ((ks >> 2) < NRS && (ks & 3) == wn) {                // this wave's residual channels: nc*128 + wn*32 + .. = stage 4 nc + wn
-#pragma unroll
-            for (int mi = 0; mi < MI; ++mi) {
-                int cr = crow[mi];
-                asm volatile("" : "+v"(cr));                    // addresses computed HERE, four times per wave: precomputed for all stages they
-#pragma unroll                                                  // would cost the 8-16 registers the residual does not leave
-                for (int j = 0; j < 2; ++j)
-#pragma unroll
-                    for (int pl = 0; pl < 2; ++pl)
-                        rs[ks >> 2][mi][j][pl] = *reinterpret_cast<const half8*>(sX + cr * ROWB + (((2 * j + lhi + 4 * pl) ^ ((cr >> 1) & 7)) << 4));
-            }
-        }
-#pragma unroll
-        for (int kk = 0; kk < CH / 16; ++kk) {
-            const int g = kk * 2 + lhi;
-            half8 wf[2];
-            const int slot0 = (g ^ fswz) << 4, slot1 = ((g + 4) ^ fswz) << 4;
-            wf[0] = *reinterpret_cast<const half8*>(sW + (wn * 32 + l31) * ROWB + slot0);
-            wf[1] = *reinterpret_cast<const half8*>(sW + (wn * 32 + l31) * ROWB + slot1);
-#pragma unroll
-            for (int j = 0; j < NB1; ++j) {                     // one block's fragments at a time (the residual already holds 128 registers);
-                const char* xr = sX + ((wm * NB1 + j) * 32 + l31) * ROWB;      // small cross terms first, then hi*hi (conv3.hip's order)
-                const half8 xh = *reinterpret_cast<const half8*>(xr + slot0);
-                const half8 xl = *reinterpret_cast<const half8*>(xr + slot1);
-                acc1[j] = MFMA_(wf[0], xl, acc1[j]);
-                acc1[j] = MFMA_(wf[1], xh, acc1[j]);
-                acc1[j] = MFMA_(wf[0], xh, acc1[j]);
-            }
-        }
-    }
-#endif
-    lds_barrier();                                              // every wave is done with the staging buffers (all DMA has landed)
+    lds_barrier_builtin();                                      // every wave is done with the staging buffers (all DMA has landed)
     // phase 2's accumulators start at b2 / scale: the loads go out now, ahead of the first weight slots
     float4 b2v[4];
 #pragma unroll
@@ -285,11 +230,11 @@ __global__ __launch_bounds__(512, 2) void bottleneck128_kernel(const ConvArgs a,
     for (int s = 0; s < NS - 1; ++s) issue_slot(s);
     // Ring protocol.  Slot s: [barrier: slot s is published, slot s-1's buffer is free] -> issue slot s + NS - 1 -> multiply ->
     // wait for slot s + 1; younger ones stay in flight.
-    auto wait_next = [&](int cur, int extra = 0) {              // in slot `cur` (its issue done): slot cur + 1 has landed; `extra` younger
-        if (cur + 1 >= NSLOT) return;                           // plain loads (the last chunk's residual) may stay in flight too
+    auto wait_next = [&](int cur) {                             // in slot `cur` (its issue done): slot cur + 1 has landed
+        if (cur + 1 >= NSLOT) return;
         const int issued = cur + NS - 1 < NSLOT ? cur + NS - 1 : NSLOT - 1;
         const int upto = cur + 1 < NSLOT ? cur + 1 : NSLOT - 1;
-        wait_vm((issued > upto ? issued - upto : 0) * LS + extra);
+        wait_vm((issued > upto ? issued - upto : 0) * LS);
     };
     // ---- accumulators -> y1 [KC][PROWS][128 B] (rows = patch pixels, conv3.hip's format).  acc[4*q + e] = channel
     //      nb*32 + 8*q + 4*lhi + e of patch row mb*32 + l31; rows outside the image are the 3x3's zero padding.
@@ -297,25 +242,7 @@ __global__ __launch_bounds__(512, 2) void bottleneck128_kernel(const ConvArgs a,
 #pragma unroll
     for (int j = 0; j < NB1; ++j) {
         const int prow = (wm * NB1 + j) * 32 + l31;
-        const int py = prow / PW, px = prow - py * PW;
-        const int iy = oy0 - 1 + py, ix = ox0 - 1 + px;
-        const bool live = prow < PH * PW && (unsigned)iy < (unsigned)a.H && (unsigned)ix < (unsigned)a.W;
-        const int sw = (prow >> 1) & 7;
-        char* row = sY1 + (wn * PROWS + prow) * ROWB + lhi * 8;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            half4 h, l;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                float x = acc1[j][4 * q + e] * a.acc_scale0;    // (bias inside: accumulator start value)
-                x = x < 0.f ? 0.f : x;                          // NaN stays NaN (torch's ReLU)
-                x = live ? x : 0.f;
-                h[e] = (_Float16)x;
-                l[e] = (_Float16)(x - (float)h[e]);
-            }
-            *reinterpret_cast<half4*>(row + ((q ^ sw) << 4)) = h;
-            *reinterpret_cast<half4*>(row + (((q + 4) ^ sw) << 4)) = l;
-        }
+        put_row_hilo<false>(sY1 + wn * PROWS * ROWB, prow, lhi, acc1[j], a.acc_scale0, patch_row_live<PW, PH>(a, prow, oy0, ox0), nullptr);   // (bias inside)
     }
     f32x16 acc2[MI];
     {
@@ -336,7 +263,6 @@ __global__ __launch_bounds__(512, 2) void bottleneck128_kernel(const ConvArgs a,
     for (int mi = 0; mi < MI; ++mi) prow0[mi] = crow[mi] - PW - 1;
     const int c_row0 = wn * 32 + l31;                           // this wave's 32 output channels: rows of a weight slot
 
-#if SMAP_CONVC_PIPE
     half8 a2a[2][MI], b2a[2], a2b[2][MI], b2b[2];
     auto rd2 = [&](int s, int kk, half8 (&af)[2][MI], half8 (&bf)[2]) {
         const char* sB = ring + (s % NS) * SLOT;
@@ -363,7 +289,7 @@ __global__ __launch_bounds__(512, 2) void bottleneck128_kernel(const ConvArgs a,
     };
 #pragma unroll
     for (int s = 0; s < NS2; ++s) {
-        lds_barrier();                                          // slot s landed for every wave; y1 complete (s = 0); slot s-1's buffer is free
+        lds_barrier_builtin();                                  // slot s landed for every wave; y1 complete (s = 0); slot s-1's buffer is free
         if (s + NS - 1 < NSLOT) issue_slot(s + NS - 1);
         rd2(s, 0, a2a, b2a);
         __builtin_amdgcn_sched_barrier(0);
@@ -377,79 +303,23 @@ __global__ __launch_bounds__(512, 2) void bottleneck128_kernel(const ConvArgs a,
         wait_next(s);
     }
     mm2(a2b, b2b);
-#else
-#pragma unroll
-    for (int s = 0; s < NS2; ++s) {
-        lds_barrier();                                          // slot s landed for every wave; y1 complete (s = 0); slot s-1's buffer is free
-        if (s + NS - 1 < NSLOT) issue_slot(s + NS - 1);
-        const char* sB = ring + (s % NS) * SLOT;
-        const int tap = s / KC, cc = s % KC;
-        const int shift = (tap / 3) * PW + (tap % 3);
-#pragma unroll
-        for (int kk = 0; kk < CH / 16; ++kk) {
-            const int g = kk * 2 + lhi;
-            half8 af[2][MI], bf[2];
-#pragma unroll
-            for (int pl = 0; pl < 2; ++pl) {
-#pragma unroll
-                for (int mi = 0; mi < MI; ++mi) {
-                    const int prow = prow0[mi] + shift;
-                    af[pl][mi] = *reinterpret_cast<const half8*>(sY1 + (cc * PROWS + prow) * ROWB + (((g + 4 * pl) ^ ((prow >> 1) & 7)) << 4));
-                }
-                bf[pl] = *reinterpret_cast<const half8*>(sB + c_row0 * ROWB + (((g + 4 * pl) ^ fswz) << 4));
-            }
-#pragma unroll
-            for (int mi = 0; mi < MI; ++mi) {
-                acc2[mi] = MFMA_(bf[0], af[1][mi], acc2[mi]);
-                acc2[mi] = MFMA_(bf[1], af[0][mi], acc2[mi]);
-                acc2[mi] = MFMA_(bf[0], af[0][mi], acc2[mi]);
-            }
-        }
-        wait_next(s);
-    }
-#endif
-    lds_barrier();                                              // every wave is done with y1: y2 may overwrite it
+    lds_barrier_builtin();                                      // every wave is done with y1: y2 may overwrite it
 
     // ---- accumulators -> y2 [KC][BM][128 B] (rows = tile pixels).  acc2[mi][4*q + e] = channel wn*32 + 8*q + 4*lhi + e
     char* sY2 = smem;
 #pragma unroll
-    for (int mi = 0; mi < MI; ++mi) {
-        const int p = wm * 64 + mi * 32 + l31;
-        const int sw = (p >> 1) & 7;
-        char* row = sY2 + (wn * BM + p) * ROWB + lhi * 8;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            half4 h, l;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                float x = acc2[mi][4 * q + e] * a.acc_scale;     // (bias inside)
-                x = x < 0.f ? 0.f : x;
-                h[e] = (_Float16)x;
-                l[e] = (_Float16)(x - (float)h[e]);
-            }
-            *reinterpret_cast<half4*>(row + ((q ^ sw) << 4)) = h;
-            *reinterpret_cast<half4*>(row + (((q + 4) ^ sw) << 4)) = l;
-        }
-    }
+    for (int mi = 0; mi < MI; ++mi)
+        put_row_hilo<false>(sY2 + wn * BM * ROWB, wm * 64 + mi * 32 + l31, lhi, acc2[mi], a.acc_scale, true, nullptr);   // (bias inside)
     float* sB3 = reinterpret_cast<float*>(smem + Y2_BYTES);    // [C] tail bias / scale: the part of y1's region y2 leaves free
     sB3[tid] = b3_mine * (1.f / a.tail_acc_scale);
 
     // ================================================================= phase 3: the tail 1x1 + residual + ReLU (+ skip adds)
     unsigned m_dense[MI], m_out[MI];
     bool m_ok[MI];
-#pragma unroll
-    for (int mi = 0; mi < MI; ++mi) {
-        const int p = wm * 64 + mi * 32 + l31;
-        const int oy = oy0 + p / TW, ox = ox0 + p % TW;
-        m_ok[mi] = oy < a.Ho && ox < a.Wo;
-        const unsigned m = m_ok[mi] ? (unsigned)((b * a.Ho + oy) * a.Wo + ox) : 0u;
-        m_dense[mi] = m * (unsigned)(2 * a.tail_cout8);
-        m_out[mi] = m * (unsigned)a.out_stride_c + (unsigned)a.out_c_off;
-    }
+    pixel_offsets<MI, TW>(m_ok, m_dense, m_out, a, b, oy0, ox0, wm * 64 + l31);
     const int p_row0 = wm * 64 + l31;                           // + mi*32: pixel rows of y2
     _Float16* __restrict__ outp = reinterpret_cast<_Float16*>(a.out);
 
-#if SMAP_CONVC_PIPE
     // Same pipeline; the epilogue of chunk nc runs half a slot late (behind the first reads of chunk nc + 1's first slot), the residual
     // loads of a chunk that is not held in registers go out behind the previous chunk's epilogue (one register set).
     f32x16 acc3[MI];                                            // start value b3 / scale: rows = channels nc*128 + wn*32 + 8*q + 4*lhi + e
@@ -574,7 +444,7 @@ __global__ __launch_bounds__(512, 2) void bottleneck128_kernel(const ConvArgs a,
 #pragma unroll
         for (int kc = 0; kc < KC; ++kc) {
             const int s = NS2 + nc * KC + kc;
-            lds_barrier();                                      // slot s landed for every wave; y2 + bias table complete (first slot); slot s-1's buffer is free
+            lds_barrier_builtin();                              // slot s landed for every wave; y2 + bias table complete (first slot); slot s-1's buffer is free
             if (s + NS - 1 < NSLOT) issue_slot(s + NS - 1);
             rd3(s, kc, 0, p3a, w3a);
             __builtin_amdgcn_sched_barrier(0);
@@ -596,119 +466,6 @@ __global__ __launch_bounds__(512, 2) void bottleneck128_kernel(const ConvArgs a,
     }
     mm3(p3b, w3b);
     epilogue(NCH3 - 1);
-#else
-#pragma unroll
-    for (int nc = 0; nc < NCH3; ++nc) {
-        f32x16 acc3[MI];                                        // start value b3 / scale: rows = channels nc*128 + wn*32 + 8*q + 4*lhi + e
-        half8 rl[MI][2][2];                                     // residual of a chunk that is not held in registers (nc >= NRS)
-#pragma unroll
-        for (int kc = 0; kc < KC; ++kc) {
-            const int s = NS2 + nc * KC + kc;
-            const char* sW = ring + (s % NS) * SLOT;
-            auto requests = [&]() {
-                if (s + NS - 1 < NSLOT) issue_slot(s + NS - 1);
-                if (nc >= NRS && kc == 0) {                     // (after the slot request: younger than every LDS-DMA the counted waits below name)
-#pragma unroll
-                    for (int mi = 0; mi < MI; ++mi)
-#pragma unroll
-                        for (int j = 0; j < 2; ++j)
-#pragma unroll
-                            for (int pl = 0; pl < 2; ++pl)
-                                rl[mi][j][pl] = *reinterpret_cast<const half8*>(a.res + m_dense[mi] + (unsigned)(nc * P + wn * 32 + 8 * lhi + 16 * j) + pl * a.tail_cout8);
-                }
-            };
-            auto init_acc = [&]() {
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const float4 b4 = *reinterpret_cast<const float4*>(sB3 + nc * P + wn * 32 + 8 * q + 4 * lhi);
-#pragma unroll
-                    for (int mi = 0; mi < MI; ++mi) {
-                        acc3[mi][4 * q + 0] = b4.x; acc3[mi][4 * q + 1] = b4.y; acc3[mi][4 * q + 2] = b4.z; acc3[mi][4 * q + 3] = b4.w;
-                    }
-                }
-            };
-            lds_barrier();                                      // slot s landed for every wave; y2 + bias table complete (first slot); slot s-1's buffer is free
-            requests();
-            if (kc == 0) init_acc();
-#pragma unroll
-            for (int kk = 0; kk < CH / 16; ++kk) {
-                const int g = kk * 2 + lhi;
-                half8 pf[2][MI], wf[2];
-#pragma unroll
-                for (int pl = 0; pl < 2; ++pl) {
-#pragma unroll
-                    for (int mi = 0; mi < MI; ++mi)
-                        pf[pl][mi] = *reinterpret_cast<const half8*>(sY2 + (kc * BM + p_row0 + mi * 32) * ROWB + (((g + 4 * pl) ^ fswz) << 4));
-                    wf[pl] = *reinterpret_cast<const half8*>(sW + c_row0 * ROWB + (((g + 4 * pl) ^ fswz) << 4));
-                }
-#pragma unroll
-                for (int mi = 0; mi < MI; ++mi) {
-                    acc3[mi] = MFMA_(wf[0], pf[1][mi], acc3[mi]);
-                    acc3[mi] = MFMA_(wf[1], pf[0][mi], acc3[mi]);
-                    acc3[mi] = MFMA_(wf[0], pf[0][mi], acc3[mi]);
-                }
-            }
-            wait_next(s, nc >= NRS ? MI * 4 : 0);               // (last k chunk: BEFORE this chunk's stores -- a counted vmcnt also counts stores)
-        }
-        // ---- register epilogue (convp.hip): half-wave swap -> acc3[mi][8*j .. 8*j+7] = channels n_lane + 16*j .. +7 of the pixel
-        const int n_lane = nc * P + wn * 32 + 8 * lhi;
-#pragma unroll
-        for (int mi = 0; mi < MI; ++mi)
-#pragma unroll
-            for (int j = 0; j < 2; ++j)
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const float2 sw = halfwave_swap(acc3[mi][8 * j + e], acc3[mi][8 * j + 4 + e]);
-                    acc3[mi][8 * j + e] = a.tail_acc_scale * sw.x;       // (bias inside)
-                    acc3[mi][8 * j + 4 + e] = a.tail_acc_scale * sw.y;
-                }
-#pragma unroll
-        for (int mi = 0; mi < MI; ++mi)                          // + x, from the registers filled in phase 1
-#pragma unroll
-            for (int j = 0; j < 2; ++j)
-#pragma unroll
-                for (int e = 0; e < 8; ++e)
-                    acc3[mi][8 * j + e] += nc < NRS ? (float)rs[nc < NRS ? nc : 0][mi][j][0][e] + (float)rs[nc < NRS ? nc : 0][mi][j][1][e]
-                                                    : (float)rl[mi][j][0][e] + (float)rl[mi][j][1][e];
-        if (a.relu) {
-#pragma unroll
-            for (int mi = 0; mi < MI; ++mi) relu16(acc3[mi]);
-        }
-        auto add_tensor = [&](const _Float16* __restrict__ tsr) {       // post-ReLU skip adds of the last block of a layer; one pixel block at
-#pragma unroll                                                          // a time: the residual registers leave room for 16 more, not 32
-            for (int mi = 0; mi < MI; ++mi) {
-                half8 h[2][2];
-#pragma unroll
-                for (int j = 0; j < 2; ++j)
-#pragma unroll
-                    for (int pl = 0; pl < 2; ++pl)
-                        h[j][pl] = *reinterpret_cast<const half8*>(tsr + m_dense[mi] + (unsigned)(n_lane + 16 * j) + pl * a.tail_cout8);
-#pragma unroll
-                for (int j = 0; j < 2; ++j)
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) acc3[mi][8 * j + e] += (float)h[j][0][e] + (float)h[j][1][e];
-            }
-        };
-        if (a.add1) add_tensor(a.add1);
-        if (a.add2) add_tensor(a.add2);
-#pragma unroll
-        for (int mi = 0; mi < MI; ++mi)
-#pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                if (!m_ok[mi]) continue;
-                _Float16* op = outp + (m_out[mi] + (unsigned)(n_lane + 16 * j));
-                half8 h, l;
-#pragma unroll
-                for (int e = 0; e < 8; ++e) {
-                    h[e] = (_Float16)acc3[mi][8 * j + e];
-                    l[e] = (_Float16)(acc3[mi][8 * j + e] - (float)h[e]);
-                }
-                if (SMAP_CONVC_ABLATE & 4) { if (h[0] == (_Float16)123.25f && l[1] == (_Float16)77.5f) *reinterpret_cast<half8*>(op) = h; continue; }   // keep the values live
-                *reinterpret_cast<half8*>(op) = h;
-                *reinterpret_cast<half8*>(op + a.out_lo) = l;
-            }
-    }
-#endif
     SMAP_TL_END(a)
 }
 

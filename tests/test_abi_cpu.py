@@ -169,32 +169,58 @@ def test_product_never_imports_oracle():
     assert not bad, bad
 
 
+def _kernel_descriptors(tmp_path, only=None):
+    """(source, kernel name, text of its .amdhsa_kernel descriptor) for every kernel of the library's sources (or of those named in
+    `only`), from device-only assembly: hipcc cross-compiles without a GPU."""
+    import subprocess
+    from smap_amd import build as B
+    procs = []
+    for src, extra in B.SOURCES:
+        if only is not None and src not in only:
+            continue
+        out = tmp_path / (src + ".s")
+        cmd = [B._hipcc()] + [f for f in B.COMMON if f not in ("-fPIC",)] + extra + ["-S", "--cuda-device-only", os.path.join(B.CSRC, src), "-o", str(out)]
+        procs.append((src, out, subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)))
+    for src, out, p in procs:
+        _, err = p.communicate(timeout=1200)
+        assert p.returncode == 0, (src, err[-2000:])
+        for m in re.finditer(r"\.amdhsa_kernel (\S+)(.*?)\.end_amdhsa_kernel", out.read_text(), re.S):
+            yield src, m.group(1), m.group(2)
+
+
 def test_no_kernel_reads_the_dispatch_packet_or_uses_scratch(tmp_path):
     """A rule this code base learned the hard way (EXPERIMENTS.md R3.6): a run-time-indexed private array in a kernel is promoted
     to LDS by the compiler and addressed through the AQL dispatch packet -- the head sum written that way returned wrong values
     in 10-30 % of the launches that overlapped another stream's kernels, and never in a serial test.  Checked on the compiled
     code of EVERY kernel of the library (device-only assembly, hipcc cross-compiles without a GPU): no dispatch-packet
     pointer, no scratch, no dynamic stack."""
-    import re
-    import subprocess
-    from smap_amd import build as B
-    procs = []
-    for src, extra in B.SOURCES:
-        out = tmp_path / (src + ".s")
-        cmd = [B._hipcc()] + [f for f in B.COMMON if f not in ("-fPIC",)] + extra + ["-S", "--cuda-device-only", os.path.join(B.CSRC, src), "-o", str(out)]
-        procs.append((src, out, subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)))
     n = 0
-    for src, out, p in procs:
-        _, err = p.communicate(timeout=1200)
-        assert p.returncode == 0, (src, err[-2000:])
-        txt = out.read_text()
-        for m in re.finditer(r"\.amdhsa_kernel (\S+)(.*?)\.end_amdhsa_kernel", txt, re.S):
-            name, body = m.group(1), m.group(2)
-            for field in ("amdhsa_user_sgpr_dispatch_ptr", "amdhsa_private_segment_fixed_size", "amdhsa_uses_dynamic_stack"):
-                v = re.search(r"\.%s (\d+)" % field, body)
-                assert v is not None and int(v.group(1)) == 0, (src, name, field, v and v.group(1))
-            n += 1
+    for src, name, body in _kernel_descriptors(tmp_path):
+        for field in ("amdhsa_user_sgpr_dispatch_ptr", "amdhsa_private_segment_fixed_size", "amdhsa_uses_dynamic_stack"):
+            v = re.search(r"\.%s (\d+)" % field, body)
+            assert v is not None and int(v.group(1)) == 0, (src, name, field, v and v.group(1))
+        n += 1
     assert n >= 100          # conv.hip alone instantiates ~90 kernels
+
+
+def test_whole_block_kernels_keep_two_waves_per_simd(tmp_path):
+    """The whole-Bottleneck kernels (csrc/convb.hip, csrc/convc.hip) are planned for two waves per SIMD: at most 256 VGPRs, and an LDS
+    array of 80 KiB (two workgroups of four waves per CU) / 160 KiB (one workgroup of eight).  The TH = 8 kernels sit less than ten
+    registers below the limit, so a change to a shared phase in csrc/block_device.h can cost the second wave without failing any
+    other test.  Read from the kernel descriptors of the compiled code."""
+    lds = {"bottleneck_kernelILi4E": 81920, "bottleneck_kernelILi8E": 81920, "bottleneck_first_kernelILi4E": 81920,
+           "bottleneck_first_kernelILi8E": 81920, "bottleneck128_kernelE": 163840}
+    found = []
+    for src, name, body in _kernel_descriptors(tmp_path, only=("convb.hip", "convc.hip")):
+        if "bottleneck" not in name:
+            continue
+        key = [k for k in lds if k in name]
+        assert len(key) == 1, (src, name)
+        found.append(key[0])
+        field = {f: int(v) for f, v in re.findall(r"\.amdhsa_(next_free_vgpr|group_segment_fixed_size) (\d+)", body)}
+        assert field["next_free_vgpr"] <= 256, (name, field)
+        assert field["group_segment_fixed_size"] == lds[key[0]], (name, field)
+    assert sorted(found) == sorted(lds)
 
 
 def test_status_words_follow_the_frame_count():

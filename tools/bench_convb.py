@@ -17,7 +17,7 @@ from types import SimpleNamespace as NS  # noqa: E402
 
 
 def main():
-    args = [a for a in sys.argv[1:] if not a.startswith("--")]
+    args = [a for prev, a in zip(sys.argv, sys.argv[1:]) if not a.startswith("--") and prev != "--n"]     # (the value of --n is no tile id)
     n = int(sys.argv[sys.argv.index("--n") + 1]) if "--n" in sys.argv else 20
     tiles = [int(t) for t in args] or [91, 90, 93, 92]
     cfg = NS(MODEL=NS(STAGE_NUM=3, UPSAMPLE_CHANNEL_NUM=256), DATASET=NS(KEYPOINT=NS(NUM=15), PAF=NS(NUM=14)), OUTPUT_SHAPE=(128, 208),

@@ -9,8 +9,8 @@ import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from smap_amd import build as B  # noqa: E402
 
-if "--convb" in sys.argv:       # csrc/convb.hip's identity kernel with parts switched off (SMAP_CONVB_ABLATE bits: 1 no x loads, 2 no MFMA,
-    B.build_lib()                # 4 no stores, 8 no weight loads): libsmap_hip_convb<N>.so = the regular objects + an ablated convb.o
+if "--convb" in sys.argv:       # csrc/convb.hip's kernels with parts switched off (SMAP_CONVB_ABLATE bits: 1 no x loads -- identity kernel only --,
+    B.build_lib()                # 2 no MFMA, 4 no stores, 8 no weight loads -- both kernels): libsmap_hip_convb<N>.so = the regular objects + an ablated convb.o
     for n in [x for x in sys.argv[sys.argv.index("--convb") + 1:]]:     # "3" = ablation bits; "lds64" = 64 KiB of LDS per workgroup
         op = os.path.join(B.OBJ, f"convb_abl{n}.o")
         flag = f"-DSMAP_CONVB_LDS_KB={n[3:]}" if n.startswith("lds") else f"-DSMAP_CONVB_ABLATE={n}"
