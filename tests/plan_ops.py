@@ -4,10 +4,9 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
-from single_op import arena_offsets
+from single_op import arena_offsets, guard_bytes
 
 OP_STEM, OP_MAXPOOL, OP_UPADD, OP_HEADSUM, OP_STEMPOOL = 1, 2, 3, 4, 5      # include/smap_hip.h smap_op_kind
-GUARD = 4096                    # bytes of the zeroed region behind an op's output
 
 # ---------------------------------------------------------------------------------------------------------------- shapes
 STEM_SHAPES = [(1, 37, 61), (2, 32, 70), (1, 7, 9), (1, 1, 1), (1, 33, 32)]                              # B, H, W
@@ -82,43 +81,50 @@ def headsum_op(B, Ho, Wo, Cout, Cin, srcs, src_offs, ext_off, status_off, flip=F
     return o
 
 
-# Each kind's arena: its tensors one behind the other (single_op.arena_offsets), the output and a guard region last.
+# Each kind's arena: its tensors one behind the other, the output last, each between two guards of its own pixel stride
+# (single_op.arena_offsets, guard_bytes) -> (byte sizes, bytes per pixel, pixels per row), one entry per tensor.
 def stem_sizes(B, H, W, x3, pool=False):
     Ho, Wo = conv_out(H), conv_out(W)
     if pool:
         Ho, Wo = conv_out(Ho), conv_out(Wo)
-    return [B * Ho * Wo * 64 * 2 * (1 + x3), GUARD]
+    return [B * Ho * Wo * 64 * 2 * (1 + x3)], [64 * 2 * (1 + x3)], [Wo]
 
 
 def maxpool_sizes(B, H, W, Cc, x3):
-    return [B * H * W * Cc * 2 * (1 + x3), B * conv_out(H) * conv_out(W) * Cc * 2 * (1 + x3), GUARD]
+    pix = Cc * 2 * (1 + x3)
+    return [B * H * W * pix, B * conv_out(H) * conv_out(W) * pix], [pix, pix], [W, conv_out(W)]
 
 
 def upadd_sizes(B, Ho, Wo, Cc, h, w):
-    return [B * Ho * Wo * Cc * 2, B * h * w * Cc * 2, B * Ho * Wo * Cc * 2, GUARD]
+    return [B * Ho * Wo * Cc * 2, B * h * w * Cc * 2, B * Ho * Wo * Cc * 2], [Cc * 2] * 3, [Wo, w, Wo]
 
 
 def headsum_sizes(B, Cin, srcs, flip=False):
-    return [(2 if flip else 1) * B * h * w * Cin * 4 for h, w in srcs]
+    return [(2 if flip else 1) * B * h * w * Cin * 4 for h, w in srcs], [Cin * 4] * len(srcs), [w for _, w in srcs]
+
+
+def laid_out(sizes, pix, rows):
+    """The arena offsets of one kind's tensors, as the GPU tests lay them out."""
+    return arena_offsets(sizes, [guard_bytes(p, w) for p, w in zip(pix, rows)])[0]
 
 
 def laid_out_stem(B, H, W, x3, flip_from=0, pool=False):
-    offs, _ = arena_offsets(stem_sizes(B, H, W, x3, pool))
+    offs = laid_out(*stem_sizes(B, H, W, x3, pool))
     return stem_op(B, H, W, x3, offs[0], 0, 64 * 176 * 2 * (1 + x3), 1.0, flip_from, pool)      # (the bias behind the weights: a multiple of 256)
 
 
 def laid_out_maxpool(B, H, W, Cc, x3):
-    offs, _ = arena_offsets(maxpool_sizes(B, H, W, Cc, x3))
+    offs = laid_out(*maxpool_sizes(B, H, W, Cc, x3))
     return maxpool_op(B, H, W, Cc, x3, offs[0], offs[1])
 
 
 def laid_out_upadd(B, Ho, Wo, Cc, h, w, relu=1):
-    offs, _ = arena_offsets(upadd_sizes(B, Ho, Wo, Cc, h, w))
+    offs = laid_out(*upadd_sizes(B, Ho, Wo, Cc, h, w))
     return upadd_op(B, Ho, Wo, Cc, h, w, relu, offs[0], offs[1], offs[2])
 
 
 def laid_out_headsum(B, Ho, Wo, Cout, Cin, srcs, flip=False, n_kpt=0, scale=False):
-    offs, _ = arena_offsets(headsum_sizes(B, Cin, srcs, flip))
+    offs = laid_out(*headsum_sizes(B, Cin, srcs, flip))
     return headsum_op(B, Ho, Wo, Cout, Cin, srcs, offs, 0, B * Cout * Ho * Wo * 4, flip, n_kpt, 0, scale)
 
 

@@ -1,5 +1,7 @@
 """GPU parity of the backbone: single conv launches of every tile shape against a plain
-PyTorch fp32 conv of the same fp16-rounded operands; the whole schedule at a small shape
+PyTorch fp32 conv of the same fp16-rounded operands, each launch run once per fill on poisoned
+arenas with guards (tests/single_op.py: it reads only its operands, writes only and all of
+its outputs); the whole schedule at a small shape
 against (a) the torch interpretation of the same schedule with the engine's rounding points
 and (b) the golden outputs of the imported reference model; size-independent properties at
 BASELINE's full 3x512x832."""
@@ -12,17 +14,21 @@ import torch.nn.functional as F
 
 from helpers import make_cfg
 from recipe import recipe_state_dict
-from single_op import DEV, arena_of, get, graph_arena, put, read_act, run_plan, stored, weight_blob
+from single_op import DEV, FilledLaunch, GraphArena, get, read_act, stored
 
 pytestmark = pytest.mark.gpu
 
 
 def _run_single_conv(B, H, W, Cin, Cout, k, stride, tile, relu, use_res, use_adds, out_fp32=False,
-                     in_stride=None, in_off=0, seed=0, x3=False, x_scale=1.0, up=None, w_pairs=None, ksplit=1):
+                     in_stride=None, in_off=0, seed=0, x3=False, x_scale=1.0, up=None, w_pairs=None, ksplit=1, short_in=0, short_out=0):
     """One CONV op through smap_plan_run.  x3: split-precision storage (hi/lo planes) and arithmetic; the operands are
     then full fp32 values and the reference is the f64 conv of THOSE.  up = (h, w): a low-resolution [B, h, w, Cout] input,
     bilinearly (align_corners) upsampled and added before the ReLU (smap_op.aux_off[0], smap.py:213-217).  w_pairs: layout of
-    the packed 32-half K tiles (default: seed % 2).  ksplit > 1: split K, with its own partial-tile scratch and tickets."""
+    the packed 32-half K tiles (default: seed % 2).  ksplit > 1: split K, with its own partial-tile scratch and tickets.
+    The launch runs once per fill on poisoned arenas with guards around every tensor (single_op.FilledLaunch): the output, the partial
+    tiles and the tickets come out byte-identical under both fills -- so no fill survives in [out_off, out_off + M * out_stride_c * esz)
+    and `got[..., cout:] == 0` is a statement about bytes the kernel wrote -- and no other byte of the arena or the blob changes.
+    short_in / short_out: the negative controls (the input's last bytes left to the fill / the output declared that much shorter)."""
     from smap_amd import lib as L
     from smap_amd.engine import TILES, split_f16
     g = torch.Generator().manual_seed(seed)
@@ -56,17 +62,24 @@ def _run_single_conv(B, H, W, Cin, Cout, k, stride, tile, relu, use_res, use_add
         wk = pack_conv_weights(wk, tile, x3, k, Cin, pairs=w_pairs)   # weight tiles as contiguous, pre-swizzled blocks (the conv ABI)
     bk = torch.zeros(cout_pad)
     bk[:Cout] = bias
-    # weight blob: [wk | bias]; arena: [x | res | a1 | a2 | low-res | out | split-K partial tiles | tickets]
-    blob, (_, w_bytes) = weight_blob([wk, bk])
+    # weight blob: [wk | bias], one packed K tile of all cout_pad rows behind each; arena: [x | res | a1 | a2 | low-res | out | split-K
+    # partial tiles | tickets], each between its guards
     esz = 4 if out_fp32 else 2
     npl = 2 if (x3 and not out_fp32) else 1
+    pl_in = 2 if x3 else 1
     bm = TILES.get(tile, (128, 64))[0]
     n_tiles = -(-(B * Ho * Wo) // bm) * (cout_pad // bn)
-    arena, offs = arena_of([t if t is None else stored(t, 1 + x3) for t in (x, res, a1, a2, lowres)], B * Ho * Wo * c8 * esz * npl,
-                           n_tiles * ksplit * bm * bn * 4 if ksplit > 1 else 0, 4 * n_tiles if ksplit > 1 else 0)
+    dense = c8 * 2 * pl_in                                     # bytes per pixel of res / add / low-res
+    st = lambda t: t if t is None else stored(t, pl_in)
+    launch = FilledLaunch([("x", st(x), in_stride * 2 * pl_in, W), ("res", st(res), dense, Wo), ("add1", st(a1), dense, Wo),
+                           ("add2", st(a2), dense, Wo), ("low-res", st(lowres), dense, up[1] if up else 0)],
+                          [("out", B * Ho * Wo * c8 * esz * npl, c8 * esz * npl, Wo),
+                           ("split-K partial tiles", n_tiles * ksplit * bm * bn * 4 if ksplit > 1 else 0, bn * 4, 0),
+                           ("split-K tickets", 4 * n_tiles if ksplit > 1 else 0, 4, 0)],
+                          [wk, bk], blob_guard=cout_pad * 64 * 2 * pl_in, short_in=short_in)
+    offs, w_bytes = launch.offs, launch.woffs[1]
     out_off, kpart_off, kcount_off = offs[5:]
     op = L.SmapOp()
-    pl_in = 2 if x3 else 1
     op.kind, op.B, op.H, op.W, op.Cin, op.in_stride_c, op.in_c_off = 0, B, H, W, Cin, in_stride * pl_in, in_off
     op.Ho, op.Wo, op.Cout, op.ksize, op.stride, op.pad, op.relu = Ho, Wo, Cout, k, stride, pad, int(relu)
     op.cout_pad, op.out_stride_c, op.out_c_off, op.out_fp32, op.tile = cout_pad, c8 * npl, 0, int(out_fp32), tile
@@ -81,7 +94,7 @@ def _run_single_conv(B, H, W, Cin, Cout, k, stride, tile, relu, use_res, use_add
     if ksplit > 1:
         op.ksplit, op.kpart_off, op.kcount_off = ksplit, kpart_off, kcount_off
     op.ext_off = -1
-    arena_d = run_plan(op, 1, arena, blob)
+    arena_d = launch.run(op, short_out=short_out)
     if ksplit > 1:                                         # the last part of every tile leaves its ticket at zero for the next run
         assert not arena_d[kcount_off:kcount_off + 4 * n_tiles].any()
     got = read_act(arena_d, out_off, (B, Ho, Wo, c8), npl, torch.float32 if out_fp32 else torch.float16)
@@ -377,6 +390,20 @@ def test_single_conv_shipped_launch_edges(case, precision):
     assert not got[..., cout:].any()
 
 
+@pytest.mark.parametrize("case", [(2, 16, 24, 64, 256, 1, 1, 0), (2, 16, 24, 64, 64, 3, 1, 30)], ids=["1x1", "halo3x3"])
+def test_poisoned_arena_detector_detects(case):
+    """The negative controls of the poisoned-arena harness, on correct kernels and without a fault.  The input declared one 16-byte
+    granule shorter than B H W in_stride_c: the last pixel's last eight channels then hold the fill, and the two fills must give different
+    output bytes.  The written range declared 16 bytes short: the kernel's (legitimate) store there must be flagged, with its region."""
+    run = lambda **kw: _run_single_conv(*case, False, False, False, seed=1, **kw)
+    got, ref, cout = run()
+    assert (got[..., :cout] - ref).abs().max().item() < 2e-3 * ref.abs().max().item() + 1e-3
+    with pytest.raises(AssertionError, match="in out, differs between fills"):
+        run(short_in=16)
+    with pytest.raises(AssertionError, match="in out, changed outside the ranges the run may write"):
+        run(short_out=16)
+
+
 def _run_tail(B, H, W, Cin, P, Cout, tile, relu, use_res, use_adds, x3, seed=0):
     """One fused Bottleneck-tail op (csrc/convf.hip): 3x3 Cin -> P (bias, ReLU) then 1x1 P -> Cout (+ res, ReLU, + adds)."""
     from smap_amd import lib as L
@@ -407,9 +434,11 @@ def _run_tail(B, H, W, Cin, P, Cout, tile, relu, use_res, use_adds, x3, seed=0):
     wk3, wk1 = pack_halo_rows(wk3, P, 9, Cin, x3), pack_halo_rows(wk1, bn2, 1, P, x3)
     bk1 = torch.zeros(cout_pad)
     bk1[:Cout] = b1
-    blob, woffs = weight_blob([wk3, b3, wk1, bk1])
     npl = 2 if x3 else 1
-    arena, offs = arena_of([t if t is None else stored(t, npl) for t in (x, res, a1, a2)], B * H * W * Cout * 2 * npl)
+    st = lambda t: t if t is None else stored(t, npl)
+    launch = FilledLaunch([("x", st(x), Cin * 2 * npl, W)] + [(nm, st(t), Cout * 2 * npl, W) for nm, t in (("res", res), ("add1", a1), ("add2", a2))],
+                          [("out", B * H * W * Cout * 2 * npl, Cout * 2 * npl, W)], [wk3, b3, wk1, bk1], blob_guard=max(P, cout_pad) * 64 * 2 * npl)
+    offs, woffs = launch.offs, launch.woffs
     out_off = offs[4]
     op = L.SmapOp()
     op.kind, op.B, op.H, op.W, op.Cin, op.in_stride_c, op.in_c_off = 0, B, H, W, Cin, Cin * npl, 0
@@ -422,7 +451,7 @@ def _run_tail(B, H, W, Cin, P, Cout, tile, relu, use_res, use_adds, x3, seed=0):
     for i in range(3):
         op.aux_off[i] = -1
     op.ext_off = -1
-    got = read_act(run_plan(op, 1, arena, blob), out_off, (B, H, W, Cout), npl)
+    got = read_act(launch.run(op), out_off, (B, H, W, Cout), npl)
     y = F.relu(F.conv2d(x.double().permute(0, 3, 1, 2), w3.double(), b3.double(), padding=1))
     if not x3:
         y = y.half().double()                                  # the 3x3's output is an fp16 activation in that mode
@@ -484,8 +513,9 @@ def _run_block(B, H, W, tile, use_adds, seed=0, mode="full", relu=True, check=Tr
     wk3 = pack_halo_rows(torch.stack([hi, lo]), P, 9, P, True)
     hi, lo, sct = split_f16(wt.reshape(Cc, P).double())
     wkt = pack_halo_rows(torch.stack([hi, lo]), bn2, 1, P, True)
-    blob, woffs = weight_blob([wk3, b3, wkt, bt, wk1, b1])
-    arena, offs = arena_of([t if t is None else stored(t) for t in (x, a1, a2)], B * H * W * Cc * 4)
+    launch = FilledLaunch([(nm, t if t is None else stored(t), Cc * 4, W) for nm, t in (("x", x), ("add1", a1), ("add2", a2))],
+                          [("out", B * H * W * Cc * 4, Cc * 4, W)], [wk3, b3, wkt, bt, wk1, b1], blob_guard=Cc * 64 * 4)
+    offs, woffs = launch.offs, launch.woffs
     out_off = offs[3]
     op = L.SmapOp()
     op.kind, op.B, op.H, op.W, op.Cin, op.in_stride_c, op.in_c_off = 0, B, H, W, P, Cc * 2, 0
@@ -499,7 +529,7 @@ def _run_block(B, H, W, tile, use_adds, seed=0, mode="full", relu=True, check=Tr
     for i in range(3):
         op.aux_off[i] = -1
     op.ext_off = -1
-    arena_d = run_plan(op, 1, arena, blob)
+    arena_d = launch.run(op)
     if not check:                                            # tools/trace_convb.py: the launch is what matters
         return None, None
     got = read_act(arena_d, out_off, (B, H, W, Cc), 2)
@@ -543,8 +573,9 @@ def _run_block_first(B, H, W, tile, seed=0, mode="full", check=True):
     sc1, sc3, sct, scd = (split_f16(t.double())[2] for t in (w1.reshape(P, Cin), w3.permute(0, 2, 3, 1).reshape(P, 9 * P), wt.reshape(Cc, P), wd.reshape(Cc, Cin)))
     wk1, wk3 = pk(w1.reshape(P, Cin), P, 1, Cin), pk(w3.permute(0, 2, 3, 1).reshape(P, 9 * P), P, 9, P)
     wkt, wkd = pk(wt.reshape(Cc, P), 64, 1, P), pk(wd.reshape(Cc, Cin), 64, 1, Cin)
-    blob, woffs = weight_blob([wk3, b3, wkt, bt + bd, wk1, b1, wkd])
-    arena, (in_off, out_off) = arena_of([stored(x)], B * H * W * Cc * 4)
+    launch = FilledLaunch([("x", stored(x), Cin * 4, W)], [("out", B * H * W * Cc * 4, Cc * 4, W)], [wk3, b3, wkt, bt + bd, wk1, b1, wkd],
+                          blob_guard=Cc * 64 * 4)
+    (in_off, out_off), woffs = launch.offs, launch.woffs
     op = L.SmapOp()
     op.kind, op.B, op.H, op.W, op.Cin, op.in_stride_c, op.in_c_off = 0, B, H, W, P, Cin * 2, 0
     op.Ho, op.Wo, op.Cout, op.ksize, op.stride, op.pad, op.relu = H, W, P, 3, 1, 1, 1
@@ -558,7 +589,7 @@ def _run_block_first(B, H, W, tile, seed=0, mode="full", check=True):
     for i in range(3):
         op.aux_off[i] = -1
     op.ext_off = -1
-    arena_d = run_plan(op, 1, arena, blob)
+    arena_d = launch.run(op)
     if not check:
         return None, None
     got = read_act(arena_d, out_off, (B, H, W, Cc), 2)
@@ -994,10 +1025,10 @@ def test_merged_1x1_launch_matches_torch(case, x3):
     xt = g.tensor("x", H, W, cin)
     ut = g.tensor("up", up[0], up[1], couts[0]) if up else None
     outs = g.conv_seg(segs, xt, up=ut, tile=tile)
-    arena = graph_arena(g, *([xt, ut] if up else [xt]))
-    xv = put(arena, xt, torch.randn(B, cin, H, W, generator=gen))
-    uv = put(arena, ut, torch.randn(B, couts[0], up[0], up[1], generator=gen)) if up else None
-    run_plan(g.emit(), 1, arena, g.weight_blob())
+    ga = GraphArena(g, *([xt, ut] if up else [xt]))
+    xv = ga.put(xt, torch.randn(B, cin, H, W, generator=gen))
+    uv = ga.put(ut, torch.randn(B, couts[0], up[0], up[1], generator=gen)) if up else None
+    arena, _ = ga.run(g.emit(), 1)                  # poisoned arenas: every segment's tensor byte-identical under both fills, nothing else written
     p = g.ops[0].p
     refs = [(p["w_ref"], p["b_ref"], p["relu"])] + [(sg["w_ref"], sg["b_ref"], sg["relu"]) for sg in p["segs"]]
     for j, (t, (w, b, r)) in enumerate(zip(outs, refs)):
@@ -1040,18 +1071,20 @@ def test_one_channel_3x3_head_as_tap_dots_and_a_stencil(shape, x3):
     xt = g.tensor("x", H, W, 256)
     t, b3 = g.conv_tapdot("t", "c1", "c3", xt)
     g.tapsum(t, b3, 0)
-    arena = graph_arena(g, xt)
-    xv = put(arena, xt, torch.randn(B, 256, H, W, generator=gen))
-    out = torch.full((B * H * W + 1,), 7.0, dtype=torch.float32, device=DEV)
+    ga = GraphArena(g, xt)
+    xv = ga.put(xt, torch.randn(B, 256, H, W, generator=gen))
     ops, lib, h = g.emit(), L.load(), C.c_void_p()
-    run_plan(ops, 2, arena, g.weight_blob(), out)
+    # the fp32 output buffer [M maps | 1 status word | 16 words nobody owns], filled like the arena: the maps and the status word (cleared by
+    # smap_plan_run) are what the run may write
+    arena, out = ga.run(ops, 2, out_for=lambda fill: torch.full((4 * (B * H * W + 17),), fill, dtype=torch.uint8).view(torch.float32),
+                        out_written=[(0, 4 * (B * H * W + 1))])
     p = g.ops[0].p
     q = (lambda w: w.double()) if x3 else (lambda w: w.to(torch.float16).double())
     y = F.relu(F.conv2d(xv, q(p["w_ref"]), p["b_ref"].double()))
     want = F.conv2d(y, p["tap"]["w_ref"].double(), g.ops[1].p["b_ref"].double(), padding=1)
     got = out[:B * H * W].view(B, 1, H, W).cpu().double()
     err, mx = (got - want).abs().max().item(), want.abs().max().item()
-    assert int(out[-1:].view(torch.int32).item()) == 0 and err < ((3e-6 * mx + 1e-6) if x3 else 2e-3 * mx), (err, mx)
+    assert int(out[B * H * W:B * H * W + 1].view(torch.int32).item()) == 0 and err < ((3e-6 * mx + 1e-6) if x3 else 2e-3 * mx), (err, mx)
     assert not get(arena, t)[:, 9:].any()                                                # the padding lanes of a pixel's 16 floats
     bad = (L.SmapOp * 2)(ops[0], ops[1])
     bad[0].tile = 50                                                             # only the one-N-tile 128 x 256 instance has the epilogue
@@ -1093,11 +1126,11 @@ def test_last_1x1_with_the_shortcut_conv_as_one_gemm(case, x3):
     g.w_pairs = int(B == 1)
     yt, xt = g.tensor("y", H, W, c1), g.tensor("x", H2, W2, c2)
     out = g.conv_cat("out", "c3", yt, "ds", xt, st2, relu=True, tile=tile)
-    arena = graph_arena(g, yt, xt)
-    yv = put(arena, yt, torch.randn(B, c1, H, W, generator=gen))
-    xv = put(arena, xt, torch.randn(B, c2, H2, W2, generator=gen))
+    ga = GraphArena(g, yt, xt)
+    yv = ga.put(yt, torch.randn(B, c1, H, W, generator=gen))
+    xv = ga.put(xt, torch.randn(B, c2, H2, W2, generator=gen))
     ops, lib, h = g.emit(), L.load(), C.c_void_p()
-    run_plan(ops, 1, arena, g.weight_blob())
+    arena, _ = ga.run(ops, 1)
     p = g.ops[0].p
     q = (lambda w: w.double()) if x3 else (lambda w: w.to(torch.float16).double())
     want = F.relu(F.conv2d(yv, q(p["w_ref"]), p["b_ref"].double()) + F.conv2d(xv[:, :, ::st2, ::st2], q(p["cat"]["w_ref"]), p["cat"]["b_ref"].double()))
@@ -1145,10 +1178,10 @@ def test_two_activated_skip_convs_as_one_launch_and_one_tensor(case, x3):
     g.w_pairs = int(B == 1)
     xt, ot = g.tensor("x", H, W, c1), g.tensor("o", H, W, c2)
     out = g.conv_relusum("s", "s1", xt, "s2", ot, tile=tile)
-    arena = graph_arena(g, xt, ot)
-    xv, ov = put(arena, xt, torch.randn(B, c1, H, W, generator=gen) * 3), put(arena, ot, torch.randn(B, c2, H, W, generator=gen))
+    ga = GraphArena(g, xt, ot)
+    xv, ov = ga.put(xt, torch.randn(B, c1, H, W, generator=gen) * 3), ga.put(ot, torch.randn(B, c2, H, W, generator=gen))
     ops, lib, h = g.emit(), L.load(), C.c_void_p()
-    run_plan(ops, 1, arena, g.weight_blob())
+    arena, _ = ga.run(ops, 1)
     p = g.ops[0].p
     q = (lambda w: w.double()) if x3 else (lambda w: w.to(torch.float16).double())
     a, b = F.conv2d(xv, q(p["w_ref"]), p["b_ref"].double()), F.conv2d(ov, q(p["cat"]["w_ref"]), p["cat"]["b_ref"].double())

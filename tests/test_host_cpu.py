@@ -928,3 +928,55 @@ def test_schedule_switches_are_read_in_from_env_only(small_sd, monkeypatch, tmp_
     monkeypatch.setenv("SMAP_NO_TILE_TABLE", "1")
     assert SchedulePolicy.from_env() != policy
     assert blob() == want
+
+
+# -- the poisoned-arena harness of the single-op GPU tests (tests/single_op.py) ---------------------------------------------------------------
+
+def test_poisoned_arena_comparator_on_synthetic_buffers():
+    """assert_only_written / assert_same_across_fills on hand-made before / after buffers laid out as the GPU tests lay theirs out (zero page,
+    guard, input, guard, guard, output, guard): a change inside a written range is accepted; ONE changed byte in a guard, in an input and in
+    the zero page's neighbour is refused, with its offset and the region it falls in; a written byte that differs between the fills is
+    refused too."""
+    import single_op as S
+    x = torch.arange(300, dtype=torch.float16)
+    guards = [S.guard_bytes(16, 5), S.guard_bytes(32, 5)]
+    assert guards == [4096, 8192]                                   # 256 pixels of each tensor's own stride
+    before, (in_off, out_off) = S.arena_of([x], 1000, fill=0xFF, guards=guards)
+    assert in_off == 16384 + 4096 and out_off == in_off + 768 + 4096 + 8192 and before.numel() == out_off + 1024 + 8192 + 256
+    assert bool((before[:in_off] == 0xFF).all()) and bool((before[in_off + 600:] == 0xFF).all())        # zero page, guards, gaps, output
+    assert torch.equal(before[in_off:in_off + 600], S.raw8(x))
+    other = S.arena_of([x], 1000, fill=0x7B, guards=guards)[0]
+    assert torch.equal(other[in_off:in_off + 600], S.raw8(x)) and bool((other[out_off:] == 0x7B).all())
+    written = [S.ZERO_PAGE_RANGE, (out_off, out_off + 1000)]
+    regions = [("the zero page",) + S.ZERO_PAGE_RANGE, ("x", in_off, in_off + 600), ("out", out_off, out_off + 1000)]
+    after = before.clone()
+    after[:16384] = 0
+    after[out_off:out_off + 1000] = 7
+    S.assert_only_written(before, after, written, regions)          # every written byte changed: accepted
+    S.assert_only_written(before, before.clone(), written, regions)
+    for off, where in ((16384, "the guard or gap behind the zero page"), (in_off - 1, "the guard or gap behind the zero page"),
+                       (in_off + 599, "in x,"), (in_off + 600, "the guard or gap behind x"), (out_off - 1, "the guard or gap behind x"),
+                       (out_off + 1000, "the guard or gap behind out"), (before.numel() - 1, "the guard or gap behind out")):
+        bad = after.clone()
+        bad[off] ^= 1
+        with pytest.raises(AssertionError, match=r"arena byte %d, .*%s.* changed outside" % (off, where)):
+            S.assert_only_written(before, bad, written, regions)
+    with pytest.raises(AssertionError, match="byte %d, in out, changed outside" % (out_off + 999)):     # the written range declared one byte short
+        S.assert_only_written(before, after, [S.ZERO_PAGE_RANGE, (out_off, out_off + 999)], regions)
+    after2 = after.clone()
+    S.assert_same_across_fills(after, after2, written, regions)
+    after2[in_off - 1] ^= 1                                          # outside the written ranges: not this check's business
+    S.assert_same_across_fills(after, after2, written, regions)
+    after2[out_off + 17] = 0x7B
+    with pytest.raises(AssertionError, match="arena byte %d, in out, differs between fills: 0x07 / 0x7b" % (out_off + 17)):
+        S.assert_same_across_fills(after, after2, written, regions)
+    # the layout of a launch: operands, outputs, weight chunks with their guards; an absent operand has offset -1 and no bytes
+    la = S.FilledLaunch([("x", x, 16, 5), ("res", None, 16, 5)], [("out", 1000, 32, 5), ("tickets", 0, 4, 0)], [torch.ones(100), torch.ones(3)],
+                        blob_guard=512)
+    assert la.offs[:3] == [in_off, -1, out_off] and la.woffs == [0, 512 + 512] and la.written() == written
+    assert la.written(short_out=16) == [S.ZERO_PAGE_RANGE, (out_off, out_off + 984)]
+    blob = la.blob(0x7B)
+    assert blob.numel() == 1024 + 256 + 512 and bool((blob[400:1024] == 0x7B).all()) and bool((blob[1024 + 12:] == 0x7B).all())
+    assert torch.equal(la.arena(0xFF)[:before.numel()], before) and la.total == before.numel() + 2 * S.guard_bytes(4)      # (the absent tickets' guards)
+    short = S.FilledLaunch([("x", x, 16, 5)], [("out", 1000, 32, 5)], short_in=16)
+    assert short.offs == [in_off, out_off] and bool((short.arena(0x7B)[in_off + 584:in_off + 600] == 0x7B).all())

@@ -1,13 +1,17 @@
 """stem_kernel, stem_pool_kernel, maxpool_kernel, upadd_kernel and headsum_kernel of csrc/plan.hip one op per plan, against float64 on
 the CPU from the operands as stored, at the shapes where their edge code runs: ragged tiles, odd extents, extents of 1, the second trip
 of the grid-stride loops, non-finite pixels, every number of head sources.  Shapes, op builders and references: tests/plan_ops.py (the
-checker's side of the same ops: test_plan_ops_cpu.py).  Every test prints its worst error as a fraction of its bound."""
+checker's side of the same ops: test_plan_ops_cpu.py).  Every test prints its worst error as a fraction of its bound.
+
+Every plan runs once per fill on poisoned arenas with guards around each tensor (single_op.FilledLaunch / run_filled): what the op may
+write -- its output, the zero page and, in the fp32 output buffer, the maps and the status words smap_plan_run clears -- is byte-identical
+under both fills, and no other byte of the arena, the output buffer or the weight blob changes."""
 import pytest
 import torch
 import torch.nn.functional as F
 
 import plan_ops as P
-from single_op import DEV, arena_of, arena_offsets, read_act, run_plan, stored, weight_blob
+from single_op import DEV, ZERO_PAGE_RANGE, FilledLaunch, arena_offsets, guard_bytes, read_act, run_filled, stored
 
 pytestmark = pytest.mark.gpu
 
@@ -28,11 +32,6 @@ def report(what, err, bound):
     return frac
 
 
-def untouched(arena_d, lo, hi):
-    """Nothing but [lo, hi) of the device arena holds a non-zero byte."""
-    return not bool(arena_d[:lo].any()) and not bool(arena_d[hi:].any())
-
-
 def same_bits(a, b):
     """fp16 tensors equal bit for bit, a NaN equal to any NaN."""
     na, nb = torch.isnan(a), torch.isnan(b)
@@ -51,17 +50,17 @@ def stem_operands(B, H, W, x3, flip_from=0, nan=False, dead_channels=False, seed
     if dead_channels:
         bias[::3] = -100.0                      # relu(conv + bias) is 0 at every pixel of these channels
     wk, acc_scale = pack_stem_weights(w, x3)
-    blob, (w_off, bias_off) = weight_blob([wk, bias])
-    return x, w, bias, blob, w_off, bias_off, acc_scale
+    return x, w, bias, [wk, bias], acc_scale
 
 
-def run_stem(ops_of, regions, x, blob):
-    """ops_of(offsets) -> the ops; regions: byte sizes of the arena's tensors.  Returns the device arena and the offsets."""
-    arena, offs = arena_of([], *regions)
-    ops = ops_of(offs)
+def run_stem(ops_of, outputs, x, chunks):
+    """ops_of(arena offsets, w_off, bias_off) -> the ops; outputs: (byte sizes, bytes per pixel, pixels per row) of the tensors they write.
+    Returns the device arena of the first fill and the offsets."""
+    launch = FilledLaunch([], [("output %d" % i, n, p, w) for i, (n, p, w) in enumerate(zip(*outputs))], chunks, blob_guard=4096)
+    ops = ops_of(launch.offs, *launch.woffs)
     from smap_amd import lib as L
     arr = (L.SmapOp * len(ops))(*ops)
-    return run_plan(arr, len(ops), arena, blob, inp=x.to(DEV)), offs
+    return launch.run(arr, len(ops), inp=x.to(DEV)), launch.offs
 
 
 STEM_CASES = [(s, 0) for s in P.STEM_SHAPES] + [(P.STEM_FLIP[:3], P.STEM_FLIP[3])]
@@ -74,16 +73,15 @@ def test_stem_vs_float64_conv(case, x3):
     """SMAP_OP_STEM against relu(F.conv2d(stride 2, padding 3) + bias) in float64 of the stored image and weights, under the single-conv
     bounds (f16: 2e-3 max|ref| + 1e-3; x3: 3e-6 max|ref| + 1e-6), at output sizes that are no multiple of the 16 x 16 tile, odd H and W
     (an incomplete last patch row / column) and images smaller than one patch; with flip_from the second half of the batch is the stem
-    of the mirrored images.  Nothing but [B, Ho, Wo, planes * 64] of the arena is written."""
+    of the mirrored images.  Nothing but [B, Ho, Wo, planes * 64] and the zero page of the poisoned arena is written (run_stem)."""
     (B, H, W), flip_from = case
-    x, w, bias, blob, w_off, bias_off, acc_scale = stem_operands(B, H, W, x3, flip_from)
+    x, w, bias, chunks, acc_scale = stem_operands(B, H, W, x3, flip_from)
     Ho, Wo, pl = P.conv_out(H), P.conv_out(W), 1 + x3
-    arena_d, offs = run_stem(lambda o: [P.stem_op(B, H, W, x3, o[0], w_off, bias_off, acc_scale, flip_from)],
-                             P.stem_sizes(B, H, W, x3), x, blob)
+    arena_d, offs = run_stem(lambda o, w_off, bias_off: [P.stem_op(B, H, W, x3, o[0], w_off, bias_off, acc_scale, flip_from)],
+                             P.stem_sizes(B, H, W, x3), x, chunks)
     got = read_act(arena_d, offs[0], (B, Ho, Wo, 64), pl, to=torch.float64)
     ref = P.stem_reference(x, w, bias, x3, flip_from)
     assert report("stem", (got - ref).abs().max().view(1), conv_tolerance(ref, x3)) <= 1.0
-    assert untouched(arena_d, offs[0], offs[0] + B * Ho * Wo * 64 * 2 * pl)
 
 
 POOLED_CASES = [(c, "") for c in STEM_CASES] + [(((1, 37, 61), 0), "nan"), (((2, 32, 70), 0), "dead")]
@@ -97,15 +95,15 @@ def test_stem_pool_vs_float64_and_vs_the_two_kernels(case, x3):
     followed by SMAP_OP_MAXPOOL.  One NaN pixel in the image: the NaN mask of both routes is torch's (max_pool2d propagates NaN).  A bias
     of -100 on every third channel: those channels are 0 at every pixel, the value the fused kernel pads its LDS tile with."""
     ((B, H, W), flip_from), special = case
-    x, w, bias, blob, w_off, bias_off, acc_scale = stem_operands(B, H, W, x3, flip_from, nan=special == "nan", dead_channels=special == "dead")
+    x, w, bias, chunks, acc_scale = stem_operands(B, H, W, x3, flip_from, nan=special == "nan", dead_channels=special == "dead")
     Hs, Ws, pl = P.conv_out(H), P.conv_out(W), 1 + x3
     Ho, Wo = P.conv_out(Hs), P.conv_out(Ws)
     stem_bytes, pool_bytes = B * Hs * Ws * 64 * 2 * pl, B * Ho * Wo * 64 * 2 * pl
-    fused_d, fo = run_stem(lambda o: [P.stem_op(B, H, W, x3, o[0], w_off, bias_off, acc_scale, flip_from, pool=True)],
-                           P.stem_sizes(B, H, W, x3, pool=True), x, blob)
-    two_d, to = run_stem(lambda o: [P.stem_op(B, H, W, x3, o[0], w_off, bias_off, acc_scale, flip_from),
-                                                            P.maxpool_op(B, Hs, Ws, 64, x3, o[0], o[1])],
-                         [stem_bytes, pool_bytes, P.GUARD], x, blob)
+    fused_d, fo = run_stem(lambda o, w_off, bias_off: [P.stem_op(B, H, W, x3, o[0], w_off, bias_off, acc_scale, flip_from, pool=True)],
+                           P.stem_sizes(B, H, W, x3, pool=True), x, chunks)
+    two_d, to = run_stem(lambda o, w_off, bias_off: [P.stem_op(B, H, W, x3, o[0], w_off, bias_off, acc_scale, flip_from),
+                                                     P.maxpool_op(B, Hs, Ws, 64, x3, o[0], o[1])],
+                         ([stem_bytes, pool_bytes], [128 * pl] * 2, [Ws, Wo]), x, chunks)
     ref = P.maxpool_reference(P.stem_reference(x, w, bias, x3, flip_from))
     if special == "dead":
         assert not ref[..., ::3].any() and ref[..., 1::3].any()
@@ -117,7 +115,6 @@ def test_stem_pool_vs_float64_and_vs_the_two_kernels(case, x3):
         assert report(name, (got - ref)[~nan].abs().max().view(1), conv_tolerance(ref, x3)) <= 1.0
     raw = lambda a, off: a[off:off + pool_bytes].cpu().view(torch.float16)
     assert same_bits(raw(fused_d, fo[0]), raw(two_d, to[1]))
-    assert untouched(fused_d, fo[0], fo[0] + pool_bytes) and untouched(two_d, to[0], to[1] + pool_bytes)
 
 
 # --------------------------------------------------------------------------------------------------------------- max-pool
@@ -150,8 +147,9 @@ def test_maxpool_is_exact(shape, x3, kind):
     B, H, W, Cc = shape
     Ho, Wo, pl = P.conv_out(H), P.conv_out(W), 1 + x3
     s = stored(pool_input(B, H, W, Cc, kind, x3), pl)
-    arena, (in_off, out_off, _) = arena_of([s], B * Ho * Wo * Cc * 2 * pl, P.GUARD)
-    arena_d = run_plan(P.maxpool_op(B, H, W, Cc, x3, in_off, out_off), 1, arena, torch.zeros(256, dtype=torch.uint8))
+    launch = FilledLaunch([("in", s, Cc * 2 * pl, W)], [("out", B * Ho * Wo * Cc * 2 * pl, Cc * 2 * pl, Wo)])
+    in_off, out_off = launch.offs
+    arena_d = launch.run(P.maxpool_op(B, H, W, Cc, x3, in_off, out_off))
     val = s.double().view(B, H, W, pl, Cc).sum(3)
     ref, win = P.maxpool_reference(val, return_indices=True)
     got = read_act(arena_d, out_off, (B, Ho, Wo, Cc), pl, to=torch.float64)
@@ -169,7 +167,6 @@ def test_maxpool_is_exact(shape, x3, kind):
         for plane in (0, 1):
             want = torch.gather(pairs_in[:, :, plane], 1, idx).view(B, Ho, Wo, Cc)
             assert torch.equal(pairs_out[..., plane, :].view(torch.int16)[fin], want.view(torch.int16)[fin]), ("hi", "lo")[plane]
-    assert untouched(arena_d, in_off, out_off + B * Ho * Wo * Cc * 2 * pl)
 
 
 def test_maxpool_beyond_the_grid_cap():
@@ -177,15 +174,19 @@ def test_maxpool_beyond_the_grid_cap():
     against torch's own fp16 max-pool on the device (exact, and not the code under test)."""
     B, H, W, Cc = P.POOL_OVER_THE_CAP
     Ho, Wo = P.conv_out(H), P.conv_out(W)
-    (in_off, out_off, _), total = arena_offsets([B * H * W * Cc * 2, B * Ho * Wo * Cc * 2, P.GUARD])
-    arena_d = torch.zeros(total, dtype=torch.uint8, device=DEV)
+    in_bytes, out_bytes = B * H * W * Cc * 2, B * Ho * Wo * Cc * 2
+    (in_off, out_off), total = arena_offsets([in_bytes, out_bytes], [guard_bytes(Cc * 2, W), guard_bytes(Cc * 2, Wo)])
     x = torch.randn(B, H, W, Cc, device=DEV, generator=torch.Generator(DEV).manual_seed(6)).half()
-    arena_d[in_off:in_off + x.numel() * 2].view(torch.float16).copy_(x.view(-1))
-    run_plan(P.maxpool_op(B, H, W, Cc, False, in_off, out_off), 1, arena_d, torch.zeros(256, dtype=torch.uint8))
-    got = arena_d[out_off:out_off + B * Ho * Wo * Cc * 2].view(torch.float16).view(B, Ho, Wo, Cc)
+
+    def arena_for(fill):                       # (built on the device: 138 MB of input)
+        a = torch.full((total,), fill, dtype=torch.uint8, device=DEV)
+        a[in_off:in_off + in_bytes].view(torch.float16).copy_(x.view(-1))
+        return a
+    (arena_d, _), _ = run_filled(P.maxpool_op(B, H, W, Cc, False, in_off, out_off), 1, arena_for, lambda fill: torch.full((256,), fill, dtype=torch.uint8),
+                                 [ZERO_PAGE_RANGE, (out_off, out_off + out_bytes)], [("in", in_off, in_off + in_bytes), ("out", out_off, out_off + out_bytes)])
+    got = arena_d[out_off:out_off + out_bytes].view(torch.float16).view(B, Ho, Wo, Cc)
     want = F.max_pool2d(x.permute(0, 3, 1, 2), 3, 2, 1).permute(0, 2, 3, 1)
     assert torch.equal(got, want)
-    assert not bool(arena_d[out_off + B * Ho * Wo * Cc * 2:].any())
 
 
 # ----------------------------------------------------------------------------------------------------------- bilinear add
@@ -200,15 +201,14 @@ def test_upadd_vs_float64(shape, relu):
     B, Ho, Wo, Cc, h, w = shape
     g = torch.Generator().manual_seed(7)
     a, t = torch.randn(B, Ho, Wo, Cc, generator=g).half(), torch.randn(B, h, w, Cc, generator=g).half()
-    arena, (a_off, t_off, out_off, _) = arena_of([a, t], a.numel() * 2, P.GUARD)
-    arena_d = run_plan(P.upadd_op(B, Ho, Wo, Cc, h, w, relu, a_off, t_off, out_off), 1, arena, torch.zeros(256, dtype=torch.uint8))
+    launch = FilledLaunch([("a", a, Cc * 2, Wo), ("t", t, Cc * 2, w)], [("out", a.numel() * 2, Cc * 2, Wo)])
+    a_off, t_off, out_off = launch.offs
+    arena_d = launch.run(P.upadd_op(B, Ho, Wo, Cc, h, w, relu, a_off, t_off, out_off))          # (the operands and the guards are as they were)
     got = read_act(arena_d, out_off, (B, Ho, Wo, Cc), to=torch.float64)
     ref, mag, slack = P.upadd_reference(a, t, relu)
     assert bool((a.double() + P.bilinear(t.double(), Ho, Wo) < 0).any())          # negative sums are present
     assert report("upadd", (got - ref).abs(), P.upadd_bound(ref, mag, slack)) <= 1.0
     assert bool((got >= 0).all()) == bool(relu)
-    assert not bool(arena_d[out_off + a.numel() * 2:].any())
-    assert torch.equal(arena_d[a_off:out_off].cpu(), arena[a_off:out_off])         # the operands are as they were
 
 
 # --------------------------------------------------------------------------------------------------------------- head sum
@@ -223,7 +223,8 @@ def test_headsum_vs_float64(run):
     (plan_ops.lerp_slack; without it the device is at up to 7.3 times the first term, with it at 0.70): one, two and three
     sources, the first one up-sampled, odd ratios, a second 32-pixel segment of one pixel, Cout = 1 and Cout = 48, and large finite
     garbage in the sources' padding channels Cout .. Cin - 1.  One source at the output's size, unmerged and unscaled, is a transposition:
-    bit for bit.  The status words stay 0 and nothing behind them is written."""
+    bit for bit.  Arena and output buffer [maps | status words | 64 words nobody owns] are poisoned: the status words end at 0 (smap_plan_run
+    clears them), nothing behind them and nothing in the arena but the zero page is written."""
     i, flip, n_kpt, scale = run
     B, Ho, Wo, Cout, Cin, sizes = P.HEAD_CASES[i]
     g = torch.Generator().manual_seed(11 + i)
@@ -234,17 +235,16 @@ def test_headsum_vs_float64(run):
         s[..., Cout:] = 1e30 * torch.sign(torch.randn(frames, h, w, Cin - Cout, generator=g))
         srcs.append(s)
     pair = P.odd_pair_table(Cout) if flip else None
-    blob, _ = weight_blob([torch.tensor(pair if flip else [0], dtype=torch.int32)])
-    arena, offs = arena_of(srcs)
+    launch = FilledLaunch([("source %d" % k, s, Cin * 4, s.shape[2]) for k, s in enumerate(srcs)], [],
+                          [torch.tensor(pair if flip else [0], dtype=torch.int32)], blob_guard=256)
     n_map, n_status = B * Cout * Ho * Wo, (B + 30) // 31
-    out = torch.full((n_map + n_status + 64,), 12345.0, device=DEV)
-    op = P.headsum_op(B, Ho, Wo, Cout, Cin, sizes, offs, 0, 4 * n_map, flip, n_kpt, 0, scale)
-    arena_d = run_plan(op, 1, arena, blob, out=out)
+    op = P.headsum_op(B, Ho, Wo, Cout, Cin, sizes, launch.offs, 0, 4 * n_map, flip, n_kpt, launch.woffs[0], scale)
+    launch.run(op, out_for=lambda fill: torch.full((4 * (n_map + n_status + 64),), fill, dtype=torch.uint8).view(torch.float32),
+               out_written=[(0, 4 * (n_map + n_status))])
+    out = launch.outs[0]
     got = out[:n_map].cpu().view(B, Cout, Ho, Wo)
     ref, mag, slack = P.headsum_reference(srcs, Ho, Wo, Cout, B, flip, pair, n_kpt, scale)
     assert report("headsum", (got.double() - ref).abs(), P.headsum_bound(mag, slack).clamp_min(1e-300)) <= 1.0
     if len(sizes) == 1 and not flip and not scale:
         assert sizes[0] == (Ho, Wo) and torch.equal(got, srcs[0][..., :Cout].permute(0, 3, 1, 2))
     assert not bool(out[n_map:n_map + n_status].view(torch.int32).any())
-    assert bool((out[n_map + n_status:] == 12345.0).all())
-    assert torch.equal(arena_d.cpu()[offs[0]:], arena[offs[0]:])
