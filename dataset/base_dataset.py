@@ -107,7 +107,7 @@ class JointDataset(Dataset):
         t = torch.from_numpy(canvas).permute(2, 0, 1).float().div(255.0)
         return (t - self.mean) / self.std, self._padded(bodys), d["img_paths"], self._meta(d, scale)
 
-    # ---- what the device loader of exps/stage3_root2/test.py asks of a dataset (CustomDataset answers the same five) ----
+    # ---- what the device loader (smap_amd/loaders.py) asks of a dataset (CustomDataset answers the same five) ----
     def path(self, index):
         """File of frame `index`."""
         return self.image_path(self.data[index])

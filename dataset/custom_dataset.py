@@ -62,7 +62,7 @@ class CustomDataset(Dataset):
         """(uint8 HxWx3 BGR image, image name) for the device pre-processing path (smap_amd/preprocess.py)."""
         return self._read_bgr(self.path(index)), self.name(index)
 
-    # ---- what the device loader of exps/stage3_root2/test.py asks of a dataset besides raw() (JointDataset answers the same) ----
+    # ---- what the device loader (smap_amd/loaders.py) asks of a dataset besides raw() (JointDataset answers the same) ----
     def path(self, index):
         """File of frame `index`."""
         return self.image_list[index].rstrip()

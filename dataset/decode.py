@@ -1,5 +1,5 @@
 """Image file -> uint8 HxWx3 BGR array (what cv2.imread(path, IMREAD_COLOR) hands the reference: dataset/custom_dataset.py:33 upstream),
-and the same as a WORKER PROCESS for the decode-ahead loader of exps/stage3_root2/test.py (SMAP_DECODE_PROCS).
+and the same as a WORKER PROCESS for the decode-ahead loader of smap_amd/loaders.py (SMAP_DECODE_PROCS: process_decoders).
 
 Only numpy and PIL are imported here: a worker starts in ~0.3 s and holds no torch, no GPU context.
 

@@ -342,6 +342,10 @@ class ValidationLoss:
         entry.update(frames=int(frames), batches=int(raw[5]))
         return {"loss": entry}
 
+    def log_lines(self, raw=None):
+        return ["validation loss over {frames} frames in {batches} batches: total {total_loss:.6g}  2d {loss_2d:.6g}  bone {loss_bone:.6g}  "
+                "root {loss_root:.6g}".format(**self.result_entry(raw)["loss"])]
+
 
 def single_head_loss(hm=None, dd=None, rd=None, labels=None, valids=None, rdepth=None, ohkm=False, topk=8):
     """ONE head with unit weights (smap_loss_forward's single mode), for lib/utils/loss_h.py: result [8] = (2D + depth + root, 2D,

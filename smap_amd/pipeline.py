@@ -505,3 +505,24 @@ def make_pipeline(model, cfg, batch, H, W, device, launch_frames=None, **kw):
     if group >= 2 and kw.get("record_mode", "run_inference") == "run_inference":
         return CoalescedPipeline(model, cfg, batch, H, W, device, group, **kw)
     return PosePipeline(model, cfg, batch, H, W, device, **kw)
+
+
+class DryRunPipeline:
+    """Stand-in for PosePipeline in the entry script's `--dry_run 1` (no GPU, no checkpoint): the same submit / flush contract -- records of
+    the batch submitted `depth` calls earlier -- with one fake person per frame.  What the rehearsal exercises is everything
+    AROUND the device work: CLI, image listing, the contiguous per-rank split, ragged last batches, the end-of-run gather
+    (gloo instead of RCCL) and the result file; `python -m torch.distributed.run --nproc-per-node 8 test.py --dry_run 1 ...`."""
+
+    def __init__(self, model, cfg, batch, H, W, device, refine_w=None, depth=2, **kw):
+        self.B, self.depth, self.q = batch, max(1, int(depth)), []
+
+    def submit(self, imgs, cams, tags, annotations=None):
+        p2 = np.zeros((1, 15, 4), np.float32)
+        self.q.append([frame_record(p2, np.zeros((1, 15, 4)), np.full((1,), float(imgs[i].mean())), t, None, as_lists=False)
+                       for i, t in enumerate(tags) if t is not None])
+        return self.q.pop(0) if len(self.q) > self.depth else None
+
+    def flush(self):
+        out = [r for recs in self.q for r in recs]
+        self.q = []
+        return out or None

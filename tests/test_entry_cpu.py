@@ -456,7 +456,7 @@ def test_clock_sampler_reads_hwmon_files_and_survives_their_absence(tmp_path, mo
 
 
 def test_process_decoders_hand_over_the_frames_the_in_thread_decoder_reads(tmp_path):
-    """exps/stage3_root2/test.py::DevicePreprocLoader with SMAP_DECODE_PROCS: worker processes (dataset/decode.py: numpy + PIL only) decode into
+    """smap_amd/loaders.py::DevicePreprocLoader with SMAP_DECODE_PROCS (process_decoders): worker processes (dataset/decode.py: numpy + PIL only) decode into
     one shared-memory block, the loader's pool threads copy their slot out.  Same bytes as the in-thread decoder for PNG, JPEG (EXIF
     orientation applied) and .npy files; a frame larger than a slot is decoded in-thread; a broken file raises in the consumer; the block
     is unlinked when the iteration ends."""
@@ -483,13 +483,13 @@ def test_process_decoders_hand_over_the_frames_the_in_thread_decoder_reads(tmp_p
         else:
             Image.fromarray(a).save(p)
         paths.append(p)
-    ds = types.SimpleNamespace(image_list=paths, dataset_path=str(tmp_path), raw=lambda i: (read_bgr(paths[i]), os.path.basename(paths[i])))
-    ld = cli.DevicePreprocLoader.__new__(cli.DevicePreprocLoader)
-    ld.ds, ld.procs, ld.slot_bytes = ds, 2, 64 * 1024        # 64 KiB slots: the 200x300 frame (180 kB) does not fit
+    from smap_amd.loaders import process_decoders
+    assert cli.DevicePreprocLoader.__module__ == "smap_amd.loaders"
+    ds = types.SimpleNamespace(path=lambda i: paths[i], name=lambda i: os.path.basename(paths[i]))
     shm_dir = "/dev/shm"
     before = set(os.listdir(shm_dir)) if os.path.isdir(shm_dir) else set()
     with contextlib.ExitStack() as stack:
-        decode = ld._process_decoders(stack, lambda img: np.array(img))
+        decode = process_decoders(stack, ds, 2, 64 * 1024, lambda img: np.array(img))     # 64 KiB slots: the 200x300 frame (180 kB) does not fit
         during = (set(os.listdir(shm_dir)) if os.path.isdir(shm_dir) else set()) - before
         with ThreadPoolExecutor(2) as ex:
             got = list(ex.map(decode, range(len(paths))))
@@ -505,3 +505,197 @@ def test_process_decoders_hand_over_the_frames_the_in_thread_decoder_reads(tmp_p
             decode(len(paths) - 1)
     if os.path.isdir(shm_dir):
         assert during and not (during & set(os.listdir(shm_dir)))       # the block existed while the loader ran and is gone now
+
+
+def _cli():
+    """exps/stage3_root2/test.py as a module (its file name is not importable by pytest's rules: loaded by path)."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("smap_cli_test", os.path.join(ROOT, "exps", "stage3_root2", "test.py"))
+    cli = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(cli)
+    return cli
+
+
+def _gt_batch(with_frames):
+    """A collate_test batch of 3 frames, B = 4 to come: 2, 0 and 1 kept persons (frame 0 carries a third whose root score is 1: dropped)."""
+    ann = torch.zeros((3, 6, 15, 11))
+    for f, p, x in ((0, 0, 10.0), (0, 1, 20.0), (2, 0, 30.0)):
+        ann[f, p, :, 0], ann[f, p, :, 3] = x, 2.0
+        ann[f, p, :, 7:] = torch.tensor([1000.0 + x, 1001.0, 416.0, 256.0])
+    ann[0, 2, :, 0], ann[0, 2, :, 3] = 40.0, 1.0
+    metas = tuple({"scale": 0.5 * (k + 1), "img_width": 1664, "img_height": 1024, "net_width": 832, "net_height": 512} for k in range(3))
+    imgs = torch.arange(3.0).view(3, 1, 1, 1).expand(3, 3, 4, 6).contiguous() if with_frames else None
+    return imgs, ann, ("a", "b", "c"), metas
+
+
+def test_shape_batch_and_pad_to():
+    """shape_batch turns a loader batch into what submit takes, pad_to(B) pads every per-frame member alike: the last entry repeated,
+    tag None, cams a float64 row; a full batch is not copied."""
+    from smap_amd.records import kept_annotations
+    cli = _cli()
+    cpu = torch.device("cpu")
+    # an inference batch of 3 frames
+    cli.cfg.TEST_MODE = "run_inference"                     # (what main() sets from -t)
+    frames = torch.arange(3.0).view(3, 1, 1, 1).expand(3, 3, 4, 6).contiguous()
+    scales = {"scale": torch.tensor([1.0, 2.0, 3.0]), "img_width": torch.tensor([832] * 3), "img_height": torch.tensor([512] * 3),
+              "net_width": torch.tensor([832] * 3), "net_height": torch.tensor([512] * 3)}
+    b = cli.pad_to(cli.shape_batch((frames, ["a", "b", "c"], scales), cli.cfg, cpu), 4)
+    assert b.imgs.shape == (4, 3, 4, 6) and [float(f.mean()) for f in b.imgs] == [0.0, 1.0, 2.0, 2.0]
+    assert b.tags == ["a", "b", "c", None] and b.annotations is None and b.map_inputs is None
+    assert isinstance(b.cams, np.ndarray) and b.cams.dtype == np.float64 and b.cams.shape == (4, 9)
+    assert b.cams[:, 0].tolist() == [1.0, 2.0, 3.0, 3.0] and np.array_equal(b.cams[2], b.cams[3])
+    # a full batch of 4: the very same tensor, nothing copied
+    full = torch.zeros((4, 3, 4, 6))
+    sc4 = {k: torch.cat([v, v[-1:]]) for k, v in scales.items()}
+    b4 = cli.shape_batch((full, ["a", "b", "c", "d"], sc4), cli.cfg, cpu)
+    assert cli.pad_to(b4, 4) is b4 and b4.imgs is full
+    # a ground-truth batch of 3 frames with 2, 0 and 1 kept persons
+    cli.cfg.TEST_MODE = "generate_result"
+    batch = _gt_batch(True)
+    b = cli.pad_to(cli.shape_batch(batch, cli.cfg, cpu), 4)
+    assert [len(a) for a in b.annotations] == [2, 0, 1, 1] and len(b.annotations) == 4
+    for a, m in zip(b.annotations[:3], batch[1]):
+        assert np.array_equal(a, kept_annotations(m.numpy(), cli.cfg.DATASET.ROOT_IDX))
+    assert b.annotations[0][:, 0, 0].tolist() == [10.0, 20.0]               # the person with root score 1 is gone
+    assert np.array_equal(b.annotations[3], b.annotations[2])
+    assert list(b.cams[1]) == [1.0] * 9 and b.cams.dtype == np.float64 and b.cams.shape == (4, 9) and np.array_equal(b.cams[2], b.cams[3])
+    assert list(b.cams[0]) == [0.5, 1664, 1024, 832, 512, 1010.0, 1001.0, 416.0, 256.0]
+    assert b.tags == ["a", "b", "c", None] and b.imgs.shape == (4, 3, 4, 6) and torch.equal(b.imgs[3], b.imgs[2]) and b.map_inputs is None
+    # the same without frames (--maps_from_gt 1)
+    batch = _gt_batch(False)
+    b = cli.pad_to(cli.shape_batch(batch, cli.cfg, cpu, maps_from_gt=True), 4)
+    H, W = cli.cfg.dataset.INPUT_SHAPE
+    assert tuple(b.imgs.shape) == (4, 3, H, W) and len(b.imgs) == 4
+    anns, scs = b.map_inputs
+    assert len(anns) == 4 and len(scs) == 4 and all(isinstance(a, torch.Tensor) for a in anns)
+    assert all(torch.equal(a, m) for a, m in zip(anns[:3], batch[1])) and torch.equal(anns[3], anns[2])
+    assert list(scs[:3]) == list(batch[3]) and scs[3] == scs[2]
+    assert [len(a) for a in b.annotations] == [2, 0, 1, 1] and b.tags == ["a", "b", "c", None] and list(b.cams[1]) == [1.0] * 9
+
+
+_REFUSALS = [
+    ("--eval_mupots X -t run_inference", "--eval_mupots requires -t generate_result"),
+    ("--eval_mupots X -t generate_result --dry_run 1", "--eval_mupots scores on the GPU: not available with --dry_run 1"),
+    ("--eval_loss 1 -t generate_train", "--eval_loss 1 requires -t generate_result"),
+    ("--eval_loss 1 -t generate_result --dry_run 1", "--eval_loss 1 runs on the GPU: not available with --dry_run 1"),
+    ("--eval_loss 1 -t generate_result --maps_from_gt 1", "--eval_loss 1 needs the network's heads: not available with --maps_from_gt 1"),
+    ("--maps_from_gt 1", "--maps_from_gt 1 renders the maps from annotations: -t run_inference has none (use -t generate_result or generate_train)"),
+    ("--maps_from_gt 1 -t generate_train --dry_run 1", "--maps_from_gt 1 renders on the GPU: not available with --dry_run 1"),
+    ("--device_decode 3 --device_preprocess 1", "--device_decode is 0, 1 or 2"),
+    ("--device_decode 2", "--device_decode 2 requires --device_preprocess 1"),
+    ("--eval_3d 1", "--eval_3d 1 requires -t generate_result"),
+    ("--eval_3d 1 -t generate_result --dry_run 1", "--eval_3d 1 scores on the GPU: not available with --dry_run 1"),
+    ("--eval_maps 1 -t generate_train", "--eval_maps 1 requires -t generate_result"),
+    ("--eval_maps 1 -t generate_result --dry_run 1", "--eval_maps 1 scores on the GPU: not available with --dry_run 1"),
+    # two rules apply: the earlier check wins
+    ("--eval_mupots X -t run_inference --dry_run 1", "--eval_mupots requires -t generate_result"),
+    ("--eval_loss 1 -t generate_result --dry_run 1 --maps_from_gt 1", "--eval_loss 1 runs on the GPU: not available with --dry_run 1"),
+]
+
+
+@pytest.mark.parametrize("k", range(len(_REFUSALS)))
+def test_flag_rules_refuse_with_their_message(k, capsys):
+    """Every rule of FLAG_RULES through parse_args: argparse's refusal (exit status 2) with the message on stderr; rule k of the table is
+    case k here, and it is the FIRST rule that applies to that command line."""
+    cli = _cli()
+    line, message = _REFUSALS[k]
+    assert len(cli.FLAG_RULES) == 13
+    with pytest.raises(SystemExit) as exc:
+        cli.parse_args(line.split())
+    assert exc.value.code == 2
+    err = capsys.readouterr().err
+    assert err.rstrip("\n").endswith("error: " + message), err
+    if k < 13:
+        assert cli.FLAG_RULES[k][1].format(device_decode=2) == message
+
+
+@pytest.mark.parametrize("line", ["-t run_inference --dataset_path x --device_preprocess 1 --device_decode 2 --dry_run 1",
+                                  "-t generate_result --eval_3d 1 --eval_maps 1 --eval_loss 1 --eval_mupots ROOT --device_preprocess 1 --device_decode 1",
+                                  "-t generate_train -d generation --maps_from_gt 1"])
+def test_parse_args_accepts_one_line_per_mode(line):
+    args = _cli().parse_args(line.split())
+    assert args.test_mode == line.split()[1] and args.batch_size == 1 and args.SMAP_path == "log/SMAP.pth"
+
+
+def test_validation_loss_log_lines_on_the_host():
+    """ValidationLoss.log_lines(raw): the one line the entry script logs; result_entry of the same raw as before."""
+    from exps.stage3_root2.config import cfg
+    from smap_amd.loss import ValidationLoss
+    raw = [6.0, 3.0, 1.5, 0.75, 3.0, 2.0]
+    vl = ValidationLoss(None, cfg, "cpu")
+    assert vl.log_lines(raw) == ["validation loss over 3 frames in 2 batches: total 2  2d 1  bone 0.5  root 0.25"]
+    assert vl.result_entry(raw) == {"loss": {"total_loss": 2.0, "loss_2d": 1.0, "loss_bone": 0.5, "loss_root": 0.25, "frames": 3, "batches": 2}}
+
+
+@pytest.mark.parametrize("threads", [1, 3])
+@pytest.mark.parametrize("mode", [0, 1, 2])
+def test_loader_variants_without_a_device(mode, threads, tmp_path, monkeypatch):
+    """DevicePreprocLoader with its device calls replaced by recorders (jpeg.reconstruct, jpeg.decode_coefficients_device -- status 0
+    exactly where the host decoder decodes the file, the device decoder's contract -- and preprocess_batch; page-locking needs a GPU and
+    is replaced by a copy): five files, batch 2, in the consumer's thread and on a pool of 3, for --device_decode 0, 1 and 2.  The
+    "truncated" JPEG is cut inside its scan with the end-of-image marker kept: the native decoders refuse it and PIL decodes it.  (A file
+    cut short at its end makes PIL raise, and so the run: tests/test_jpeg_huff_gpu.py.)"""
+    import io
+    import threading
+    from PIL import Image
+    from exps.stage3_root2.config import cfg
+    from dataset.custom_dataset import CustomDataset
+    from dataset.decode import read_bgr
+    try:
+        from smap_amd import jpeg as J, lib as L
+        L.load()
+    except Exception as e:                                    # a checkout without the built library: the parser is not faked
+        pytest.skip(f"smap_amd.jpeg's host side needs the built library: {e!r}")
+    import smap_amd.loaders as LD
+    rng = np.random.default_rng(3)
+    pics = [rng.integers(0, 256, (40 + 8 * k, 56, 3), dtype=np.uint8) for k in range(5)]
+    for k in (0, 1):
+        Image.fromarray(pics[k]).save(tmp_path / f"f{k}.jpg", quality=90)
+    Image.fromarray(pics[2]).save(tmp_path / "f2.png")
+    np.save(tmp_path / "f3.npy", pics[3])
+    b = io.BytesIO()
+    Image.fromarray(pics[4]).save(b, "JPEG", quality=90)
+    whole = b.getvalue()
+    (tmp_path / "f4.jpg").write_bytes(whole[:(J.probe(whole).scan_offset + len(whole)) // 2] + b"\xff\xd9")
+    seen = []
+
+    def fake_reconstruct(coeffs, info, device):
+        assert coeffs is not None
+        return ("reconstructed", J.output_shape(info))
+
+    def fake_device_decode(frame, info, scan, device):
+        co = J.decode_coefficients(J.frame_bytes(frame), info)
+        return co, torch.tensor([0 if co is not None else 1], dtype=torch.int32)
+
+    def fake_preprocess(raws, means, stds, device, **kw):
+        assert not kw                                         # an image folder: the letter-box
+        seen.append(list(raws))
+        return torch.zeros((len(raws), 3, 2, 2)), {"scale": [1.0] * len(raws)}
+    monkeypatch.setattr(J, "reconstruct", fake_reconstruct)
+    monkeypatch.setattr(J, "decode_coefficients_device", fake_device_decode)
+    monkeypatch.setattr(LD, "preprocess_batch", fake_preprocess)
+    monkeypatch.setattr(LD, "pinned", lambda img: torch.from_numpy(np.array(img)))
+    monkeypatch.setenv("SMAP_DECODE_THREADS", str(threads))
+    monkeypatch.delenv("SMAP_DECODE_PROCS", raising=False)
+    ds = CustomDataset(cfg, str(tmp_path))
+    names = [ds.name(i) for i in range(len(ds))]             # the listing's order: the file order of the run
+    assert sorted(names) == ["f0.jpg", "f1.jpg", "f2.png", "f3.npy", "f4.jpg"]
+    loader = LD.DevicePreprocLoader(ds, range(len(ds)), 2, cfg, torch.device("cpu"), device_decode=mode)
+    assert len(loader) == 3
+    before, during, got = threading.active_count(), [], []
+    for imgs, batch_names, scales in loader:
+        during.append(threading.active_count())
+        got.append((len(imgs), list(batch_names)))
+    assert got == [(2, names[0:2]), (2, names[2:4]), (1, names[4:5])]               # file order, a ragged last batch of one frame
+    if threads == 1:
+        assert max(during) <= before                          # nothing was started
+    raws = dict(zip(names, [r for batch in seen for r in batch]))
+    for n in ("f2.png", "f3.npy", "f4.jpg"):                  # the PNG, the .npy and the truncated JPEG arrive as frames decoded on the host
+        assert np.array_equal(np.asarray(raws[n]), read_bgr(str(tmp_path / n))), n
+    for k, n in enumerate(("f0.jpg", "f1.jpg")):
+        if mode:
+            assert raws[n] == ("reconstructed", pics[k].shape[:2])
+        else:
+            assert np.array_equal(np.asarray(raws[n]), read_bgr(str(tmp_path / n)))
+    # the parent's rules: PIL frames are counted under --device_decode only, .npy frames never; mode 2 redoes on the host what the device refuses
+    assert (loader.pil_frames, loader.host_frames) == {0: (0, 0), 1: (2, 0), 2: (2, 1)}[mode]
