@@ -2,8 +2,8 @@
 
 Only the inference-side stages exist here -- `test` (the validation frames of cfg.TEST.JSON_PATH, images under
 cfg.TEST.ROOT_PATH) and `generation` (the training frames of the 3D datasets, the input of RefineNet training-pair
-export); stage `train` is the training loader (augmentation, label assembly), which is outside this repository -- the label maps
-themselves are rendered by smap_amd/labels.py (dataset/representation.py).
+export); stage `train` is not a host dataset here: its samples are planned on the host and augmented and labelled on the GPU by
+smap_amd/loaders.py::TrainSet / TrainLoader (lib/utils/dataloader.py::get_train_loader; smap_amd/augment.py, smap_amd/labels.py).
 
 A sample is what the reference returns for these stages (base_dataset.py:157-166):
     (normalised BGR CHW image, annotations [MAX_PEOPLE,15,C] fp32 zero padded, image path, scale dict)
@@ -40,10 +40,10 @@ def croppad_geometry(img_w, img_h, crop_x, crop_y):
 class JointDataset(Dataset):
     def __init__(self, cfg, stage, transform=None, with_augmentation=False, with_mds=False):
         if stage == "train":
-            raise NotImplementedError("stage 'train' (label generation for training) is outside this repository")
+            raise NotImplementedError("stage 'train' is smap_amd.loaders.TrainSet / lib.utils.dataloader.get_train_loader (augmented and labelled on the GPU)")
         assert stage in ("test", "generation")
         if with_augmentation:
-            raise NotImplementedError("augmentation belongs to training")
+            raise NotImplementedError("augmentation belongs to training: smap_amd.loaders.TrainSet / lib.utils.dataloader.get_train_loader")
         self.stage = stage
         ds = cfg.dataset
         if stage == "generation":

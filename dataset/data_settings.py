@@ -47,7 +47,9 @@ def _build():
         d[name + "_JSON_PATH"] = os.path.join(d[name + "_ROOT_PATH"], "annotations", ann + ".json")
     d.USED_3D_DATASETS = ["MUCO"]
     # label rendering (data_settings.py:64): the blur size of each of the five label scales, coarse to fine; read by smap_amd/labels.py
-    d.TRAIN = AttrDict(GAUSSIAN_KERNELS=[(k, k) for k in (15, 11, 9, 7, 5)])
+    # and the augmentation ranges of a training sample (data_settings.py:56-62); read by smap_amd/augment.py
+    d.TRAIN = AttrDict(GAUSSIAN_KERNELS=[(k, k) for k in (15, 11, 9, 7, 5)], CENTER_TRANS_MAX=40, ROTATE_MAX=10, FLIP_PROB=0.5,
+                       SCALE_MAX=1.1, SCALE_MIN=0.8)
     return d
 
 

@@ -1,6 +1,6 @@
 """Run configuration of the stage3_root2 experiment, inference subset (reference:
-exps/stage3_root2/config.py:10-71; SOLVER / DATALOADER / tensorboard entries belong to training,
-which is out of scope).  `cfg` has the attribute layout `test.py`, `SMAP(cfg)` and the dataset read."""
+exps/stage3_root2/config.py:10-71) plus the two SOLVER entries the training loader reads; the optimiser's entries and
+tensorboard belong to the training loop, which is out of scope.  `cfg` has the attribute layout `test.py`, `SMAP(cfg)` and the dataset read."""
 import os
 import os.path as osp
 
@@ -23,6 +23,7 @@ def _make():
         MODEL=AttrDict(STAGE_NUM=3, UPSAMPLE_CHANNEL_NUM=256, DEVICE="cuda", WEIGHT=None),
         LOSS=AttrDict(OHKM=True, TOPK=8, COARSE_TO_FINE=True),     # read by SMAP.__init__ only
         RUN_EFFICIENT=False,
+        SOLVER=AttrDict(IMG_PER_GPU=2, MAX_ITER=96000 * 2),        # config.py:50,53: what the training loader reads (get_train_loader)
         DATALOADER=AttrDict(NUM_WORKERS=int(os.environ.get("SMAP_NUM_WORKERS", 0))),
         # generate_result / generate_train read the MuPoTS annotations from here (config.py:67-70)
         TEST=AttrDict(IMG_PER_GPU=16, ROOT_PATH=os.environ.get("SMAP_TEST_ROOT", "/data/MultiPersonTestSet"),

@@ -153,6 +153,41 @@ int smap_sizeof_prep_frame(void);
 int smap_preprocess_batch(const struct smap_prep_frame* frames, int B, float* dst, int net_h, int net_w, const float* mean3,
                           const float* std3, void* stream);
 
+/* ---- training samples: dataset/ImageAugmentation.py aug_rotate + aug_croppad + aug_flip + ToTensor + Normalize in one launch ---- */
+
+/* The 1024 x 16 int16 weight table of OpenCV's 8-bit bicubic remap (INTER_CUBIC, INTER_BITS = 5, INTER_REMAP_COEF_BITS = 15): entry
+ * alpha = (fy5 * 32 + fx5) holds the 4 x 4 weights [row][column] of the fractional offset (fx5 / 32, fy5 / 32).  The 1-D float cubic has
+ * A = -0.75 and its fourth coefficient is 1 - c0 - c1 - c2; the 2-D weight is saturate_cast<short>(vy * vx * 32768); every entry is
+ * forced to sum to 32768 as initInterTab2D does.  Plain host code, no GPU.  out: HOST, 16384 int16.  SMAP_E_ARG: null. */
+int smap_cubic_table(int16_t* out);
+
+/* One training sample of smap_augment_batch.  The staged pipeline it stands for: cv2.warpAffine(src, m, (rw, rh), INTER_CUBIC,
+ * BORDER_CONSTANT 128) when `rotate`, rounded to uint8; cv2.resize(.., fx, fy) [INTER_LINEAR] of THAT image (rh x rw; the stored frame
+ * when rotate == 0) to nh x nw; pasted at (top, left) of the 128-grey canvas (clipped as in smap_preprocess_batch); mirrored in x when
+ * `flip`; ToTensor + Normalize.  The rotated image is never written: every linear tap is computed as the 8-bit result of the remap.
+ * m: the FORWARD 2 x 3 matrix as handed to cv2.warpAffine (it is inverted here as cv::warpAffine inverts it).  With rotate == 0, m is
+ * not read and rh, rw must still be positive (the caller sets them to h, w); with rotate == 0 and flip == 0 the output is byte for byte
+ * smap_preprocess_batch's.  h, w, rh, rw are at most SMAP_AUG_MAX_SIDE: NARROWER than OpenCV, whose fixed-point map saturates its
+ * coordinates at 16 bits -- no coordinate reaches that saturation here. */
+#define SMAP_AUG_MAX_SIDE 16384
+struct smap_aug_frame {
+    const unsigned char* src;           /* uint8 [h][w][3] BGR, device */
+    int32_t h, w;                       /* stored frame */
+    int32_t rotate;                     /* 0: no warp (aug_rotate was not called) */
+    int32_t rh, rw;                     /* size of the rotated image (nH, nW of rotate_bound) */
+    int32_t nh, nw, top, left;          /* resized size and where it sits in the canvas, as in smap_prep_frame */
+    int32_t flip;                       /* mirror the canvas in x */
+    double m[6];                        /* forward affine matrix, row major */
+    double fx, fy;                      /* the factors given to cv2.resize */
+};
+int smap_sizeof_aug_frame(void);
+/* frames: HOST array of B descriptors (copied into the kernel arguments, SMAP_PREP_MAX_FRAMES per launch, a larger B is split on the
+ * same stream); dst: fp32 [B][3][net_h][net_w]; mean3 / std3: HOST, 3 floats; cubic_tab: DEVICE copy of smap_cubic_table's output,
+ * 16-byte aligned, may be null only if no frame rotates.  SMAP_E_ARG: null pointers, B <= 0, non-positive sizes, fx / fy not positive,
+ * a non-finite matrix entry of a rotating frame, a misaligned cubic_tab, any of h, w, rh, rw above SMAP_AUG_MAX_SIDE. */
+int smap_augment_batch(const struct smap_aug_frame* frames, int B, float* dst, int net_h, int net_w, const float* mean3,
+                       const float* std3, const int16_t* cubic_tab, void* stream);
+
 /* ---- backbone: replaces model/smap.py SMAP.forward (eval) ------------------ */
 
 /* One op of the static inference schedule.  Offsets are BYTE offsets into the

@@ -21,6 +21,8 @@ SOURCES = [
     ("eval.hip", ["-ffp-contract=off"]),
     ("mupots.hip", ["-ffp-contract=off"]),       # MuPoTS-3D protocol: float64 in a fixed order; its arithmetic is csrc/mupots_core.h (also built alone for the CPU)
     ("labels.hip", ["-ffp-contract=off"]),       # label maps: held to the reference's bits as well
+    ("augment.hip", ["-ffp-contract=off"]),      # training samples: the warp's coordinate map in double, the resize of csrc/prep_device.h
+    ("cubic_table.cpp", ["-ffp-contract=off"]),  # host-only C++: the bicubic remap's weight table (also built alone under sanitizers)
     ("loss.hip", ["-ffp-contract=off"]),         # training loss: fixed-order double sums; its finish is csrc/loss_core.h (also built alone for the CPU)
     ("conv.hip", []),
     ("conv3.hip", []),

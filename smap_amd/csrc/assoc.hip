@@ -22,6 +22,7 @@
 #include <type_traits>
 #include "smap_hip.h"
 #include "hip_rc.h"
+#include "prep_device.h"
 
 namespace {
 
@@ -819,71 +820,17 @@ __global__ void flip_merge_kernel(float* __restrict__ hms, const float* __restri
 }
 
 // ------------------------------------------------------------ preprocess --
-// dataset/custom_dataset.py:41-68 (aug_croppad) and dataset/base_dataset.py (the annotated sets' crop-and-pad) + ToTensor + Normalize on
-// the device: OpenCV's 8-bit INTER_LINEAR resize, paste into the net_h x net_w canvas padded with 128, /255, (x - mean) / std, in ATen's
-// operation order so that it matches the host path bit for bit.  ONE per-pixel function (prep_pixel + prep_norm) behind both entry
-// points: smap_preprocess (one frame, one thread per canvas pixel) and smap_preprocess_batch (up to SMAP_PREP_MAX_FRAMES frames of
+// The per-pixel arithmetic (prep_pixel + prep_norm: OpenCV's 8-bit INTER_LINEAR resize, the paste's clip, ToTensor + Normalize) is
+// csrc/prep_device.h, shared with augment.hip.  ONE per-pixel function behind both entry points here, over the plain memory fetch:
+// smap_preprocess (one frame, one thread per canvas pixel) and smap_preprocess_batch (up to SMAP_PREP_MAX_FRAMES frames of
 // separate buffers per launch, four pixels and one 16-byte store per channel plane and thread).
-// One frame: the stored image, the window (nh x nw at (top, left), which may stick out of the canvas on any side) and 1 / fx, 1 / fy.
-struct PrepFrame { const unsigned char* src; int h, w, nh, nw, top, left; double scale_x, scale_y; };
-struct PrepCanvas { int net_h, net_w; float mean[3], stdv[3]; };
+// One frame: the stored image and its window.
+struct PrepFrame { const unsigned char* src; PrepWindow win; };
 struct PrepTable { PrepFrame f[SMAP_PREP_MAX_FRAMES]; };        // by value in the kernel arguments: 48 bytes per frame
 
-// One axis of OpenCV's 8-bit INTER_LINEAR (modules/imgproc/src/resize.cpp, cv::resize -> resizeGeneric_ set-up):
-//   fx = (float)((d + 0.5) * scale - 0.5) with scale = 1 / fx_arg (double); s = floor(fx); fx -= s;
-//   s < 0 -> (0, 0);  s >= n - 1 -> (n - 1, 0);  coefficients = cvRound(c * 2048) as shorts (INTER_RESIZE_COEF_BITS = 11).
-struct CvTap { int s0, s1; int c0, c1; };
-__device__ __forceinline__ CvTap cv_tap(int d, double scale, int n)
+__device__ __forceinline__ bool prep_pixel(const PrepFrame& f, int x, int y, float v[3])
 {
-    float f = (float)(((double)d + 0.5) * scale - 0.5);
-    int s = (int)floorf(f);
-    f -= (float)s;
-    if (s < 0) { f = 0.f; s = 0; }
-    if (s >= n - 1) { f = 0.f; s = n - 1; }
-    CvTap t;
-    t.s0 = s;
-    t.s1 = s + 1 < n ? s + 1 : s;                        // its coefficient is 0 whenever the clamp applies
-    t.c0 = (int)rintf((1.f - f) * 2048.f);               // saturate_cast<short>(float) = cvRound: half to even
-    t.c1 = (int)rintf(f * 2048.f);
-    return t;
-}
-
-// ToTensor + Normalize of one 8-bit value, in that order.
-__device__ __forceinline__ float prep_norm(float v, float mean, float stdv) { return (v / 255.0f - mean) / stdv; }
-
-// Canvas pixel (x, y) of one frame as three 8-bit values: cv2.resize(img, (0,0), fx=s, fy=s) [INTER_LINEAR, 8-bit fixed point] where the
-// window covers the pixel, else false (padding).  The window test is the paste's clip: a pixel of the canvas is the resized image's
-// (y - top, x - left) if that exists, whatever the sign of top / left and however far the window overhangs (64-bit: no int overflow).
-// The resize follows OpenCV's published algorithm operation by operation: horizontal pass in 11-bit fixed point (int32), vertical pass
-// ((b0*(S0>>4))>>16) + ((b1*(S1>>4))>>16) + 2) >> 2 (VResizeLinear<uchar,int,short,FixedPtCast<int,uchar,22>>), and the exact 2x shrink
-// as the 2x2 box mean (cv::resize switches INTER_LINEAR to INTER_AREA there).  cv2 is not in this image: parity unpinned by execution.
-// Every tap is clamped to the STORED image (h, w), so no read leaves it even when nh / nw were derived from another size.
-__device__ __forceinline__ bool prep_pixel(const PrepFrame& p, int x, int y, float v[3])
-{
-    const long long ry64 = (long long)y - p.top, rx64 = (long long)x - p.left;
-    if (ry64 < 0 || ry64 >= p.nh || rx64 < 0 || rx64 >= p.nw) return false;
-    const int ry = (int)ry64, rx = (int)rx64;
-    const unsigned char* __restrict__ src = p.src;
-    if (p.scale_x == 2.0 && p.scale_y == 2.0) {          // INTER_AREA fast path: (a + b + c + d + 2) >> 2
-        const int y0 = ry * 2 < p.h ? ry * 2 : p.h - 1, y1 = ry * 2 + 1 < p.h ? ry * 2 + 1 : p.h - 1;
-        const int x0 = rx * 2 < p.w ? rx * 2 : p.w - 1, x1 = rx * 2 + 1 < p.w ? rx * 2 + 1 : p.w - 1;
-#pragma unroll
-        for (int c = 0; c < 3; ++c)
-            v[c] = (float)((src[((size_t)y0 * p.w + x0) * 3 + c] + src[((size_t)y0 * p.w + x1) * 3 + c] +
-                            src[((size_t)y1 * p.w + x0) * 3 + c] + src[((size_t)y1 * p.w + x1) * 3 + c] + 2) >> 2);
-    } else {
-        const CvTap ty = cv_tap(ry, p.scale_y, p.h), tx = cv_tap(rx, p.scale_x, p.w);
-        const unsigned char* r0 = src + ((size_t)ty.s0 * p.w) * 3;
-        const unsigned char* r1 = src + ((size_t)ty.s1 * p.w) * 3;
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            const int h0 = r0[tx.s0 * 3 + c] * tx.c0 + r0[tx.s1 * 3 + c] * tx.c1;
-            const int h1 = r1[tx.s0 * 3 + c] * tx.c0 + r1[tx.s1 * 3 + c] * tx.c1;
-            const int t = (((ty.c0 * (h0 >> 4)) >> 16) + ((ty.c1 * (h1 >> 4)) >> 16) + 2) >> 2;
-            v[c] = (float)(t < 0 ? 0 : (t > 255 ? 255 : t));
-        }
-    }
-    return true;
+    return prep_pixel(f.win, MemFetch{f.src, f.win.w}, x, y, v);
 }
 
 // smap_preprocess: one frame, one thread per canvas pixel.
@@ -1108,7 +1055,7 @@ extern "C" int smap_preprocess(const unsigned char* src, int h, int w, int nh, i
 {
     if (!src || !dst || !mean3 || !std3 || h <= 0 || w <= 0 || nh <= 0 || nw <= 0 || net_h <= 0 || net_w <= 0 || !(fx > 0) || !(fy > 0))
         return SMAP_E_ARG;
-    const PrepFrame f{src, h, w, nh, nw, top, left, 1.0 / fx, 1.0 / fy};
+    const PrepFrame f{src, {h, w, nh, nw, top, left, 1.0 / fx, 1.0 / fy}};
     const PrepCanvas cv{net_h, net_w, {mean3[0], mean3[1], mean3[2]}, {std3[0], std3[1], std3[2]}};
     hipLaunchKernelGGL(preprocess_kernel, dim3((net_w + 255) / 256, net_h), dim3(256), 0, (hipStream_t)stream, f, dst, cv);
     return hip_rc(hipGetLastError());
@@ -1133,7 +1080,7 @@ extern "C" int smap_preprocess_batch(const smap_prep_frame* frames, int B, float
         PrepTable t;
         for (int i = 0; i < SMAP_PREP_MAX_FRAMES; ++i) {                    // unused entries repeat the last frame: never read (grid.z = n)
             const smap_prep_frame& s = frames[b0 + (i < n ? i : n - 1)];
-            t.f[i] = PrepFrame{s.src, s.h, s.w, s.nh, s.nw, s.top, s.left, 1.0 / s.fx, 1.0 / s.fy};
+            t.f[i] = PrepFrame{s.src, {s.h, s.w, s.nh, s.nw, s.top, s.left, 1.0 / s.fx, 1.0 / s.fy}};
         }
         const dim3 grid((net_w + 256 * px - 1) / (256 * px), net_h, n);
         float* out = dst + (size_t)b0 * frame_floats;

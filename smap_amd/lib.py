@@ -26,6 +26,7 @@ SYMBOLS = [
     "smap_sizeof_jpeg_info", "smap_jpeg_probe", "smap_jpeg_decode_coefficients", "smap_jpeg_workspace_bytes", "smap_jpeg_reconstruct",
     "smap_sizeof_jpeg_scan", "smap_jpeg_scan_tables", "smap_jpeg_huff_workspace_bytes", "smap_jpeg_decode_coefficients_device",
     "smap_sizeof_prep_frame", "smap_preprocess_batch",
+    "smap_cubic_table", "smap_sizeof_aug_frame", "smap_augment_batch",
     "smap_render_labels",
     "smap_loss_workspace_bytes", "smap_loss_forward", "smap_loss_backward", "smap_loss_finish_host",
     "smap_sizeof_head_src", "smap_loss_src_workspace_bytes", "smap_loss_forward_src",
@@ -107,6 +108,13 @@ class PrepFrame(C.Structure):
                 ("left", C.c_int32), ("fx", C.c_double), ("fy", C.c_double)]
 
 
+class AugFrame(C.Structure):
+    """Mirror of `struct smap_aug_frame`."""
+    _fields_ = [("src", C.c_void_p), ("h", C.c_int32), ("w", C.c_int32), ("rotate", C.c_int32), ("rh", C.c_int32), ("rw", C.c_int32),
+                ("nh", C.c_int32), ("nw", C.c_int32), ("top", C.c_int32), ("left", C.c_int32), ("flip", C.c_int32),
+                ("m", C.c_double * 6), ("fx", C.c_double), ("fy", C.c_double)]
+
+
 class HeadSrc(C.Structure):
     """Mirror of `struct smap_head_src`."""
     _fields_ = [("ptr", C.c_void_p), ("h", C.c_int32), ("w", C.c_int32), ("c", C.c_int32), ("pix_stride", C.c_int32),
@@ -115,6 +123,7 @@ class HeadSrc(C.Structure):
 
 LABEL_C, LABEL_MAX_SCALES, LABEL_MAX_TAPS, LABEL_MAX_PERSONS = 57, 8, 16, 64      # SMAP_LABEL_*
 PREP_MAX_FRAMES = 16      # SMAP_PREP_MAX_FRAMES
+AUG_MAX_SIDE = 16384      # SMAP_AUG_MAX_SIDE
 JPEG_UNSUPPORTED = 1      # SMAP_JPEG_UNSUPPORTED
 JPEG_E_DATA = -2          # SMAP_JPEG_E_DATA
 JPEG_DEV_E_DATA = 1       # SMAP_JPEG_DEV_E_DATA
@@ -160,6 +169,8 @@ def load():
     lib.smap_refine_gt.argtypes = lib.smap_refine.argtypes
     lib.smap_preprocess.argtypes = [vp, ip, ip, ip, ip, ip, ip, vp, ip, ip, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_double, C.c_double, vp]
     lib.smap_preprocess_batch.argtypes = [C.POINTER(PrepFrame), ip, vp, ip, ip, C.POINTER(C.c_float), C.POINTER(C.c_float), vp]
+    lib.smap_cubic_table.argtypes = [vp]
+    lib.smap_augment_batch.argtypes = [C.POINTER(AugFrame), ip, vp, ip, ip, C.POINTER(C.c_float), C.POINTER(C.c_float), vp, vp]
     lib.smap_conv_tile_dims.argtypes = [ip, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     lib.smap_conv_tile_bk.argtypes = [ip, ip]
     lib.smap_conv_tile_tail_bn.argtypes = [ip]
@@ -212,6 +223,8 @@ def load():
         raise ImportError(f"smap_jpeg_scan layout mismatch: C {lib.smap_sizeof_jpeg_scan()} vs ctypes {C.sizeof(JpegScan)}")
     if lib.smap_sizeof_prep_frame() != C.sizeof(PrepFrame):
         raise ImportError(f"smap_prep_frame layout mismatch: C {lib.smap_sizeof_prep_frame()} vs ctypes {C.sizeof(PrepFrame)}")
+    if lib.smap_sizeof_aug_frame() != C.sizeof(AugFrame):
+        raise ImportError(f"smap_aug_frame layout mismatch: C {lib.smap_sizeof_aug_frame()} vs ctypes {C.sizeof(AugFrame)}")
     if lib.smap_sizeof_head_src() != C.sizeof(HeadSrc):
         raise ImportError(f"smap_head_src layout mismatch: C {lib.smap_sizeof_head_src()} vs ctypes {C.sizeof(HeadSrc)}")
     _lib = lib

@@ -1,11 +1,14 @@
 """The batch loaders of the entry script (exps/stage3_root2/test.py): DevicePreprocLoader (`--device_preprocess 1 [--device_decode 1|2]`:
-frames decoded ahead of the consumer, resized / padded / normalised on the GPU) and AnnotationLoader (`--maps_from_gt 1`: annotations, no frames)."""
+frames decoded ahead of the consumer, resized / padded / normalised on the GPU) and AnnotationLoader (`--maps_from_gt 1`: annotations, no frames);
+and the training side: TrainSet + TrainLoader (lib/utils/dataloader.py::get_train_loader), whose batches are augmented and labelled on the GPU."""
 import collections
 import contextlib
 import functools
+import json
 import logging
 import os
 import queue
+import random
 import subprocess
 import sys
 from concurrent.futures import ThreadPoolExecutor
@@ -15,6 +18,8 @@ import numpy as np
 import torch
 
 from dataset.decode import read_bgr
+from .augment import AugParams, augment_batch, draw, plan_sample
+from .labels import label_spec, render_labels, root_depth_labels, valid_vector
 from .preprocess import preprocess_batch
 
 
@@ -262,3 +267,76 @@ class AnnotationLoader:
             idx = self.idx[s:s + self.bs]
             annotations, metas = zip(*[self.ds.extras(i) for i in idx])
             yield None, torch.stack(annotations, 0), tuple(self.ds.name(i) for i in idx), tuple(metas)
+
+
+class TrainSet:
+    """The annotation records of stage `train` (reference: dataset/base_dataset.py:32-56,65-66): the COCO JSON with every set of
+    USED_3D_DATASETS put in front of it, entries with isValidation == 0; a frame lies under its own dataset's root path.
+    A sample key is (epoch, index), or a bare index (epoch 0): its five draws come from a random.Random seeded with (seed, epoch,
+    index), so a sample does not depend on which pool thread plans it, nor on the batch it falls into.  It answers what
+    DevicePreprocLoader asks of a dataset: path / name / geometry (the image plan of smap_amd.augment.plan_sample) / extras
+    ((bodys [P,15,C] float64 in network pixels, valid [57,1], meta)); no file is opened for the latter two."""
+
+    def __init__(self, cfg, with_augmentation=True, seed=0, data=None):
+        ds = cfg.dataset
+        if data is None:
+            with open(ds.COCO_JSON_PATH) as f:
+                data = json.load(f)["root"]
+            for name in ds.USED_3D_DATASETS:
+                with open(ds["%s_JSON_PATH" % name]) as f:
+                    data = json.load(f)["root"] + data
+        self.data = [d for d in data if d["isValidation"] == 0]
+        self.root_path = {name: ds["%s_ROOT_PATH" % name] for name in ["COCO"] + list(ds.USED_3D_DATASETS) if ("%s_ROOT_PATH" % name) in ds}
+        self.params = AugParams.from_cfg(cfg)
+        self.with_augmentation, self.seed = bool(with_augmentation), seed
+
+    def __len__(self):
+        return len(self.data)
+
+    @staticmethod
+    def _key(key):
+        return (0, int(key)) if isinstance(key, (int, np.integer)) else (int(key[0]), int(key[1]))
+
+    def path(self, key):
+        d = self.data[self._key(key)[1]]
+        return os.path.join(self.root_path[d["dataset"].upper()], d["img_paths"])
+
+    def name(self, key):
+        return self.data[self._key(key)[1]]["img_paths"]
+
+    def plan(self, key):
+        """(bodys, meta, fields) of smap_amd.augment.plan_sample for sample `key`."""
+        epoch, index = self._key(key)
+        rng = random.Random("%s:%d:%d" % (self.seed, epoch, index))
+        return plan_sample(self.data[index], draw(rng), self.params, self.with_augmentation)
+
+    def geometry(self, key):
+        return self.plan(key)[2]
+
+    def extras(self, key):
+        bodys, meta, _ = self.plan(key)
+        return bodys, valid_vector(meta["dataset"]), meta
+
+
+class TrainLoader(DevicePreprocLoader):
+    """Training batches on the device, in the shapes of the reference's BatchCollator (lib/utils/dataloader.py:48-58):
+    (imgs [B,3,H,W], valids [B,57,1], labels [B,S,57,H/4,W/4], rdepth [B,MAX_PEOPLE,3]), all fp32 on `device` -- what
+    SMAP.forward(imgs, valids, labels, rdepth) and SMAPLoss consume.  The decode-ahead walk, the page-locked uploads and the decode
+    variants are DevicePreprocLoader's, unchanged; a batch is one smap_augment_batch launch (smap_amd/augment.py) on the planned
+    geometry and the label renderer's two launches (smap_amd/labels.py) on the planned key points.  dataset: a TrainSet; indices: its
+    sample keys."""
+
+    def __init__(self, dataset, indices, batch_size, cfg, device, device_decode=False, with_mds=False):
+        super().__init__(dataset, indices, batch_size, cfg, device, device_decode)
+        self.spec, self.with_mds = label_spec(cfg), bool(with_mds)
+
+    def _batch(self, got, along):
+        raws, _ = zip(*got)
+        plans, extras = zip(*along)
+        bodys, valids, metas = zip(*extras)
+        net_h, net_w = self.cfg.dataset.INPUT_SHAPE
+        imgs = augment_batch(raws, plans, self.cfg.INPUT.MEANS, self.cfg.INPUT.STDS, self.device, net_w=net_w, net_h=net_h)
+        labels = render_labels(list(bodys), self.spec, self.with_mds, self.device)
+        rdepth = np.stack([root_depth_labels(b, m["scale"], self.spec) for b, m in zip(bodys, metas)])
+        to = lambda a: torch.from_numpy(np.ascontiguousarray(a, np.float32)).to(self.device, non_blocking=True)
+        return imgs, to(np.stack(valids)), labels, to(rdepth)
