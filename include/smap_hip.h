@@ -701,7 +701,7 @@ int smap_loss_finish_host(const double* sums, const float* valids, const float* 
  *   every operation rounded once -- the expression of the engine's head sum.  root_d is read the same way at the rows' cells.
  * Everything else (labels, valids, rdepth, the integers, result) as smap_loss_forward.  The workspace begins with smap_loss_forward's
  *   layout (sums, ..., rd_at, root_cell: what the shared finish launch reads and writes) followed by the per-chunk partial sums
- *   f64 [n_heads][B][ceil(H * W / 256)][57]; smap_loss_src_workspace_bytes has its size.  It does not feed smap_loss_backward: no gradient.
+ *   f64 [n_heads][B][ceil(H * W / 256)][57]; smap_loss_src_workspace_bytes has its size.  It does not feed smap_loss_backward; smap_loss_backward_src (below) is its gradient.
  * Three launches on `stream` (reduce: one workgroup per (256 output pixels, frame, head) over all 57 channels; fold: the chunks in
  *   order; finish), no atomics: the same bits run to run, and a frame's sums depend on that frame only.  No allocation, no
  *   synchronisation.
@@ -719,6 +719,34 @@ int64_t smap_loss_src_workspace_bytes(int n_heads, int B, int R, int H, int W);
 int smap_loss_forward_src(const struct smap_head_src* sources, const float* labels, const float* valids, const float* rdepth, int stage_num,
                           int ohkm, int topk, int ctf, int B, int S, int R, int H, int W, void* workspace, int64_t workspace_bytes,
                           float* result, void* stream);
+
+/* ---- the gradient of total at the heads' OWN resolution: the adjoint of smap_loss_forward_src's upsampling ----
+ * Runs behind smap_loss_forward_src on the same sources, labels and integers, with the workspace as that call left it (read-only
+ * here: coef, root_cell and root_fac of the leading smap_loss_forward layout; nothing behind it is needed).
+ * grads: HOST array of 3 * n_heads descriptors, [i] = where the gradient of sources[i] goes: the same h, w, c, its own pointer and
+ *   strides in either order (NCHW, or NHWC with a padded pixel).  A null ptr: that gradient is not wanted (the rest of the descriptor
+ *   is not read).  Every one of the B x c x h x w described elements is written exactly once; padding floats and every other byte stay.
+ * Value at source cell (i, j) of a 2D / depth channel: with up_p and the taps i0, i1, l0, l1 of smap_loss_forward_src at output pixel
+ *   p = (y, x) and e_p = (up_p - label_p) * f, f = fp32(coef * upstream[0]):   sum_y wy(y, i) * sum_x wx(x, j) * e[y, x],
+ *   wy(y, i) = l0(y) where i0(y) == i, plus l1(y) where i1(y) == i (both at the last source row), wx alike.  A source of H x W: e itself;
+ *   one of height or width 1: the plain sum over that dimension.  f == 0: zeros, the channel's source and label planes are not read.
+ *   root_d: zeros, then per counted row on the map, in row order, root_fac * upstream times the four tap weights of the row's cell.
+ * Two launches on `stream`, no atomics, no allocation, no synchronisation.  part: one thread per (interval between source cells,
+ *   channel, frame, head) reads its output pixels once -- every label element is read by exactly one thread -- and writes four partial
+ *   sums (a pixel's first / second tap in y times first / second tap in x) to scratch; sources of H x W and root_d are finished there.
+ *   fold: one thread per source cell adds the up to nine partial sums that name it in a fixed order.  The order of every sum depends on
+ *   (h, w, H, W) alone: the same bits run to run and whichever of the two layouts sources and grads have.
+ * scratch: 16-byte aligned, f32 [B][c][h][w][4] for each heatmap_2d / det_d tensor that is smaller than H x W and whose gradient is
+ *   wanted.  smap_loss_backward_src_scratch_bytes (HOST, needs no GPU) sums that over all 2 * n_heads tensors of `sources` -- it knows
+ *   neither H x W nor grads, so it is an upper bound; the call itself takes any buffer that holds what it needs.
+ * upstream: DEVICE fp32 scalar, d L / d total.
+ * SMAP_E_ARG: everything smap_loss_forward_src refuses (valids, rdepth and result are not taken), a grads[i] with a pointer whose h, w, c
+ *   differ from sources[i]'s, whose pointer is misaligned or whose strides are neither order, a scratch buffer that is too small or
+ *   misaligned, a null upstream. */
+int64_t smap_loss_backward_src_scratch_bytes(const struct smap_head_src* sources, int n_heads, int B);
+int smap_loss_backward_src(const struct smap_head_src* sources, const struct smap_head_src* grads, const float* labels, int stage_num,
+                           int ohkm, int topk, int ctf, int B, int S, int R, int H, int W, const void* workspace, int64_t workspace_bytes,
+                           void* scratch, int64_t scratch_bytes, const float* upstream, void* stream);
 
 #if defined(__GNUC__)
 #pragma GCC visibility pop

@@ -19,6 +19,10 @@
 //               double accumulators per lane, folded over the lanes once at the end -> partial [head][frame][chunk][57].
 //   fold_src    one workgroup per (frame, head): the chunks' partials added in chunk order -> sums; root_d at the frame's rows.
 //   finish      as above.
+// smap_loss_backward_src: the gradient of that value at the heads' own resolution, the adjoint of the upsampling -- two launches:
+//   part        one thread per (interval between source cells, channel, frame, head): its output pixels once, four partial sums to scratch;
+//               the heads of H x W element-wise; root_d zeroed, then one thread per (frame, head) adds the rows' taps in order.
+//   fold        one thread per (source cell, channel, frame, head): the up to nine partial sums of its cell in a fixed order.
 // Compiled with -ffp-contract=off: every operation rounds once, in the order written.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -311,6 +315,148 @@ __global__ __launch_bounds__(NT) void loss_backward_kernel(HeadPtrs hp, const fl
     }
 }
 
+// ---- the gradient at the head sources: the adjoint of the on-the-fly upsampling ----------------------------------------------------
+// Every output pixel (y, x) has its taps i0 / i1 (lerp_index); the pixels that share (i0(y), i0(x)) = (a, b) form the INTERVAL (a, b)
+// of a source, and all of them read the same four source cells.  part: one thread per (interval, channel, frame, head) walks its
+// pixels row by row, x ascending -- e = (up - label) * f with src_value1's tap expression -- and leaves the four sums
+//     P[ry][rx] = sum_y l_ry(y) * sum_x l_rx(x) * e[y, x]           (r = 0: the pixel's weight on its first tap, 1: on its second)
+// in `scratch`; each label is read by exactly one thread.  fold: one thread per (cell, channel, frame, head) adds the up to nine
+// partial sums that name its cell -- intervals a = i - 1, i, within each b = j - 1, j, the second-tap sum before the first-tap one --
+// and stores the gradient.  The order depends on (h, w, H, W) alone and the addressing of a layout never enters the arithmetic.  A source of H x W is one
+// element-wise pass inside the first launch, which also owns root_d: zero-fill, then one thread walks the frame's rows.
+struct GradDst {
+    float* p;                // element (frame b, cell i, j, channel c) = p[b * frame + (i * w + j) * pix + c * ch]; null: not wanted
+    int pix, ch;
+    long long frame;
+};
+struct GradTable {
+    GradDst g[3 * MAX_HEADS];
+    long long part[2 * MAX_HEADS];      // [2 * h + 0 / 1]: where the partial sums of heatmap_2d / det_d of head h begin in scratch (floats)
+};
+
+// lerp_index's i1 for every pixel whose i0 is a
+__device__ __forceinline__ int second_tap(int a, int in_size, int out_size)
+{
+    return in_size == out_size ? a : a + (a < in_size - 1 ? 1 : 0);
+}
+// the first dst in [0, out_size] whose i0 is at least a (i0 never decreases with dst); out_size when there is none
+__device__ __forceinline__ int first_at_least(int a, int in_size, int out_size)
+{
+    int lo = 0, hi = out_size;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (lerp_index(mid, in_size, out_size).i0 >= a) hi = mid; else lo = mid + 1;
+    }
+    return lo;
+}
+
+// grid (58 * nblk, B, n_heads): block = (channel, slice of the tensor's intervals | pixels).
+__global__ __launch_bounds__(NT) void loss_backward_src_part_kernel(SrcTable tab, GradTable gt, const float* __restrict__ labels, Params p,
+                                                                     const float* __restrict__ coef, const int32_t* __restrict__ root_cell,
+                                                                     const float* __restrict__ root_fac, const float* __restrict__ upstream,
+                                                                     float* __restrict__ scratch, int nblk)
+{
+    const int c = blockIdx.x / nblk, blk = blockIdx.x % nblk, b = blockIdx.y, h = blockIdx.z, t = threadIdx.x;
+    const int HW = p.H * p.W;
+    const float up = upstream[0];
+    if (c == NC) {                                             // root_d: zeros, then ONE thread adds the frame's rows in order
+        const Src s = tab.s[3 * h + 2];
+        const GradDst gd = gt.g[3 * h + 2];
+        if (blk != 0 || !gd.p) return;
+        float* g = gd.p + (int64_t)b * gd.frame;
+        const int cells = s.h * s.w;
+        for (int i = t; i < cells; i += NT) g[(int64_t)i * gd.pix] = 0.0f;
+        __syncthreads();                                       // the workgroup's own stores: visible to its thread 0 behind the barrier
+        if (t == 0) {
+            const int64_t base = ((int64_t)h * p.B + b) * p.R;
+            const bool same = s.h == p.H && s.w == p.W;
+            for (int r = 0; r < p.R; ++r) {
+                const int cell = root_cell[base + r];
+                if (cell < 0 || cell >= HW) continue;          // skipped, or outside the map: never dereferenced
+                const float v = root_fac[base + r] * up;
+                if (same) {
+                    g[(int64_t)cell * gd.pix] += v;
+                    continue;
+                }
+                const Lerp ly = lerp_index(cell / p.W, s.h, p.H), lx = lerp_index(cell % p.W, s.w, p.W);
+                g[((int64_t)ly.i0 * s.w + lx.i0) * gd.pix] += v * (ly.l0 * lx.l0);
+                g[((int64_t)ly.i0 * s.w + lx.i1) * gd.pix] += v * (ly.l0 * lx.l1);
+                g[((int64_t)ly.i1 * s.w + lx.i0) * gd.pix] += v * (ly.l1 * lx.l0);
+                g[((int64_t)ly.i1 * s.w + lx.i1) * gd.pix] += v * (ly.l1 * lx.l1);
+            }
+        }
+        return;
+    }
+    const int k = c < N2D ? 0 : 1, cc = k ? c - N2D : c, cn = k ? NDD : N2D;
+    const Src s = tab.s[3 * h + k];
+    const GradDst gd = gt.g[3 * h + k];
+    if (!gd.p) return;
+    const float f = coef[((int64_t)h * p.B + b) * NC + c] * up;
+    const float* lab = label_plane(labels, p, h, b, c, HW);
+    const float* src = s.p + (int64_t)b * s.frame + (int64_t)cc * s.ch;
+    if (s.h == p.H && s.w == p.W) {                            // the identity: g = e; zero weight or not selected: zeros, nothing read
+        float* g = gd.p + (int64_t)b * gd.frame + (int64_t)cc * gd.ch;
+        for (int i = blk * NT + t; i < HW; i += nblk * NT) g[(int64_t)i * gd.pix] = f == 0.0f ? 0.0f : (src[(int64_t)i * s.pix] - lab[i]) * f;
+        return;
+    }
+    const int idx = blk * NT + t;
+    if (f == 0.0f || idx >= s.h * s.w) return;                 // (the fold writes a zero-factor channel's zeros)
+    const int a = idx / s.w, bc = idx - a * s.w;
+    const int a1 = second_tap(a, s.h, p.H), b1 = second_tap(bc, s.w, p.W);
+    const float v00 = src[((int64_t)a * s.w + bc) * s.pix], v01 = src[((int64_t)a * s.w + b1) * s.pix];
+    const float v10 = src[((int64_t)a1 * s.w + bc) * s.pix], v11 = src[((int64_t)a1 * s.w + b1) * s.pix];
+    const int y0 = first_at_least(a, s.h, p.H), y1 = first_at_least(a + 1, s.h, p.H);
+    const int x0 = first_at_least(bc, s.w, p.W), x1 = first_at_least(bc + 1, s.w, p.W);
+    float p00 = 0.0f, p01 = 0.0f, p10 = 0.0f, p11 = 0.0f;
+    for (int y = y0; y < y1; ++y) {
+        const Lerp ly = lerp_index(y, s.h, p.H);
+        const float* row = lab + (int64_t)y * p.W;
+        float r0 = 0.0f, r1 = 0.0f;
+        for (int x = x0; x < x1; ++x) {
+            const Lerp lx = lerp_index(x, s.w, p.W);
+            const float u = ly.l0 * (lx.l0 * v00 + lx.l1 * v01) + ly.l1 * (lx.l0 * v10 + lx.l1 * v11);      // src_value1's expression
+            const float e = (u - row[x]) * f;
+            r0 += lx.l0 * e;
+            r1 += lx.l1 * e;
+        }
+        p00 += ly.l0 * r0;
+        p01 += ly.l0 * r1;
+        p10 += ly.l1 * r0;
+        p11 += ly.l1 * r1;
+    }
+    float4* out = reinterpret_cast<float4*>(scratch + gt.part[2 * h + k]) + (((int64_t)b * cn + cc) * s.h + a) * s.w + bc;
+    *out = make_float4(p00, p01, p10, p11);
+}
+
+// grid (57 * nblk, B, n_heads): block = (channel, slice of the tensor's cells); sources of H x W were finished by the first launch.
+__global__ __launch_bounds__(NT) void loss_backward_src_fold_kernel(SrcTable tab, GradTable gt, Params p, const float* __restrict__ coef,
+                                                                     const float* __restrict__ upstream, const float* __restrict__ scratch,
+                                                                     int nblk)
+{
+    const int c = blockIdx.x / nblk, blk = blockIdx.x % nblk, b = blockIdx.y, h = blockIdx.z, t = threadIdx.x;
+    const int k = c < N2D ? 0 : 1, cc = k ? c - N2D : c, cn = k ? NDD : N2D;
+    const Src s = tab.s[3 * h + k];
+    const GradDst gd = gt.g[3 * h + k];
+    const int idx = blk * NT + t;
+    if (!gd.p || (s.h == p.H && s.w == p.W) || idx >= s.h * s.w) return;
+    const int i = idx / s.w, j = idx - i * s.w;
+    const float f = coef[((int64_t)h * p.B + b) * NC + c] * upstream[0];
+    float acc = 0.0f;
+    if (f != 0.0f) {
+        const float* part = scratch + gt.part[2 * h + k] + (((int64_t)b * cn + cc) * s.h) * s.w * 4;
+        for (int a = max(i - 1, 0); a <= i; ++a)
+            for (int ry = 1; ry >= 0; --ry) {                  // interval a names cell row i with its second tap, then with its first
+                if (ry ? second_tap(a, s.h, p.H) != i : a != i) continue;
+                for (int bc = max(j - 1, 0); bc <= j; ++bc)
+                    for (int rx = 1; rx >= 0; --rx) {
+                        if (rx ? second_tap(bc, s.w, p.W) != j : bc != j) continue;
+                        acc += part[((int64_t)a * s.w + bc) * 4 + 2 * ry + rx];
+                    }
+            }
+    }
+    gd.p[(int64_t)b * gd.frame + (int64_t)idx * gd.pix + (int64_t)cc * gd.ch] = acc;
+}
+
 // ---- host side -----------------------------------------------------------------------------------------------------------------
 Params make_params(int stage_num, int ohkm, int topk, int ctf, int single, int B, int S, int R, int H, int W)
 {
@@ -352,6 +498,24 @@ int take_heads(const void* const* heads, Params& p, HeadPtrs& hp, const float* l
 // smap_loss_forward_src's workspace: the layout above, then partial [n_heads][B][chunks][57] f64
 int src_chunks(int H, int W) { return (H * W + SRC_CHUNK - 1) / SRC_CHUNK; }
 int64_t src_partial_offset(int n_heads, int B, int R) { return workspace_layout(n_heads, B, R).bytes; }
+
+// a descriptor of c channels under an H x W output, as the kernels take it; 0 or SMAP_E_ARG
+int take_src(const smap_head_src& s, int c, int H, int W, Src& out)
+{
+    if (!s.ptr || ((uintptr_t)s.ptr & 3) || s.h < 1 || s.w < 1 || s.h > H || s.w > W || s.c != c || s.pix_stride < 1 || s.ch_stride < 1 ||
+        s.frame_stride < 1)
+        return SMAP_E_ARG;
+    // the strides describe a tensor that does not fold onto itself: channel-minor (NHWC, padded or not) or pixel-minor (NCHW) order
+    const int64_t px = (int64_t)s.h * s.w;
+    const bool nhwc = s.ch_stride == 1 && s.pix_stride >= c && s.frame_stride >= px * s.pix_stride;
+    const bool nchw = s.pix_stride == 1 && s.ch_stride >= px && s.frame_stride >= (int64_t)c * s.ch_stride;
+    if (!nhwc && !nchw) return SMAP_E_ARG;
+    out = Src{s.ptr, s.h, s.w, s.pix_stride, s.ch_stride, (long long)s.frame_stride};
+    return 0;
+}
+
+// smap_loss_backward_src's scratch: per tensor the four partial sums of every interval, f32 [B][c][h][w][4]
+int64_t part_floats(int h, int w, int c, int B) { return (int64_t)B * c * h * w * 4; }
 
 }  // namespace
 
@@ -405,19 +569,8 @@ int smap_loss_forward_src(const smap_head_src* sources, const float* labels, con
     if (check_params(p) || !sources || !labels || !valids || !rdepth || !workspace || !result || ((uintptr_t)workspace & 7))
         return SMAP_E_ARG;
     SrcTable tab{};
-    for (int i = 0; i < 3 * p.n_heads; ++i) {
-        const smap_head_src& s = sources[i];
-        const int c = i % 3 == 0 ? N2D : (i % 3 == 1 ? NDD : 1);
-        if (!s.ptr || ((uintptr_t)s.ptr & 3) || s.h < 1 || s.w < 1 || s.h > H || s.w > W || s.c != c || s.pix_stride < 1 || s.ch_stride < 1 ||
-            s.frame_stride < 1)
-            return SMAP_E_ARG;
-        // the strides describe a tensor that does not fold onto itself: channel-minor (NHWC, padded or not) or pixel-minor (NCHW) order
-        const int64_t px = (int64_t)s.h * s.w;
-        const bool nhwc = s.ch_stride == 1 && s.pix_stride >= c && s.frame_stride >= px * s.pix_stride;
-        const bool nchw = s.pix_stride == 1 && s.ch_stride >= px && s.frame_stride >= (int64_t)c * s.ch_stride;
-        if (!nhwc && !nchw) return SMAP_E_ARG;
-        tab.s[i] = Src{s.ptr, s.h, s.w, s.pix_stride, s.ch_stride, (long long)s.frame_stride};
-    }
+    for (int i = 0; i < 3 * p.n_heads; ++i)
+        if (take_src(sources[i], i % 3 == 0 ? N2D : (i % 3 == 1 ? NDD : 1), H, W, tab.s[i])) return SMAP_E_ARG;
     const Workspace w = workspace_layout(p.n_heads, B, R);
     const int chunks = src_chunks(H, W);
     if (workspace_bytes < smap_loss_src_workspace_bytes(p.n_heads, B, R, H, W)) return SMAP_E_ARG;
@@ -452,6 +605,63 @@ int smap_loss_backward(const void* const* heads, const float* labels, int stage_
     else
         hipLaunchKernelGGL(loss_backward_kernel<false>, grid, dim3(NT), 0, (hipStream_t)stream, hp, labels, p, (const float*)(ws + w.coef),
                            (const int32_t*)(ws + w.root_cell), (const float*)(ws + w.root_fac), upstream, grad);
+    return hip_rc(hipGetLastError());
+}
+
+int64_t smap_loss_backward_src_scratch_bytes(const smap_head_src* sources, int n_heads, int B)
+{
+    if (!sources || n_heads < 1 || n_heads > MAX_HEADS || B < 1 || B > 65535) return SMAP_E_ARG;
+    int64_t floats = 0;
+    for (int i = 0; i < 3 * n_heads; ++i) {
+        const smap_head_src& s = sources[i];
+        if (s.h < 1 || s.w < 1 || (int64_t)s.h * s.w > (1 << 24)) return SMAP_E_ARG;
+        if (i % 3 < 2) floats += part_floats(s.h, s.w, i % 3 ? NDD : N2D, B);
+    }
+    return floats * 4;
+}
+
+int smap_loss_backward_src(const smap_head_src* sources, const smap_head_src* grads, const float* labels, int stage_num, int ohkm, int topk,
+                           int ctf, int B, int S, int R, int H, int W, const void* workspace, int64_t workspace_bytes, void* scratch,
+                           int64_t scratch_bytes, const float* upstream, void* stream)
+{
+    Params p = make_params(stage_num, ohkm, topk, ctf, 0, B, S, R, H, W);
+    if (check_params(p) || !sources || !grads || !labels || !workspace || !upstream || ((uintptr_t)workspace & 7) || ((uintptr_t)scratch & 15))
+        return SMAP_E_ARG;
+    if (workspace_bytes < workspace_layout(p.n_heads, B, R).bytes) return SMAP_E_ARG;
+    SrcTable tab{};
+    GradTable gt{};
+    int64_t floats = 0;
+    int nblk_part = 1, nblk_fold = 0;
+    for (int i = 0; i < 3 * p.n_heads; ++i) {
+        const int c = i % 3 == 0 ? N2D : (i % 3 == 1 ? NDD : 1);
+        if (take_src(sources[i], c, H, W, tab.s[i])) return SMAP_E_ARG;
+        const smap_head_src& g = grads[i];
+        if (!g.ptr) continue;                                   // not wanted: gt.g[i].p stays null
+        Src dst;
+        if (g.h != sources[i].h || g.w != sources[i].w || take_src(g, c, H, W, dst)) return SMAP_E_ARG;
+        gt.g[i] = GradDst{const_cast<float*>(g.ptr), g.pix_stride, g.ch_stride, (long long)g.frame_stride};
+        if (i % 3 == 2) continue;
+        const int64_t cells = (int64_t)g.h * g.w;
+        if (g.h == H && g.w == W) {
+            nblk_part = max(nblk_part, (int)((cells + 4 * NT - 1) / (4 * NT)));
+        } else {
+            gt.part[2 * (i / 3) + i % 3] = floats;
+            floats += part_floats(g.h, g.w, c, B);
+            nblk_part = max(nblk_part, (int)((cells + NT - 1) / NT));
+            nblk_fold = max(nblk_fold, (int)((cells + NT - 1) / NT));
+        }
+    }
+    if (floats && (!scratch || scratch_bytes < floats * 4)) return SMAP_E_ARG;
+    const Workspace w = workspace_layout(p.n_heads, B, R);
+    const char* ws = (const char*)workspace;
+    const float* coef = (const float*)(ws + w.coef);
+    hipLaunchKernelGGL(loss_backward_src_part_kernel, dim3((unsigned)(GRAD_C * nblk_part), (unsigned)B, (unsigned)p.n_heads), dim3(NT), 0,
+                       (hipStream_t)stream, tab, gt, labels, p, coef, (const int32_t*)(ws + w.root_cell), (const float*)(ws + w.root_fac),
+                       upstream, (float*)scratch, nblk_part);
+    if (hipError_t e = hipGetLastError(); e != hipSuccess) return hip_rc(e);
+    if (!nblk_fold) return 0;
+    hipLaunchKernelGGL(loss_backward_src_fold_kernel, dim3((unsigned)(NC * nblk_fold), (unsigned)B, (unsigned)p.n_heads), dim3(NT), 0,
+                       (hipStream_t)stream, tab, gt, p, coef, upstream, (const float*)scratch, nblk_fold);
     return hip_rc(hipGetLastError());
 }
 

@@ -30,6 +30,7 @@ SYMBOLS = [
     "smap_render_labels",
     "smap_loss_workspace_bytes", "smap_loss_forward", "smap_loss_backward", "smap_loss_finish_host",
     "smap_sizeof_head_src", "smap_loss_src_workspace_bytes", "smap_loss_forward_src",
+    "smap_loss_backward_src_scratch_bytes", "smap_loss_backward_src",
 ]
 MAX_INPUTS = 8                         # SMAP_MAX_INPUTS
 
@@ -206,9 +207,13 @@ def load():
     lib.smap_loss_finish_host.argtypes = [vp, vp, vp, vp, ip, ip, ip, ip, ip, ip, ip, ip, ip, vp, vp, vp, vp, vp, vp, vp]
     lib.smap_loss_src_workspace_bytes.argtypes = [ip, ip, ip, ip, ip]
     lib.smap_loss_forward_src.argtypes = [C.POINTER(HeadSrc), vp, vp, vp, ip, ip, ip, ip, ip, ip, ip, ip, ip, vp, i64, vp, vp]
+    lib.smap_loss_backward_src_scratch_bytes.argtypes = [C.POINTER(HeadSrc), ip, ip]
+    lib.smap_loss_backward_src.argtypes = [C.POINTER(HeadSrc), C.POINTER(HeadSrc), vp, ip, ip, ip, ip, ip, ip, ip, ip, ip, vp, i64, vp, i64, vp, vp]
+    lib.smap_loss_backward_src_scratch_bytes.restype = C.c_int64
     for s in SYMBOLS:
         if s not in ("smap_version", "smap_plan_destroy", "smap_nms_workspace_bytes", "smap_jpeg_workspace_bytes",
-                     "smap_jpeg_huff_workspace_bytes", "smap_loss_workspace_bytes", "smap_loss_src_workspace_bytes"):  # everything else returns int
+                     "smap_jpeg_huff_workspace_bytes", "smap_loss_workspace_bytes", "smap_loss_src_workspace_bytes",
+                     "smap_loss_backward_src_scratch_bytes"):  # everything else returns int
             getattr(lib, s).restype = ip
     lib.smap_nms_workspace_bytes.restype = C.c_int64
     lib.smap_jpeg_workspace_bytes.restype = C.c_int64

@@ -16,6 +16,10 @@ Differences from the reference, on purpose:
 `EngineLoss` is the same value, forward only, for the validation loss: it reads the 36 head tensors where an all-heads engine
 (smap_amd/engine.py, BackboneEngine(all_heads=True).head_sources()) leaves them, at their own resolutions, and interpolates to H x W inside
 the reduction (smap_loss_forward_src).  Its values carry no graph.
+
+`SMAPLossNative` is SMAPLoss for heads that were not upsampled: value (smap_loss_forward_src) and gradient (smap_loss_backward_src, the
+adjoint of the upsampling: two launches, a fixed summation order) at the tensors' own resolutions, one autograd.Function.
+`EngineLoss.value_and_grad` is the same pair on an all-heads engine's tensors, gradients in their layout.
 """
 import ctypes as C
 
@@ -118,6 +122,48 @@ def forward_from_sources(cfg, sources, labels, valids, rdepth):
                                                cfg.B, cfg.S, cfg.R, cfg.H, cfg.W, ws.data_ptr(), bytes_, result.data_ptr(),
                                                torch.cuda.current_stream(dev).cuda_stream), "smap_loss_forward_src")
     return result, ws
+
+
+def _source_array(cfg, sources, what):
+    """The 3 * n_heads smap_head_src descriptors of n_heads dicts of HeadSource tuples (a None entry or pointer: a null descriptor)."""
+    if cfg.single or len(sources) != cfg.n_heads:
+        raise ValueError("%s: %d heads for %d stages of 4" % (what, len(sources), cfg.stage_num))
+    arr = (L.HeadSrc * (3 * cfg.n_heads))()
+    for h, d in enumerate(sources):
+        for k, (key, _) in enumerate(SOURCE_KEYS):
+            if d.get(key) is None:
+                continue
+            ptr, sh, sw, c, pix, ch, frame = d[key]
+            arr[3 * h + k] = L.HeadSrc(int(ptr) if ptr else None, int(sh), int(sw), int(c), int(pix), int(ch), 0, int(frame))
+    return arr
+
+
+def source_scratch_bytes(cfg, sources, grads):
+    """Bytes of smap_loss_backward_src's scratch: f32 [B][c][h][w][4] per heatmap_2d / det_d tensor below H x W whose gradient is wanted
+    (csrc/loss.hip part_floats; smap_loss_backward_src_scratch_bytes is the bound over all of them)."""
+    total = 0
+    for d, g in zip(sources, grads):
+        for key, c in SOURCE_KEYS[:2]:
+            _, sh, sw = d[key][:3]
+            if g.get(key) is not None and g[key][0] and (sh, sw) != (cfg.H, cfg.W):
+                total += cfg.B * c * sh * sw * 16
+    return total
+
+
+def backward_to_sources(cfg, sources, grads, labels, ws, upstream):
+    """smap_loss_backward_src on the current stream, behind forward_from_sources on the same `sources` and `labels`: writes d total /
+    d source * upstream[0] through the descriptors `grads` (n_heads dicts like `sources`: the same h, w, c, their own pointers and
+    strides; None or a null pointer: not wanted).  ws: the workspace forward_from_sources returned; upstream: device fp32 tensor, its
+    first element is read on the device.  No synchronisation, no graph.  Returns the scratch tensor (done with once the stream is)."""
+    dev = ws.device
+    src, dst = _source_array(cfg, sources, "sources"), _source_array(cfg, grads, "grads")
+    bytes_ = source_scratch_bytes(cfg, sources, grads)
+    scratch = torch.empty((max(bytes_, 16),), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        L.check(L.load().smap_loss_backward_src(src, dst, _ptr(labels), cfg.stage_num, cfg.ohkm, cfg.topk, cfg.ctf, cfg.B, cfg.S, cfg.R,
+                                                cfg.H, cfg.W, ws.data_ptr(), ws.numel(), scratch.data_ptr(), bytes_, upstream.data_ptr(),
+                                                torch.cuda.current_stream(dev).cuda_stream), "smap_loss_backward_src")
+    return scratch
 
 
 def backward_raw(cfg, tensors, labels, ws, upstream):
@@ -237,6 +283,84 @@ class SMAPLoss:
     forward = __call__
 
 
+def _nchw_source(t):
+    """HeadSource tuple of a dense [B, c, h, w] tensor."""
+    _, c, h, w = t.shape
+    return (t.data_ptr(), h, w, c, 1, h * w, c * h * w)
+
+
+class _NativeLossFunction(torch.autograd.Function):
+    """result [8] of smap_loss_forward_src as a function of the head tensors at their own resolutions; the gradient (smap_loss_backward_src)
+    flows from result[0] alone, into one buffer from which the 3 * n_heads views are cut."""
+
+    @staticmethod
+    def forward(ctx, cfg, labels, valids, rdepth, *tensors):
+        sources = [{key: _nchw_source(tensors[3 * h + k]) for k, (key, _) in enumerate(SOURCE_KEYS)} for h in range(cfg.n_heads)]
+        result, ws = forward_from_sources(cfg, sources, labels, valids, rdepth)
+        ctx.cfg, ctx.ws = cfg, ws
+        ctx.save_for_backward(labels, *tensors)
+        return result
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_result):
+        labels, *tensors = ctx.saved_tensors
+        cfg = ctx.cfg
+        buf = torch.empty((sum(t.numel() for t in tensors),), dtype=torch.float32, device=labels.device)
+        views, sources, grads, at = [], [], [], 0
+        for h in range(cfg.n_heads):
+            s, g = {}, {}
+            for k, (key, _) in enumerate(SOURCE_KEYS):
+                t = tensors[3 * h + k]
+                v = buf[at:at + t.numel()].view(t.shape)
+                at += t.numel()
+                views.append(v)
+                s[key], g[key] = _nchw_source(t), _nchw_source(v)
+            sources.append(s)
+            grads.append(g)
+        backward_to_sources(cfg, sources, grads, labels, ctx.ws, grad_result.contiguous())
+        return (None, None, None, None) + tuple(views)
+
+
+class SMAPLossNative(SMAPLoss):
+    """SMAPLoss on heads that were NOT upsampled: outputs[key][i][j] is [B, 43 | 14 | 1, h, w] with any 1 <= h <= H, 1 <= w <= W (H x W:
+    the labels' size), the tensor the reference hands to F.interpolate(size=(H, W), mode='bilinear', align_corners=True).  The upsampling
+    happens inside the reduction (smap_loss_forward_src) and its adjoint inside the backward pass (smap_loss_backward_src): no H x W
+    tensor is written in either direction, the gradients arrive at the tensors' own resolutions in a fixed summation order (the same bits
+    run to run).  Call signature, returned dict, `strict` and the differences from the reference are SMAPLoss's."""
+
+    def _check(self, outputs, valids, labels, rdepth):
+        cfg, labels, valids, rdepth = EngineLoss(self.stage_num, self.ohkm, self.topk, self.ctf).check(valids, labels, rdepth)
+        tensors = []
+        for i in range(self.stage_num):
+            for j in range(4):
+                for key, ch in SOURCE_KEYS:
+                    what = "outputs['%s'][%d][%d]" % (key, i, j)
+                    try:
+                        t = outputs[key][i][j]
+                    except (KeyError, IndexError, TypeError):
+                        raise ValueError("%s is missing: %d stages of 4 heads each" % (what, self.stage_num))
+                    t = _device_fp32(t, what)
+                    if t.dim() != 4 or tuple(t.shape[:2]) != (cfg.B, ch) or not (1 <= t.shape[2] <= cfg.H and 1 <= t.shape[3] <= cfg.W):
+                        raise ValueError("%s: expected [%d, %d, h <= %d, w <= %d], got %s" % (what, cfg.B, ch, cfg.H, cfg.W, tuple(t.shape)))
+                    if t.device != labels.device:
+                        raise ValueError("all tensors live on one GPU: labels on %s, %s on %s" % (labels.device, what, t.device))
+                    tensors.append(t)
+        return cfg, tensors, labels, valids, rdepth
+
+    def __call__(self, outputs, valids, labels, rdepth):
+        cfg, tensors, labels, valids, rdepth = self._check(outputs, valids, labels, rdepth)
+        result = _NativeLossFunction.apply(cfg, labels, valids, rdepth, *tensors)
+        if self.strict:
+            bad = int(result[4].item())                       # the one synchronisation of strict mode
+            if bad:
+                raise ValueError("rdepth: %d row(s) with Z > 0 lie outside the %d x %d map" % (bad, cfg.H, cfg.W))
+        logged = result.detach()
+        return dict(total_loss=result[0], loss_2d=logged[1], loss_bone=logged[2], loss_root=logged[3])
+
+    forward = __call__
+
+
 class EngineLoss:
     """SMAP._calculate_loss, forward only, on the heads of an all-heads engine (the validation loss).
 
@@ -280,6 +404,36 @@ class EngineLoss:
         with torch.no_grad():
             result, _ = self.raw(sources, valids, labels, rdepth)
         return dict(total_loss=result[0], loss_2d=result[1], loss_bone=result[2], loss_root=result[3])
+
+    def value_and_grad(self, sources, valids, labels, rdepth, upstream=None):
+        """(losses, grads): the dict of __call__ and d (total_loss * upstream) / d source for every head tensor, at its own resolution --
+        the seam a backward pass through the backbone starts from (smap_loss_backward_src).  grads: one dict per head of
+        {"heatmap_2d", "det_d", "root_d": tensor [B, c, h, w]}, each in its source's own order: a view of a zeroed [B, h, w, pix_stride]
+        buffer where the source is NHWC with a padded pixel, dense NCHW otherwise.  upstream: None (1) or a device fp32 tensor whose
+        first element is read on the device.  No graph, no synchronisation."""
+        with torch.no_grad():
+            cfg, labels, valids, rdepth = self.check(valids, labels, rdepth)
+            result, ws = forward_from_sources(cfg, sources, labels, valids, rdepth)
+            dev = labels.device
+            if upstream is None:
+                upstream = torch.ones((1,), dtype=torch.float32, device=dev)
+            upstream = _device_fp32(upstream, "upstream").reshape(-1)
+            grads, desc = [], []
+            for d in sources:
+                g, gd = {}, {}
+                for key, _ in SOURCE_KEYS:
+                    _, sh, sw, c, pix, ch, _ = d[key]
+                    if ch == 1 and pix >= c:                  # NHWC, the pixel padded as the source's is
+                        buf = torch.zeros((cfg.B, sh, sw, pix), dtype=torch.float32, device=dev)
+                        g[key] = buf[..., :c].permute(0, 3, 1, 2)
+                        gd[key] = (buf.data_ptr(), sh, sw, c, pix, 1, sh * sw * pix)
+                    else:
+                        g[key] = torch.empty((cfg.B, c, sh, sw), dtype=torch.float32, device=dev)
+                        gd[key] = _nchw_source(g[key])
+                grads.append(g)
+                desc.append(gd)
+            backward_to_sources(cfg, sources, desc, labels, ws, upstream)
+        return dict(total_loss=result[0], loss_2d=result[1], loss_bone=result[2], loss_root=result[3]), grads
 
 
 class ValidationLoss:

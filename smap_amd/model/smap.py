@@ -202,3 +202,24 @@ class SMAP(nn.Module):
         if os.environ.get("SMAP_CHECK_FINITE"):
             eng.raise_if_nonfinite(out)
         return dict(total_loss=result[0], loss_2d=result[1], loss_bone=result[2], loss_root=result[3])
+
+    def loss_and_head_gradients(self, imgs, valids, labels, rdepth):
+        """The loss of _loss and the gradient of total_loss at the 36 head tensors where the all-heads schedule leaves them, at their own
+        resolutions and in their own layouts (smap_loss_backward_src): the seam a backward pass through the backbone starts from.  Eval
+        mode, the current stream, no synchronisation.  Returns (dict as forward's loss branch, EngineLoss.value_and_grad's grads)."""
+        from ..loss import EngineLoss
+        if self.training:
+            raise RuntimeError("smap_amd.SMAP evaluates the loss in eval mode only (folded BatchNorm): call model.eval() first")
+        if not imgs.is_cuda:
+            raise NotImplementedError("smap_amd.SMAP evaluates the loss on a ROCm GPU only: images on %s, there is no CPU fallback" % imgs.device)
+        if imgs.dim() != 4 or imgs.shape[1] != 3:
+            raise ValueError(f"imgs must be [B,3,H,W], got {tuple(imgs.shape)}")
+        B, _, H, W = imgs.shape
+        crit = EngineLoss(self.stage_num, self.ohkm, self.topk, self.ctf)
+        cfg, labels, valids, rdepth = crit.check(valids, labels, rdepth)
+        if (cfg.B, cfg.H, cfg.W) != (B, H // 4, W // 4) or labels.device != imgs.device:
+            raise ValueError(f"labels must be [{B},S,57,{H // 4},{W // 4}] on {imgs.device}, got {tuple(labels.shape)} on {labels.device}")
+        eng = self.engine(B, H, W, imgs.device, all_heads=True)
+        out = eng.new_output()
+        eng.run(imgs.float(), out=out)
+        return crit.value_and_grad(eng.head_sources(out), valids, labels, rdepth)
