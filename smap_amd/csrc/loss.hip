@@ -1,27 +1,27 @@
 // loss.hip -- the training loss of the network on gfx950: value and gradient of SMAP._calculate_loss (model/smap.py:355-401) with
-// JointsL2Loss / DepthLoss (lib/utils/loss_h.py), over all 4 * stage_num heads in two launches forward and one backward.
+// JointsL2Loss / DepthLoss (lib/utils/loss_h.py), over all 4 * stage_num heads.  Two routes, dense heads of H x W (HeadPtrs) and heads
+// read where the engine left them (SrcTable: pointer, size and strides per tensor), both passed by value in the kernel arguments; they
+// stay apart because their reductions add in different orders, and share the steps below.
 //
+// smap_loss_forward: reduce, finish.  smap_loss_backward: backward.
 //   reduce    one workgroup per (channel of 57, frame, head): d = out - label in fp32 (one correctly rounded subtraction), the sum of
 //             double(d) * double(d) in a FIXED order -- every thread walks the plane with the workgroup's stride, lanes fold with
-//             shuffles, waves through LDS -- so a value depends on its plane alone and is the same bits run to run.  No atomics.
-//             One more workgroup per (frame, head) finds the cells of the frame's root-depth rows and reads root_d there.
+//             wave_sum, waves through LDS -- so a value depends on its plane alone and is the same bits run to run.  No atomics.
+//             One more workgroup per (frame, head) is root_rows: the cells of the frame's root-depth rows and root_d there.
 //   finish    one workgroup: csrc/loss_core.h (the same text the host runs), a phase per barrier.
 //   backward  one workgroup per (channel of 58, frame, head): grad = (out - label) * fp32(coef * upstream); a channel whose factor is
-//             zero is written as zeros without reading anything.  The root_d plane is zeroed, then ONE thread adds its frame's rows in
+//             zero is zero_plane, nothing read.  The root_d plane is root_grad_plane: zeroed, then ONE thread adds its frame's rows in
 //             order, so two persons on one cell add up the same way every time.
-// The 3 * n_heads tensor pointers travel by value in the kernel arguments (HeadPtrs), as smap_preprocess_batch passes its frames.
-//
-// smap_loss_forward_src: the same value with every head read where the engine left it (SrcTable: pointer, size and strides per tensor, by
-// value too), at its own resolution, interpolated to H x W on the fly -- three launches:
+// smap_loss_forward_src: the same value, every head at its own resolution, interpolated to H x W on the fly (src_value1 / src_value4:
+// lerp_index and the tap expression `tap`, as plan.hip's head_source4) -- reduce_src, fold_src, finish:
 //   reduce_src  one workgroup per (chunk of 256 output pixels, frame, head), all 57 channels: 64 pixels at a time, the source values (16-byte
-//               reads of four channels where the source is pixel-major, the tap expression of plan.hip's head_source4) go through an LDS
-//               transpose, then wave w owns channels w, w + 4, ... and lane l pixel l, so a label row is read 256 bytes at a time; fifteen
-//               double accumulators per lane, folded over the lanes once at the end -> partial [head][frame][chunk][57].
-//   fold_src    one workgroup per (frame, head): the chunks' partials added in chunk order -> sums; root_d at the frame's rows.
-//   finish      as above.
-// smap_loss_backward_src: the gradient of that value at the heads' own resolution, the adjoint of the upsampling -- two launches:
+//               reads of four channels where the source is pixel-major) go through an LDS transpose, then wave w owns channels w, w + 4, ...
+//               and lane l pixel l, so a label row is read 256 bytes at a time; fifteen double accumulators per lane, folded over the
+//               lanes once at the end -> partial [head][frame][chunk][57].
+//   fold_src    one workgroup per (frame, head): the chunks' partials added in chunk order -> sums; root_rows through src_value1.
+// smap_loss_backward_src: the gradient of that value at the heads' own resolution, the adjoint of the upsampling -- part, fold:
 //   part        one thread per (interval between source cells, channel, frame, head): its output pixels once, four partial sums to scratch;
-//               the heads of H x W element-wise; root_d zeroed, then one thread per (frame, head) adds the rows' taps in order.
+//               the heads of H x W element-wise; root_d is root_grad_plane with the destination's stride and the four taps of a row.
 //   fold        one thread per (source cell, channel, frame, head): the up to nine partial sums of its cell in a fixed order.
 // Compiled with -ffp-contract=off: every operation rounds once, in the order written.
 #include <hip/hip_runtime.h>
@@ -41,16 +41,81 @@ struct HeadPtrs {
     const float* p[3 * MAX_HEADS];        // [3 * h + 0 / 1 / 2] = heatmap_2d [B, 43, H, W], det_d [B, 14, H, W], root_d [B, 1, H, W]
 };
 
-// the plane of output channel c (0..56) of frame b in its head, and the label plane it is compared with
+struct Chan { int k, cc, cn; };          // of output channel c (0..56): its tensor within the head (0 / 1), its channel there, the tensor's channels
+__device__ __forceinline__ Chan channel_of(int c) { return c < N2D ? Chan{0, c, N2D} : Chan{1, c - N2D, NDD}; }
+// the plane of output channel c of frame b in its head, and the label plane it is compared with
 __device__ __forceinline__ const float* out_plane(const HeadPtrs& hp, int h, int b, int c, int HW)
 {
-    const float* t = c < N2D ? hp.p[3 * h] : hp.p[3 * h + 1];
+    const Chan ch = channel_of(c);
+    const float* t = hp.p[3 * h + ch.k];
     if (!t) return nullptr;
-    return t + ((int64_t)b * (c < N2D ? N2D : NDD) + (c < N2D ? c : c - N2D)) * HW;
+    return t + ((int64_t)b * ch.cn + ch.cc) * HW;
 }
 __device__ __forceinline__ const float* label_plane(const float* labels, const Params& p, int h, int b, int c, int HW)
 {
     return labels + (((int64_t)b * p.S + head_scale(p, h)) * NC + label_channel(c)) * HW;
+}
+
+__device__ __forceinline__ double wave_sum(double a)                   // lane 0 ends with the wave's sum, lanes added in a fixed order
+{
+    for (int o = 32; o > 0; o >>= 1) a += __shfl_down(a, o, 64);
+    return a;
+}
+
+// this thread's share (first, first + step, ...) of n zeros `stride` floats apart.  VEC: stride 1, n % 4 == 0, g 16-byte aligned
+template <bool VEC>
+__device__ __forceinline__ void zero_plane(float* g, int n, int stride, int first, int step)
+{
+    if (VEC) {
+        float4* g4 = (float4*)g;
+        for (int i = first; i < (n >> 2); i += step) g4[i] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    } else {
+        for (int i = first; i < n; i += step) g[(int64_t)i * stride] = 0.0f;
+    }
+}
+
+// the root-depth rows of frame b for head h, by nt threads: the cell of each and root_d there, rd(cell).  A row outside the map is never
+// dereferenced, and root_row_cell is ROW_SKIPPED throughout when the head has no root_d
+template <class ReadRd>
+__device__ __forceinline__ void root_rows(const Params& p, const float* rdepth, int b, int h, int t, int nt, float* rd_at,
+                                          int32_t* root_cell, ReadRd rd)
+{
+    const int64_t base = ((int64_t)h * p.B + b) * p.R;
+    for (int r = t; r < p.R; r += nt) {
+        const int cell = root_row_cell(p, rdepth + ((int64_t)b * p.R + r) * 3);
+        rd_at[base + r] = cell >= 0 ? rd(cell) : 0.0f;
+        root_cell[base + r] = cell;
+    }
+}
+
+// the bilinear tap expression (head_source4's, csrc/plan.hip)
+__device__ __forceinline__ float tap(const Lerp& ly, const Lerp& lx, float v00, float v01, float v10, float v11)
+{
+    return ly.l0 * (lx.l0 * v00 + lx.l1 * v01) + ly.l1 * (lx.l0 * v10 + lx.l1 * v11);
+}
+
+// the root_d gradient plane of frame b, head h -- g: sh x sw cells `stride` floats apart -- by a workgroup of NT: zeros, then ONE thread
+// adds the frame's rows in order, each at its cell (a plane of H x W) or spread over the cell's four taps
+template <bool VEC>
+__device__ __forceinline__ void root_grad_plane(float* g, int sh, int sw, int stride, const Params& p, int h, int b,
+                                                const int32_t* root_cell, const float* root_fac, float up, int t)
+{
+    zero_plane<VEC>(g, sh * sw, stride, t, NT);
+    __syncthreads();                                           // the workgroup's own stores: visible to its thread 0 behind the barrier
+    if (t != 0) return;
+    const int64_t base = ((int64_t)h * p.B + b) * p.R;
+    const bool same = sh == p.H && sw == p.W;
+    for (int r = 0; r < p.R; ++r) {
+        const int cell = root_cell[base + r];
+        if (cell < 0 || cell >= p.H * p.W) continue;           // skipped, or outside the map: never dereferenced
+        const float v = root_fac[base + r] * up;
+        if (same) { g[(int64_t)cell * stride] += v; continue; }
+        const Lerp ly = lerp_index(cell / p.W, sh, p.H), lx = lerp_index(cell % p.W, sw, p.W);
+        g[((int64_t)ly.i0 * sw + lx.i0) * stride] += v * (ly.l0 * lx.l0);
+        g[((int64_t)ly.i0 * sw + lx.i1) * stride] += v * (ly.l0 * lx.l1);
+        g[((int64_t)ly.i1 * sw + lx.i0) * stride] += v * (ly.l1 * lx.l0);
+        g[((int64_t)ly.i1 * sw + lx.i1) * stride] += v * (ly.l1 * lx.l1);
+    }
 }
 
 // ---- launch A ------------------------------------------------------------------------------------------------------------------
@@ -63,16 +128,7 @@ __global__ __launch_bounds__(NT) void loss_reduce_kernel(HeadPtrs hp, const floa
     __shared__ double s_part[NT / 64];
     const int c = blockIdx.x, b = blockIdx.y, h = blockIdx.z, t = threadIdx.x;
     const int HW = p.H * p.W;
-    if (c == NC) {                                             // root_d at the frame's rows; a row outside the map is never dereferenced
-        const float* rd = hp.p[3 * h + 2];
-        for (int r = t; r < p.R; r += NT) {
-            const int64_t row = (int64_t)b * p.R + r;
-            const int cell = root_row_cell(p, rdepth + row * 3);           // ROW_SKIPPED throughout when the head has no root_d
-            rd_at[(int64_t)h * p.B * p.R + row] = cell >= 0 ? rd[(int64_t)b * HW + cell] : 0.0f;
-            root_cell[(int64_t)h * p.B * p.R + row] = cell;
-        }
-        return;
-    }
+    if (c == NC) return root_rows(p, rdepth, b, h, t, NT, rd_at, root_cell, [&](int cell) { return hp.p[3 * h + 2][(int64_t)b * HW + cell]; });
     const float* out = out_plane(hp, h, b, c, HW);
     double acc = 0.0;
     if (out) {
@@ -98,7 +154,7 @@ __global__ __launch_bounds__(NT) void loss_reduce_kernel(HeadPtrs hp, const floa
             }
         }
     }
-    for (int o = 32; o > 0; o >>= 1) acc += __shfl_down(acc, o, 64);
+    acc = wave_sum(acc);
     if ((t & 63) == 0) s_part[t >> 6] = acc;
     __syncthreads();
     if (t == 0) sums[((int64_t)h * p.B + b) * NC + c] = ((s_part[0] + s_part[1]) + s_part[2]) + s_part[3];
@@ -120,8 +176,7 @@ __device__ __forceinline__ bool src_vec(const Src& s, int c)
     return s.ch == 1 && !(s.pix & 3) && s.pix >= ((c + 3) & ~3) && !(s.frame & 3) && !((uintptr_t)s.p & 15);
 }
 
-// the source's bilinear (align_corners) image at output pixel (y, x), channel c: ATen's index rule (lerp_index) and the tap expression of
-// head_source4 (csrc/plan.hip); a source at the output's size is read as it is, one of height or width 1 has all its taps at index 0
+// the source's bilinear (align_corners) image at output pixel (y, x), channel c: ATen's index rule (lerp_index) and `tap`; a source at the output's size is read as it is, one of height or width 1 has all its taps at index 0
 __device__ __forceinline__ float src_value1(const Src& s, int b, int y, int x, int c, int H, int W)
 {
     const float* base = s.p + (int64_t)b * s.frame + (int64_t)c * s.ch;
@@ -129,7 +184,7 @@ __device__ __forceinline__ float src_value1(const Src& s, int b, int y, int x, i
     const Lerp ly = lerp_index(y, s.h, H), lx = lerp_index(x, s.w, W);
     const float v00 = base[((int64_t)ly.i0 * s.w + lx.i0) * s.pix], v01 = base[((int64_t)ly.i0 * s.w + lx.i1) * s.pix];
     const float v10 = base[((int64_t)ly.i1 * s.w + lx.i0) * s.pix], v11 = base[((int64_t)ly.i1 * s.w + lx.i1) * s.pix];
-    return ly.l0 * (lx.l0 * v00 + lx.l1 * v01) + ly.l1 * (lx.l0 * v10 + lx.l1 * v11);
+    return tap(ly, lx, v00, v01, v10, v11);
 }
 __device__ __forceinline__ float4 src_value4(const Src& s, int b, int y, int x, int c, int H, int W)
 {
@@ -140,12 +195,8 @@ __device__ __forceinline__ float4 src_value4(const Src& s, int b, int y, int x, 
     const float4 v01 = *reinterpret_cast<const float4*>(base + ((int64_t)ly.i0 * s.w + lx.i1) * s.pix);
     const float4 v10 = *reinterpret_cast<const float4*>(base + ((int64_t)ly.i1 * s.w + lx.i0) * s.pix);
     const float4 v11 = *reinterpret_cast<const float4*>(base + ((int64_t)ly.i1 * s.w + lx.i1) * s.pix);
-    float4 up;
-    up.x = ly.l0 * (lx.l0 * v00.x + lx.l1 * v01.x) + ly.l1 * (lx.l0 * v10.x + lx.l1 * v11.x);
-    up.y = ly.l0 * (lx.l0 * v00.y + lx.l1 * v01.y) + ly.l1 * (lx.l0 * v10.y + lx.l1 * v11.y);
-    up.z = ly.l0 * (lx.l0 * v00.z + lx.l1 * v01.z) + ly.l1 * (lx.l0 * v10.z + lx.l1 * v11.z);
-    up.w = ly.l0 * (lx.l0 * v00.w + lx.l1 * v01.w) + ly.l1 * (lx.l0 * v10.w + lx.l1 * v11.w);
-    return up;
+    return make_float4(tap(ly, lx, v00.x, v01.x, v10.x, v11.x), tap(ly, lx, v00.y, v01.y, v10.y, v11.y),
+                       tap(ly, lx, v00.z, v01.z, v10.z, v11.z), tap(ly, lx, v00.w, v01.w, v10.w, v11.w));
 }
 
 // grid (chunks, B, n_heads).  partial [n_heads][B][chunks][57].  acc[] is indexed by unrolled loops only: registers, no private array
@@ -202,14 +253,13 @@ __global__ __launch_bounds__(NT) void loss_reduce_src_kernel(SrcTable tab, const
     }
 #pragma unroll
     for (int k = 0; k < SRC_ROWS; ++k) {
-        double a = acc[k];
-        for (int o = 32; o > 0; o >>= 1) a += __shfl_down(a, o, 64);
+        const double a = wave_sum(acc[k]);
         const int c = wave + 4 * k;
         if (lane == 0 && c < NC) partial[((((int64_t)h * p.B + b) * chunks) + chunk) * NC + c] = a;
     }
 }
 
-// grid (B, n_heads), 64 threads: the chunks in order; root_d at the frame's rows (a row outside the map is never dereferenced)
+// grid (B, n_heads), 64 threads: the chunks in order; root_d at the frame's rows
 __global__ __launch_bounds__(64) void loss_fold_src_kernel(SrcTable tab, const float* __restrict__ rdepth, Params p,
                                                            const double* __restrict__ partial, int chunks, double* __restrict__ sums,
                                                            float* __restrict__ rd_at, int32_t* __restrict__ root_cell)
@@ -223,11 +273,7 @@ __global__ __launch_bounds__(64) void loss_fold_src_kernel(SrcTable tab, const f
         sums[frame * NC + t] = s;
     }
     const Src sr = tab.s[3 * h + 2];
-    for (int r = t; r < p.R; r += 64) {
-        const int cell = root_row_cell(p, rdepth + ((int64_t)b * p.R + r) * 3);
-        rd_at[frame * p.R + r] = cell >= 0 ? src_value1(sr, b, cell / p.W, cell % p.W, 0, p.H, p.W) : 0.0f;
-        root_cell[frame * p.R + r] = cell;
-    }
+    root_rows(p, rdepth, b, h, t, 64, rd_at, root_cell, [&](int cell) { return src_value1(sr, b, cell / p.W, cell % p.W, 0, p.H, p.W); });
 }
 
 // ---- finish: csrc/loss_core.h, one workgroup ---------------------------------------------------------------------------------------
@@ -268,37 +314,14 @@ __global__ __launch_bounds__(NT) void loss_backward_kernel(HeadPtrs hp, const fl
     const float up = upstream[0];
     float* gh = grad + (int64_t)h * p.B * GRAD_C * HW;
     if (c == NC) {
-        if (!hp.p[3 * h + 2]) return;
-        float* g = gh + ((int64_t)p.B * NC + b) * HW;
-        if (VEC) {
-            float4* g4 = (float4*)g;
-            for (int i = t; i < (HW >> 2); i += NT) g4[i] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-        } else {
-            for (int i = t; i < HW; i += NT) g[i] = 0.0f;
-        }
-        __syncthreads();                                       // the workgroup's own stores: visible to its thread 0 behind the barrier
-        if (t == 0) {
-            const int64_t base = ((int64_t)h * p.B + b) * p.R;
-            for (int r = 0; r < p.R; ++r) {
-                const int cell = root_cell[base + r];
-                if (cell >= 0 && cell < HW) g[cell] += root_fac[base + r] * up;
-            }
-        }
+        if (hp.p[3 * h + 2]) root_grad_plane<VEC>(gh + ((int64_t)p.B * NC + b) * HW, p.H, p.W, 1, p, h, b, root_cell, root_fac, up, t);
         return;
     }
     const float* out = out_plane(hp, h, b, c, HW);
     if (!out) return;
     float* g = gh + (c < N2D ? (int64_t)b * N2D + c : (int64_t)p.B * N2D + (int64_t)b * NDD + (c - N2D)) * HW;
     const float f = coef[((int64_t)h * p.B + b) * NC + c] * up;
-    if (f == 0.0f) {                                           // zero weight or not selected: exactly zero, nothing read
-        if (VEC) {
-            float4* g4 = (float4*)g;
-            for (int i = t; i < (HW >> 2); i += NT) g4[i] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-        } else {
-            for (int i = t; i < HW; i += NT) g[i] = 0.0f;
-        }
-        return;
-    }
+    if (f == 0.0f) return zero_plane<VEC>(g, HW, 1, t, NT);    // zero weight or not selected: exactly zero, nothing read
     const float* lab = label_plane(labels, p, h, b, c, HW);
     if (VEC) {
         const float4* o4 = (const float4*)out;
@@ -318,7 +341,7 @@ __global__ __launch_bounds__(NT) void loss_backward_kernel(HeadPtrs hp, const fl
 // ---- the gradient at the head sources: the adjoint of the on-the-fly upsampling ----------------------------------------------------
 // Every output pixel (y, x) has its taps i0 / i1 (lerp_index); the pixels that share (i0(y), i0(x)) = (a, b) form the INTERVAL (a, b)
 // of a source, and all of them read the same four source cells.  part: one thread per (interval, channel, frame, head) walks its
-// pixels row by row, x ascending -- e = (up - label) * f with src_value1's tap expression -- and leaves the four sums
+// pixels row by row, x ascending -- e = (tap - label) * f -- and leaves the four sums
 //     P[ry][rx] = sum_y l_ry(y) * sum_x l_rx(x) * e[y, x]           (r = 0: the pixel's weight on its first tap, 1: on its second)
 // in `scratch`; each label is read by exactly one thread.  fold: one thread per (cell, channel, frame, head) adds the up to nine
 // partial sums that name its cell -- intervals a = i - 1, i, within each b = j - 1, j, the second-tap sum before the first-tap one --
@@ -359,35 +382,13 @@ __global__ __launch_bounds__(NT) void loss_backward_src_part_kernel(SrcTable tab
     const int c = blockIdx.x / nblk, blk = blockIdx.x % nblk, b = blockIdx.y, h = blockIdx.z, t = threadIdx.x;
     const int HW = p.H * p.W;
     const float up = upstream[0];
-    if (c == NC) {                                             // root_d: zeros, then ONE thread adds the frame's rows in order
-        const Src s = tab.s[3 * h + 2];
+    if (c == NC) {
         const GradDst gd = gt.g[3 * h + 2];
-        if (blk != 0 || !gd.p) return;
-        float* g = gd.p + (int64_t)b * gd.frame;
-        const int cells = s.h * s.w;
-        for (int i = t; i < cells; i += NT) g[(int64_t)i * gd.pix] = 0.0f;
-        __syncthreads();                                       // the workgroup's own stores: visible to its thread 0 behind the barrier
-        if (t == 0) {
-            const int64_t base = ((int64_t)h * p.B + b) * p.R;
-            const bool same = s.h == p.H && s.w == p.W;
-            for (int r = 0; r < p.R; ++r) {
-                const int cell = root_cell[base + r];
-                if (cell < 0 || cell >= HW) continue;          // skipped, or outside the map: never dereferenced
-                const float v = root_fac[base + r] * up;
-                if (same) {
-                    g[(int64_t)cell * gd.pix] += v;
-                    continue;
-                }
-                const Lerp ly = lerp_index(cell / p.W, s.h, p.H), lx = lerp_index(cell % p.W, s.w, p.W);
-                g[((int64_t)ly.i0 * s.w + lx.i0) * gd.pix] += v * (ly.l0 * lx.l0);
-                g[((int64_t)ly.i0 * s.w + lx.i1) * gd.pix] += v * (ly.l0 * lx.l1);
-                g[((int64_t)ly.i1 * s.w + lx.i0) * gd.pix] += v * (ly.l1 * lx.l0);
-                g[((int64_t)ly.i1 * s.w + lx.i1) * gd.pix] += v * (ly.l1 * lx.l1);
-            }
-        }
+        if (blk == 0 && gd.p)
+            root_grad_plane<false>(gd.p + (int64_t)b * gd.frame, tab.s[3 * h + 2].h, tab.s[3 * h + 2].w, gd.pix, p, h, b, root_cell, root_fac, up, t);
         return;
     }
-    const int k = c < N2D ? 0 : 1, cc = k ? c - N2D : c, cn = k ? NDD : N2D;
+    const auto [k, cc, cn] = channel_of(c);
     const Src s = tab.s[3 * h + k];
     const GradDst gd = gt.g[3 * h + k];
     if (!gd.p) return;
@@ -396,7 +397,8 @@ __global__ __launch_bounds__(NT) void loss_backward_src_part_kernel(SrcTable tab
     const float* src = s.p + (int64_t)b * s.frame + (int64_t)cc * s.ch;
     if (s.h == p.H && s.w == p.W) {                            // the identity: g = e; zero weight or not selected: zeros, nothing read
         float* g = gd.p + (int64_t)b * gd.frame + (int64_t)cc * gd.ch;
-        for (int i = blk * NT + t; i < HW; i += nblk * NT) g[(int64_t)i * gd.pix] = f == 0.0f ? 0.0f : (src[(int64_t)i * s.pix] - lab[i]) * f;
+        if (f == 0.0f) zero_plane<false>(g, HW, gd.pix, blk * NT + t, nblk * NT);
+        else for (int i = blk * NT + t; i < HW; i += nblk * NT) g[(int64_t)i * gd.pix] = (src[(int64_t)i * s.pix] - lab[i]) * f;
         return;
     }
     const int idx = blk * NT + t;
@@ -414,8 +416,7 @@ __global__ __launch_bounds__(NT) void loss_backward_src_part_kernel(SrcTable tab
         float r0 = 0.0f, r1 = 0.0f;
         for (int x = x0; x < x1; ++x) {
             const Lerp lx = lerp_index(x, s.w, p.W);
-            const float u = ly.l0 * (lx.l0 * v00 + lx.l1 * v01) + ly.l1 * (lx.l0 * v10 + lx.l1 * v11);      // src_value1's expression
-            const float e = (u - row[x]) * f;
+            const float e = (tap(ly, lx, v00, v01, v10, v11) - row[x]) * f;
             r0 += lx.l0 * e;
             r1 += lx.l1 * e;
         }
@@ -434,7 +435,7 @@ __global__ __launch_bounds__(NT) void loss_backward_src_fold_kernel(SrcTable tab
                                                                      int nblk)
 {
     const int c = blockIdx.x / nblk, blk = blockIdx.x % nblk, b = blockIdx.y, h = blockIdx.z, t = threadIdx.x;
-    const int k = c < N2D ? 0 : 1, cc = k ? c - N2D : c, cn = k ? NDD : N2D;
+    const auto [k, cc, cn] = channel_of(c);
     const Src s = tab.s[3 * h + k];
     const GradDst gd = gt.g[3 * h + k];
     const int idx = blk * NT + t;
@@ -460,20 +461,7 @@ __global__ __launch_bounds__(NT) void loss_backward_src_fold_kernel(SrcTable tab
 // ---- host side -----------------------------------------------------------------------------------------------------------------
 Params make_params(int stage_num, int ohkm, int topk, int ctf, int single, int B, int S, int R, int H, int W)
 {
-    Params p{};
-    p.stage_num = stage_num;
-    p.n_heads = single ? 1 : 4 * stage_num;
-    p.ohkm = ohkm ? 1 : 0;
-    p.topk = topk;
-    p.ctf = ctf ? 1 : 0;
-    p.single = single ? 1 : 0;
-    p.B = B;
-    p.S = S;
-    p.R = R;
-    p.H = H;
-    p.W = W;
-    p.has_hm = p.has_dd = p.has_rd = 1;
-    return p;
+    return Params{single ? 1 : 4 * stage_num, stage_num, ohkm ? 1 : 0, topk, ctf ? 1 : 0, single ? 1 : 0, B, S, R, H, W, 1, 1, 1};
 }
 
 // the heads of a launch: all three tensors of every head, or in single-head mode at least one; labels where a map is compared with them
@@ -497,7 +485,36 @@ int take_heads(const void* const* heads, Params& p, HeadPtrs& hp, const float* l
 
 // smap_loss_forward_src's workspace: the layout above, then partial [n_heads][B][chunks][57] f64
 int src_chunks(int H, int W) { return (H * W + SRC_CHUNK - 1) / SRC_CHUNK; }
-int64_t src_partial_offset(int n_heads, int B, int R) { return workspace_layout(n_heads, B, R).bytes; }
+int64_t src_partial_bytes(int n_heads, int B, int H, int W) { return (int64_t)n_heads * B * src_chunks(H, W) * NC * 8; }
+
+// what every launching entry point begins with: the parameters, and the workspace -- given, 8-byte aligned, the layout (and the
+// partial sums behind it) in size
+struct Call { Params p; Workspace w; char* ws; };
+int begin_call(Call& c, int stage_num, int ohkm, int topk, int ctf, int single, int B, int S, int R, int H, int W, const void* workspace,
+               int64_t workspace_bytes, bool partials = false)
+{
+    c.p = make_params(stage_num, ohkm, topk, ctf, single, B, S, R, H, W);
+    if (check_params(c.p) || !workspace || ((uintptr_t)workspace & 7)) return SMAP_E_ARG;
+    c.w = workspace_layout(c.p.n_heads, B, R);
+    c.ws = (char*)workspace;
+    return workspace_bytes < c.w.bytes + (partials ? src_partial_bytes(c.p.n_heads, B, H, W) : 0) ? SMAP_E_ARG : 0;
+}
+
+// the VEC instantiation of a kernel where every plane is 16-byte aligned and a multiple of four floats, its scalar twin otherwise
+template <class... P, class... A>
+void launch_planes(bool vec, void (*vec_kernel)(P...), void (*scalar_kernel)(P...), dim3 grid, void* stream, A... args)
+{
+    hipLaunchKernelGGL(vec ? vec_kernel : scalar_kernel, grid, dim3(NT), 0, (hipStream_t)stream, args...);
+}
+
+int launch_finish(const Call& c, const float* valids, const float* rdepth, float* result, void* stream)
+{
+    if (hipError_t e = hipGetLastError(); e != hipSuccess) return hip_rc(e);     // of the reduction launched just before
+    hipLaunchKernelGGL(loss_finish_kernel, dim3(1), dim3(FINISH_NT), 0, (hipStream_t)stream, c.p, valids, rdepth, c.ws, result);
+    return hip_rc(hipGetLastError());
+}
+
+int tensor_channels(int i) { return i % 3 == 0 ? N2D : (i % 3 == 1 ? NDD : 1); }      // of tensor i of the 3 * n_heads
 
 // a descriptor of c channels under an H x W output, as the kernels take it; 0 or SMAP_E_ARG
 int take_src(const smap_head_src& s, int c, int H, int W, Src& out)
@@ -511,6 +528,14 @@ int take_src(const smap_head_src& s, int c, int H, int W, Src& out)
     const bool nchw = s.pix_stride == 1 && s.ch_stride >= px && s.frame_stride >= (int64_t)c * s.ch_stride;
     if (!nhwc && !nchw) return SMAP_E_ARG;
     out = Src{s.ptr, s.h, s.w, s.pix_stride, s.ch_stride, (long long)s.frame_stride};
+    return 0;
+}
+// smap_head_src[3 * n_heads] as the kernels take it; 0 or SMAP_E_ARG
+int take_sources(const smap_head_src* sources, const Params& p, SrcTable& tab)
+{
+    if (!sources) return SMAP_E_ARG;
+    for (int i = 0; i < 3 * p.n_heads; ++i)
+        if (take_src(sources[i], tensor_channels(i), p.H, p.W, tab.s[i])) return SMAP_E_ARG;
     return 0;
 }
 
@@ -531,80 +556,59 @@ int smap_loss_forward(const void* const* heads, const float* labels, const float
                       int topk, int ctf, int single, int B, int S, int R, int H, int W, void* workspace, int64_t workspace_bytes,
                       float* result, void* stream)
 {
-    Params p = make_params(stage_num, ohkm, topk, ctf, single, B, S, R, H, W);
-    if (check_params(p) || !workspace || !result || ((uintptr_t)workspace & 7)) return SMAP_E_ARG;
+    Call c;
+    if (begin_call(c, stage_num, ohkm, topk, ctf, single, B, S, R, H, W, workspace, workspace_bytes) || !result) return SMAP_E_ARG;
+    Params& p = c.p;
     HeadPtrs hp;
     bool aligned;
     if (take_heads(heads, p, hp, labels, aligned)) return SMAP_E_ARG;
     if (((p.has_hm || p.has_dd) && !valids) || !rdepth) return SMAP_E_ARG;       // the forward pass alone reads these two
-    const Workspace w = workspace_layout(p.n_heads, B, R);
-    if (workspace_bytes < w.bytes) return SMAP_E_ARG;
-    char* ws = (char*)workspace;
-    const dim3 grid(NC + 1, (unsigned)B, (unsigned)p.n_heads);
-    if (aligned && (H * W) % 4 == 0)
-        hipLaunchKernelGGL(loss_reduce_kernel<true>, grid, dim3(NT), 0, (hipStream_t)stream, hp, labels, rdepth, p, (double*)(ws + w.sums),
-                           (float*)(ws + w.rd_at), (int32_t*)(ws + w.root_cell));
-    else
-        hipLaunchKernelGGL(loss_reduce_kernel<false>, grid, dim3(NT), 0, (hipStream_t)stream, hp, labels, rdepth, p, (double*)(ws + w.sums),
-                           (float*)(ws + w.rd_at), (int32_t*)(ws + w.root_cell));
-    if (hipError_t e = hipGetLastError(); e != hipSuccess) return hip_rc(e);
-    hipLaunchKernelGGL(loss_finish_kernel, dim3(1), dim3(FINISH_NT), 0, (hipStream_t)stream, p, valids, rdepth, ws, result);
-    return hip_rc(hipGetLastError());
+    launch_planes(aligned && (H * W) % 4 == 0, loss_reduce_kernel<true>, loss_reduce_kernel<false>,
+                  dim3(NC + 1, (unsigned)B, (unsigned)p.n_heads), stream, hp, labels, rdepth, p, (double*)(c.ws + c.w.sums),
+                  (float*)(c.ws + c.w.rd_at), (int32_t*)(c.ws + c.w.root_cell));
+    return launch_finish(c, valids, rdepth, result, stream);
 }
 
 int smap_sizeof_head_src(void) { return (int)sizeof(smap_head_src); }
 
 int64_t smap_loss_src_workspace_bytes(int n_heads, int B, int R, int H, int W)
 {
-    if (n_heads < 1 || n_heads > MAX_HEADS || B < 1 || B > 65535 || R < 1 || R > 65535 || H < 1 || W < 1 || (int64_t)H * W > (1 << 24))
-        return SMAP_E_ARG;
-    return src_partial_offset(n_heads, B, R) + (int64_t)n_heads * B * src_chunks(H, W) * NC * 8;
+    const int64_t layout = smap_loss_workspace_bytes(n_heads, B, R);
+    if (layout < 0 || H < 1 || W < 1 || (int64_t)H * W > (1 << 24)) return SMAP_E_ARG;
+    return layout + src_partial_bytes(n_heads, B, H, W);
 }
 
 int smap_loss_forward_src(const smap_head_src* sources, const float* labels, const float* valids, const float* rdepth, int stage_num,
                           int ohkm, int topk, int ctf, int B, int S, int R, int H, int W, void* workspace, int64_t workspace_bytes,
                           float* result, void* stream)
 {
-    Params p = make_params(stage_num, ohkm, topk, ctf, 0, B, S, R, H, W);
-    if (check_params(p) || !sources || !labels || !valids || !rdepth || !workspace || !result || ((uintptr_t)workspace & 7))
+    Call c;
+    if (begin_call(c, stage_num, ohkm, topk, ctf, 0, B, S, R, H, W, workspace, workspace_bytes, true) || !labels || !valids || !rdepth || !result)
         return SMAP_E_ARG;
+    const Params& p = c.p;
     SrcTable tab{};
-    for (int i = 0; i < 3 * p.n_heads; ++i)
-        if (take_src(sources[i], i % 3 == 0 ? N2D : (i % 3 == 1 ? NDD : 1), H, W, tab.s[i])) return SMAP_E_ARG;
-    const Workspace w = workspace_layout(p.n_heads, B, R);
+    if (take_sources(sources, p, tab)) return SMAP_E_ARG;
     const int chunks = src_chunks(H, W);
-    if (workspace_bytes < smap_loss_src_workspace_bytes(p.n_heads, B, R, H, W)) return SMAP_E_ARG;
-    char* ws = (char*)workspace;
-    double* partial = (double*)(ws + src_partial_offset(p.n_heads, B, R));
+    double* partial = (double*)(c.ws + c.w.bytes);
     hipLaunchKernelGGL(loss_reduce_src_kernel, dim3((unsigned)chunks, (unsigned)B, (unsigned)p.n_heads), dim3(NT), 0, (hipStream_t)stream, tab,
                        labels, p, partial);
     if (hipError_t e = hipGetLastError(); e != hipSuccess) return hip_rc(e);
     hipLaunchKernelGGL(loss_fold_src_kernel, dim3((unsigned)B, (unsigned)p.n_heads), dim3(64), 0, (hipStream_t)stream, tab, rdepth, p, partial,
-                       chunks, (double*)(ws + w.sums), (float*)(ws + w.rd_at), (int32_t*)(ws + w.root_cell));
-    if (hipError_t e = hipGetLastError(); e != hipSuccess) return hip_rc(e);
-    hipLaunchKernelGGL(loss_finish_kernel, dim3(1), dim3(FINISH_NT), 0, (hipStream_t)stream, p, valids, rdepth, ws, result);
-    return hip_rc(hipGetLastError());
+                       chunks, (double*)(c.ws + c.w.sums), (float*)(c.ws + c.w.rd_at), (int32_t*)(c.ws + c.w.root_cell));
+    return launch_finish(c, valids, rdepth, result, stream);
 }
 
 int smap_loss_backward(const void* const* heads, const float* labels, int stage_num, int ohkm, int topk, int ctf, int single, int B, int S,
                        int R, int H, int W, const void* workspace, int64_t workspace_bytes, const float* upstream, float* grad, void* stream)
 {
-    Params p = make_params(stage_num, ohkm, topk, ctf, single, B, S, R, H, W);
-    if (check_params(p) || !workspace || !upstream || !grad || ((uintptr_t)workspace & 7)) return SMAP_E_ARG;
+    Call c;
+    if (begin_call(c, stage_num, ohkm, topk, ctf, single, B, S, R, H, W, workspace, workspace_bytes) || !upstream || !grad) return SMAP_E_ARG;
     HeadPtrs hp;
     bool aligned;
-    if (take_heads(heads, p, hp, labels, aligned)) return SMAP_E_ARG;            // valids and rdepth: the workspace's tables hold them
-    if ((uintptr_t)grad & 15) aligned = false;
-    const Workspace w = workspace_layout(p.n_heads, B, R);
-    if (workspace_bytes < w.bytes) return SMAP_E_ARG;
-    const char* ws = (const char*)workspace;
-    const dim3 grid(GRAD_C, (unsigned)B, (unsigned)p.n_heads);
-    if (aligned && (H * W) % 4 == 0)
-        hipLaunchKernelGGL(loss_backward_kernel<true>, grid, dim3(NT), 0, (hipStream_t)stream, hp, labels, p, (const float*)(ws + w.coef),
-                           (const int32_t*)(ws + w.root_cell), (const float*)(ws + w.root_fac), upstream, grad);
-    else
-        hipLaunchKernelGGL(loss_backward_kernel<false>, grid, dim3(NT), 0, (hipStream_t)stream, hp, labels, p, (const float*)(ws + w.coef),
-                           (const int32_t*)(ws + w.root_cell), (const float*)(ws + w.root_fac), upstream, grad);
+    if (take_heads(heads, c.p, hp, labels, aligned)) return SMAP_E_ARG;          // valids and rdepth: the workspace's tables hold them
+    launch_planes(aligned && !((uintptr_t)grad & 15) && (H * W) % 4 == 0, loss_backward_kernel<true>, loss_backward_kernel<false>,
+                  dim3(GRAD_C, (unsigned)B, (unsigned)c.p.n_heads), stream, hp, labels, c.p, (const float*)(c.ws + c.w.coef),
+                  (const int32_t*)(c.ws + c.w.root_cell), (const float*)(c.ws + c.w.root_fac), upstream, grad);
     return hip_rc(hipGetLastError());
 }
 
@@ -615,7 +619,7 @@ int64_t smap_loss_backward_src_scratch_bytes(const smap_head_src* sources, int n
     for (int i = 0; i < 3 * n_heads; ++i) {
         const smap_head_src& s = sources[i];
         if (s.h < 1 || s.w < 1 || (int64_t)s.h * s.w > (1 << 24)) return SMAP_E_ARG;
-        if (i % 3 < 2) floats += part_floats(s.h, s.w, i % 3 ? NDD : N2D, B);
+        if (i % 3 < 2) floats += part_floats(s.h, s.w, tensor_channels(i), B);
     }
     return floats * 4;
 }
@@ -624,21 +628,21 @@ int smap_loss_backward_src(const smap_head_src* sources, const smap_head_src* gr
                            int ctf, int B, int S, int R, int H, int W, const void* workspace, int64_t workspace_bytes, void* scratch,
                            int64_t scratch_bytes, const float* upstream, void* stream)
 {
-    Params p = make_params(stage_num, ohkm, topk, ctf, 0, B, S, R, H, W);
-    if (check_params(p) || !sources || !grads || !labels || !workspace || !upstream || ((uintptr_t)workspace & 7) || ((uintptr_t)scratch & 15))
+    Call call;
+    if (begin_call(call, stage_num, ohkm, topk, ctf, 0, B, S, R, H, W, workspace, workspace_bytes) || !grads || !labels || !upstream ||
+        ((uintptr_t)scratch & 15))
         return SMAP_E_ARG;
-    if (workspace_bytes < workspace_layout(p.n_heads, B, R).bytes) return SMAP_E_ARG;
+    const Params& p = call.p;
     SrcTable tab{};
+    if (take_sources(sources, p, tab)) return SMAP_E_ARG;
     GradTable gt{};
     int64_t floats = 0;
     int nblk_part = 1, nblk_fold = 0;
     for (int i = 0; i < 3 * p.n_heads; ++i) {
-        const int c = i % 3 == 0 ? N2D : (i % 3 == 1 ? NDD : 1);
-        if (take_src(sources[i], c, H, W, tab.s[i])) return SMAP_E_ARG;
         const smap_head_src& g = grads[i];
         if (!g.ptr) continue;                                   // not wanted: gt.g[i].p stays null
         Src dst;
-        if (g.h != sources[i].h || g.w != sources[i].w || take_src(g, c, H, W, dst)) return SMAP_E_ARG;
+        if (g.h != sources[i].h || g.w != sources[i].w || take_src(g, tensor_channels(i), H, W, dst)) return SMAP_E_ARG;
         gt.g[i] = GradDst{const_cast<float*>(g.ptr), g.pix_stride, g.ch_stride, (long long)g.frame_stride};
         if (i % 3 == 2) continue;
         const int64_t cells = (int64_t)g.h * g.w;
@@ -646,18 +650,16 @@ int smap_loss_backward_src(const smap_head_src* sources, const smap_head_src* gr
             nblk_part = max(nblk_part, (int)((cells + 4 * NT - 1) / (4 * NT)));
         } else {
             gt.part[2 * (i / 3) + i % 3] = floats;
-            floats += part_floats(g.h, g.w, c, B);
+            floats += part_floats(g.h, g.w, tensor_channels(i), B);
             nblk_part = max(nblk_part, (int)((cells + NT - 1) / NT));
             nblk_fold = max(nblk_fold, (int)((cells + NT - 1) / NT));
         }
     }
     if (floats && (!scratch || scratch_bytes < floats * 4)) return SMAP_E_ARG;
-    const Workspace w = workspace_layout(p.n_heads, B, R);
-    const char* ws = (const char*)workspace;
-    const float* coef = (const float*)(ws + w.coef);
+    const float* coef = (const float*)(call.ws + call.w.coef);
     hipLaunchKernelGGL(loss_backward_src_part_kernel, dim3((unsigned)(GRAD_C * nblk_part), (unsigned)B, (unsigned)p.n_heads), dim3(NT), 0,
-                       (hipStream_t)stream, tab, gt, labels, p, coef, (const int32_t*)(ws + w.root_cell), (const float*)(ws + w.root_fac),
-                       upstream, (float*)scratch, nblk_part);
+                       (hipStream_t)stream, tab, gt, labels, p, coef, (const int32_t*)(call.ws + call.w.root_cell),
+                       (const float*)(call.ws + call.w.root_fac), upstream, (float*)scratch, nblk_part);
     if (hipError_t e = hipGetLastError(); e != hipSuccess) return hip_rc(e);
     if (!nblk_fold) return 0;
     hipLaunchKernelGGL(loss_backward_src_fold_kernel, dim3((unsigned)(NC * nblk_fold), (unsigned)B, (unsigned)p.n_heads), dim3(NT), 0,

@@ -76,6 +76,12 @@ def _ptr(t):
     return None if t is None else t.data_ptr()
 
 
+def result_dict(result, logged=None):
+    """The reference's dict of a result [8]; logged: where the three logging values come from (SMAPLoss: the detached result)."""
+    logged = result if logged is None else logged
+    return dict(total_loss=result[0], loss_2d=logged[1], loss_bone=logged[2], loss_root=logged[3])
+
+
 def _head_array(tensors):
     return (C.c_void_p * len(tensors))(*[_ptr(t) for t in tensors])
 
@@ -99,7 +105,7 @@ SOURCE_KEYS = (("heatmap_2d", N2D), ("det_d", NDD), ("root_d", 1))
 
 def source_workspace_bytes(n_heads, B, R, H, W):
     """Bytes of smap_loss_forward_src's workspace: workspace_layout, then the per-chunk partial sums (csrc/loss.hip)."""
-    return workspace_layout(n_heads, B, R)["bytes"] + n_heads * B * ((H * W + 255) // 256) * NC * 8
+    return L.load().smap_loss_src_workspace_bytes(n_heads, B, R, H, W)
 
 
 def forward_from_sources(cfg, sources, labels, valids, rdepth):
@@ -107,15 +113,9 @@ def forward_from_sources(cfg, sources, labels, valids, rdepth):
     {"heatmap_2d", "det_d", "root_d": (ptr, h, w, c, pix_stride, ch_stride, frame_stride)} (engine.HeadSource), strides in floats;
     labels, valids, rdepth: checked device tensors.  No synchronisation, no graph."""
     dev = rdepth.device
-    if cfg.single or len(sources) != cfg.n_heads:
-        raise ValueError("sources: %d heads for %d stages of 4" % (len(sources), cfg.stage_num))
-    arr = (L.HeadSrc * (3 * cfg.n_heads))()
-    for h, d in enumerate(sources):
-        for k, (key, _) in enumerate(SOURCE_KEYS):
-            ptr, sh, sw, c, pix, ch, frame = d[key]
-            arr[3 * h + k] = L.HeadSrc(int(ptr), int(sh), int(sw), int(c), int(pix), int(ch), 0, int(frame))
+    arr = _source_array(cfg, sources, "sources")
     bytes_ = source_workspace_bytes(cfg.n_heads, cfg.B, cfg.R, cfg.H, cfg.W)
-    ws = torch.empty((bytes_,), dtype=torch.uint8, device=dev)
+    ws = torch.empty((max(bytes_, 0),), dtype=torch.uint8, device=dev)      # (negative: sizes the library refuses below)
     result = torch.empty((8,), dtype=torch.float32, device=dev)
     with torch.cuda.device(dev):
         L.check(L.load().smap_loss_forward_src(arr, _ptr(labels), _ptr(valids), _ptr(rdepth), cfg.stage_num, cfg.ohkm, cfg.topk, cfg.ctf,
@@ -224,6 +224,68 @@ def _valids_2d(valids, B, what="valids"):
     return _device_fp32(valids, what, (B, NC))
 
 
+def _on_device(t, dev, what="another"):
+    if t.device != dev:
+        raise ValueError("all tensors live on one GPU: labels on %s, %s on %s" % (dev, what, t.device))
+    return t
+
+
+def _rdepth_rows(rdepth, B):
+    rdepth = _device_fp32(rdepth, "rdepth")
+    if rdepth.dim() != 3 or rdepth.shape[0] != B or rdepth.shape[2] != 3 or rdepth.shape[1] < 1:
+        raise ValueError("rdepth: expected [%d, R >= 1, 3], got %s" % (B, tuple(rdepth.shape)))
+    return rdepth
+
+
+def _settings(stage_num, ohkm, topk, ctf):
+    """(stage_num, ohkm, topk, ctf) of a criterion, checked."""
+    stage_num, ohkm, topk, ctf = int(stage_num), bool(ohkm), int(topk), bool(ctf)
+    if not 1 <= stage_num <= 4:
+        raise ValueError("stage_num is 1 to 4, got %d" % stage_num)
+    if ohkm and not 1 <= topk <= NDD:
+        raise ValueError("topk is 1 to %d with ohkm, got %d" % (NDD, topk))
+    return stage_num, ohkm, topk, ctf
+
+
+def _check_inputs(crit, valids, labels, rdepth):
+    """(_Config, labels, valids, rdepth) of checked inputs: the rules every criterion (its stage_num, ohkm, topk, ctf) shares."""
+    labels = _device_fp32(labels, "labels")
+    if labels.dim() != 5 or labels.shape[2] != NC or labels.shape[1] < 4 + int(crit.ctf):
+        raise ValueError("labels: expected [B, S >= %d, 57, H, W], got %s" % (4 + int(crit.ctf), tuple(labels.shape)))
+    B, S, _, H, W = labels.shape
+    valids, rdepth = _valids_2d(valids, B), _rdepth_rows(rdepth, B)
+    _on_device(valids, labels.device), _on_device(rdepth, labels.device)
+    return _Config(crit.stage_num, crit.ohkm, crit.topk, crit.ctf, 0, B, S, rdepth.shape[1], H, W), labels, valids, rdepth
+
+
+def _upsampled(t, what, ch, cfg, dev):
+    """The shape rule of SMAPLoss: exactly (B, ch, H, W)."""
+    return _on_device(_device_fp32(t, what, (cfg.B, ch, cfg.H, cfg.W)), dev)
+
+
+def _native(t, what, ch, cfg, dev):
+    """The shape rule of SMAPLossNative: (B, ch, h <= H, w <= W)."""
+    t = _device_fp32(t, what)
+    if t.dim() != 4 or tuple(t.shape[:2]) != (cfg.B, ch) or not (1 <= t.shape[2] <= cfg.H and 1 <= t.shape[3] <= cfg.W):
+        raise ValueError("%s: expected [%d, %d, h <= %d, w <= %d], got %s" % (what, cfg.B, ch, cfg.H, cfg.W, tuple(t.shape)))
+    return _on_device(t, dev, what)
+
+
+def _head_tensors(outputs, cfg, dev, rule):
+    """outputs[key][i][j] of every head in the library's order, each through the shape rule."""
+    tensors = []
+    for i in range(cfg.stage_num):
+        for j in range(4):
+            for key, ch in SOURCE_KEYS:
+                what = "outputs['%s'][%d][%d]" % (key, i, j)
+                try:
+                    t = outputs[key][i][j]
+                except (KeyError, IndexError, TypeError):
+                    raise ValueError("%s is missing: %d stages of 4 heads each" % (what, cfg.stage_num))
+                tensors.append(rule(t, what, ch, cfg, dev))
+    return tensors
+
+
 class SMAPLoss:
     """SMAP._calculate_loss on the GPU.
 
@@ -235,50 +297,28 @@ class SMAPLoss:
     SMAP.forward collects); valids [B, 57, 1] or [B, 57]; labels [B, S, 57, H, W] with S >= 4 + ctf; rdepth [B, R, 3].  All fp32 on one
     GPU.  Returns {'total_loss', 'loss_2d', 'loss_bone', 'loss_root'}: 0-d fp32 tensors, the last three detached."""
 
+    _function, _shape_rule = _LossFunction, staticmethod(_upsampled)      # what a subclass replaces
+
     def __init__(self, stage_num=3, ohkm=True, topk=8, ctf=True, strict=False):
-        self.stage_num, self.ohkm, self.topk, self.ctf, self.strict = int(stage_num), bool(ohkm), int(topk), bool(ctf), bool(strict)
-        if not 1 <= self.stage_num <= 4:
-            raise ValueError("stage_num is 1 to 4, got %d" % self.stage_num)
-        if self.ohkm and not 1 <= self.topk <= NDD:
-            raise ValueError("topk is 1 to %d with ohkm, got %d" % (NDD, self.topk))
+        self.stage_num, self.ohkm, self.topk, self.ctf = _settings(stage_num, ohkm, topk, ctf)
+        self.strict = bool(strict)
 
     @classmethod
     def from_cfg(cls, cfg, strict=False):
         return cls(cfg.MODEL.STAGE_NUM, cfg.LOSS.OHKM, cfg.LOSS.TOPK, cfg.LOSS.COARSE_TO_FINE, strict)
 
     def _check(self, outputs, valids, labels, rdepth):
-        labels = _device_fp32(labels, "labels")
-        if labels.dim() != 5 or labels.shape[2] != NC or labels.shape[1] < 4 + int(self.ctf):
-            raise ValueError("labels: expected [B, S >= %d, 57, H, W], got %s" % (4 + int(self.ctf), tuple(labels.shape)))
-        B, S, _, H, W = labels.shape
-        valids = _valids_2d(valids, B)
-        rdepth = _device_fp32(rdepth, "rdepth")
-        if rdepth.dim() != 3 or rdepth.shape[0] != B or rdepth.shape[2] != 3 or rdepth.shape[1] < 1:
-            raise ValueError("rdepth: expected [%d, R >= 1, 3], got %s" % (B, tuple(rdepth.shape)))
-        tensors = []
-        for i in range(self.stage_num):
-            for j in range(4):
-                for key, ch in (("heatmap_2d", N2D), ("det_d", NDD), ("root_d", 1)):
-                    what = "outputs['%s'][%d][%d]" % (key, i, j)
-                    try:
-                        t = outputs[key][i][j]
-                    except (KeyError, IndexError, TypeError):
-                        raise ValueError("%s is missing: %d stages of 4 heads each" % (what, self.stage_num))
-                    tensors.append(_device_fp32(t, what, (B, ch, H, W)))
-        for t in tensors + [valids, rdepth]:
-            if t.device != labels.device:
-                raise ValueError("all tensors live on one GPU: labels on %s, another on %s" % (labels.device, t.device))
-        return _Config(self.stage_num, self.ohkm, self.topk, self.ctf, 0, B, S, rdepth.shape[1], H, W), tensors, labels, valids, rdepth
+        cfg, labels, valids, rdepth = _check_inputs(self, valids, labels, rdepth)
+        return cfg, _head_tensors(outputs, cfg, labels.device, self._shape_rule), labels, valids, rdepth
 
     def __call__(self, outputs, valids, labels, rdepth):
         cfg, tensors, labels, valids, rdepth = self._check(outputs, valids, labels, rdepth)
-        result = _LossFunction.apply(cfg, labels, valids, rdepth, *tensors)
+        result = self._function.apply(cfg, labels, valids, rdepth, *tensors)
         if self.strict:
             bad = int(result[4].item())                       # the one synchronisation of strict mode
             if bad:
                 raise ValueError("rdepth: %d row(s) with Z > 0 lie outside the %d x %d map" % (bad, cfg.H, cfg.W))
-        logged = result.detach()
-        return dict(total_loss=result[0], loss_2d=logged[1], loss_bone=logged[2], loss_root=logged[3])
+        return result_dict(result, result.detach())
 
     forward = __call__
 
@@ -329,36 +369,7 @@ class SMAPLossNative(SMAPLoss):
     tensor is written in either direction, the gradients arrive at the tensors' own resolutions in a fixed summation order (the same bits
     run to run).  Call signature, returned dict, `strict` and the differences from the reference are SMAPLoss's."""
 
-    def _check(self, outputs, valids, labels, rdepth):
-        cfg, labels, valids, rdepth = EngineLoss(self.stage_num, self.ohkm, self.topk, self.ctf).check(valids, labels, rdepth)
-        tensors = []
-        for i in range(self.stage_num):
-            for j in range(4):
-                for key, ch in SOURCE_KEYS:
-                    what = "outputs['%s'][%d][%d]" % (key, i, j)
-                    try:
-                        t = outputs[key][i][j]
-                    except (KeyError, IndexError, TypeError):
-                        raise ValueError("%s is missing: %d stages of 4 heads each" % (what, self.stage_num))
-                    t = _device_fp32(t, what)
-                    if t.dim() != 4 or tuple(t.shape[:2]) != (cfg.B, ch) or not (1 <= t.shape[2] <= cfg.H and 1 <= t.shape[3] <= cfg.W):
-                        raise ValueError("%s: expected [%d, %d, h <= %d, w <= %d], got %s" % (what, cfg.B, ch, cfg.H, cfg.W, tuple(t.shape)))
-                    if t.device != labels.device:
-                        raise ValueError("all tensors live on one GPU: labels on %s, %s on %s" % (labels.device, what, t.device))
-                    tensors.append(t)
-        return cfg, tensors, labels, valids, rdepth
-
-    def __call__(self, outputs, valids, labels, rdepth):
-        cfg, tensors, labels, valids, rdepth = self._check(outputs, valids, labels, rdepth)
-        result = _NativeLossFunction.apply(cfg, labels, valids, rdepth, *tensors)
-        if self.strict:
-            bad = int(result[4].item())                       # the one synchronisation of strict mode
-            if bad:
-                raise ValueError("rdepth: %d row(s) with Z > 0 lie outside the %d x %d map" % (bad, cfg.H, cfg.W))
-        logged = result.detach()
-        return dict(total_loss=result[0], loss_2d=logged[1], loss_bone=logged[2], loss_root=logged[3])
-
-    forward = __call__
+    _function, _shape_rule = _NativeLossFunction, staticmethod(_native)
 
 
 class EngineLoss:
@@ -373,7 +384,7 @@ class EngineLoss:
     grad_fn.  Runs on the current stream behind whatever wrote the sources; no synchronisation."""
 
     def __init__(self, stage_num=3, ohkm=True, topk=8, ctf=True):
-        self._rules = SMAPLoss(stage_num, ohkm, topk, ctf)
+        self.stage_num, self.ohkm, self.topk, self.ctf = _settings(stage_num, ohkm, topk, ctf)
 
     @classmethod
     def from_cfg(cls, cfg):
@@ -381,19 +392,7 @@ class EngineLoss:
 
     def check(self, valids, labels, rdepth):
         """(_Config, labels, valids, rdepth) of checked inputs: SMAPLoss's rules."""
-        r = self._rules
-        labels = _device_fp32(labels, "labels")
-        if labels.dim() != 5 or labels.shape[2] != NC or labels.shape[1] < 4 + int(r.ctf):
-            raise ValueError("labels: expected [B, S >= %d, 57, H, W], got %s" % (4 + int(r.ctf), tuple(labels.shape)))
-        B, S, _, H, W = labels.shape
-        valids = _valids_2d(valids, B)
-        rdepth = _device_fp32(rdepth, "rdepth")
-        if rdepth.dim() != 3 or rdepth.shape[0] != B or rdepth.shape[2] != 3 or rdepth.shape[1] < 1:
-            raise ValueError("rdepth: expected [%d, R >= 1, 3], got %s" % (B, tuple(rdepth.shape)))
-        for t in (valids, rdepth):
-            if t.device != labels.device:
-                raise ValueError("all tensors live on one GPU: labels on %s, another on %s" % (labels.device, t.device))
-        return _Config(r.stage_num, r.ohkm, r.topk, r.ctf, 0, B, S, rdepth.shape[1], H, W), labels, valids, rdepth
+        return _check_inputs(self, valids, labels, rdepth)
 
     def raw(self, sources, valids, labels, rdepth):
         """(result [8], workspace): result[4] counts the rows with Z > 0 outside the map (total_loss is NaN then)."""
@@ -403,7 +402,7 @@ class EngineLoss:
     def __call__(self, sources, valids, labels, rdepth):
         with torch.no_grad():
             result, _ = self.raw(sources, valids, labels, rdepth)
-        return dict(total_loss=result[0], loss_2d=result[1], loss_bone=result[2], loss_root=result[3])
+        return result_dict(result)
 
     def value_and_grad(self, sources, valids, labels, rdepth, upstream=None):
         """(losses, grads): the dict of __call__ and d (total_loss * upstream) / d source for every head tensor, at its own resolution --
@@ -433,7 +432,7 @@ class EngineLoss:
                 grads.append(g)
                 desc.append(gd)
             backward_to_sources(cfg, sources, desc, labels, ws, upstream)
-        return dict(total_loss=result[0], loss_2d=result[1], loss_bone=result[2], loss_root=result[3]), grads
+        return result_dict(result), grads
 
 
 class ValidationLoss:
@@ -521,8 +520,6 @@ def single_head_loss(hm=None, dd=None, rd=None, labels=None, valids=None, rdepth
         labels = valids = None
     if rdepth is None:
         rdepth = torch.zeros((B, 1, 3), dtype=torch.float32, device=given[0].device)
-    rdepth = _device_fp32(rdepth, "rdepth")
-    if rdepth.dim() != 3 or rdepth.shape[0] != B or rdepth.shape[2] != 3 or rdepth.shape[1] < 1:
-        raise ValueError("rdepth: expected [%d, R >= 1, 3], got %s" % (B, tuple(rdepth.shape)))
+    rdepth = _rdepth_rows(rdepth, B)
     cfg = _Config(1, ohkm, topk, False, 1, B, S, rdepth.shape[1], H, W)
     return _LossFunction.apply(cfg, labels, valids, rdepth, *tensors)

@@ -181,32 +181,10 @@ class SMAP(nn.Module):
             eng.raise_if_nonfinite(out)
         return res
 
-    def _loss(self, imgs, valids, labels, rdepth):
-        """The loss branch of the reference's forward (smap.py:355-401, :403-415) in eval mode: the all-heads schedule, then
-        smap_loss_forward_src on the heads where the engine left them -- both on the current stream, no synchronisation.  Returns
-        dict(total_loss, loss_2d, loss_bone, loss_root) of 0-d device tensors without grad_fn."""
-        from ..loss import EngineLoss
-        if valids is None or labels is None or rdepth is None:
-            raise ValueError("the loss needs valids [B,57(,1)], labels [B,S,57,H,W] and rdepth [B,R,3] (as smap_amd.loss.SMAPLoss takes them)")
-        B, _, H, W = imgs.shape
-        crit = EngineLoss(self.stage_num, self.ohkm, self.topk, self.ctf)
-        cfg, labels, valids, rdepth = crit.check(valids, labels, rdepth)
-        if (cfg.B, cfg.H, cfg.W) != (B, H // 4, W // 4) or labels.device != imgs.device:
-            raise ValueError(f"labels must be [{B},S,57,{H // 4},{W // 4}] on {imgs.device}, got {tuple(labels.shape)} on {labels.device}")
-        eng = self.engine(B, H, W, imgs.device, all_heads=True)
-        out = eng.new_output()                             # (the finest root-depth map may be read from it: kept until the loss has run)
-        eng.run(imgs.float(), out=out)
-        from ..loss import forward_from_sources
-        with torch.no_grad():
-            result, _ = forward_from_sources(cfg, eng.head_sources(out), labels, valids, rdepth)
-        if os.environ.get("SMAP_CHECK_FINITE"):
-            eng.raise_if_nonfinite(out)
-        return dict(total_loss=result[0], loss_2d=result[1], loss_bone=result[2], loss_root=result[3])
-
-    def loss_and_head_gradients(self, imgs, valids, labels, rdepth):
-        """The loss of _loss and the gradient of total_loss at the 36 head tensors where the all-heads schedule leaves them, at their own
-        resolutions and in their own layouts (smap_loss_backward_src): the seam a backward pass through the backbone starts from.  Eval
-        mode, the current stream, no synchronisation.  Returns (dict as forward's loss branch, EngineLoss.value_and_grad's grads)."""
+    def _engine_heads(self, imgs, valids, labels, rdepth):
+        """What the loss branches share: the mode, device and shape rules, the labels checked against the image, and the all-heads
+        schedule on the current stream.  Returns (EngineLoss, engine, out, head sources, valids, labels, rdepth); `out` may hold the
+        finest root-depth map the sources name, so the caller keeps it until the loss has been enqueued."""
         from ..loss import EngineLoss
         if self.training:
             raise RuntimeError("smap_amd.SMAP evaluates the loss in eval mode only (folded BatchNorm): call model.eval() first")
@@ -222,4 +200,24 @@ class SMAP(nn.Module):
         eng = self.engine(B, H, W, imgs.device, all_heads=True)
         out = eng.new_output()
         eng.run(imgs.float(), out=out)
-        return crit.value_and_grad(eng.head_sources(out), valids, labels, rdepth)
+        return crit, eng, out, eng.head_sources(out), valids, labels, rdepth
+
+    def _loss(self, imgs, valids, labels, rdepth):
+        """The loss branch of the reference's forward (smap.py:355-401, :403-415) in eval mode: the all-heads schedule, then
+        smap_loss_forward_src on the heads where the engine left them -- both on the current stream, no synchronisation.  Returns
+        dict(total_loss, loss_2d, loss_bone, loss_root) of 0-d device tensors without grad_fn.  (forward has applied its own mode,
+        device and shape rules before.)"""
+        if valids is None or labels is None or rdepth is None:
+            raise ValueError("the loss needs valids [B,57(,1)], labels [B,S,57,H,W] and rdepth [B,R,3] (as smap_amd.loss.SMAPLoss takes them)")
+        crit, eng, out, sources, valids, labels, rdepth = self._engine_heads(imgs, valids, labels, rdepth)
+        losses = crit(sources, valids, labels, rdepth)
+        if os.environ.get("SMAP_CHECK_FINITE"):
+            eng.raise_if_nonfinite(out)
+        return losses
+
+    def loss_and_head_gradients(self, imgs, valids, labels, rdepth):
+        """The loss of _loss and the gradient of total_loss at the 36 head tensors where the all-heads schedule leaves them, at their own
+        resolutions and in their own layouts (smap_loss_backward_src): the seam a backward pass through the backbone starts from.  Eval
+        mode, the current stream, no synchronisation.  Returns (dict as forward's loss branch, EngineLoss.value_and_grad's grads)."""
+        crit, _, out, sources, valids, labels, rdepth = self._engine_heads(imgs, valids, labels, rdepth)
+        return crit.value_and_grad(sources, valids, labels, rdepth)
