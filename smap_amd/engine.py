@@ -109,8 +109,6 @@ def tile_ids(family=None, cap=None, x3=None):
 
 
 # names older call sites import: one-line views of the table
-X3_TILES = tuple(t for t in tile_ids(("igemm", "persist"), x3=True) if TILE_TABLE[t].bn >= 64)      # conv.hip / convp.hip, split precision, any Cout > 32
-REGEPI_TILES = tile_ids(cap="regepi")
 TILES = {t: (r.bm, r.bn) for t, r in TILE_TABLE.items()}                      # tile id -> (BM, BN)
 TAIL_BN = {t: r.tail_bn for t, r in TILE_TABLE.items() if r.tail_bn}          # tile id -> output channels per chunk of the fused 1x1
 HALO_ROWS = ("halo", "tail", "block")     # families whose 3x3 weights are packed as 128-byte halo rows (pack_halo_rows)
@@ -166,9 +164,9 @@ class SchedulePolicy:
     deep_tile: bool = True
     """SMAP_DEEP_TILE=0 switches Graph.deep_pipeline_tile (tile 2 -> 7 for launches of <= 256 workgroups, profiles/r5_v9_*) off."""
     lanes: bool = False
-    """SMAP_LANES=1: the independent head chains on forked streams (use_lanes; profiles/r5_v3_ab_b1.log)."""
+    """SMAP_LANES=1: the independent head chains on forked streams (Graph.lanes; profiles/r5_v3_ab_b1.log)."""
     wpairs: int = None
-    """SMAP_WPAIRS=0|1 forces one layout of the packed 32-half weight tiles; None = pairs in small schedules (use_w_pairs; profiles/r3_ab_wpairs*.log)."""
+    """SMAP_WPAIRS=0|1 forces one layout of the packed 32-half weight tiles; None = pairs in small schedules (Graph.w_pairs; profiles/r3_ab_wpairs*.log)."""
     x3_tile: int = None
     """SMAP_X3_TILE: one split-precision tile id put before the table's candidates wherever it fits (Graph._pick)."""
     cat_tile: int = None
@@ -303,24 +301,6 @@ def pick_tile_x3(M, cout, key=None, policy=None):
         if blocks > best_blocks:
             best, best_blocks = t, blocks
     return cands + [best]
-
-
-def use_lanes(frames, H, W, policy=None):
-    """Forked streams for the independent head chains (smap_op.lane).  OFF by default: measured at batch 1 (profiles/r5_v3_ab_b1.log) the
-    forward is SLOWER with them, launched kernel by kernel (3.619 -> 3.706 ms) and replayed from a graph (3.129 -> 3.436 ms): the head
-    chains are 6 of 170 launches, and every fork / join costs an event round trip on the critical path.  SchedulePolicy.lanes switches
-    them on (the mechanism stays tested: tests/test_backbone_gpu.py::test_lanes_fork_the_head_chains_and_change_nothing)."""
-    return int((policy or SchedulePolicy.from_env()).lanes)
-
-
-# 32-half K tiles of the packed weights are stored in PAIRS (128-byte rows [tile 2p | tile 2p+1]) for SMALL schedules (<= 2 frames of
-# 512x832 worth of pixels): every launch of those is latency-bound and lives on the L1 hit the second half of each fetched line
-# gives the next K tile (batch 1: 226 vs 195 frames/s); larger schedules are bandwidth-bound and prefer one contiguous block
-# per K tile (batch 8: 751 vs 738).  A per-launch rule (pairs for <= 512 workgroups) sits in between on both (226 / 745):
-# profiles/r3_ab_wpairs*.log.  SchedulePolicy.wpairs forces one layout.
-def use_w_pairs(small, policy=None):
-    forced = (policy or SchedulePolicy.from_env()).wpairs
-    return int(small) if forced is None else forced
 
 
 def pack_conv_weights(w2, tile, x3, ksize, cin, pairs=True):
@@ -460,6 +440,13 @@ class Op:
     aux2: Tensor = None                           # second input, concatenated along K (Graph.conv_cat)
     scratch: list = field(default_factory=list)   # arena scratch that lives for this op only (split K: the partial tiles)
 
+    # Every Tensor field above is named in exactly ONE of reads() / writes() / scratch: what Graph.allocate and Graph.emit enumerate.
+    def reads(self):
+        return [t for t in [self.inp, self.res, self.add1, self.add2, self.aux2] + list(self.aux) if t is not None]
+
+    def writes(self):
+        return ([self.out] if self.out is not None else []) + list(self.outs)
+
 
 def pick_tile_heuristic(M, cout):
     """Largest tile that still gives >= 2 waves of workgroups on 256 CUs."""
@@ -527,6 +514,35 @@ def arena_budget(device):
     return int(0.9 * total / max(1, int(os.environ.get("SMAP_ARENAS_PER_DEVICE", ARENAS_PER_DEVICE))))
 
 
+class _FreeList:
+    """The free byte ranges of the arena, as Graph._place uses them."""
+    def __init__(self):
+        self.blocks = []                 # (off, size); sorted and merged by give(), remainders of take() at the end
+
+    def take(self, need):
+        """Best fit: the offset of `need` bytes at the head of the smallest block that holds them (the first such in list order), or None."""
+        pick = None
+        for k, (_, sz) in enumerate(self.blocks):
+            if sz >= need and (pick is None or sz < self.blocks[pick][1]):
+                pick = k
+        if pick is None:
+            return None
+        off, sz = self.blocks.pop(pick)
+        if sz > need:
+            self.blocks.append((off + need, sz - need))
+        return off
+
+    def give(self, off, size):
+        """Hand a range back and merge neighbours (blocks on either side of a zero page are never adjacent)."""
+        merged = []
+        for o, sz in sorted(self.blocks + [(off, size)]):
+            if merged and merged[-1][0] + merged[-1][1] == o:
+                merged[-1] = (merged[-1][0], merged[-1][1] + sz)
+            else:
+                merged.append((o, sz))
+        self.blocks = merged
+
+
 class Graph:
     def __init__(self, sd, B, H, W, stage_num=3, chl=256, kpt_paf=43, paf=14, keep_ref=False, precision="f16",
                  flip_pair=None, build=True, scaled_hms=False, all_heads=False, policy=None):
@@ -562,8 +578,17 @@ class Graph:
             B = 2 * B                         # frames of every activation tensor
         assert not build or (H % 32 == 0 and W % 32 == 0), "input must be a multiple of 32 (5 stride-2 levels)"
         self.sd, self.B, self.H, self.W = sd, B, H, W
-        self.w_pairs = use_w_pairs(self.small, self.policy)  # layout of the packed 32-half weight tiles (whole schedule)
-        self.lanes = use_lanes(B, H, W, self.policy)         # head chains on forked streams (BackboneEngine switches the plan's lanes on)
+        # 32-half K tiles of the packed weights are stored in PAIRS (128-byte rows [tile 2p | tile 2p+1]) for SMALL schedules (<= 2 frames of
+        # 512x832 worth of pixels): every launch of those is latency-bound and lives on the L1 hit the second half of each fetched line
+        # gives the next K tile (batch 1: 226 vs 195 frames/s); larger schedules are bandwidth-bound and prefer one contiguous block
+        # per K tile (batch 8: 751 vs 738).  A per-launch rule (pairs for <= 512 workgroups) sits in between on both (226 / 745):
+        # profiles/r3_ab_wpairs*.log.  SchedulePolicy.wpairs forces one layout for the whole schedule.
+        self.w_pairs = int(self.small) if self.policy.wpairs is None else self.policy.wpairs
+        # Forked streams for the independent head chains (smap_op.lane; BackboneEngine switches the plan's lanes on).  OFF by default: measured
+        # at batch 1 (profiles/r5_v3_ab_b1.log) the forward is SLOWER with them, launched kernel by kernel (3.619 -> 3.706 ms) and replayed from
+        # a graph (3.129 -> 3.436 ms): the head chains are 6 of 170 launches, and every fork / join costs an event round trip on the critical
+        # path.  The mechanism stays tested: tests/test_backbone_gpu.py::test_lanes_fork_the_head_chains_and_change_nothing.
+        self.lanes = int(self.policy.lanes)
         self.cur_lane = 0                                    # lane of the ops being appended (Graph.on_lane)
         self.ops, self.tensors = [], []
         self.scratch_tensors, self.kcount, self.kcount_tiles = [], None, 0      # split K: partial-tile scratch per op, one ticket region per schedule
@@ -1072,151 +1097,129 @@ class Graph:
         return dict(TAIL_DEFAULT if self.policy.tail is None else self.policy.tail).get(planes)
 
     def _stage(self, s, x, skip1, skip2, gen_skip, heads):
-        pre = f"stage{s}."
+        """Stage s on x: the ResNet layers (+ the previous stage's skips), Upsample_module (smap.py:244-286: up1 on x4 ... up4 on x1) and, behind
+        the last stage (heads), the output buffer.  Returns (cross_conv, skip1 list, skip2 list) for the next stage; the lists are fine -> coarse
+        (smap.py:283-284)."""
+        x1, x2, x3, x4 = self._layers(s, x, skip1, skip2)
+        out, tl, s1, s2, cross, head_t = None, None, [None] * 4, [None] * 4, None, {}
+        for ind, xin in enumerate((x4, x3, x2, x1)):
+            out, tl, s1[3 - ind], s2[3 - ind], cross = self._unit(s, ind, xin, out, tl, gen_skip, heads, head_t)
+        if heads:
+            self._outputs(head_t)
+        return cross, (s1 if gen_skip else None), (s2 if gen_skip else None)
+
+    def _layers(self, s, x, skip1, skip2):
+        """layer1..4 of stage s -> [x1, x2, x3, x4]; the last block of layer li adds skip1[li] + skip2[li] of the previous stage (smap.py:142-153)."""
         feats = []
         inpl = 64
         for li, (planes, nblk) in enumerate(zip(PLANES, LAYERS)):
             stride = 1 if li == 0 else 2
             for j in range(nblk):
                 lastb = j == nblk - 1
-                a1 = skip1[li] if (skip1 is not None and lastb) else None   # smap.py:142-153
+                a1 = skip1[li] if (skip1 is not None and lastb) else None
                 a2 = skip2[li] if (skip2 is not None and lastb) else None
                 has_ds = j == 0 and (stride != 1 or inpl != planes * 4)
-                x = self._bottleneck(f"{pre}downsample.layer{li + 1}.{j}", x, planes, stride if j == 0 else 1,
-                                     has_ds, a1, a2)
+                x = self._bottleneck(f"stage{s}.downsample.layer{li + 1}.{j}", x, planes, stride if j == 0 else 1, has_ds, a1, a2)
                 inpl = planes * 4
             feats.append(x)
-        x1, x2, x3, x4 = feats
-        # Upsample_module (smap.py:244-286): up1 on x4 ... up4 on x1
-        out, s1, s2, cross = None, [None] * 4, [None] * 4, None
-        head_t = {}
-        # Shared-input 1x1s of an Upsample_unit as ONE launch with one output per conv (conv_seg).  Measured (profiles/r5_v1_*): the
-        # launches on `out` (skip2 | cross_conv | res_conv1 | the next unit's up_conv) are 3-33 % faster merged than one by one at every
-        # level; u_skip | skip1 on x is faster merged where u_skip has no fused bilinear add (up1: 228 vs 244 us at 16 frames) and SLOWER
-        # where it has one (128x208: 712 vs 610 us; 32x52: 277 vs 256): one tile shape must then serve the bilinear epilogue (which wants
-        # the 256-wide tile) and the plain skip1 (which wants the eight-wave 128x128 one).  SchedulePolicy.merge_1x1: 1 (default) = the
-        # merges that pay, 2 = all of them, 0 = one launch per conv.
-        merge_mode = self.policy.merge_1x1
-        merge = merge_mode != 0
-        tl = None                                                 # up_conv@low of the unit at hand (a segment of the previous unit's launch on `out`)
-        for ind, xin in enumerate((x4, x3, x2, x1)):
-            u = f"{pre}upsample.up{ind + 1}"
-            un = f"{pre}upsample.up{ind + 2}"                     # the next unit: its up_conv reads this unit's `out` (commuted with the upsample)
-            # The inter-stage skips as ONE tensor per level: skip1(x) + skip2(out) in one launch (conv_relusum); the next stage adds that one tensor.
-            # SchedulePolicy.skipsum = False: round 5's two tensors (skip1 beside u_skip, skip2 as a segment of the launch on `out`).  Not beyond one 4 GiB window.
-            ss = self.policy.skipsum
-            skipsum = gen_skip and merge and ss is not False and self.one_window and (ss or not self.small)    # (small schedules: as conv_cat)
-            if merge:
-                # launch 1, on x:   out = relu(u_skip(x) [+ bilinear(up_conv@low)])  |  skip1 = relu(skip1(x))
-                if gen_skip and not skipsum and (tl is None or merge_mode == 2):
-                    out, s1[3 - ind] = self.conv_seg([(u + ".out", u + ".u_skip", True), (u + ".skip1", u + ".skip1", True)], xin, up=tl)
+        return feats
+
+    def _shared_input(self, convs, x, merge, up=None):
+        """1x1 convs [(tensor name, prefix, relu)] that all read x -> {tensor name: tensor}: ONE launch with one output per conv (conv_seg)
+        where `merge` says so and there are at least two of them, else one launch each, in order.  up (the fused bilinear add) belongs to the first."""
+        if merge and len(convs) >= 2:
+            outs = self.conv_seg(convs, x, up=up)
+        else:
+            outs = [self.conv(nm, [pre], x, relu=relu, up=up if k == 0 else None) for k, (nm, pre, relu) in enumerate(convs)]
+        return dict(zip([nm for nm, _, _ in convs], outs))
+
+    def _unit(self, s, ind, xin, below, tl, gen_skip, heads, head_t):
+        """Upsample_unit up{ind + 1} of stage s on xin (smap.py:210-241).  below: the previous unit's `out`; tl: this unit's up_conv@low
+        (up_conv commuted with the upsample: evaluated on `below`) where the previous unit's launch on `out` has made it already.  heads: the
+        inference heads of the last stage, into head_t.  Returns (out, the next unit's up_conv@low or None, skip1, skip2, cross_conv) -- None for
+        what this unit does not make.
+
+        Shared-input 1x1s as ONE launch with one output per conv (conv_seg).  Measured (profiles/r5_v1_*): the launches on `out` (skip2 |
+        cross_conv | res_conv1 | the next unit's up_conv) are 3-33 % faster merged than one by one at every level; u_skip | skip1 on x is faster
+        merged where u_skip has no fused bilinear add (up1: 228 vs 244 us at 16 frames) and SLOWER where it has one (128x208: 712 vs 610 us;
+        32x52: 277 vs 256): one tile shape must then serve the bilinear epilogue (which wants the 256-wide tile) and the plain skip1 (which
+        wants the eight-wave 128x128 one).  SchedulePolicy.merge_1x1: 1 (default) = the merges that pay, 2 = all of them, 0 = one launch per
+        conv -- the baseline the merged schedules are compared against: nothing merged, no two-input or tap-dot launch, no side lane, and this
+        unit's up_conv@low at the top of the unit."""
+        mode, pol = self.policy.merge_1x1, self.policy
+        u = f"stage{s}.upsample.up{ind + 1}"
+        un = f"stage{s}.upsample.up{ind + 2}"                    # the next unit: its up_conv reads this unit's `out`
+        side = lambda lane: self.on_lane(lane if mode else 0)
+        if ind and not mode:
+            tl = self.conv(u + ".up_conv@low", [u + ".up_conv"], below, relu=False)
+        # The inter-stage skips as ONE tensor per level: skip1(x) + skip2(out) in one launch (conv_relusum); the next stage adds that one tensor.
+        # SchedulePolicy.skipsum = False: round 5's two tensors (skip1 beside u_skip, skip2 as a segment of the launch on `out`).  Not beyond one
+        # 4 GiB window; small schedules: as conv_cat.
+        skipsum = gen_skip and mode != 0 and pol.skipsum is not False and self.one_window and (pol.skipsum or not self.small)
+        # on the unit's input:  out = relu(u_skip(x) [+ bilinear(up_conv@low)])  |  skip1 = relu(skip1(x))
+        on_x = [(u + ".out", u + ".u_skip", True)] + ([(u + ".skip1", u + ".skip1", True)] if gen_skip and not skipsum else [])
+        if tl is not None and not mode and pol.no_upadd_fusion and not self.x3:      # the bilinear add as a launch of its own, not the conv's epilogue
+            a = self.conv(u + ".u_skip", [u + ".u_skip"], xin, relu=False)
+            out = self.tensor(u + ".out", a.H, a.W, a.C)
+            self.ops.append(Op(OP_UPADD, out=out, inp=a, aux=[tl], p=dict(relu=1)))
+            got = self._shared_input(on_x[1:], xin, False)
+        else:
+            got = self._shared_input(on_x, xin, mode == 2 or (mode == 1 and tl is None), up=tl)
+            out = got[u + ".out"]
+        if skipsum:
+            got[u + ".skip1"] = self.conv_relusum(u + ".skipsum", u + ".skip1", xin, u + ".skip2", out)
+        # on `out`: skip2 | cross_conv (stages with skips), res_conv1 (last stage), the next unit's up_conv@low
+        on_out = [(u + ".skip2", u + ".skip2", True)] if gen_skip and not skipsum else []
+        if gen_skip and ind == 3:
+            on_out.append((u + ".cross_conv", u + ".cross_conv", True))
+        if heads and 1 <= ind < 3:
+            on_out.append((u + ".res1", u + ".res_conv1", True))
+        if ind < 3 and mode:
+            on_out.append((un + ".up_conv@low", un + ".up_conv", False))
+        got.update(self._shared_input(on_out, out, mode != 0))
+        if heads and ind == 3:
+            # The root-depth head (res_rd_conv1 -> res_rd_conv2, a 3x3 with ONE output channel) as a 1x1 launch whose epilogue
+            # keeps nine dot products per pixel instead of the 256-channel activation, + a nine-term stencil (conv_tapdot / tapsum):
+            # 0.87 GB per 16 frames and the N = 1 MFMA launch (8.9 TFLOP/s) gone.  SchedulePolicy.taphead = False: round 5's three-way 1x1 + 3x3.
+            tap = mode != 0 and self.chl == 256 and pol.taphead is not False and (pol.taphead or not self.small)
+            m = self.conv(u + ".heads1x1", [u + ".res_conv1", u + ".res_d_conv1"] + ([] if tap else [u + ".res_rd_conv1"]), out, relu=True)
+            c = self.chl
+            head_t["res4"] = self.conv(u + ".res", [u + ".res_conv2"], m, 3, relu=False, in_c_off=0, cin=c, out_fp32=True)
+            with side(1):     # the three 3x3 heads read disjoint channel slices of m: side by side
+                head_t["res_d"] = self.conv(u + ".res_d", [u + ".res_d_conv2"], m, 3, relu=False, in_c_off=c, cin=c, out_fp32=True, frames=self.frames)
+            with side(2):
+                if tap:
+                    head_t["res_rd_tap"] = self.conv_tapdot(u + ".res_rd_t", u + ".res_rd_conv1", u + ".res_rd_conv2", out, frames=self.frames)
                 else:
-                    out = self.conv(u + ".out", [u + ".u_skip"], xin, relu=True, up=tl)
-                    if gen_skip and not skipsum:
-                        s1[3 - ind] = self.conv(u + ".skip1", [u + ".skip1"], xin, relu=True)
-                if skipsum:
-                    s1[3 - ind] = self.conv_relusum(u + ".skipsum", u + ".skip1", xin, u + ".skip2", out)
-                # launch 2, on out: skip2 | cross_conv (stages with skips), res_conv1 (last stage), the next unit's up_conv@low
-                sg = []
-                if gen_skip:
-                    if not skipsum:
-                        sg.append((u + ".skip2", u + ".skip2", True))
-                    if ind == 3:
-                        sg.append((u + ".cross_conv", u + ".cross_conv", True))
-                if heads and 1 <= ind < 3:
-                    sg.append((u + ".res1", u + ".res_conv1", True))
-                if ind < 3:
-                    sg.append((un + ".up_conv@low", un + ".up_conv", False))
-                got = {}
-                if len(sg) >= 2:
-                    got = dict(zip([n_ for n_, _, _ in sg], self.conv_seg(sg, out)))
-                elif len(sg) == 1:
-                    got = {sg[0][0]: self.conv(sg[0][0], [sg[0][1]], out, relu=sg[0][2])}
-                tl = got.get(un + ".up_conv@low")
-                if gen_skip:
-                    s2[3 - ind] = None if skipsum else got[u + ".skip2"]
-                    if ind == 3:
-                        cross = got[u + ".cross_conv"]
-                if heads:
-                    if ind == 3:
-                        # The root-depth head (res_rd_conv1 -> res_rd_conv2, a 3x3 with ONE output channel) as a 1x1 launch whose epilogue
-                        # keeps nine dot products per pixel instead of the 256-channel activation, + a nine-term stencil (conv_tapdot / tapsum):
-                        # 0.87 GB per 16 frames and the N = 1 MFMA launch (8.9 TFLOP/s) gone.  SchedulePolicy.taphead = False: round 5's three-way 1x1 + 3x3.
-                        tap = self.chl == 256 and self.policy.taphead is not False and (self.policy.taphead or not self.small)
-                        m = self.conv(u + ".heads1x1", [u + ".res_conv1", u + ".res_d_conv1"] + ([] if tap else [u + ".res_rd_conv1"]), out, relu=True)
-                        c = self.chl
-                        head_t["res4"] = self.conv(u + ".res", [u + ".res_conv2"], m, 3, relu=False, in_c_off=0, cin=c, out_fp32=True)
-                        with self.on_lane(1):     # the three 3x3 heads read disjoint channel slices of m: side by side
-                            head_t["res_d"] = self.conv(u + ".res_d", [u + ".res_d_conv2"], m, 3, relu=False, in_c_off=c, cin=c, out_fp32=True,
-                                                        frames=self.frames)
-                        with self.on_lane(2):
-                            if tap:
-                                head_t["res_rd_tap"] = self.conv_tapdot(u + ".res_rd_t", u + ".res_rd_conv1", u + ".res_rd_conv2", out, frames=self.frames)
-                            else:
-                                head_t["res_rd"] = self.conv(u + ".res_rd", [u + ".res_rd_conv2"], m, 3, relu=False, in_c_off=2 * c, cin=c,
-                                                             out_fp32=True, frames=self.frames)
-                    elif ind >= 1:
-                        with self.on_lane(1):     # the 3x3 head of this unit runs beside the next unit's launches
-                            head_t[f"res{ind + 1}"] = self.conv(u + ".res", [u + ".res_conv2"], got[u + ".res1"], 3, relu=False, out_fp32=True)
-                self._train_heads(s, ind, u, out, head_t if heads else {})
-                continue
-            if ind == 0:
-                out = self.conv(u + ".out", [u + ".u_skip"], xin, relu=True)
+                    head_t["res_rd"] = self.conv(u + ".res_rd", [u + ".res_rd_conv2"], m, 3, relu=False, in_c_off=2 * c, cin=c,
+                                                 out_fp32=True, frames=self.frames)
+        elif heads and ind >= 1:
+            with side(1):     # the 3x3 head of this unit runs beside the next unit's launches
+                head_t[f"res{ind + 1}"] = self.conv(u + ".res", [u + ".res_conv2"], got[u + ".res1"], 3, relu=False, out_fp32=True)
+        self._train_heads(s, ind, u, out, head_t if heads else {})
+        return out, got.get(un + ".up_conv@low"), got.get(u + ".skip1"), got.get(u + ".skip2"), got.get(u + ".cross_conv")
+
+    def _outputs(self, head_t):
+        """The output buffer: its layout (out_layout, the status words behind the maps) and the ops that write it from the last stage's heads."""
+        B, h, w = self.frames, self.out_h, self.out_w
+        n_hms, n_d = self.kpt_paf, self.paf
+        flip_p = {}
+        if self.flip_pair is not None:         # pair table of the in-schedule flip-TTA merge lives in the weight blob
+            flip_p = dict(flip_from=self.frames, n_kpt=n_hms - 2 * n_d, w_off=self._add_w(torch.tensor(self.flip_pair, dtype=torch.int32)))
+        self.out_layout = dict(hms=(0, n_hms), det_d=(B * n_hms * h * w * 4, n_d), root_d=(B * (n_hms + n_d) * h * w * 4, 1))
+        self.out_bytes = B * (n_hms + n_d + 1) * h * w * 4
+        self.status_off = self.out_bytes                 # int32 status words behind the maps (include/smap_hip.h)
+        self.status_words = (B + 30) // 31               # SMAP_STATUS_WORDS: frame f = word f // 31, bit 1 + f % 31
+        # outputs_2d = res4 + res3 + res2 (smap.py:417)
+        self.ops.append(Op(OP_HEADSUM, aux=[head_t["res4"], head_t["res3"], head_t["res2"]],
+                           p={**dict(Cout=n_hms, ext_off=self.out_layout["hms"][0], n_kpt=n_hms - 2 * n_d, scale_hms=int(self.scaled_hms)), **flip_p}))
+        with self.on_lane(1):
+            self.ops.append(Op(OP_HEADSUM, aux=[head_t["res_d"]], p=dict(Cout=n_d, ext_off=self.out_layout["det_d"][0])))
+        with self.on_lane(2):
+            if "res_rd_tap" in head_t:
+                self.tapsum(*head_t["res_rd_tap"], self.out_layout["root_d"][0])
             else:
-                tl = self.conv(u + ".up_conv@low", [u + ".up_conv"], out, relu=False)   # commuted with the upsample
-                if self.policy.no_upadd_fusion and not self.x3:
-                    a = self.conv(u + ".u_skip", [u + ".u_skip"], xin, relu=False)
-                    o = self.tensor(u + ".out", a.H, a.W, a.C)
-                    self.ops.append(Op(OP_UPADD, out=o, inp=a, aux=[tl], p=dict(relu=1)))
-                    out = o
-                else:       # relu(u_skip(x) + bilinear(tl)) in the u_skip conv's epilogue
-                    out = self.conv(u + ".out", [u + ".u_skip"], xin, relu=True, up=tl)
-            if gen_skip:
-                lvl = 3 - ind                      # skip lists are fine -> coarse (smap.py:283-284)
-                s1[lvl] = self.conv(u + ".skip1", [u + ".skip1"], xin, relu=True)
-                s2[lvl] = self.conv(u + ".skip2", [u + ".skip2"], out, relu=True)
-                if ind == 3:
-                    cross = self.conv(u + ".cross_conv", [u + ".cross_conv"], out, relu=True)
-            if heads:
-                if ind == 3:
-                    m = self.conv(u + ".heads1x1", [u + ".res_conv1", u + ".res_d_conv1", u + ".res_rd_conv1"],
-                                  out, relu=True)
-                    c = self.chl
-                    head_t["res4"] = self.conv(u + ".res", [u + ".res_conv2"], m, 3, relu=False, in_c_off=0,
-                                               cin=c, out_fp32=True)
-                    head_t["res_d"] = self.conv(u + ".res_d", [u + ".res_d_conv2"], m, 3, relu=False, in_c_off=c,
-                                                cin=c, out_fp32=True, frames=self.frames)
-                    head_t["res_rd"] = self.conv(u + ".res_rd", [u + ".res_rd_conv2"], m, 3, relu=False,
-                                                 in_c_off=2 * c, cin=c, out_fp32=True, frames=self.frames)
-                elif ind >= 1:
-                    m = self.conv(u + ".res1", [u + ".res_conv1"], out, relu=True)
-                    head_t[f"res{ind + 1}"] = self.conv(u + ".res", [u + ".res_conv2"], m, 3, relu=False,
-                                                        out_fp32=True)
-            self._train_heads(s, ind, u, out, head_t if heads else {})
-        if heads:
-            B, h, w = self.frames, self.out_h, self.out_w
-            n_hms, n_d = self.kpt_paf, self.paf
-            flip_p = {}
-            if self.flip_pair is not None:         # pair table of the in-schedule flip-TTA merge lives in the weight blob
-                flip_p = dict(flip_from=self.frames, n_kpt=n_hms - 2 * n_d,
-                              w_off=self._add_w(torch.tensor(self.flip_pair, dtype=torch.int32)))
-            self.out_layout = dict(hms=(0, n_hms), det_d=(B * n_hms * h * w * 4, n_d),
-                                   root_d=(B * (n_hms + n_d) * h * w * 4, 1))
-            self.out_bytes = B * (n_hms + n_d + 1) * h * w * 4
-            self.status_off = self.out_bytes                 # int32 status words behind the maps (include/smap_hip.h)
-            self.status_words = (B + 30) // 31               # SMAP_STATUS_WORDS: frame f = word f // 31, bit 1 + f % 31
-            # outputs_2d = res4 + res3 + res2 (smap.py:417)
-            self.ops.append(Op(OP_HEADSUM, aux=[head_t["res4"], head_t["res3"], head_t["res2"]],
-                               p={**dict(Cout=n_hms, ext_off=self.out_layout["hms"][0], n_kpt=n_hms - 2 * n_d, scale_hms=int(self.scaled_hms)),
-                                  **flip_p}))
-            with self.on_lane(1):
-                self.ops.append(Op(OP_HEADSUM, aux=[head_t["res_d"]], p=dict(Cout=n_d, ext_off=self.out_layout["det_d"][0])))
-            with self.on_lane(2):
-                if "res_rd_tap" in head_t:
-                    self.tapsum(*head_t["res_rd_tap"], self.out_layout["root_d"][0])
-                else:
-                    self.ops.append(Op(OP_HEADSUM, aux=[head_t["res_rd"]], p=dict(Cout=1, ext_off=self.out_layout["root_d"][0])))
-        return cross, (s1 if gen_skip else None), (s2 if gen_skip else None)
+                self.ops.append(Op(OP_HEADSUM, aux=[head_t["res_rd"]], p=dict(Cout=1, ext_off=self.out_layout["root_d"][0])))
 
     def _train_heads(self, s, ind, u, out, head_t):
         """all_heads: the head chains of unit `u` (stage s, up{ind + 1}) that the inference schedule does not run, on `out`, with the launches
@@ -1240,36 +1243,44 @@ class Graph:
         self.keep += [t for t in have.values() if t is not None]
 
     # -- arena: liveness-based first-fit allocation
+    def _producers(self):
+        """id(tensor) -> index of the op that writes it."""
+        return {id(t): i for i, op in enumerate(self.ops) for t in op.writes()}
+
     def allocate(self, reuse=True):
+        """Offsets for every tensor; reuse=False: no two tensors share a byte (read_tensor).  Returns the arena's size."""
+        self._liveness()
+        return self._place(reuse)
+
+    def _liveness(self):
+        """first / last of every tensor = the ops between which its bytes are its own."""
         for i, op in enumerate(self.ops):
-            for t in [op.inp, op.res, op.add1, op.add2, op.aux2] + list(op.aux):
-                if t is not None:
-                    t.last = i
-            for t in ([op.out] if op.out is not None else []) + list(op.outs):
+            for t in op.reads():
+                t.last = i
+            for t in op.writes():
                 t.first = i
                 t.last = max(t.last, i)
             for t in op.scratch:
                 t.first = t.last = i
         # Lanes: an op on a side lane may start as soon as its producers are done and end as late as the schedule does.  What it WRITES is
         # therefore live from the op after its last producer, what it READS stays live to the end of the schedule (smap_op.lane's contract).
-        producer = {}
-        for i, op in enumerate(self.ops):
-            for t in ([op.out] if op.out is not None else []) + list(op.outs):
-                producer[id(t)] = i
+        producer = self._producers()
         n_last = len(self.ops) - 1
-        for i, op in enumerate(self.ops):
+        for op in self.ops:
             if not op.lane:
                 continue
-            reads = [t for t in [op.inp, op.res, op.add1, op.add2, op.aux2] + list(op.aux) if t is not None]
-            start = 1 + max([producer.get(id(t), -1) for t in reads] + [-1])
-            for t in ([op.out] if op.out is not None else []) + list(op.outs) + list(op.scratch):
+            start = 1 + max([producer.get(id(t), -1) for t in op.reads()] + [-1])
+            for t in op.writes() + op.scratch:
                 t.first = min(t.first, start)
-            for t in reads + list(op.scratch):
+            for t in op.reads() + op.scratch:
                 t.last = n_last
         if self.kcount is not None:                                # the tickets of every split-K op: one region, alive for the whole schedule
-            self.kcount.first, self.kcount.last = 0, len(self.ops) - 1
+            self.kcount.first, self.kcount.last = 0, n_last
         for t in self.keep:                                        # (all_heads: the loss reads the head tensors behind the schedule)
             t.last = n_last
+
+    def _place(self, reuse):
+        """Window-aware first fit in order of `first`: a tensor takes the smallest free block that holds it, else the top of the arena."""
         every = self.tensors + self.scratch_tensors + ([self.kcount] if self.kcount is not None else [])
         # arena[k * WINDOW : k * WINDOW + ZERO_PAGE] are the conv kernels' zero pages (csrc/plan.hip): never allocated, so no
         # tensor crosses a window boundary and every conv input is within 32 bits of its window's base
@@ -1277,11 +1288,9 @@ class Graph:
             if _rup(t.nbytes, ALIGN) > WINDOW - ZERO_PAGE:
                 raise ArenaTooLarge(f"{t.name}: {t.nbytes / 2 ** 30:.2f} GiB ({self.B} frames, precision {self.precision}) does not fit a "
                                     "4 GiB addressing window of the conv kernels -- use a smaller batch (PosePipeline splits by itself)")
-        by_first = {}
+        by_first, expiring = {}, {}
         for t in every:
             by_first.setdefault(t.first, []).append(t)
-        expiring = {}
-        for t in every:
             expiring.setdefault(t.last, []).append(t)
         # Both inputs of a two-input launch (conv_cat / conv_relusum) are addressed from one 64-bit base: they must share a window.  The
         # builder makes such launches only where the reusing arena fits one window; an arena that keeps every tensor (reuse=False, for
@@ -1294,44 +1303,28 @@ class Graph:
                     for t in g:
                         group[id(t)] = g
                         t.off = -1
-        free, top = [], ZERO_PAGE    # free: list of (off, size)
+        free, top = _FreeList(), ZERO_PAGE
         for i in range(len(self.ops)):
             for t in by_first.get(i, []):
                 if t.off >= 0 and id(t) in group:                  # (placed with its partner)
                     continue
-                need = _rup(t.nbytes, ALIGN)
-                pick = None
-                if reuse:
-                    for k, (o, sz) in enumerate(free):
-                        if sz >= need and (pick is None or sz < free[pick][1]):
-                            pick = k
-                if pick is not None:
-                    o, sz = free.pop(pick)
-                    t.off = o
-                    if sz > need:
-                        free.append((o + need, sz - need))
-                else:
-                    members = [m for m in group.get(id(t), [t]) if m is t or m.off < 0]
-                    need = sum(_rup(m.nbytes, ALIGN) for m in members)
-                    nxt = (top // WINDOW + 1) * WINDOW                 # start of the next window = its zero page
-                    if top + need > nxt:                               # would run into it: leave the rest of this window free
-                        if reuse and nxt > top:
-                            free.append((top, nxt - top))
-                        top = nxt + ZERO_PAGE
-                    for m in members:
-                        m.off = top
-                        top += _rup(m.nbytes, ALIGN)
+                off = free.take(_rup(t.nbytes, ALIGN)) if reuse else None
+                if off is not None:
+                    t.off = off
+                    continue
+                members = [m for m in group.get(id(t), [t]) if m is t or m.off < 0]
+                need = sum(_rup(m.nbytes, ALIGN) for m in members)
+                nxt = (top // WINDOW + 1) * WINDOW                 # start of the next window = its zero page
+                if top + need > nxt:                               # would run into it: leave the rest of this window free
+                    if reuse and nxt > top:
+                        free.blocks.append((top, nxt - top))
+                    top = nxt + ZERO_PAGE
+                for m in members:
+                    m.off = top
+                    top += _rup(m.nbytes, ALIGN)
             for t in expiring.get(i, []):
                 if reuse and t.off >= 0:
-                    free.append((t.off, _rup(t.nbytes, ALIGN)))
-                    free.sort()
-                    merged = []
-                    for o, sz in free:                                 # (blocks on either side of a zero page are never adjacent)
-                        if merged and merged[-1][0] + merged[-1][1] == o:
-                            merged[-1] = (merged[-1][0], merged[-1][1] + sz)
-                        else:
-                            merged.append((o, sz))
-                    free = merged
+                    free.give(t.off, _rup(t.nbytes, ALIGN))
         self.arena_bytes = max(top, ALIGN)
         for t in every:
             if t.off >= 0:
@@ -1340,20 +1333,16 @@ class Graph:
 
     def emit(self):
         arr = (_L.SmapOp * len(self.ops))()
-        producer = {}
-        for i, op in enumerate(self.ops):
-            for t in ([op.out] if op.out is not None else []) + list(op.outs):
-                producer[id(t)] = i
+        producer = self._producers()
         for i, op in enumerate(self.ops):
             o = arr[i]
             C.memset(C.byref(o), 0, C.sizeof(o))
             # lanes: wait for the latest producer on every OTHER lane (ops of one lane are ordered by their stream)
             o.lane = op.lane
             waits = {}
-            for t in [op.inp, op.res, op.add1, op.add2, op.aux2] + list(op.aux):
-                pi = producer.get(id(t)) if t is not None else None
-                if pi is not None and self.ops[pi].lane != op.lane:
-                    ln = self.ops[pi].lane
+            for pi in (producer[id(t)] for t in op.reads() if id(t) in producer):
+                ln = self.ops[pi].lane
+                if ln != op.lane:
                     waits[ln] = max(waits.get(ln, -1), pi)
             for k in range(4):
                 o.wait_op[k] = -1
@@ -1369,49 +1358,7 @@ class Graph:
             o.precision, o.acc_scale = int(self.x3), 1.0
             p = op.p
             if op.kind == OP_CONV:
-                x, y = op.inp, op.out
-                o.B = p["frames"]
-                o.H, o.W, o.Cin, o.in_stride_c, o.in_c_off = x.H, x.W, p["Cin"], x.C * x.planes, p["in_c_off"]
-                o.Ho, o.Wo, o.Cout = y.H, y.W, p["Cout"]
-                o.ksize, o.stride, o.pad, o.relu = p["ksize"], p["stride"], p["pad"], p["relu"]
-                o.cout_pad, o.out_stride_c, o.out_c_off = p["cout_pad"], y.C * y.planes, 0
-                o.acc_scale = p["acc_scale"]
-                o.w_pairs = p["w_pairs"]
-                o.out_fp32, o.tile = p["out_fp32"], p["tile"]
-                if "tail" in p:
-                    tl = p["tail"]
-                    o.tail_cout, o.tail_cout_pad, o.tail_acc_scale = tl["cout"], tl["cout_pad"], tl["acc_scale"]
-                    o.tail_w_off, o.tail_bias_off = tl["w_off"], tl["bias_off"]
-                if "head" in p:
-                    hd = p["head"]
-                    o.head_cin, o.head_acc_scale, o.head_w_off, o.head_bias_off = hd["cin"], hd["acc_scale"], hd["w_off"], hd["bias_off"]
-                if "short" in p:
-                    o.short_w_off, o.short_acc_scale = p["short"]["w_off"], p["short"]["acc_scale"]
-                o.in_off, o.out_off, o.w_off, o.bias_off = x.off, y.off, p["w_off"], p["bias_off"]
-                for nm in ("res", "add1", "add2"):
-                    t = getattr(op, nm)
-                    if t is not None:
-                        assert (t.H, t.W, t.C) == (y.H, y.W, y.C) and t.esize == 2, (y.name, nm)
-                        setattr(o, nm + "_off", t.off)
-                if op.aux:
-                    t = op.aux[0]
-                    assert t.C == y.C and t.esize == 2
-                    o.aux_off[0], o.aux_h[0], o.aux_w[0] = t.off, t.H, t.W
-                if "tap" in p:
-                    o.tap_n, o.tap_w_off, o.tap_scale = 9, p["tap"]["w_off"], p["tap"]["scale"]
-                    o.out_stride_c = 16
-                if "cat" in p:
-                    t = op.aux2
-                    assert t.off // WINDOW == x.off // WINDOW, (y.name, "both inputs of a conv_cat launch must lie in one 4 GiB window")
-                    o.in2_off, o.in2_H, o.in2_W, o.in2_C, o.in2_stride_c, o.in2_stride = t.off, t.H, t.W, p["cat"]["cin"], t.C * t.planes, p["cat"]["stride"]
-                    if p["cat"].get("relusum"):
-                        o.in2_mode, o.in2_acc_scale, o.in2_bias_off = 1, p["cat"]["acc_scale"], p["cat"]["bias_off"]
-                if p.get("ksplit", 1) > 1:
-                    o.ksplit, o.kpart_off, o.kcount_off = p["ksplit"], op.scratch[0].off, self.kcount.off + 4 * p["kcount_first"]
-                for j, (sg, t) in enumerate(zip(p.get("segs", []), op.outs)):
-                    assert (t.H, t.W, t.C) == (y.H, y.W, sg["cout"]) and t.esize == 2
-                    o.seg_n[j], o.seg_cout[j], o.seg_relu[j], o.seg_acc_scale[j] = sg["n0"], sg["cout"], sg["relu"], sg["acc_scale"]
-                    o.seg_out_stride_c[j], o.seg_out_off[j] = t.C * t.planes, t.off
+                self._emit_conv(o, op)
             elif op.kind in (OP_STEM, OP_STEMPOOL):
                 y = op.out
                 o.H, o.W, o.Cin, o.Ho, o.Wo, o.Cout = self.H, self.W, 3, y.H, y.W, 64
@@ -1452,6 +1399,52 @@ class Graph:
                 if p.get("scale_hms"):
                     o.scale_hms, o.in_c_off = 1, p["n_kpt"]
         return arr
+
+    def _emit_conv(self, o, op):
+        """The smap_op fields of a conv launch (every Graph.conv* emitter), behind the defaults emit() has set."""
+        p, x, y = op.p, op.inp, op.out
+        o.B = p["frames"]
+        o.H, o.W, o.Cin, o.in_stride_c, o.in_c_off = x.H, x.W, p["Cin"], x.C * x.planes, p["in_c_off"]
+        o.Ho, o.Wo, o.Cout = y.H, y.W, p["Cout"]
+        o.ksize, o.stride, o.pad, o.relu = p["ksize"], p["stride"], p["pad"], p["relu"]
+        o.cout_pad, o.out_stride_c, o.out_c_off = p["cout_pad"], y.C * y.planes, 0
+        o.acc_scale = p["acc_scale"]
+        o.w_pairs = p["w_pairs"]
+        o.out_fp32, o.tile = p["out_fp32"], p["tile"]
+        if "tail" in p:
+            tl = p["tail"]
+            o.tail_cout, o.tail_cout_pad, o.tail_acc_scale = tl["cout"], tl["cout_pad"], tl["acc_scale"]
+            o.tail_w_off, o.tail_bias_off = tl["w_off"], tl["bias_off"]
+        if "head" in p:
+            hd = p["head"]
+            o.head_cin, o.head_acc_scale, o.head_w_off, o.head_bias_off = hd["cin"], hd["acc_scale"], hd["w_off"], hd["bias_off"]
+        if "short" in p:
+            o.short_w_off, o.short_acc_scale = p["short"]["w_off"], p["short"]["acc_scale"]
+        o.in_off, o.out_off, o.w_off, o.bias_off = x.off, y.off, p["w_off"], p["bias_off"]
+        for nm in ("res", "add1", "add2"):
+            t = getattr(op, nm)
+            if t is not None:
+                assert (t.H, t.W, t.C) == (y.H, y.W, y.C) and t.esize == 2, (y.name, nm)
+                setattr(o, nm + "_off", t.off)
+        if op.aux:
+            t = op.aux[0]
+            assert t.C == y.C and t.esize == 2
+            o.aux_off[0], o.aux_h[0], o.aux_w[0] = t.off, t.H, t.W
+        if "tap" in p:
+            o.tap_n, o.tap_w_off, o.tap_scale = 9, p["tap"]["w_off"], p["tap"]["scale"]
+            o.out_stride_c = 16
+        if "cat" in p:
+            t = op.aux2
+            assert t.off // WINDOW == x.off // WINDOW, (y.name, "both inputs of a conv_cat launch must lie in one 4 GiB window")
+            o.in2_off, o.in2_H, o.in2_W, o.in2_C, o.in2_stride_c, o.in2_stride = t.off, t.H, t.W, p["cat"]["cin"], t.C * t.planes, p["cat"]["stride"]
+            if p["cat"].get("relusum"):
+                o.in2_mode, o.in2_acc_scale, o.in2_bias_off = 1, p["cat"]["acc_scale"], p["cat"]["bias_off"]
+        if p.get("ksplit", 1) > 1:
+            o.ksplit, o.kpart_off, o.kcount_off = p["ksplit"], op.scratch[0].off, self.kcount.off + 4 * p["kcount_first"]
+        for j, (sg, t) in enumerate(zip(p.get("segs", []), op.outs)):
+            assert (t.H, t.W, t.C) == (y.H, y.W, sg["cout"]) and t.esize == 2
+            o.seg_n[j], o.seg_cout[j], o.seg_relu[j], o.seg_acc_scale[j] = sg["n0"], sg["cout"], sg["relu"], sg["acc_scale"]
+            o.seg_out_stride_c[j], o.seg_out_off[j] = t.C * t.planes, t.off
 
     def blob(self):
         """The allocated schedule as one relocatable byte image (include/smap_hip.h "plan blob": smap_blob_header | smap_op[n]

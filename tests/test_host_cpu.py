@@ -980,3 +980,103 @@ def test_poisoned_arena_comparator_on_synthetic_buffers():
     assert torch.equal(la.arena(0xFF)[:before.numel()], before) and la.total == before.numel() + 2 * S.guard_bytes(4)      # (the absent tickets' guards)
     short = S.FilledLaunch([("x", x, 16, 5)], [("out", 1000, 32, 5)], short_in=16)
     assert short.offs == [in_off, out_off] and bool((short.arena(0x7B)[in_off + 584:in_off + 600] == 0x7B).all())
+
+
+# -- what the schedule builder enumerates: an op's operands, the arena's lifetimes, the convs of an Upsample_unit ------------------------------
+
+def _digest_tool():
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("schedule_digest", os.path.join(ROOT, "tools", "schedule_digest.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+@pytest.fixture(scope="module")
+def small_schedules(small_sd):
+    """Every 2x64x96 case of tools/schedule_digest.py (the smallest shape the builder accepts with all five levels present), built and
+    allocated with reuse=True ONCE: [(case, ops, every tensor of the arena)].  The weights go with the Graph; ops and tensors are small."""
+    from smap_amd.engine import Graph
+    T = _digest_tool()
+    out, refused = [], []
+    with pytest.MonkeyPatch.context() as mp:
+        for label, prec, kw, sw in T.small_cases():
+            for k in T.SWITCHES:
+                mp.delenv("SMAP_" + k, raising=False)
+            for k, v in sw.items():
+                mp.setenv("SMAP_" + k, v)
+            case = "%s %s %s" % (label, prec, sw)
+            try:
+                g = Graph(small_sd, *T.SMALL, precision=prec, **kw)
+            except ValueError:
+                refused.append(case)
+                continue
+            g.allocate(reuse=True)
+            out.append((case, g.ops, T.every_tensor(g)))
+    assert len(refused) == 1 and "TILE_POLICY" in refused[0] and "MERGE_1X1" not in refused[0], refused      # (the tool's list says why)
+    assert len(out) >= 60
+    return out
+
+
+def _tensor_fields(op):
+    """(field name, the Tensors in it) of every dataclass field of `op` that holds a Tensor or a list of them."""
+    import dataclasses
+    from smap_amd.engine import Tensor
+    for f in dataclasses.fields(op):
+        v = getattr(op, f.name)
+        ts = [v] if isinstance(v, Tensor) else [t for t in v if isinstance(t, Tensor)] if isinstance(v, (list, tuple)) else []
+        if ts:
+            yield f.name, ts
+
+
+def test_every_tensor_field_of_an_op_is_a_read_a_write_or_scratch(small_schedules):
+    """Graph.allocate and Graph.emit enumerate an op's tensors through Op.reads(), Op.writes() and Op.scratch only: every dataclass field of
+    Op that holds a Tensor (or a list of them) must be covered by one of the three -- over every op of the small schedules, and on a probe op
+    with a tensor of its own in EVERY field that can hold one (found from dataclasses.fields: a field added later and classified by nobody
+    fails here before a schedule uses it).  A field left out gives its tensor too short a lifetime: the packer then hands its bytes on while
+    they are still read, and nothing else fails."""
+    import dataclasses
+    from smap_amd.engine import Op, Tensor
+    seen = set()
+    for case, ops, _ in small_schedules:
+        for i, op in enumerate(ops):
+            covered = {id(t) for t in op.reads() + op.writes() + list(op.scratch)}
+            for name, ts in _tensor_fields(op):
+                seen.add(name)
+                assert all(id(t) in covered for t in ts), (case, i, name)
+    assert seen == {"out", "inp", "res", "add1", "add2", "aux", "outs", "aux2", "scratch"}       # (the schedules use every field there is)
+    can_hold = [f for f in dataclasses.fields(Op) if f.type in (Tensor, list)]
+    probe = Op(0, **{f.name: Tensor(f.name, 1, 1, 1, 8) if f.type is Tensor else [Tensor(f.name, 1, 1, 1, 8)] for f in can_hold})
+    assert {f.name for f in can_hold} == {name for name, _ in _tensor_fields(probe)} >= seen
+    covered = {id(t) for t in probe.reads() + probe.writes() + list(probe.scratch)}
+    assert all(id(t) in covered for _, ts in _tensor_fields(probe) for t in ts)
+    assert not {id(t) for t in probe.reads()} & {id(t) for t in probe.writes()} and Op(0).reads() == Op(0).writes() == []
+
+
+def test_small_schedules_have_no_live_overlap_and_keep_off_the_zero_pages(small_schedules):
+    """reuse=True: no two arena tensors (split-K scratch and the ticket region included) whose [first, last] intervals intersect share a
+    byte, every tensor is placed, and none touches a zero page or crosses a window -- in every small schedule, the all-heads and lanes ones
+    (whose side-lane operands live to the end of the schedule) included."""
+    from smap_amd.engine import WINDOW, ZERO_PAGE
+    for case, ops, every in small_schedules:
+        assert all(0 <= t.first <= t.last < len(ops) for t in every), case
+        for t in every:
+            assert t.off >= 0 and t.off % WINDOW >= ZERO_PAGE and t.off // WINDOW == (t.off + t.nbytes - 1) // WINDOW, (case, t.name)
+        live = sorted((t.first, t.last, t.off, t.off + t.nbytes, t.name) for t in every)
+        for i, a in enumerate(live):
+            for b in live[i + 1:]:
+                if b[0] > a[1]:
+                    break
+                assert a[3] <= b[2] or b[3] <= a[2], (case, a[4], b[4])
+
+
+@pytest.mark.parametrize("all_heads", [False, True], ids=["inference", "all_heads"])
+def test_merge_modes_compute_the_same_convs(small_sd, all_heads):
+    """SMAP_MERGE_1X1 = 0, 1 and 2 change how an Upsample_unit's 1x1 convs are LAUNCHED, never which convs of the reference run: the
+    sorted state-dict prefixes are the same list, with and without every head chain (policy: no skip1 + skip2 launch, no K-concatenated
+    shortcut, no tap-dot head -- mode 0 never has them)."""
+    from dataclasses import replace
+    from smap_amd.engine import Graph, SchedulePolicy
+    base = SchedulePolicy.from_env({"SMAP_CAT": "0", "SMAP_SKIPSUM": "0", "SMAP_TAPHEAD": "0"})
+    convs = [sorted(Graph(small_sd, 2, 64, 96, all_heads=all_heads, policy=replace(base, merge_1x1=m)).convs) for m in (0, 1, 2)]
+    assert convs[0] == convs[1] == convs[2] and len(convs[0]) == len(set(convs[0])) == (268 if all_heads else 206)
