@@ -748,6 +748,46 @@ int smap_loss_backward_src(const struct smap_head_src* sources, const struct sma
                            int ohkm, int topk, int ctf, int B, int S, int R, int H, int W, const void* workspace, int64_t workspace_bytes,
                            void* scratch, int64_t scratch_bytes, const float* upstream, void* stream);
 
+/* ---- the three head arms of one Upsample_unit, BN folded, in fp32: forward and its exact gradient (csrc/heads.hip) ----
+ * One unit: P = B * h * w pixels, X = the unit's `out` [P, chl], arms a = 0, 1, 2 with C_a channels (43 | 14 | 1 in the network).
+ *   forward   Z_a = X W1_a^T + b1_a      M_a = relu(Z_a)      Y_a = conv3x3(M_a, W2_a, pad 1) + b2_a
+ *   backward  gb2_a = sum_p G_a          gW2_a[c, ci, t] = sum_p G_a[p, c] M_a[p + t, ci]   (p + t inside the image)
+ *             gM_a = conv3x3^T(G_a, W2_a)   gZ_a = gM_a where Z_a > 0, else 0   gb1_a = sum_p gZ_a   gW1_a = gZ_a^T X   gX = sum_a gZ_a W1_a
+ * x: X in one of three layouts, NHWC with frames back to back (frame stride h * w * pix_stride), pix_stride in ELEMENTS and a multiple
+ *   of 4: SMAP_HEADS_X_F32 fp32, pix_stride >= chl, 16-byte aligned; SMAP_HEADS_X_F16 fp16, pix_stride >= chl, 8-byte aligned;
+ *   SMAP_HEADS_X_F16_HILO fp16 [2][chl] per pixel (the engine's x3 planes), pix_stride >= 2 * chl, value = fp32(hi) + fp32(lo).
+ * w1cat [3 * chl][chl], b1cat [3 * chl]: the three arms' folded 1x1 weights one after the other; w2 / b2: HOST arrays of three DEVICE
+ *   pointers, w2[a] [C_a][chl][3][3], b2[a] [C_a]; all dense fp32 as torch keeps them.  gw1cat, gb1cat, gw2[a], gb2[a]: the same shapes.
+ * y / g: HOST arrays of three smap_head_src, Y_a (written) and G_a (read): h x w, c = C_a in 1..64, NHWC with a padded pixel or NCHW.
+ *   Every one of the B * C_a * h * w described elements of Y_a is written exactly once; padding floats and every other byte stay.
+ * gx: fp32 NHWC [P] pixels of gx_pix_stride >= chl floats, chl written per pixel; null: not wanted, that launch is left out.
+ * workspace: 256-byte aligned, smap_heads_ws_bytes(B, h, w, chl, backward) bytes (HOST, needs no GPU), floats, every region a multiple
+ *   of 64 floats: M [P][3 * chl] (all the forward pass needs) | gZ [P][3 * chl] | part [slices][chl * max(3 * chl, 576)] |
+ *   colpart [slices][3 * chl], slices = ceil(P / L), L = 256 pixels while P <= 16384, else ceil(P / 64) rounded up to 16.
+ *   smap_heads_backward computes M again itself (it needs no earlier forward call) and leaves M and gZ there.
+ * Arithmetic: every sum is an fp32 fmaf chain from 0 in a fixed order -- Z over ci; Y and gM over (chunk of 16 channels, tap, channel); gX over
+ *   the 3 * chl columns of gZ; the pixel sums over the pixels of a slice in order, then the slices in order -- then the bias added
+ *   once.  No atomics: the same bits run to run, and the same bits whichever layout holds the same values.
+ * Launches on `stream`: forward 4, backward 12 (13 with gx).  No allocation, no synchronisation.
+ * SMAP_E_ARG: null pointers, B outside 1..65535, h * w outside 1..2^24, P above 2^26, chl outside 64..1024 or not a multiple of 64,
+ *   a stride smaller than its channels, an unknown layout, a misaligned pointer, a head descriptor of another size or with strides of
+ *   neither order, a workspace that is too small or misaligned. */
+#define SMAP_HEADS_X_F32 0
+#define SMAP_HEADS_X_F16 1
+#define SMAP_HEADS_X_F16_HILO 2
+struct smap_heads_x {
+    const void* ptr;
+    int32_t layout;
+    int32_t pix_stride;
+};
+int smap_sizeof_heads_x(void);
+int64_t smap_heads_ws_bytes(int B, int h, int w, int chl, int backward);
+int smap_heads_forward(const struct smap_heads_x* x, const float* w1cat, const float* b1cat, const float* const* w2, const float* const* b2,
+                       const struct smap_head_src* y, int B, int h, int w, int chl, void* workspace, int64_t workspace_bytes, void* stream);
+int smap_heads_backward(const struct smap_heads_x* x, const float* w1cat, const float* b1cat, const float* const* w2,
+                        const struct smap_head_src* g, int B, int h, int w, int chl, float* gw1cat, float* gb1cat, float* const* gw2,
+                        float* const* gb2, float* gx, int gx_pix_stride, void* workspace, int64_t workspace_bytes, void* stream);
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif

@@ -24,6 +24,7 @@ SOURCES = [
     ("augment.hip", ["-ffp-contract=off"]),      # training samples: the warp's coordinate map in double, the resize of csrc/prep_device.h
     ("cubic_table.cpp", ["-ffp-contract=off"]),  # host-only C++: the bicubic remap's weight table (also built alone under sanitizers)
     ("loss.hip", ["-ffp-contract=off"]),         # training loss: fixed-order double sums; its finish is csrc/loss_core.h (also built alone for the CPU)
+    ("heads.hip", ["-ffp-contract=off"]),        # head arms forward / backward in fp32: fixed-order MFMA chains, every other operation rounds once
     ("conv.hip", []),
     ("conv3.hip", []),
     ("convp.hip", []),

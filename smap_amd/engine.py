@@ -545,7 +545,7 @@ class _FreeList:
 
 class Graph:
     def __init__(self, sd, B, H, W, stage_num=3, chl=256, kpt_paf=43, paf=14, keep_ref=False, precision="f16",
-                 flip_pair=None, build=True, scaled_hms=False, all_heads=False, policy=None):
+                 flip_pair=None, build=True, scaled_hms=False, all_heads=False, policy=None, keep_unit_out=False):
         """policy: the SchedulePolicy to build under (None: the environment's, read here) -- also what the emitters below consult when a
         harness calls them.
         build=False: an EMPTY schedule with all the book-keeping in place (single-op harnesses of tests / tools append to it with
@@ -557,7 +557,10 @@ class Graph:
         all_heads: every Upsample_unit of every stage also runs its three head chains (smap.py:221-229: res_conv1 -> res_conv2,
         res_d_conv1 -> res_d_conv2, res_rd_conv1 -> res_rd_conv2) -- the 62 convs the inference schedule leaves out -- and keeps the 36
         results as fp32 tensors at the unit's own resolution to the end of the schedule (Graph.head_tensors: what the validation loss
-        reads).  The launches the inference outputs come from are the default schedule's, unchanged."""
+        reads).  The launches the inference outputs come from are the default schedule's, unchanged.
+        keep_unit_out (with all_heads): the twelve `out` tensors of the units stay allocated to the end of the schedule as well
+        (Graph.unit_out: what the head arms' fp32 forward and backward read, smap_amd/heads.py).  Nothing else changes: the same ops in
+        the same order, the arena alone grows."""
         assert precision in PRECISIONS, precision
         self.precision, self.x3 = precision, precision == "x3"
         self.policy = policy or SchedulePolicy.from_env()
@@ -567,6 +570,10 @@ class Graph:
         # association (smap_op.scale_hms) -- what the pipelines ask for; SMAP.forward keeps the raw maps of smap.py:417-419
         self.scaled_hms = bool(scaled_hms)
         self.all_heads = bool(all_heads)
+        self.keep_unit_out = bool(keep_unit_out)
+        if self.keep_unit_out and not self.all_heads:
+            raise ValueError("keep_unit_out needs all_heads=True")
+        self.unit_out = {}                    # keep_unit_out: (stage, unit) -> the unit's `out` Tensor
         self.convs = []                       # state-dict prefix of every conv of the reference the schedule computes, in build order
         self.head_tensors = {}                # all_heads: (stage, unit) -> {"heatmap_2d" | "det_d" | "root_d": Tensor, or None = the output buffer's map}
         self.keep = []                        # tensors that stay allocated to the end of the schedule whoever reads them (allocate)
@@ -1228,6 +1235,9 @@ class Graph:
         stage's inference heads).  Flip-TTA: the first `frames` frames only, the loss never reads the mirrored half."""
         if not self.all_heads:
             return
+        if self.keep_unit_out:
+            self.unit_out[(s, ind)] = out
+            self.keep.append(out)
         have = {"heatmap_2d": head_t.get(f"res{ind + 1}"), "det_d": head_t.get("res_d") if ind == 3 else None,
                 "root_d": head_t.get("res_rd") if ind == 3 else None}
         rd_in_output = ind == 3 and "res_rd_tap" in head_t       # tap-dot route: the map exists as the output buffer's NCHW block only
@@ -1512,12 +1522,13 @@ def state_hash(sd):
 BUILDER_SOURCES = ("engine.py",)
 
 
-def plan_cache_key(sd, B, H, W, stage_num, chl, kpt_paf, paf, precision, flip_pair, scaled_hms, all_heads=False, policy=None):
+def plan_cache_key(sd, B, H, W, stage_num, chl, kpt_paf, paf, precision, flip_pair, scaled_hms, all_heads=False, policy=None, keep_unit_out=False):
     import hashlib
     policy = policy or SchedulePolicy.from_env()
     h = hashlib.blake2b(digest_size=16)
     h.update(repr((state_hash(sd), B, H, W, stage_num, chl, kpt_paf, paf, precision, tuple(flip_pair) if flip_pair is not None else None,
-                   bool(scaled_hms), _L.BLOB_VERSION, C.sizeof(_L.SmapOp), _L.version(), policy.cache_token(), bool(all_heads))).encode())
+                   bool(scaled_hms), _L.BLOB_VERSION, C.sizeof(_L.SmapOp), _L.version(), policy.cache_token(), bool(all_heads))
+                  + ((True,) if keep_unit_out else ())).encode())        # (the tuple grows only where the flag is set)
     for f in BUILDER_SOURCES:
         h.update(open(os.path.join(_HERE, f), "rb").read())
     return h.hexdigest()
@@ -1550,7 +1561,7 @@ class BackboneEngine:
     """Device-resident schedule for one (B, H, W): weights, arena, output buffer, plan."""
 
     def __init__(self, state_dict, B, H, W, device, stage_num=3, chl=256, kpt_paf=43, paf=14, reuse=True,
-                 precision="f16", flip_pair=None, scaled_hms=False, all_heads=False):
+                 precision="f16", flip_pair=None, scaled_hms=False, all_heads=False, keep_unit_out=False):
         self.lib = _L.load()          # fails loudly when libsmap_hip.so is missing
         self.precision = precision
         self.device = torch.device(device)
@@ -1558,8 +1569,11 @@ class BackboneEngine:
             raise RuntimeError("BackboneEngine needs a ROCm GPU device (no CPU path in smap_amd)")
         sd = {k: v.detach().cpu() for k, v in state_dict.items()}
         self.policy = SchedulePolicy.from_env()            # what the plan is made under: the cache key, and engine.graph whenever it is built
-        self._graph_args = (sd, B, H, W, stage_num, chl, kpt_paf, paf, precision, flip_pair, scaled_hms, reuse, bool(all_heads), self.policy)
-        self.all_heads, self.stage_num = bool(all_heads), stage_num
+        self._graph_args = (sd, B, H, W, stage_num, chl, kpt_paf, paf, precision, flip_pair, scaled_hms, reuse, bool(all_heads), self.policy,
+                            bool(keep_unit_out))
+        if keep_unit_out and not all_heads:
+            raise ValueError("keep_unit_out needs all_heads=True")
+        self.all_heads, self.stage_num, self.keep_unit_out = bool(all_heads), stage_num, bool(keep_unit_out)
         self._graph = None
         self.B, self.H, self.W = B, H, W
         self.kpt_paf, self.paf = kpt_paf, paf
@@ -1567,7 +1581,8 @@ class BackboneEngine:
         cdir = plan_cache_dir() if reuse else None         # (reuse=False: debugging layouts, never cached)
         meta = None
         if cdir is not None:
-            self.cache_key = plan_cache_key(sd, B, H, W, stage_num, chl, kpt_paf, paf, precision, flip_pair, scaled_hms, all_heads, self.policy)
+            self.cache_key = plan_cache_key(sd, B, H, W, stage_num, chl, kpt_paf, paf, precision, flip_pair, scaled_hms, all_heads, self.policy,
+                                            keep_unit_out)
             meta = self._load_cached(cdir)
         if meta is None:
             g = self.graph                                 # builds and allocates the schedule
@@ -1605,9 +1620,9 @@ class BackboneEngine:
         """The schedule as Python objects (ops, tensors, weight chunks).  An engine loaded from the plan cache builds it only when somebody
         asks (profiling tools, tests, blob()): the launches themselves need the plan handle alone."""
         if self._graph is None:
-            sd, B, H, W, stage_num, chl, kpt_paf, paf, precision, flip_pair, scaled_hms, reuse, all_heads, policy = self._graph_args
+            sd, B, H, W, stage_num, chl, kpt_paf, paf, precision, flip_pair, scaled_hms, reuse, all_heads, policy, keep_unit_out = self._graph_args
             g = Graph(sd, B, H, W, stage_num, chl, kpt_paf, paf, precision=precision, flip_pair=flip_pair, scaled_hms=scaled_hms,
-                      all_heads=all_heads, policy=policy)
+                      all_heads=all_heads, policy=policy, keep_unit_out=keep_unit_out)
             g.allocate(reuse=reuse)
             self._graph = g
         return self._graph
@@ -1746,6 +1761,19 @@ class BackboneEngine:
         if not self.all_heads:
             raise RuntimeError("head_sources() needs an engine built with all_heads=True")
         return graph_head_sources(self.graph, self.arena.data_ptr(), (self.out if out is None else out).data_ptr())
+
+    def unit_out_sources(self):
+        """keep_unit_out engines: {(stage, unit): the unit's `out` of the last run}, unit 0 = up1 (the coarsest), as views of the arena
+        in the layouts smap_amd/heads.py reads: fp16 [B, h, w, 2, chl] hi|lo planes ("x3") or fp16 [B, h, w, chl] ("f16").  Flip-TTA: the
+        first B (unmirrored) frames.  Views, not copies: the next run overwrites them."""
+        if not self.keep_unit_out:
+            raise RuntimeError("unit_out_sources() needs an engine built with all_heads=True, keep_unit_out=True")
+        res = {}
+        for key, t in self.graph.unit_out.items():
+            assert t.esize == 2 and t.off >= 0
+            raw = self.arena[t.off:t.off + t.nbytes].view(torch.float16)
+            res[key] = (raw.view(t.B, t.H, t.W, 2, t.C) if t.planes == 2 else raw.view(t.B, t.H, t.W, t.C))[:self.B]
+        return res
 
     def blob(self):
         """The whole schedule as one relocatable byte image (Graph.blob): what a host without this Python builder loads with

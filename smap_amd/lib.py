@@ -31,6 +31,7 @@ SYMBOLS = [
     "smap_loss_workspace_bytes", "smap_loss_forward", "smap_loss_backward", "smap_loss_finish_host",
     "smap_sizeof_head_src", "smap_loss_src_workspace_bytes", "smap_loss_forward_src",
     "smap_loss_backward_src_scratch_bytes", "smap_loss_backward_src",
+    "smap_sizeof_heads_x", "smap_heads_ws_bytes", "smap_heads_forward", "smap_heads_backward",
 ]
 MAX_INPUTS = 8                         # SMAP_MAX_INPUTS
 
@@ -122,6 +123,12 @@ class HeadSrc(C.Structure):
                 ("ch_stride", C.c_int32), ("reserved", C.c_int32), ("frame_stride", C.c_int64)]
 
 
+class HeadsX(C.Structure):
+    """Mirror of `struct smap_heads_x`."""
+    _fields_ = [("ptr", C.c_void_p), ("layout", C.c_int32), ("pix_stride", C.c_int32)]
+
+
+HEADS_X_F32, HEADS_X_F16, HEADS_X_F16_HILO = 0, 1, 2      # SMAP_HEADS_X_*
 LABEL_C, LABEL_MAX_SCALES, LABEL_MAX_TAPS, LABEL_MAX_PERSONS = 57, 8, 16, 64      # SMAP_LABEL_*
 PREP_MAX_FRAMES = 16      # SMAP_PREP_MAX_FRAMES
 AUG_MAX_SIDE = 16384      # SMAP_AUG_MAX_SIDE
@@ -210,10 +217,15 @@ def load():
     lib.smap_loss_backward_src_scratch_bytes.argtypes = [C.POINTER(HeadSrc), ip, ip]
     lib.smap_loss_backward_src.argtypes = [C.POINTER(HeadSrc), C.POINTER(HeadSrc), vp, ip, ip, ip, ip, ip, ip, ip, ip, ip, vp, i64, vp, i64, vp, vp]
     lib.smap_loss_backward_src_scratch_bytes.restype = C.c_int64
+    lib.smap_heads_ws_bytes.argtypes = [ip, ip, ip, ip, ip]
+    lib.smap_heads_ws_bytes.restype = C.c_int64
+    lib.smap_heads_forward.argtypes = [C.POINTER(HeadsX), vp, vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(HeadSrc), ip, ip, ip, ip, vp, i64, vp]
+    lib.smap_heads_backward.argtypes = [C.POINTER(HeadsX), vp, vp, C.POINTER(vp), C.POINTER(HeadSrc), ip, ip, ip, ip, vp, vp, C.POINTER(vp),
+                                        C.POINTER(vp), vp, ip, vp, i64, vp]
     for s in SYMBOLS:
         if s not in ("smap_version", "smap_plan_destroy", "smap_nms_workspace_bytes", "smap_jpeg_workspace_bytes",
                      "smap_jpeg_huff_workspace_bytes", "smap_loss_workspace_bytes", "smap_loss_src_workspace_bytes",
-                     "smap_loss_backward_src_scratch_bytes"):  # everything else returns int
+                     "smap_loss_backward_src_scratch_bytes", "smap_heads_ws_bytes"):  # everything else returns int
             getattr(lib, s).restype = ip
     lib.smap_nms_workspace_bytes.restype = C.c_int64
     lib.smap_jpeg_workspace_bytes.restype = C.c_int64
@@ -232,6 +244,8 @@ def load():
         raise ImportError(f"smap_aug_frame layout mismatch: C {lib.smap_sizeof_aug_frame()} vs ctypes {C.sizeof(AugFrame)}")
     if lib.smap_sizeof_head_src() != C.sizeof(HeadSrc):
         raise ImportError(f"smap_head_src layout mismatch: C {lib.smap_sizeof_head_src()} vs ctypes {C.sizeof(HeadSrc)}")
+    if lib.smap_sizeof_heads_x() != C.sizeof(HeadsX):
+        raise ImportError(f"smap_heads_x layout mismatch: C {lib.smap_sizeof_heads_x()} vs ctypes {C.sizeof(HeadsX)}")
     _lib = lib
     return lib
 

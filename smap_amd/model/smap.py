@@ -140,18 +140,20 @@ class SMAP(nn.Module):
         self.invalidate_engine()
         return super()._apply(fn, *a, **k)
 
-    def engine(self, B, H, W, device, flip_pair=None, scaled_hms=False, all_heads=False):
+    def engine(self, B, H, W, device, flip_pair=None, scaled_hms=False, all_heads=False, keep_unit_out=False):
         """flip_pair: 43 channel indices (FLIP_ORDER + 15 + PAF FLIP_CHANNEL) -> an engine that runs the flip-TTA of
         test.py:55-70 inside its schedule (B frames in, merged maps of B frames out).  scaled_hms: the engine writes hms / 255 | / 127,
         the maps as test.py:111-112 hands them to dapalib (the pipelines); forward() keeps the raw maps the reference returns.  all_heads: the
-        schedule also runs the 62 training-only head convs and keeps all 36 head tensors (BackboneEngine.head_sources: the loss)."""
-        key = (B, H, W, str(device), self.precision, tuple(flip_pair) if flip_pair is not None else None, bool(scaled_hms)) + ((True,) if all_heads else ())
+        schedule also runs the 62 training-only head convs and keeps all 36 head tensors (BackboneEngine.head_sources: the loss).
+        keep_unit_out (with all_heads): the twelve units' `out` tensors stay too (BackboneEngine.unit_out_sources: smap_amd/heads.py)."""
+        key = (B, H, W, str(device), self.precision, tuple(flip_pair) if flip_pair is not None else None, bool(scaled_hms)) + ((True,) if all_heads else ()) + (("out",) if keep_unit_out else ())
         if key not in self._engines:
             if (H // 4, W // 4) != self.output_shape:
                 raise ValueError(f"input {H}x{W} does not match cfg.OUTPUT_SHAPE {self.output_shape} (stride 4)")
             self._engines[key] = BackboneEngine(self.state_dict(), B, H, W, device, self.stage_num,
                                                 self.upsample_chl_num, self.kpt_paf_num, self.paf_num,
-                                                precision=self.precision, flip_pair=flip_pair, scaled_hms=scaled_hms, all_heads=all_heads)
+                                                precision=self.precision, flip_pair=flip_pair, scaled_hms=scaled_hms, all_heads=all_heads,
+                                                keep_unit_out=keep_unit_out)
         return self._engines[key]
 
     def forward(self, imgs, valids=None, labels=None, rdepth=None):
@@ -221,3 +223,12 @@ class SMAP(nn.Module):
         mode, the current stream, no synchronisation.  Returns (dict as forward's loss branch, EngineLoss.value_and_grad's grads)."""
         crit, _, out, sources, valids, labels, rdepth = self._engine_heads(imgs, valids, labels, rdepth)
         return crit.value_and_grad(sources, valids, labels, rdepth)
+
+    def head_parameter_gradients(self, imgs, valids, labels, rdepth):
+        """The loss and its gradient at the parameters of the 72 head convs, the backbone frozen and BatchNorm in eval mode: the all-heads
+        schedule with the units' `out` tensors kept, the three head arms of every unit again in fp32 (smap_amd/heads.py UnitHeads),
+        SMAPLossNative, autograd.  Returns (losses, {state_dict key: gradient} -- conv.weight, conv.bias, bn.weight, bn.bias of each conv,
+        288 entries at three stages --, {(stage, unit): gradient at the unit's out [B, h, w, chl]}).  The last is the next seam: nothing
+        here consumes it.  Eval mode, the current stream, no synchronisation."""
+        from ..heads import head_parameter_gradients
+        return head_parameter_gradients(self, imgs, valids, labels, rdepth)
