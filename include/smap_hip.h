@@ -788,6 +788,38 @@ int smap_heads_backward(const struct smap_heads_x* x, const float* w1cat, const 
                         const struct smap_head_src* g, int B, int h, int w, int chl, float* gw1cat, float* gb1cat, float* const* gw2,
                         float* const* gb2, float* gx, int gx_pix_stride, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---- the trunk of one Upsample_unit, BN folded, in fp32: forward and its exact gradient (csrc/trunk.hip) ----
+ * out = relu(u_skip(x) + up_conv(interpolate(out_prev))) (model/smap.py Upsample_unit.forward).  P = B * h * w pixels, X [P, cin];
+ * O_prev [P', chl] at hp x wp, P' = B * hp * wp; I = bilinear align_corners interpolation hp x wp -> h x w by ATen's fp32 index and weight
+ * rule.  The rows of I sum to 1, so the 1x1 is applied at LOW resolution and the result interpolated:
+ *   forward   S = X Wu^T        U = O_prev Wc^T       O = relu((S + I(U)) + b),  b = bu + bc
+ *   backward  gPre = gO where O > 0, else 0       gb = sum_p gPre  (the gradient of bu and of bc alike)
+ *             gWu = gPre^T X    gX = gPre Wu      gU = I^T gPre [P', chl]      gWc = gU^T O_prev      gO_prev = gU Wc
+ * x, o_prev: smap_heads_x descriptors (above) of h x w pixels of cin channels and of hp x wp pixels of chl channels, any of the three
+ *   layouts.  o_prev null: the coarsest unit, no up path -- then hp and wp are 0 and wc, gwc and g_o_prev are null; otherwise none of them is.
+ * wu [chl][cin], wc [chl][chl], b [chl]: dense fp32 as torch keeps them; gwu, gwc, gb: the same shapes.  b is 16-byte aligned.
+ * o (written by forward, read by backward), g_o: dense fp32 [P][chl], 16-byte aligned.  g_o_prev: dense fp32 [P'][chl], written.
+ * gx: fp32 NHWC [P] pixels of gx_pix_stride >= cin floats, cin written per pixel; null: not wanted, that launch is left out.
+ * workspace: 256-byte aligned, smap_trunk_ws_bytes(B, h, w, hp, wp, cin, chl, backward) bytes (HOST, needs no GPU), floats, every region a
+ *   multiple of 64 floats.  forward: S [P][chl] | U [P'][chl].  backward: gPre [P][chl] | gU [P'][chl] |
+ *   part [max(slices * chl * cin, slices' * chl * chl)] | colpart [max(slices, slices')][chl] | colsum [chl], slices = ceil(P / L) by the
+ *   slice rule of the heads block, slices' the same of P'.  The backward call needs no earlier forward call: it reads o.
+ * Arithmetic: S, U, gX, gO_prev are fp32 fmaf chains from 0 over the input channels in order; gWu, gWc and gb over the pixels of a slice in
+ *   order, then the slices in order; the interpolation is ATen's tap expression ly0 (lx0 v00 + lx1 v01) + ly1 (lx0 v10 + lx1 v11); gU is
+ *   an fmaf chain from 0 of (wy * wx) * gPre over the pixels whose taps name the cell, (y, x) ascending.  No atomics: the same bits
+ *   run to run, and the same bits whichever layout holds the same values.
+ * Launches on `stream`: forward 3 (1 without an up path); backward 3 without an up path, 8 with one, + 1 with gx.  No allocation, no
+ *   synchronisation.
+ * SMAP_E_ARG, before any HIP call: null pointers, B outside 1..65535, h * w or hp * wp outside 1..2^24, P or P' above 2^26, chl outside
+ *   64..1024 or cin outside 64..4096 or either not a multiple of 64, an up path given in part (o_prev, wc, gwc, g_o_prev, hp, wp), a
+ *   stride smaller than its channels, an unknown layout, a misaligned pointer, a workspace that is too small or misaligned. */
+int64_t smap_trunk_ws_bytes(int B, int h, int w, int hp, int wp, int cin, int chl, int backward);
+int smap_trunk_forward(const struct smap_heads_x* x, const struct smap_heads_x* o_prev, const float* wu, const float* wc, const float* b,
+                       float* o, int B, int h, int w, int hp, int wp, int cin, int chl, void* workspace, int64_t workspace_bytes, void* stream);
+int smap_trunk_backward(const struct smap_heads_x* x, const struct smap_heads_x* o_prev, const float* o, const float* wu, const float* wc,
+                        const float* g_o, float* gwu, float* gwc, float* gb, float* g_o_prev, float* gx, int gx_pix_stride, int B, int h,
+                        int w, int hp, int wp, int cin, int chl, void* workspace, int64_t workspace_bytes, void* stream);
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif

@@ -25,6 +25,7 @@ SOURCES = [
     ("cubic_table.cpp", ["-ffp-contract=off"]),  # host-only C++: the bicubic remap's weight table (also built alone under sanitizers)
     ("loss.hip", ["-ffp-contract=off"]),         # training loss: fixed-order double sums; its finish is csrc/loss_core.h (also built alone for the CPU)
     ("heads.hip", ["-ffp-contract=off"]),        # head arms forward / backward in fp32: fixed-order MFMA chains, every other operation rounds once
+    ("trunk.hip", ["-ffp-contract=off"]),        # Upsample_unit trunk forward / backward in fp32: the same GEMMs (csrc/gemm_f32_device.h) and the bilinear add
     ("conv.hip", []),
     ("conv3.hip", []),
     ("convp.hip", []),

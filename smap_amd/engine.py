@@ -545,7 +545,7 @@ class _FreeList:
 
 class Graph:
     def __init__(self, sd, B, H, W, stage_num=3, chl=256, kpt_paf=43, paf=14, keep_ref=False, precision="f16",
-                 flip_pair=None, build=True, scaled_hms=False, all_heads=False, policy=None, keep_unit_out=False):
+                 flip_pair=None, build=True, scaled_hms=False, all_heads=False, policy=None, keep_unit_out=False, keep_unit_in=False):
         """policy: the SchedulePolicy to build under (None: the environment's, read here) -- also what the emitters below consult when a
         harness calls them.
         build=False: an EMPTY schedule with all the book-keeping in place (single-op harnesses of tests / tools append to it with
@@ -560,7 +560,9 @@ class Graph:
         reads).  The launches the inference outputs come from are the default schedule's, unchanged.
         keep_unit_out (with all_heads): the twelve `out` tensors of the units stay allocated to the end of the schedule as well
         (Graph.unit_out: what the head arms' fp32 forward and backward read, smap_amd/heads.py).  Nothing else changes: the same ops in
-        the same order, the arena alone grows."""
+        the same order, the arena alone grows.
+        keep_unit_in (with all_heads): the twelve INPUT tensors of the units (x4 .. x1 of every stage) stay allocated as well
+        (Graph.unit_in: what the trunk's fp32 forward and backward read, smap_amd/trunk.py).  Again the arena alone grows."""
         assert precision in PRECISIONS, precision
         self.precision, self.x3 = precision, precision == "x3"
         self.policy = policy or SchedulePolicy.from_env()
@@ -574,6 +576,10 @@ class Graph:
         if self.keep_unit_out and not self.all_heads:
             raise ValueError("keep_unit_out needs all_heads=True")
         self.unit_out = {}                    # keep_unit_out: (stage, unit) -> the unit's `out` Tensor
+        self.keep_unit_in = bool(keep_unit_in)
+        if self.keep_unit_in and not self.all_heads:
+            raise ValueError("keep_unit_in needs all_heads=True")
+        self.unit_in = {}                     # keep_unit_in: (stage, unit) -> the unit's input Tensor
         self.convs = []                       # state-dict prefix of every conv of the reference the schedule computes, in build order
         self.head_tensors = {}                # all_heads: (stage, unit) -> {"heatmap_2d" | "det_d" | "root_d": Tensor, or None = the output buffer's map}
         self.keep = []                        # tensors that stay allocated to the end of the schedule whoever reads them (allocate)
@@ -1203,6 +1209,9 @@ class Graph:
         elif heads and ind >= 1:
             with side(1):     # the 3x3 head of this unit runs beside the next unit's launches
                 head_t[f"res{ind + 1}"] = self.conv(u + ".res", [u + ".res_conv2"], got[u + ".res1"], 3, relu=False, out_fp32=True)
+        if self.keep_unit_in:
+            self.unit_in[(s, ind)] = xin
+            self.keep.append(xin)
         self._train_heads(s, ind, u, out, head_t if heads else {})
         return out, got.get(un + ".up_conv@low"), got.get(u + ".skip1"), got.get(u + ".skip2"), got.get(u + ".cross_conv")
 
@@ -1522,13 +1531,14 @@ def state_hash(sd):
 BUILDER_SOURCES = ("engine.py",)
 
 
-def plan_cache_key(sd, B, H, W, stage_num, chl, kpt_paf, paf, precision, flip_pair, scaled_hms, all_heads=False, policy=None, keep_unit_out=False):
+def plan_cache_key(sd, B, H, W, stage_num, chl, kpt_paf, paf, precision, flip_pair, scaled_hms, all_heads=False, policy=None, keep_unit_out=False,
+                   keep_unit_in=False):
     import hashlib
     policy = policy or SchedulePolicy.from_env()
     h = hashlib.blake2b(digest_size=16)
     h.update(repr((state_hash(sd), B, H, W, stage_num, chl, kpt_paf, paf, precision, tuple(flip_pair) if flip_pair is not None else None,
                    bool(scaled_hms), _L.BLOB_VERSION, C.sizeof(_L.SmapOp), _L.version(), policy.cache_token(), bool(all_heads))
-                  + ((True,) if keep_unit_out else ())).encode())        # (the tuple grows only where the flag is set)
+                  + ((True,) if keep_unit_out else ()) + (("in",) if keep_unit_in else ())).encode())        # (the tuple grows only where a flag is set)
     for f in BUILDER_SOURCES:
         h.update(open(os.path.join(_HERE, f), "rb").read())
     return h.hexdigest()
@@ -1561,7 +1571,7 @@ class BackboneEngine:
     """Device-resident schedule for one (B, H, W): weights, arena, output buffer, plan."""
 
     def __init__(self, state_dict, B, H, W, device, stage_num=3, chl=256, kpt_paf=43, paf=14, reuse=True,
-                 precision="f16", flip_pair=None, scaled_hms=False, all_heads=False, keep_unit_out=False):
+                 precision="f16", flip_pair=None, scaled_hms=False, all_heads=False, keep_unit_out=False, keep_unit_in=False):
         self.lib = _L.load()          # fails loudly when libsmap_hip.so is missing
         self.precision = precision
         self.device = torch.device(device)
@@ -1570,10 +1580,12 @@ class BackboneEngine:
         sd = {k: v.detach().cpu() for k, v in state_dict.items()}
         self.policy = SchedulePolicy.from_env()            # what the plan is made under: the cache key, and engine.graph whenever it is built
         self._graph_args = (sd, B, H, W, stage_num, chl, kpt_paf, paf, precision, flip_pair, scaled_hms, reuse, bool(all_heads), self.policy,
-                            bool(keep_unit_out))
+                            bool(keep_unit_out), bool(keep_unit_in))
         if keep_unit_out and not all_heads:
             raise ValueError("keep_unit_out needs all_heads=True")
-        self.all_heads, self.stage_num, self.keep_unit_out = bool(all_heads), stage_num, bool(keep_unit_out)
+        if keep_unit_in and not all_heads:
+            raise ValueError("keep_unit_in needs all_heads=True")
+        self.all_heads, self.stage_num, self.keep_unit_out, self.keep_unit_in = bool(all_heads), stage_num, bool(keep_unit_out), bool(keep_unit_in)
         self._graph = None
         self.B, self.H, self.W = B, H, W
         self.kpt_paf, self.paf = kpt_paf, paf
@@ -1582,7 +1594,7 @@ class BackboneEngine:
         meta = None
         if cdir is not None:
             self.cache_key = plan_cache_key(sd, B, H, W, stage_num, chl, kpt_paf, paf, precision, flip_pair, scaled_hms, all_heads, self.policy,
-                                            keep_unit_out)
+                                            keep_unit_out, keep_unit_in)
             meta = self._load_cached(cdir)
         if meta is None:
             g = self.graph                                 # builds and allocates the schedule
@@ -1620,9 +1632,9 @@ class BackboneEngine:
         """The schedule as Python objects (ops, tensors, weight chunks).  An engine loaded from the plan cache builds it only when somebody
         asks (profiling tools, tests, blob()): the launches themselves need the plan handle alone."""
         if self._graph is None:
-            sd, B, H, W, stage_num, chl, kpt_paf, paf, precision, flip_pair, scaled_hms, reuse, all_heads, policy, keep_unit_out = self._graph_args
+            sd, B, H, W, stage_num, chl, kpt_paf, paf, precision, flip_pair, scaled_hms, reuse, all_heads, policy, keep_unit_out, keep_unit_in = self._graph_args
             g = Graph(sd, B, H, W, stage_num, chl, kpt_paf, paf, precision=precision, flip_pair=flip_pair, scaled_hms=scaled_hms,
-                      all_heads=all_heads, policy=policy, keep_unit_out=keep_unit_out)
+                      all_heads=all_heads, policy=policy, keep_unit_out=keep_unit_out, keep_unit_in=keep_unit_in)
             g.allocate(reuse=reuse)
             self._graph = g
         return self._graph
@@ -1768,8 +1780,18 @@ class BackboneEngine:
         first B (unmirrored) frames.  Views, not copies: the next run overwrites them."""
         if not self.keep_unit_out:
             raise RuntimeError("unit_out_sources() needs an engine built with all_heads=True, keep_unit_out=True")
+        return self._unit_views(self.graph.unit_out)
+
+    def unit_in_sources(self):
+        """keep_unit_in engines: {(stage, unit): the unit's INPUT of the last run} -- x4 for unit 0 (up1) .. x1 for unit 3 -- as views of
+        the arena in the layouts heads.x_descriptor reads, like unit_out_sources."""
+        if not self.keep_unit_in:
+            raise RuntimeError("unit_in_sources() needs an engine built with all_heads=True, keep_unit_in=True")
+        return self._unit_views(self.graph.unit_in)
+
+    def _unit_views(self, tensors):
         res = {}
-        for key, t in self.graph.unit_out.items():
+        for key, t in tensors.items():
             assert t.esize == 2 and t.off >= 0
             raw = self.arena[t.off:t.off + t.nbytes].view(torch.float16)
             res[key] = (raw.view(t.B, t.H, t.W, 2, t.C) if t.planes == 2 else raw.view(t.B, t.H, t.W, t.C))[:self.B]

@@ -242,14 +242,42 @@ def head_parameter_keys(stage_num):
     return ["%s.%s" % (m, k) for s in range(stage_num) for ind in range(4) for pair in arm_prefixes(unit_name(s, ind)) for m in pair for k in TRAINED]
 
 
-def head_leaves(model, device=None):
-    """(leaves, frozen): fp32 copies of the model's head parameters as autograd leaves, and of the head BNs' running statistics."""
+def parameter_leaves(model, keys, device=None):
+    """(leaves, frozen): fp32 copies of the model's parameters `keys` as autograd leaves, and of their BNs' running statistics."""
     sd = model.state_dict()
-    keys = head_parameter_keys(model.stage_num)
     mv = lambda t: t.detach().to(device=device or t.device, dtype=torch.float32).clone()
     leaves = {k: mv(sd[k]).requires_grad_(True) for k in keys}
     frozen = {k[:-len("conv.weight")] + f: mv(sd[k[:-len("conv.weight")] + f]) for k in keys if k.endswith("conv.weight") for f in FROZEN}
     return leaves, frozen
+
+
+def head_leaves(model, device=None):
+    """parameter_leaves of the model's head parameters."""
+    return parameter_leaves(model, head_parameter_keys(model.stage_num), device)
+
+
+def check_trainable(model, imgs, what):
+    if model.training:
+        raise RuntimeError("%s training runs on a frozen backbone with BatchNorm in eval mode: call model.eval() first" % what)
+    if not imgs.is_cuda:
+        raise NotImplementedError("%s training runs on a ROCm GPU only: images on %s, there is no CPU fallback" % (what, imgs.device))
+
+
+def units_loss(model, params, unit_x, valids, labels, rdepth, sinks=None):
+    """UnitHeads in fp32 on unit_x(stage, unit) -- each unit's `out` -- for all 4 * stage_num units in schedule order, then SMAPLossNative.
+    sinks: None, or a dict that receives {(stage, unit): {"gx": gradient at out}} during backward().  Returns the loss dict."""
+    from .loss import SMAPLossNative
+    outputs = {k: [[None] * 4 for _ in range(model.stage_num)] for k in HEAD_KEYS}
+    for s in range(model.stage_num):
+        for ind in range(4):
+            sink = None
+            if sinks is not None:
+                sink = sinks.setdefault((s, ind), {})
+            ys = unit_heads(unit_x(s, ind), params, arm_prefixes(unit_name(s, ind)), sink=sink)
+            for k, y in zip(HEAD_KEYS, ys):
+                outputs[k][s][ind] = y
+    crit = SMAPLossNative(model.stage_num, model.ohkm, model.topk, model.ctf)
+    return crit(outputs, valids, labels, rdepth)
 
 
 def heads_loss(model, leaves, frozen, imgs, valids, labels, rdepth, sinks=None):
@@ -257,27 +285,12 @@ def heads_loss(model, leaves, frozen, imgs, valids, labels, rdepth, sinks=None):
     (keep_unit_out), UnitHeads in fp32 on each of the kept `out` tensors, SMAPLossNative.  Eval mode, the current stream, no host
     synchronisation.  sinks: None, or a dict that receives {(stage, unit): {"gx": gradient at out}} during backward().  Returns the
     loss dict (total_loss carries the graph)."""
-    from .loss import SMAPLossNative
-    if model.training:
-        raise RuntimeError("head training runs on a frozen backbone with BatchNorm in eval mode: call model.eval() first")
-    if not imgs.is_cuda:
-        raise NotImplementedError("head training runs on a ROCm GPU only: images on %s, there is no CPU fallback" % imgs.device)
+    check_trainable(model, imgs, "head")
     B, _, H, W = imgs.shape
     eng = model.engine(B, H, W, imgs.device, all_heads=True, keep_unit_out=True)       # built once: `out` does not depend on the heads
     eng.run(imgs.float(), out=eng.new_output())
     outs = eng.unit_out_sources()
-    params = {**frozen, **leaves}
-    outputs = {k: [[None] * 4 for _ in range(model.stage_num)] for k in HEAD_KEYS}
-    for s in range(model.stage_num):
-        for ind in range(4):
-            sink = None
-            if sinks is not None:
-                sink = sinks.setdefault((s, ind), {})
-            ys = unit_heads(outs[(s, ind)], params, arm_prefixes(unit_name(s, ind)), sink=sink)
-            for k, y in zip(HEAD_KEYS, ys):
-                outputs[k][s][ind] = y
-    crit = SMAPLossNative(model.stage_num, model.ohkm, model.topk, model.ctf)
-    return crit(outputs, valids, labels, rdepth)
+    return units_loss(model, {**frozen, **leaves}, lambda s, ind: outs[(s, ind)], valids, labels, rdepth, sinks)
 
 
 def head_parameter_gradients(model, imgs, valids, labels, rdepth):
@@ -290,7 +303,44 @@ def head_parameter_gradients(model, imgs, valids, labels, rdepth):
     return ({k: v.detach() for k, v in losses.items()}, {k: v.grad for k, v in leaves.items()}, {k: d["gx"] for k, d in sinks.items()})
 
 
-class HeadFineTuner:
+class FrozenBackboneTuner:
+    """What HeadFineTuner and trunk.DecoderFineTuner share: the reference's Adam (lib/utils/solver.py make_optimizer) over fp32 leaves of
+    the model's parameters `keys`, and loss / step / commit around `loss_fn(model, leaves, frozen, imgs, valids, labels, rdepth)`."""
+
+    def __init__(self, model, cfg, keys, loss_fn, lr=None, weight_decay=None, num_gpu=1, device=None):
+        solver = getattr(cfg, "SOLVER", None)
+        base, decay = getattr(solver, "BASE_LR", None), getattr(solver, "WEIGHT_DECAY", None)
+        if (lr is None and base is None) or (weight_decay is None and decay is None):
+            raise ValueError("cfg.SOLVER has no BASE_LR / WEIGHT_DECAY (this repository's inference config leaves the optimiser's entries out): "
+                             "give lr and weight_decay")
+        lr = base * num_gpu if lr is None else lr
+        weight_decay = decay if weight_decay is None else weight_decay
+        self.model, self.loss_fn = model, loss_fn
+        self.leaves, self.frozen = parameter_leaves(model, keys, device)
+        self.optimizer = torch.optim.Adam(list(self.leaves.values()), lr=lr, betas=(0.9, 0.999), eps=1e-08, weight_decay=weight_decay)
+
+    def loss(self, imgs, valids, labels, rdepth):
+        """The loss dict at the tuner's current parameters (no graph)."""
+        with torch.no_grad():
+            return self.loss_fn(self.model, self.leaves, self.frozen, imgs, valids, labels, rdepth)
+
+    def step(self, imgs, valids, labels, rdepth):
+        """One optimizer step; returns the loss dict BEFORE the step (detached device scalars, no synchronisation)."""
+        self.optimizer.zero_grad(set_to_none=True)
+        losses = self.loss_fn(self.model, self.leaves, self.frozen, imgs, valids, labels, rdepth)
+        losses["total_loss"].backward()
+        self.optimizer.step()
+        return {k: v.detach() for k, v in losses.items()}
+
+    def commit(self):
+        own = dict(self.model.named_parameters())
+        with torch.no_grad():
+            for k, v in self.leaves.items():
+                own[k].copy_(v)
+        self.model.invalidate_engine()
+
+
+class HeadFineTuner(FrozenBackboneTuner):
     """Adam on the head parameters of `model`, the backbone frozen (the common way to adapt the key-point, relative-depth and
     root-depth heads to a new camera or data set).  The optimizer is configured as the reference's lib/utils/solver.py make_optimizer
     configures it from the experiment's cfg: Adam(lr = cfg.SOLVER.BASE_LR * num_gpu, betas (0.9, 0.999), eps 1e-8,
@@ -307,33 +357,4 @@ class HeadFineTuner:
     calls model.invalidate_engine() once, so the next model(...) rebuilds its schedules from the trained weights."""
 
     def __init__(self, model, cfg, lr=None, weight_decay=None, num_gpu=1, device=None):
-        solver = getattr(cfg, "SOLVER", None)
-        base, decay = getattr(solver, "BASE_LR", None), getattr(solver, "WEIGHT_DECAY", None)
-        if (lr is None and base is None) or (weight_decay is None and decay is None):
-            raise ValueError("cfg.SOLVER has no BASE_LR / WEIGHT_DECAY (this repository's inference config leaves the optimiser's entries out): "
-                             "give lr and weight_decay")
-        lr = base * num_gpu if lr is None else lr
-        weight_decay = decay if weight_decay is None else weight_decay
-        self.model = model
-        self.leaves, self.frozen = head_leaves(model, device)
-        self.optimizer = torch.optim.Adam(list(self.leaves.values()), lr=lr, betas=(0.9, 0.999), eps=1e-08, weight_decay=weight_decay)
-
-    def loss(self, imgs, valids, labels, rdepth):
-        """The loss dict at the tuner's current parameters (no graph)."""
-        with torch.no_grad():
-            return heads_loss(self.model, self.leaves, self.frozen, imgs, valids, labels, rdepth)
-
-    def step(self, imgs, valids, labels, rdepth):
-        """One optimizer step; returns the loss dict BEFORE the step (detached device scalars, no synchronisation)."""
-        self.optimizer.zero_grad(set_to_none=True)
-        losses = heads_loss(self.model, self.leaves, self.frozen, imgs, valids, labels, rdepth)
-        losses["total_loss"].backward()
-        self.optimizer.step()
-        return {k: v.detach() for k, v in losses.items()}
-
-    def commit(self):
-        own = dict(self.model.named_parameters())
-        with torch.no_grad():
-            for k, v in self.leaves.items():
-                own[k].copy_(v)
-        self.model.invalidate_engine()
+        super().__init__(model, cfg, head_parameter_keys(model.stage_num), heads_loss, lr, weight_decay, num_gpu, device)

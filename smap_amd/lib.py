@@ -32,6 +32,7 @@ SYMBOLS = [
     "smap_sizeof_head_src", "smap_loss_src_workspace_bytes", "smap_loss_forward_src",
     "smap_loss_backward_src_scratch_bytes", "smap_loss_backward_src",
     "smap_sizeof_heads_x", "smap_heads_ws_bytes", "smap_heads_forward", "smap_heads_backward",
+    "smap_trunk_ws_bytes", "smap_trunk_forward", "smap_trunk_backward",
 ]
 MAX_INPUTS = 8                         # SMAP_MAX_INPUTS
 
@@ -222,10 +223,15 @@ def load():
     lib.smap_heads_forward.argtypes = [C.POINTER(HeadsX), vp, vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(HeadSrc), ip, ip, ip, ip, vp, i64, vp]
     lib.smap_heads_backward.argtypes = [C.POINTER(HeadsX), vp, vp, C.POINTER(vp), C.POINTER(HeadSrc), ip, ip, ip, ip, vp, vp, C.POINTER(vp),
                                         C.POINTER(vp), vp, ip, vp, i64, vp]
+    lib.smap_trunk_ws_bytes.argtypes = [ip] * 8
+    lib.smap_trunk_ws_bytes.restype = C.c_int64
+    lib.smap_trunk_forward.argtypes = [C.POINTER(HeadsX), C.POINTER(HeadsX), vp, vp, vp, vp, ip, ip, ip, ip, ip, ip, ip, vp, i64, vp]
+    lib.smap_trunk_backward.argtypes = [C.POINTER(HeadsX), C.POINTER(HeadsX), vp, vp, vp, vp, vp, vp, vp, vp, vp, ip, ip, ip, ip, ip, ip, ip, ip,
+                                        vp, i64, vp]
     for s in SYMBOLS:
         if s not in ("smap_version", "smap_plan_destroy", "smap_nms_workspace_bytes", "smap_jpeg_workspace_bytes",
                      "smap_jpeg_huff_workspace_bytes", "smap_loss_workspace_bytes", "smap_loss_src_workspace_bytes",
-                     "smap_loss_backward_src_scratch_bytes", "smap_heads_ws_bytes"):  # everything else returns int
+                     "smap_loss_backward_src_scratch_bytes", "smap_heads_ws_bytes", "smap_trunk_ws_bytes"):  # everything else returns int
             getattr(lib, s).restype = ip
     lib.smap_nms_workspace_bytes.restype = C.c_int64
     lib.smap_jpeg_workspace_bytes.restype = C.c_int64

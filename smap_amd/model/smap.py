@@ -140,20 +140,21 @@ class SMAP(nn.Module):
         self.invalidate_engine()
         return super()._apply(fn, *a, **k)
 
-    def engine(self, B, H, W, device, flip_pair=None, scaled_hms=False, all_heads=False, keep_unit_out=False):
+    def engine(self, B, H, W, device, flip_pair=None, scaled_hms=False, all_heads=False, keep_unit_out=False, keep_unit_in=False):
         """flip_pair: 43 channel indices (FLIP_ORDER + 15 + PAF FLIP_CHANNEL) -> an engine that runs the flip-TTA of
         test.py:55-70 inside its schedule (B frames in, merged maps of B frames out).  scaled_hms: the engine writes hms / 255 | / 127,
         the maps as test.py:111-112 hands them to dapalib (the pipelines); forward() keeps the raw maps the reference returns.  all_heads: the
         schedule also runs the 62 training-only head convs and keeps all 36 head tensors (BackboneEngine.head_sources: the loss).
-        keep_unit_out (with all_heads): the twelve units' `out` tensors stay too (BackboneEngine.unit_out_sources: smap_amd/heads.py)."""
-        key = (B, H, W, str(device), self.precision, tuple(flip_pair) if flip_pair is not None else None, bool(scaled_hms)) + ((True,) if all_heads else ()) + (("out",) if keep_unit_out else ())
+        keep_unit_out (with all_heads): the twelve units' `out` tensors stay too (BackboneEngine.unit_out_sources: smap_amd/heads.py);
+        keep_unit_in (with all_heads): and the units' input tensors x4 .. x1 (BackboneEngine.unit_in_sources: smap_amd/trunk.py)."""
+        key = (B, H, W, str(device), self.precision, tuple(flip_pair) if flip_pair is not None else None, bool(scaled_hms)) + ((True,) if all_heads else ()) + (("out",) if keep_unit_out else ()) + (("in",) if keep_unit_in else ())
         if key not in self._engines:
             if (H // 4, W // 4) != self.output_shape:
                 raise ValueError(f"input {H}x{W} does not match cfg.OUTPUT_SHAPE {self.output_shape} (stride 4)")
             self._engines[key] = BackboneEngine(self.state_dict(), B, H, W, device, self.stage_num,
                                                 self.upsample_chl_num, self.kpt_paf_num, self.paf_num,
                                                 precision=self.precision, flip_pair=flip_pair, scaled_hms=scaled_hms, all_heads=all_heads,
-                                                keep_unit_out=keep_unit_out)
+                                                keep_unit_out=keep_unit_out, keep_unit_in=keep_unit_in)
         return self._engines[key]
 
     def forward(self, imgs, valids=None, labels=None, rdepth=None):
@@ -232,3 +233,12 @@ class SMAP(nn.Module):
         here consumes it.  Eval mode, the current stream, no synchronisation."""
         from ..heads import head_parameter_gradients
         return head_parameter_gradients(self, imgs, valids, labels, rdepth)
+
+    def decoder_parameter_gradients(self, imgs, valids, labels, rdepth):
+        """The loss and its gradient at the whole decoder of the last stage and the heads of the stages before it, the ResNets frozen:
+        head_parameter_gradients with the last stage's four trunks (u_skip, up_conv) run again in fp32 from the engine's kept x4 .. x1
+        (smap_amd/trunk.py UnitTrunk).  Returns (losses, {state_dict key: gradient} -- the 288 head entries and the 28 trunk entries of the
+        last stage --, [gradients at the last stage's x4, x3, x2, x1, [B, h, w, Cin] fp32]).  Eval mode, the current stream, no
+        synchronisation."""
+        from ..trunk import decoder_parameter_gradients
+        return decoder_parameter_gradients(self, imgs, valids, labels, rdepth)
