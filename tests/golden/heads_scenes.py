@@ -4,7 +4,9 @@ tests, so it imports neither the reference nor this repository's package: numpy,
 
 Shapes are the smallest at which each thing can still go wrong: 2x3 (every pixel is border), 5x7 (odd, 70 pixels: a ragged tile in both
 kernels), 16x24 (the small network's finest level, 768 pixels: three reduction slices), 33x41 (2706 pixels: eleven slices of 256, the
-last of 146).  chl 64 and 256; C = (43, 14, 1); B = 2.
+last of 146), 91x91 (16562 pixels, above the 16384 up to which a slice has 256: 61 slices of 272, the last of 242, whose last k-step
+of 16 holds 2), 9x15 at chl 320 (two column tiles of 256 times nine taps in gW2; ragged 128-wide tiles at N = 960 and 320).  chl 64, 256
+and 320; C = (43, 14, 1); B = 2.
 
 X is drawn post-ReLU: relu(N(0, 1)), about half of it zero.  G_a ~ N(0, 1) * g_scale with g_scale = 3e-7: most of it below fp16's
 smallest normal number (6.1e-5) and a good part below its smallest subnormal (6e-8), as loss gradients are.
@@ -35,6 +37,8 @@ SCENES = {
     "o5x7w": dict(h=5, w=7, chl=256, unit="stage2.upsample.up1", seed=103),
     "f16x24": dict(h=16, w=24, chl=256, unit="stage2.upsample.up4", seed=104),
     "s33x41": dict(h=33, w=41, chl=64, unit="stage0.upsample.up3", seed=105),
+    "l91x91": dict(h=91, w=91, chl=64, unit="stage1.upsample.up4", seed=106),
+    "w9x15": dict(h=9, w=15, chl=320, unit="stage2.upsample.up2", seed=107),
 }
 FULL_Y = ("b2x3", "o5x7", "o5x7w")           # scenes whose head tensors the golden file keeps whole
 PARAM_KINDS = ("conv.weight", "conv.bias", "bn.weight", "bn.bias")       # what is trained; the running statistics stay frozen

@@ -10,6 +10,9 @@ torch and the weight recipe only.
     d      3    8x12 -> 16x24        256   256   the small network's up4
     e      0    2x3                 2048   256   longest K, widest N, one slice
     f      2    17x21 -> 33x41        64    64   eleven reduction slices, the last ragged
+    g      3    46x46 -> 91x91        64    64   16562 pixels: 61 slices of 272 (the last of 242) on gWu and gb; 17 of 256 on gWc
+    h      1    4x6 -> 4x6           192   320   identity interpolation; 80 channel quads, no power of two; ragged 128-wide column tiles
+    i      2    2x3 -> 7x10           64    64   ratios 3.5 and 3.33: many pixels inside one cell's range, one-sided ranges at the border
 
 X and O_prev are drawn post-ReLU: relu(N(0, 1)).  G ~ N(0, 1) * 3e-7, as loss gradients are.
 
@@ -38,6 +41,9 @@ SCENES = {
     "d": dict(ind=3, h=16, w=24, hp=8, wp=12, cin=256, chl=256, unit="stage2.upsample.up4", seed=204),
     "e": dict(ind=0, h=2, w=3, hp=0, wp=0, cin=2048, chl=256, unit="stage2.upsample.up1", seed=205),
     "f": dict(ind=2, h=33, w=41, hp=17, wp=21, cin=64, chl=64, unit="stage2.upsample.up3", seed=206),
+    "g": dict(ind=3, h=91, w=91, hp=46, wp=46, cin=64, chl=64, unit="stage2.upsample.up4", seed=207),
+    "h": dict(ind=1, h=4, w=6, hp=4, wp=6, cin=192, chl=320, unit="stage2.upsample.up2", seed=208),
+    "i": dict(ind=2, h=7, w=10, hp=2, wp=3, cin=64, chl=64, unit="stage2.upsample.up3", seed=209),
 }
 FULL_O = ("a", "b", "c")                     # scenes whose out tensor the golden file keeps whole
 PARAM_KINDS = ("conv.weight", "conv.bias", "bn.weight", "bn.bias")

@@ -7,14 +7,36 @@
 
 Every function is one launch of the library and takes that launch's inputs; called on magnitudes (absolute values, no bias sign) the
 same function gives sum |a * b|, the quantity the fp32 chain bound  |err| <= (K + 2) * 2^-24 * sum |a * b|  is stated in (K: the
-launch's reduction length; K fused multiply-adds and one bias addition, each within 2^-24 relative).
+launch's reduction length; K fused multiply-adds and one bias addition, each within 2^-24 relative).  A reduction over the P pixels
+is not one chain of P terms: it is sliced, and its K is red_chain(P).
 Layouts: X, Z, M, gZ, gX are [B, h, w, channels]; heads and their gradients [B, C_a, h, w]; weights as torch keeps them.
 """
 import torch
 import torch.nn.functional as F
 
+from smap_amd.heads import slice_len
+
 U = 2.0 ** -24
 TAPS = [(ky, kx) for ky in range(3) for kx in range(3)]
+
+
+def K_red(P):
+    """slice_len(P) + slices(P): the chain length of a reduction over P pixels (reduce_gemm + reduce_fold; gW and the column sums gb
+    alike).  Within a slice every output is ONE fmaf chain of at most slice_len terms, k ascending -- rows beyond the slice's end add
+    exact zeros -- and reduce_fold then adds the `slices` parts in order: K_red roundings on any term, so
+    |err| <= gamma_K sum |a * b| <= (K_red + 2) * 2^-24 * sum |a * b|  while  K_red^2 * 2^-24 <= 2, which is asserted here: it holds up
+    to about 3.7e5 pixels (K_red = 5792), not for every P the library admits, and not for K = P itself from P = 5793 on."""
+    n = slice_len(P)
+    k = n + -(-P // n)
+    assert k * k * U <= 2, (P, k)
+    return k
+
+
+def red_chain(P):
+    """The K of a reduction's bound: min(P, K_red(P)).  Up to slice_len pixels the one slice is a chain of P terms and the fold adds
+    it to zero exactly, and in any order of summation no term of a sum of P products is rounded more than P times; P is the smaller
+    of the two only below 260 pixels.  Never larger than the P the bounds used before."""
+    return min(P, K_red(P))
 
 
 def z_launch(x, w1cat, b1cat):
@@ -93,15 +115,15 @@ def forward_bounds(x, w1cat, b1cat, w2, b2, z):
 def backward_bounds(x, w1cat, w2, g, z, mask, e_m):
     """Bounds for the composed backward given the mask both sides use and e_M of forward_bounds, each launch's chain bound on its own
     (perturbed) inputs plus the perturbation carried through: dict like backward's."""
-    chl, P = x.shape[-1], x.shape[0] * x.shape[1] * x.shape[2]
+    chl, K = x.shape[-1], red_chain(x.shape[0] * x.shape[1] * x.shape[2])
     m, em = arms(torch.relu(z), chl), arms(e_m, chl)
     out = {"gw2": [], "gb2": []}
     gz_mag, e_gz = [], []
     for a in range(3):
         ga = g[a].abs()
         gw_mag, gb_mag = gw2_launch(ga, m[a] + em[a])
-        out["gw2"].append((P + 2) * U * gw_mag + gw2_launch(ga, em[a])[0])
-        out["gb2"].append((P + 2) * U * gb_mag)
+        out["gw2"].append((K + 2) * U * gw_mag + gw2_launch(ga, em[a])[0])
+        out["gb2"].append((K + 2) * U * gb_mag)
         mag = gm_launch(ga, w2[a].abs())
         gz_mag.append(mag)
         e_gz.append((9 * g[a].shape[1] + 2) * U * mag)
@@ -109,7 +131,7 @@ def backward_bounds(x, w1cat, w2, g, z, mask, e_m):
     out["gz"] = e_gz
     w_mag, b_mag = gw1_launch(gz_mag + e_gz, x.abs())
     w_e, b_e = gw1_launch(e_gz, x.abs())
-    out["gw1"], out["gb1"] = (P + 2) * U * w_mag + w_e, (P + 2) * U * b_mag + b_e
+    out["gw1"], out["gb1"] = (K + 2) * U * w_mag + w_e, (K + 2) * U * b_mag + b_e
     out["gx"] = (3 * chl + 2) * U * gx_launch(gz_mag + e_gz, w1cat.abs()) + gx_launch(e_gz, w1cat.abs())
     return out
 

@@ -100,9 +100,19 @@ def test_scene_pixels_span_ragged_slices():
     P = HS.B * s["h"] * s["w"]
     lay = H.workspace_layout(HS.B, s["h"], s["w"], s["chl"], True)
     assert lay["slices"] >= 3 and P % lay["slice_len"] != 0 and P % 128 != 0 and P % 256 != 0
+    # l91x91: above the 16384 pixels up to which a slice has 256 -- 61 slices of 272, the last of 242, whose last k-step of 16 is ragged
+    s = HS.SCENES["l91x91"]
+    P = HS.B * s["h"] * s["w"]
+    lay = H.workspace_layout(HS.B, s["h"], s["w"], s["chl"], True)
+    assert P > 16384 and lay["slice_len"] == 272 and lay["slices"] == 61 and P % lay["slice_len"] == 242 and 242 % 16 != 0 and P % 128 != 0
+    assert R.K_red(P) == 272 + 61 and R.red_chain(P) == 333 and R.red_chain(70) == 70 and R.red_chain(2706) == 256 + 11
+    # w9x15: more than one 256-wide column tile beside the nine taps of gW2, and more than one slice
+    s = HS.SCENES["w9x15"]
+    assert s["chl"] > 256 and H.workspace_layout(HS.B, s["h"], s["w"], s["chl"], True)["slices"] >= 2
 
 
-@pytest.mark.parametrize("dims", [(2, 2, 3, 64), (2, 5, 7, 256), (2, 33, 41, 64), (1, 1, 1, 128), (8, 128, 208, 256), (3, 100, 171, 192)])
+@pytest.mark.parametrize("dims", [(2, 2, 3, 64), (2, 5, 7, 256), (2, 33, 41, 64), (1, 1, 1, 128), (8, 128, 208, 256), (3, 100, 171, 192),
+                                  (2, 91, 91, 64), (2, 9, 15, 320)])
 @pytest.mark.parametrize("backward", [0, 1])
 def test_ws_bytes_matches_python_layout(dims, backward):
     B, h, w, chl = dims

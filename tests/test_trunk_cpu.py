@@ -11,6 +11,7 @@ import torch
 import trunk_restate as R
 import trunk_scenes as TS
 import smap_amd.lib as L
+from smap_amd import heads as H
 from smap_amd import trunk as T
 
 RTOL = 1e-12           # of the tensor's largest magnitude: both sides are float64 and differ in summation order only
@@ -110,10 +111,24 @@ def test_scene_pixels_span_ragged_slices():
     assert lay["slices"] == 11 and lay["P"] % 256 != 0 and lay["slices_lo"] == 3 and lay["Pl"] % 256 != 0
     s = TS.SCENES["e"]
     assert T.workspace_layout(TS.B, s["h"], s["w"], 0, 0, s["cin"], s["chl"], True)["slices"] == 1
+    # g: long slices at high resolution (61 of 272, the last of 242, its last k-step of 16 ragged), slices of 256 at low resolution
+    s = TS.SCENES["g"]
+    lay = T.workspace_layout(TS.B, s["h"], s["w"], s["hp"], s["wp"], s["cin"], s["chl"], True)
+    n = H.slice_len(lay["P"])
+    assert lay["P"] > 16384 and n == 272 and lay["slices"] == 61 and lay["P"] % n == 242 and 242 % 16 != 0
+    assert lay["slices_lo"] >= 2 and H.slice_len(lay["Pl"]) == 256 and lay["Pl"] % 256 != 0
+    assert R.K_red(lay["P"]) == 333 and R.red_chain(lay["Pl"]) == 256 + lay["slices_lo"]
+    # h: identity interpolation, and a quad count that is no power of two
+    s = TS.SCENES["h"]
+    assert s["hp"] == s["h"] and s["wp"] == s["w"] and (s["chl"] // 4) & (s["chl"] // 4 - 1) != 0
+    # i: both ratios above 2, so a cell's range holds pixels whose two taps both lie strictly inside it
+    s = TS.SCENES["i"]
+    assert (s["h"] - 1) / (s["hp"] - 1) > 2 and (s["w"] - 1) / (s["wp"] - 1) > 2
 
 
 DIMS = [(2, 2, 3, 0, 0, 64, 64), (2, 5, 7, 3, 4, 128, 64), (2, 33, 41, 17, 21, 64, 64), (1, 1, 1, 1, 1, 64, 128), (8, 128, 208, 64, 104, 256, 256),
-        (8, 16, 26, 0, 0, 2048, 256), (3, 100, 171, 50, 86, 512, 192), (2, 4, 4, 16, 16, 4096, 1024)]
+        (8, 16, 26, 0, 0, 2048, 256), (3, 100, 171, 50, 86, 512, 192), (2, 4, 4, 16, 16, 4096, 1024),
+        (2, 91, 91, 46, 46, 64, 64), (2, 4, 6, 4, 6, 192, 320), (2, 7, 10, 2, 3, 64, 64)]
 
 
 @pytest.mark.parametrize("dims", DIMS)

@@ -17,6 +17,7 @@ import heads_restate as HR
 import trunk_scenes as TS
 
 U = 2.0 ** -24
+K_red, red_chain = HR.K_red, HR.red_chain          # the chain length of a reduction over the pixels: sliced here as in the head arms
 
 
 class Interp:
@@ -96,18 +97,18 @@ def backward_bounds(x, o_prev, wu, wc, g, mask, it):
     """Bounds for the composed backward given the mask both sides use: each launch's chain bound on its own (perturbed) inputs plus the
     perturbation carried through.  gPre is a selection: exact."""
     chl = wu.shape[0]
-    P = x.shape[0] * x.shape[1] * x.shape[2]
+    K = red_chain(x.shape[0] * x.shape[1] * x.shape[2])          # the sliced reduction's chain length, not the pixel count
     ga = (g * mask).abs()
     out = {"gpre": torch.zeros_like(ga)}
     w_mag, b_mag = reduce_launch(ga, x.abs())
-    out["gwu"], out["gb"] = (P + 2) * U * w_mag, (P + 2) * U * b_mag
+    out["gwu"], out["gb"] = (K + 2) * U * w_mag, (K + 2) * U * b_mag
     out["gx"] = (chl + 2) * U * (ga @ wu.abs())
     if o_prev is not None:
-        Pl = o_prev.shape[0] * o_prev.shape[1] * o_prev.shape[2]
+        Kl = red_chain(o_prev.shape[0] * o_prev.shape[1] * o_prev.shape[2])
         gu_mag = it.down(ga)
         e_gu = (it.taps[None, :, :, None] + 3) * U * gu_mag
         out["gu"] = e_gu
-        out["gwc"] = (Pl + 2) * U * reduce_launch(gu_mag + e_gu, o_prev.abs())[0] + reduce_launch(e_gu, o_prev.abs())[0]
+        out["gwc"] = (Kl + 2) * U * reduce_launch(gu_mag + e_gu, o_prev.abs())[0] + reduce_launch(e_gu, o_prev.abs())[0]
         out["gprev"] = (chl + 2) * U * ((gu_mag + e_gu) @ wc.abs()) + e_gu @ wc.abs()
     return out
 
