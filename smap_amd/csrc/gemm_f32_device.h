@@ -342,6 +342,9 @@ int take_x(const smap_heads_x* x, int h, int w, int C, Pix& out)
     return 0;
 }
 bool bad_f32(const void* p) { return !p || ((uintptr_t)p & 3); }
+bool bad_image(int B, int h, int w) { return B < 1 || B > 65535 || h < 1 || w < 1 || (int64_t)h * w > (1 << 24) || (int64_t)B * h * w > (1 << 26); }
+// a workspace of `floats` floats: 256-byte aligned, ws_bytes long at least
+bool bad_ws(const void* ws, int64_t ws_bytes, int64_t floats) { return !ws || ((uintptr_t)ws & 255) || ws_bytes < floats * 4; }
 
 Pix dense(const float* p, int hw, int pix_stride, int C)
 {

@@ -38,7 +38,7 @@ Layout layout_of(int64_t P, int chl, int backward)
 }
 bool bad_dims(int B, int h, int w, int chl)
 {
-    return B < 1 || B > 65535 || h < 1 || w < 1 || (int64_t)h * w > (1 << 24) || (int64_t)B * h * w > (1 << 26) || chl < 64 || chl > 1024 || chl % 64;
+    return bad_image(B, h, w) || chl < 64 || chl > 1024 || chl % 64;
 }
 // the three head tensors of a unit (c = 1 .. 64 each, h x w); 0 or SMAP_E_ARG
 int take_heads(const smap_head_src* s, int h, int w, Pix out[3])
@@ -56,7 +56,6 @@ int take_heads(const smap_head_src* s, int h, int w, Pix out[3])
     }
     return 0;
 }
-bool bad_ws(const void* ws, int64_t ws_bytes, const Layout& l) { return !ws || ((uintptr_t)ws & 255) || ws_bytes < l.floats * 4; }
 
 RedWs red_ws(const Layout& l, float* ws) { return RedWs{ws + l.part, ws + l.colpart, l.slices, l.slice_len}; }
 // M = relu(X W1cat^T + b1cat) into the workspace
@@ -90,7 +89,7 @@ int smap_heads_forward(const smap_heads_x* x, const float* w1cat, const float* b
     for (int a = 0; a < 3; ++a)
         if (bad_f32(w2[a]) || bad_f32(b2[a])) return SMAP_E_ARG;
     const Layout l = layout_of((int64_t)B * h * w, chl, 0);
-    if (bad_ws(workspace, workspace_bytes, l)) return SMAP_E_ARG;
+    if (bad_ws(workspace, workspace_bytes, l.floats)) return SMAP_E_ARG;
     float* ws = (float*)workspace;
     hipStream_t st = (hipStream_t)stream;
     if (int rc = launch_m(px, w1cat, b1cat, B, h, w, chl, ws + l.m, st)) return rc;
@@ -116,7 +115,7 @@ int smap_heads_backward(const smap_heads_x* x, const float* w1cat, const float* 
         if (bad_f32(w2[a]) || bad_f32(gw2[a]) || bad_f32(gb2[a])) return SMAP_E_ARG;
     if (gx && (((uintptr_t)gx & 3) || gx_pix_stride < chl)) return SMAP_E_ARG;          // gx null: that gradient is not wanted
     const Layout l = layout_of((int64_t)B * h * w, chl, 1);
-    if (bad_ws(workspace, workspace_bytes, l)) return SMAP_E_ARG;
+    if (bad_ws(workspace, workspace_bytes, l.floats)) return SMAP_E_ARG;
     float* ws = (float*)workspace;
     hipStream_t st = (hipStream_t)stream;
     const int hw = h * w;

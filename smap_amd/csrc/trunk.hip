@@ -134,16 +134,14 @@ Layout layout_of(int64_t P, int64_t Pl, int cin, int chl, int backward)
     l.floats += G::round64(chl);
     return l;
 }
-bool bad_image(int B, int h, int w) { return B < 1 || B > 65535 || h < 1 || w < 1 || (int64_t)h * w > (1 << 24) || (int64_t)B * h * w > (1 << 26); }
 // hp == 0 and wp == 0: no up path
 bool bad_dims(int B, int h, int w, int hp, int wp, int cin, int chl)
 {
-    if (bad_image(B, h, w) || chl < 64 || chl > 1024 || chl % 64 || cin < 64 || cin > 4096 || cin % 64) return true;
+    if (G::bad_image(B, h, w) || chl < 64 || chl > 1024 || chl % 64 || cin < 64 || cin > 4096 || cin % 64) return true;
     if (hp == 0 && wp == 0) return false;
-    return bad_image(B, hp, wp);
+    return G::bad_image(B, hp, wp);
 }
 bool bad_f32x4(const void* p) { return !p || ((uintptr_t)p & 15); }
-bool bad_ws(const void* ws, int64_t ws_bytes, const Layout& l) { return !ws || ((uintptr_t)ws & 255) || ws_bytes < l.floats * 4; }
 unsigned blocks_of(long long threads) { return (unsigned)((threads + NT - 1) / NT); }
 
 // out [P][out_ps] (N channels written) = a W (+ bias, relu), W element (k, n) at w[k * ks + n * ns]
@@ -176,7 +174,7 @@ int smap_trunk_forward(const smap_heads_x* x, const smap_heads_x* o_prev, const 
     Pix px, pl;
     if (G::take_x(x, h, w, cin, px) || (up && G::take_x(o_prev, hp, wp, chl, pl))) return SMAP_E_ARG;
     const Layout l = layout_of((int64_t)B * h * w, (int64_t)B * hp * wp, cin, chl, 0);
-    if (bad_ws(workspace, workspace_bytes, l)) return SMAP_E_ARG;
+    if (G::bad_ws(workspace, workspace_bytes, l.floats)) return SMAP_E_ARG;
     float* ws = (float*)workspace;
     hipStream_t st = (hipStream_t)stream;
     if (!up) return launch_1x1(px, wu, 1, cin, cin, chl, b, 1, o, chl, B, h, w, st);             // O = relu(X Wu^T + b)
@@ -199,7 +197,7 @@ int smap_trunk_backward(const smap_heads_x* x, const smap_heads_x* o_prev, const
     Pix px, pl;
     if (G::take_x(x, h, w, cin, px) || (up && G::take_x(o_prev, hp, wp, chl, pl))) return SMAP_E_ARG;
     const Layout l = layout_of((int64_t)B * h * w, (int64_t)B * hp * wp, cin, chl, 1);
-    if (bad_ws(workspace, workspace_bytes, l)) return SMAP_E_ARG;
+    if (G::bad_ws(workspace, workspace_bytes, l.floats)) return SMAP_E_ARG;
     float* ws = (float*)workspace;
     hipStream_t st = (hipStream_t)stream;
     const long long P = (long long)B * h * w;

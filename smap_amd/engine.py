@@ -1784,7 +1784,7 @@ class BackboneEngine:
 
     def unit_in_sources(self):
         """keep_unit_in engines: {(stage, unit): the unit's INPUT of the last run} -- x4 for unit 0 (up1) .. x1 for unit 3 -- as views of
-        the arena in the layouts heads.x_descriptor reads, like unit_out_sources."""
+        the arena in the layouts gemm_f32.x_descriptor reads, like unit_out_sources."""
         if not self.keep_unit_in:
             raise RuntimeError("unit_in_sources() needs an engine built with all_heads=True, keep_unit_in=True")
         return self._unit_views(self.graph.unit_in)

@@ -227,11 +227,11 @@ class SMAP(nn.Module):
 
     def head_parameter_gradients(self, imgs, valids, labels, rdepth):
         """The loss and its gradient at the parameters of the 72 head convs, the backbone frozen and BatchNorm in eval mode: the all-heads
-        schedule with the units' `out` tensors kept, the three head arms of every unit again in fp32 (smap_amd/heads.py UnitHeads),
+        schedule with the units' `out` tensors kept, the three head arms of every unit again in fp32 (smap_amd/heads.py UnitHeads; smap_amd/finetune.py),
         SMAPLossNative, autograd.  Returns (losses, {state_dict key: gradient} -- conv.weight, conv.bias, bn.weight, bn.bias of each conv,
         288 entries at three stages --, {(stage, unit): gradient at the unit's out [B, h, w, chl]}).  The last is the next seam: nothing
         here consumes it.  Eval mode, the current stream, no synchronisation."""
-        from ..heads import head_parameter_gradients
+        from ..finetune import head_parameter_gradients
         return head_parameter_gradients(self, imgs, valids, labels, rdepth)
 
     def decoder_parameter_gradients(self, imgs, valids, labels, rdepth):
@@ -240,5 +240,5 @@ class SMAP(nn.Module):
         (smap_amd/trunk.py UnitTrunk).  Returns (losses, {state_dict key: gradient} -- the 288 head entries and the 28 trunk entries of the
         last stage --, [gradients at the last stage's x4, x3, x2, x1, [B, h, w, Cin] fp32]).  Eval mode, the current stream, no
         synchronisation."""
-        from ..trunk import decoder_parameter_gradients
+        from ..finetune import decoder_parameter_gradients
         return decoder_parameter_gradients(self, imgs, valids, labels, rdepth)

@@ -14,7 +14,7 @@ Layouts: X, Z, M, gZ, gX are [B, h, w, channels]; heads and their gradients [B, 
 import torch
 import torch.nn.functional as F
 
-from smap_amd.heads import slice_len
+from smap_amd.gemm_f32 import slice_len
 
 U = 2.0 ** -24
 TAPS = [(ky, kx) for ky in range(3) for kx in range(3)]
@@ -136,10 +136,12 @@ def backward_bounds(x, w1cat, w2, g, z, mask, e_m):
     return out
 
 
-def fold(p, eps=1e-5):
-    """Folded (w', b') of one conv_bn_relu: p = dict of conv.weight, conv.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var."""
+def fold(p, eps=1e-5, matrix=False):
+    """Folded (w', b') of one conv_bn_relu: p = dict of conv.weight, conv.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var.
+    matrix: w' as [out, in * taps] (what the trunk's 1x1 GEMMs take)."""
     s = p["bn.weight"] / torch.sqrt(p["bn.running_var"] + eps)
-    return p["conv.weight"] * s.view(-1, 1, 1, 1), (p["conv.bias"] - p["bn.running_mean"]) * s + p["bn.bias"]
+    w = p["conv.weight"] * s.view(-1, 1, 1, 1)
+    return (w.flatten(1) if matrix else w), (p["conv.bias"] - p["bn.running_mean"]) * s + p["bn.bias"]
 
 
 def unfold_grads(p, gw, gb, eps=1e-5, magnitudes=False):

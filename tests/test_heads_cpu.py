@@ -11,7 +11,9 @@ import torch
 import heads_restate as R
 import heads_scenes as HS
 import smap_amd.lib as L
+from smap_amd import gemm_f32 as G
 from smap_amd import heads as H
+from train_kit import FAKE, set_attr as _set, set_fields as _d
 
 RTOL = 1e-12           # of the tensor's largest magnitude: both sides are float64 and differ in summation order only
 
@@ -128,9 +130,6 @@ def test_ws_bytes_rejects(dims):
     assert L.load().smap_heads_ws_bytes(*dims, 1) == -1
 
 
-FAKE = 0x7F0000000000            # never dereferenced: every call below is refused before any HIP call
-
-
 class Args:
     """A valid argument set of both calls on fake pointers; one field is broken per case."""
 
@@ -166,10 +165,6 @@ class Args:
                                       ws_bytes, None)
 
 
-def _set(name, value):
-    return lambda a: setattr(a, name, value)
-
-
 def _item(name, i, value):
     return lambda a: getattr(a, name).__setitem__(i, value)
 
@@ -178,17 +173,10 @@ def _head(i, field, value):
     return lambda a: a.heads[i].__setitem__(field, value)
 
 
-def _x(**kw):
-    def f(a):
-        for k, v in kw.items():
-            setattr(a.x, k, v)
-    return f
-
-
 BOTH = {
-    "x null": lambda a: a.null.add("x"), "x ptr null": _x(ptr=None), "x misaligned": _x(ptr=FAKE + 8), "x layout": _x(layout=3),
-    "x stride below chl": _x(pix_stride=60), "x stride not 4n": _x(pix_stride=66),
-    "x f16 misaligned": _x(ptr=FAKE + 4, layout=L.HEADS_X_F16), "x hilo stride below 2 chl": _x(layout=L.HEADS_X_F16_HILO, pix_stride=64),
+    "x null": lambda a: a.null.add("x"), "x ptr null": _d("x", ptr=None), "x misaligned": _d("x", ptr=FAKE + 8), "x layout": _d("x", layout=3),
+    "x stride below chl": _d("x", pix_stride=60), "x stride not 4n": _d("x", pix_stride=66),
+    "x f16 misaligned": _d("x", ptr=FAKE + 4, layout=L.HEADS_X_F16), "x hilo stride below 2 chl": _d("x", layout=L.HEADS_X_F16_HILO, pix_stride=64),
     "w1 null": _set("w1", None), "w1 misaligned": _set("w1", FAKE + 2), "b1 null": _set("b1", None),
     "w2 null": lambda a: a.null.add("w2"), "w2[1] null": _item("w2", 1, None), "w2[2] misaligned": _item("w2", 2, FAKE + 1),
     "heads null": lambda a: a.null.add("heads"), "head ptr null": _head(0, 0, None), "head misaligned": _head(1, 0, FAKE + 2),
@@ -228,7 +216,7 @@ def test_fold_bn_is_the_restatement_fold_and_differentiable():
     sd = {k: v.double() for k, v in HS.weights(name).items()}
     m = HS.module_names(name)[1][1]
     p = {k: sd["%s.%s" % (m, k)].clone().requires_grad_(k in HS.PARAM_KINDS) for k in HS.PARAM_KINDS + ("bn.running_mean", "bn.running_var")}
-    w, b = H.fold_bn(p["conv.weight"], p["conv.bias"], p["bn.weight"], p["bn.bias"], p["bn.running_mean"], p["bn.running_var"], HS.EPS)
+    w, b = G.fold_bn(p["conv.weight"], p["conv.bias"], p["bn.weight"], p["bn.bias"], p["bn.running_mean"], p["bn.running_var"], HS.EPS)
     rw, rb = R.fold({k: v.detach() for k, v in p.items()}, HS.EPS)
     assert torch.allclose(w, rw, rtol=1e-15, atol=0) and torch.allclose(b, rb, rtol=1e-15, atol=0)
     gen = torch.Generator().manual_seed(5)

@@ -14,16 +14,16 @@ import torch
 
 import heads_restate as R
 import heads_scenes as HS
+from smap_amd import gemm_f32 as G
 from smap_amd import heads as H
+from train_kit import DEV, GUARD, U, guarded, held, layouts, unfolded_held
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
-U = R.U
 _cache = {}
 
 
 def scene(name):
-    """Device operands of a scene (fp32, folded on the device by heads.fold_bn), their float64 copies, and one forward + backward run."""
+    """Device operands of a scene (fp32, folded on the device by gemm_f32.fold_bn), their float64 copies, and one forward + backward run."""
     if name in _cache:
         return _cache[name]
     s = HS.SCENES[name]
@@ -46,16 +46,6 @@ def scene(name):
                f64=dict(x=d(x), g=[d(t) for t in g], w1cat=d(w1cat), b1cat=d(b1cat), w2=[d(t) for t in w2], b2=[d(t) for t in b2]))
     _cache[name] = out
     return out
-
-
-def held(what, got, want, bound):
-    """got within bound of want on every element; returns the largest measured / bound ratio (0 / 0 counts as 0)."""
-    err = (got - want).abs()
-    inf, zero = torch.full_like(err, float("inf")), torch.zeros_like(err)
-    ratio = float(torch.where(bound > 0, err / bound.clamp_min(1e-300), torch.where(err > 0, inf, zero)).max())
-    print("  %-22s max err %.3e  measured / bound %.4f" % (what, float(err.max()), ratio))
-    assert ratio <= 1.0, (what, ratio)
-    return ratio
 
 
 @pytest.mark.parametrize("name", list(HS.SCENES))
@@ -143,13 +133,9 @@ def run_all(x, c, nhwc):
 @pytest.mark.parametrize("name", ["o5x7", "o5x7w", "s33x41", "l91x91", "w9x15"])
 def test_layouts_and_runs_give_the_same_bits(name):
     c = scene(name)
-    x16 = c["x"].half()                                        # values every layout can hold
-    hi = x16
+    variants = layouts(c["x"])                                 # values every layout can hold
+    hi = c["x"].half()
     lo = (c["x"] - hi.float()).half()                          # a second case for the planes: hi + lo, rounded once to fp32
-    variants = {
-        "f32": x16.float(), "f32 padded pixel": torch.cat([x16.float(), torch.full_like(x16, float("nan"), dtype=torch.float32)], -1)[..., :x16.shape[-1]],
-        "f16": x16, "hi|lo, lo = 0": torch.stack([hi, torch.zeros_like(hi)], dim=3),
-    }
     base = run_all(variants["f32"], c, nhwc=False)
     again = run_all(variants["f32"], c, nhwc=False)
     assert all(torch.equal(a, b) for a, b in zip(base, again)), "two runs"
@@ -161,15 +147,7 @@ def test_layouts_and_runs_give_the_same_bits(name):
     summed = hi.float() + lo.float()
     a, b = run_all(planes, c, nhwc=True), run_all(summed, c, nhwc=False)
     assert all(torch.equal(p, q) for p, q in zip(a, b)), "hi + lo"
-    assert not torch.equal(summed, x16.float())
-
-
-GUARD = 64           # floats, 256 bytes: the payload keeps the buffer's alignment
-
-
-def guarded(n, byte):
-    buf = torch.full((4 * (n + 2 * GUARD),), byte, dtype=torch.uint8, device=DEV)
-    return buf, buf.view(torch.float32)[GUARD:GUARD + n]
+    assert not torch.equal(summed, hi.float())
 
 
 @pytest.mark.parametrize("name", ["b2x3", "o5x7w", "s33x41", "l91x91", "w9x15"])
@@ -190,12 +168,13 @@ def test_writes_stay_inside_the_described_elements(name):
         ws = torch.full((ws_bytes + tail,), byte, dtype=torch.uint8, device=DEV)
         ysrc = [(bufs["y%d" % a][1].data_ptr(), h, w, ca, p, 1, h * w * p) for a, (ca, p) in enumerate(zip(HS.ARM_C, PADS))]
         lib, stream = L.load(), torch.cuda.current_stream().cuda_stream
-        xd = H.x_descriptor(c["x"])[0]
+        xd = G.x_descriptor(c["x"])[0]
         ptrs = lambda ts: (C.c_void_p * 3)(*[t.data_ptr() for t in ts])
-        L.check(lib.smap_heads_forward(C.byref(xd), c["w1cat"].data_ptr(), c["b1cat"].data_ptr(), ptrs(c["w2"]), ptrs(c["b2"]), H._sources(ysrc),
+        srcs = lambda ss: (L.HeadSrc * 3)(*[L.HeadSrc(p, sh, sw, sc, pix, ch, 0, fr) for p, sh, sw, sc, pix, ch, fr in ss])
+        L.check(lib.smap_heads_forward(C.byref(xd), c["w1cat"].data_ptr(), c["b1cat"].data_ptr(), ptrs(c["w2"]), ptrs(c["b2"]), srcs(ysrc),
                                        B, h, w, chl, ws.data_ptr(), ws_bytes, stream), "smap_heads_forward")
         L.check(lib.smap_heads_backward(C.byref(xd), c["w1cat"].data_ptr(), c["b1cat"].data_ptr(), ptrs(c["w2"]),
-                                        H._sources([H.nchw_source(g) for g in c["g"]]), B, h, w, chl, bufs["gw1"][1].data_ptr(),
+                                        srcs([H.nchw_source(g) for g in c["g"]]), B, h, w, chl, bufs["gw1"][1].data_ptr(),
                                         bufs["gb1"][1].data_ptr(), ptrs([bufs["gw2_%d" % a][1] for a in range(3)]),
                                         ptrs([bufs["gb2_%d" % a][1] for a in range(3)]), bufs["gx"][1].data_ptr(), gx_stride, ws.data_ptr(),
                                         ws_bytes, stream), "smap_heads_backward")
@@ -226,7 +205,7 @@ def test_writes_stay_inside_the_described_elements(name):
 
 @pytest.mark.parametrize("name", ["o5x7", "f16x24"])
 def test_unit_heads_autograd_reaches_the_unfolded_parameters(name):
-    """UnitHeads under torch.autograd with heads.fold_bn in front: the gradients at conv.weight, conv.bias, bn.weight, bn.bias of the six
+    """UnitHeads under torch.autograd with gemm_f32.fold_bn in front: the gradients at conv.weight, conv.bias, bn.weight, bn.bias of the six
     modules and at X against the restatement's chain rule (frozen statistics).  Bound: the folded gradients' composed bounds carried
     through the fold's Jacobian on magnitudes, plus torch's own fp32 fold arithmetic: (n + 8) * 2^-24 on the magnitudes of its terms,
     n = the terms of bn.weight's sum (the conv's fan-in + 1)."""
@@ -251,11 +230,4 @@ def test_unit_heads_autograd_reaches_the_unfolded_parameters(name):
         sl = slice(a * chl, (a + 1) * chl)
         for m, gw, gb, ew, eb in ((c1, want["gw1"][sl], want["gb1"][sl], e["gw1"][sl], e["gb1"][sl]),
                                   (c2, want["gw2"][a], want["gb2"][a], e["gw2"][a], e["gb2"][a])):
-            p = {k: params["%s.%s" % (m, k)].detach().double().cpu() for k in HS.PARAM_KINDS + ("bn.running_mean", "bn.running_var")}
-            n = p["conv.weight"][0].numel() + 1
-            ref = R.unfold_grads(p, gw, gb, HS.EPS)
-            carried = R.unfold_grads(p, ew, eb, HS.EPS, magnitudes=True)
-            mags = R.unfold_grads(p, gw.abs() + ew, gb.abs() + eb, HS.EPS, magnitudes=True)
-            for kind in HS.PARAM_KINDS:
-                held("%s.%s" % (m.rsplit(".", 1)[-1], kind), params["%s.%s" % (m, kind)].grad.double().cpu(), ref[kind],
-                     carried[kind] + (n + 8) * U * mags[kind])
+            unfolded_held(m, params, lambda k: params[k].grad, gw, gb, ew, eb, HS.EPS)

@@ -15,8 +15,6 @@ parameter gradients, and the relative distance of the four losses.  These two ar
 from float64 by a few 1e-6 and no bound is derived for what that does to a gradient -- recorded in profiles/heads_parity.json and
 asserted at 4 times the largest recorded value (the results are bit-reproducible: the margin absorbs a toolchain change):
 GRADIENT_DISTANCE and FORWARD_DISTANCE below."""
-import types
-
 import numpy as np
 import pytest
 import torch
@@ -24,14 +22,13 @@ import torch
 import heads_restate as R
 import heads_scenes as HS
 import valloss_inputs as VI
-from helpers import make_cfg
-from recipe import recipe_state_dict
+from smap_amd import finetune as F
+from smap_amd import gemm_f32 as G
 from smap_amd import heads as H
+from train_kit import DEV, golden_distances, held, inputs, largest_per_kind, small_net, source_tensor, tuner_contract, unfolded_held, value
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
 LOSSES = ("total_loss", "loss_2d", "loss_bone", "loss_root")
-U = R.U
 # profiles/heads_parity.json, the largest over both cases: end_to_end_gradient_relative_l2 (over the 288 tensors) and
 # forward_distance_relative (over the four losses, |value - reference| / reference)
 GRADIENT_DISTANCE = 3.6e-6
@@ -41,14 +38,7 @@ MARGIN = 4
 
 @pytest.fixture(scope="module")
 def small():
-    from smap_amd.model.smap import SMAP
-    torch.manual_seed(0)
-    net = SMAP(make_cfg((16, 24))).eval()
-    sd = recipe_state_dict(net.state_dict())
-    net.load_state_dict(sd)
-    net = net.to(DEV)
-    net.precision = "x3"
-    return net, sd
+    return small_net()
 
 
 @pytest.fixture(scope="module")
@@ -64,17 +54,6 @@ def golden_gradients(golden_dir):
 @pytest.fixture(scope="module")
 def x(golden_dir):
     return torch.from_numpy(np.load(f"{golden_dir}/backbone_small.npz")["x"]).to(DEV)
-
-
-def inputs(case):
-    return {k: torch.from_numpy(v).to(DEV) for k, v in VI.inputs(case).items()}
-
-
-def source_tensor(eng, s, out):
-    """[frames, c, h, w] view of a head source through its descriptor."""
-    base = eng.arena if eng.arena.data_ptr() <= s.ptr < eng.arena.data_ptr() + eng.arena.numel() else out.view(torch.uint8)
-    off = (s.ptr - base.data_ptr()) // 4
-    return torch.as_strided(base.view(torch.float32), (eng.B, s.c, s.h, s.w), (s.frame_stride, s.ch_stride, s.w * s.pix_stride, s.pix_stride), off)
 
 
 @pytest.mark.parametrize("precision", ["x3", "f16"])
@@ -103,21 +82,11 @@ def test_keeping_unit_out_changes_no_output(small, x, precision):
     for (s, ind), t in srcs.items():
         h, w = 2 << ind, 3 << ind
         assert t.dtype == torch.float16 and tuple(t.shape) == ((2, h, w, 2, 256) if precision == "x3" else (2, h, w, 256))
-        want = kept.read_tensor(H.unit_name(s, ind) + ".out")[:2]
-        got = t[..., 0, :].float() + t[..., 1, :].float() if precision == "x3" else t
+        want = kept.read_tensor(F.unit_name(s, ind) + ".out")[:2]
+        got = value(t) if precision == "x3" else t
         assert torch.equal(got, want), (s, ind)
         assert float(want.min()) >= 0 and float(want.max()) > 0                      # post-ReLU, and alive
-        H.x_descriptor(t)
-
-
-def held(what, got, want, bound, worst):
-    """got within bound of want on every element; worst: the largest measured / bound ratio per kind of tensor."""
-    err = (got.double().cpu() - want).abs()
-    inf, zero = torch.full_like(err, float("inf")), torch.zeros_like(err)
-    ratio = float(torch.where(bound > 0, err / bound.clamp_min(1e-300), torch.where(err > 0, inf, zero)).max())
-    kind = ".".join(what.rsplit(".", 2)[-2:])
-    worst[kind] = max(worst.get(kind, 0.0), ratio)
-    assert ratio <= 1.0, (what, ratio)
+        G.x_descriptor(t)
 
 
 @pytest.mark.parametrize("case", VI.CASES)
@@ -127,12 +96,12 @@ def test_head_parameter_gradients(small, golden, x, case):
     losses, grads, gouts = net.head_parameter_gradients(x, inp["valids"], inp["labels"], inp["rdepth"])
     n_engines = len(net._engines)
     # the same bits from the pieces, which also hand over what the restatement needs: G at every head, the engine's own `out`
-    leaves, frozen = H.head_leaves(net)
+    leaves, frozen = F.head_leaves(net)
     sinks = {}
-    again = H.heads_loss(net, leaves, frozen, x, inp["valids"], inp["labels"], inp["rdepth"], sinks)
+    again = F.heads_loss(net, leaves, frozen, x, inp["valids"], inp["labels"], inp["rdepth"], sinks)
     again["total_loss"].backward()
     assert len(net._engines) == n_engines
-    assert sorted(grads) == sorted(H.head_parameter_keys(3)) and len(grads) == 288 and sorted(gouts) == sorted(sinks) and len(gouts) == 12
+    assert sorted(grads) == sorted(F.head_parameter_keys(3)) and len(grads) == 288 and sorted(gouts) == sorted(sinks) and len(gouts) == 12
     sd = net.state_dict()
     for k, g in grads.items():
         assert g.shape == sd[k].shape and g.dtype == torch.float32 and torch.equal(g, leaves[k].grad), k
@@ -150,11 +119,11 @@ def test_head_parameter_gradients(small, golden, x, case):
     worst = {}
     for (s, ind), sink in sinks.items():
         assert torch.equal(gouts[(s, ind)], sink["gx"]) and tuple(sink["gx"].shape) == (2, 2 << ind, 3 << ind, 256)
-        arms = H.arm_prefixes(H.unit_name(s, ind))
+        arms = F.arm_prefixes(F.unit_name(s, ind))
         params = {**frozen, **{k: v.detach() for k, v in leaves.items()}}
         w1cat, b1cat, w2, b2 = (H.folded_unit_weights(params, arms))
         t = outs[(s, ind)]
-        xs = d(t[..., 0, :].float() + t[..., 1, :].float())
+        xs = d(value(t))
         f = dict(w1cat=d(w1cat), b1cat=d(b1cat), w2=[d(v) for v in w2], b2=[d(v) for v in b2], g=[d(v) for v in sink["g"]])
         z, _ = R.forward(xs, f["w1cat"], f["b1cat"], f["w2"], f["b2"])
         e_m, _ = R.forward_bounds(xs, f["w1cat"], f["b1cat"], f["w2"], f["b2"], z)
@@ -172,13 +141,7 @@ def test_head_parameter_gradients(small, golden, x, case):
             sl = slice(a * 256, (a + 1) * 256)
             for m, gw, gb, ew, eb in ((c1, want["gw1"][sl], want["gb1"][sl], e["gw1"][sl], e["gb1"][sl]),
                                       (c2, want["gw2"][a], want["gb2"][a], e["gw2"][a], e["gb2"][a])):
-                p = {k: d(params["%s.%s" % (m, k)]) for k in H.TRAINED + H.FROZEN}
-                n = p["conv.weight"][0].numel() + 1
-                ref = R.unfold_grads(p, gw, gb, HS.EPS)
-                carried = R.unfold_grads(p, ew, eb, HS.EPS, magnitudes=True)
-                mags = R.unfold_grads(p, gw.abs() + ew, gb.abs() + eb, HS.EPS, magnitudes=True)
-                for kind in H.TRAINED:
-                    held("%s.%s" % (m, kind), grads["%s.%s" % (m, kind)], ref[kind], carried[kind] + (n + 8) * U * mags[kind], worst)
+                unfolded_held(m, params, grads.get, gw, gb, ew, eb, HS.EPS, worst)
     print(case, "largest measured / bound", {k: round(v, 4) for k, v in worst.items()})
 
 
@@ -191,26 +154,9 @@ def test_parameter_gradients_against_the_reference(small, golden_gradients, x, c
     net, _ = small
     inp = inputs(case)
     _, grads, _ = net.head_parameter_gradients(x, inp["valids"], inp["labels"], inp["rdepth"])
-    keys = H.head_parameter_keys(3)
     whole, digests = golden_gradients[case + "_whole"], golden_gradients[case + "_digests"]
     assert int(golden_gradients["seed"]) == VI.SEED and digests.shape[0] == 72
-    at, row, worst = 0, 0, {}
-    for k in keys:
-        got = grads[k].double().cpu().numpy()
-        if k.endswith("conv.weight"):
-            d, scale = HS.digest(k, got, digests.shape[1] - 2 - HS.N_PROJ)
-            want, first = digests[row], 2 + HS.N_PROJ
-            row += 1
-            rel = np.linalg.norm(d[first:] - want[first:]) / np.linalg.norm(want[first:])
-            rel = max(rel, float((np.abs(d[:first] - want[:first]) / scale[:first]).max()))
-        else:
-            want = whole[at:at + got.size].reshape(got.shape)
-            at += got.size
-            rel = np.linalg.norm(got - want) / np.linalg.norm(want)
-        kind = ".".join(k.rsplit(".", 2)[-2:])
-        if rel > worst.get(kind, (0.0, ""))[0]:
-            worst[kind] = (float(rel), k)
-    assert at == whole.size and row == 72
+    worst = largest_per_kind(golden_distances(F.head_parameter_keys(3), grads, whole, digests))
     print(case, "end-to-end relative L2 against the reference, largest per kind", worst)
     largest = max(v[0] for v in worst.values())
     print(case, "end-to-end relative L2 against the reference, largest", largest)
@@ -222,38 +168,7 @@ def test_fine_tuner_lowers_the_loss_and_commits_once(small, golden, x, monkeypat
     the model's own validation loss (SMAP.forward with labels: the x3 all-heads schedule, rebuilt from the committed weights) agrees
     with the tuner's fp32-arm loss at those weights within the recorded forward distance (FORWARD_DISTANCE, relative, times MARGIN):
     the two paths share the engine's `out` and differ in the head arms' arithmetic alone, x3 against fp32."""
-    import smap_amd.model.smap as M
-    net = M.SMAP(make_cfg((16, 24))).eval()                      # its own model: commit() changes it
-    net.load_state_dict(small[1])
-    net = net.to(DEV)
-    net.precision = "x3"
-    inp = inputs("ones")
-    built = []
-    real = M.BackboneEngine
-    monkeypatch.setattr(M, "BackboneEngine", lambda *a, **k: (built.append(k), real(*a, **k))[1])
-    cfg = make_cfg((16, 24))
-    cfg.SOLVER = types.SimpleNamespace(BASE_LR=2e-4, WEIGHT_DECAY=8e-6)             # the reference's config.py:51,54
-    assert H.HeadFineTuner(net, cfg, num_gpu=2).optimizer.defaults["lr"] == 4e-4 and \
-        H.HeadFineTuner(net, cfg).optimizer.defaults["weight_decay"] == 8e-6      # as make_optimizer configures it
-    with pytest.raises(ValueError, match="BASE_LR"):
-        H.HeadFineTuner(net, make_cfg((16, 24)))
-    tuner = H.HeadFineTuner(net, cfg, lr=1e-5)
-    before = {k: v.detach().clone() for k, v in net.state_dict().items()}
-    seen = [float(tuner.step(x, inp["valids"], inp["labels"], inp["rdepth"])["total_loss"]) for _ in range(5)]
-    final = tuner.loss(x, inp["valids"], inp["labels"], inp["rdepth"])
-    seen.append(float(final["total_loss"]))
-    print("total_loss per step", seen)
-    assert all(b < a for a, b in zip(seen, seen[1:])), seen
-    assert len(built) == 1 and built[0].get("keep_unit_out") and built[0].get("all_heads")
-    assert all(torch.equal(v, before[k]) for k, v in net.state_dict().items())      # nothing written before commit
-    gen = net.weights_generation
-    tuner.commit()
-    assert net.weights_generation == gen + 1
-    keys = set(H.head_parameter_keys(3))
-    after = net.state_dict()
-    assert all(torch.equal(after[k], before[k]) == (k not in keys) for k in after)   # the head parameters moved, nothing else did
-    own = net(x, inp["valids"], inp["labels"], inp["rdepth"])
-    assert len(built) == 2 and not built[1].get("keep_unit_out")
+    own, final = tuner_contract(F.HeadFineTuner, F.head_parameter_keys(3), ("keep_unit_out", "all_heads"), small[1], x, monkeypatch)
     for n, k in enumerate(LOSSES):
         err, allowed = abs(float(own[k]) - float(final[k])), MARGIN * FORWARD_DISTANCE * abs(float(final[k]))
         print(k, "x3 schedule", float(own[k]), "fp32 arms", float(final[k]), "difference", err, "allowed", allowed)

@@ -11,8 +11,10 @@ import torch
 import trunk_restate as R
 import trunk_scenes as TS
 import smap_amd.lib as L
-from smap_amd import heads as H
+from smap_amd import finetune as F
+from smap_amd import gemm_f32 as G
 from smap_amd import trunk as T
+from train_kit import FAKE, set_attr as _set, set_fields as _d
 
 RTOL = 1e-12           # of the tensor's largest magnitude: both sides are float64 and differ in summation order only
 
@@ -27,10 +29,10 @@ def restate(name):
     s = TS.SCENES[name]
     x, o_prev, g, params = R.scene_operands(name)
     mods = TS.module_names(name)
-    wu, bu = R.fold(params[mods[0]], TS.EPS)
+    wu, bu = R.fold(params[mods[0]], TS.EPS, matrix=True)
     wc, b, it = None, bu, None
     if s["ind"] > 0:
-        wc, bc = R.fold(params[mods[1]], TS.EPS)
+        wc, bc = R.fold(params[mods[1]], TS.EPS, matrix=True)
         b, it = bu + bc, R.Interp(s["hp"], s["wp"], s["h"], s["w"], fp32=False)
     pre, _, _ = R.forward(x, o_prev, wu, wc, b, it)
     gr = R.backward(x, o_prev, wu, wc, g, pre > 0, it)
@@ -45,10 +47,10 @@ def test_scene_fold_matches_restatement():
         _, _, _, params = R.scene_operands(name)
         mods = TS.module_names(name)
         wu, wc, b = TS.folded64(name)
-        fw, fb = R.fold(params[mods[0]], TS.EPS)
+        fw, fb = R.fold(params[mods[0]], TS.EPS, matrix=True)
         assert torch.equal(fw, wu)
         if wc is not None:
-            cw, cb = R.fold(params[mods[1]], TS.EPS)
+            cw, cb = R.fold(params[mods[1]], TS.EPS, matrix=True)
             assert torch.equal(cw, wc)
             fb = fb + cb
         assert torch.equal(fb, b)
@@ -114,9 +116,9 @@ def test_scene_pixels_span_ragged_slices():
     # g: long slices at high resolution (61 of 272, the last of 242, its last k-step of 16 ragged), slices of 256 at low resolution
     s = TS.SCENES["g"]
     lay = T.workspace_layout(TS.B, s["h"], s["w"], s["hp"], s["wp"], s["cin"], s["chl"], True)
-    n = H.slice_len(lay["P"])
+    n = G.slice_len(lay["P"])
     assert lay["P"] > 16384 and n == 272 and lay["slices"] == 61 and lay["P"] % n == 242 and 242 % 16 != 0
-    assert lay["slices_lo"] >= 2 and H.slice_len(lay["Pl"]) == 256 and lay["Pl"] % 256 != 0
+    assert lay["slices_lo"] >= 2 and G.slice_len(lay["Pl"]) == 256 and lay["Pl"] % 256 != 0
     assert R.K_red(lay["P"]) == 333 and R.red_chain(lay["Pl"]) == 256 + lay["slices_lo"]
     # h: identity interpolation, and a quad count that is no power of two
     s = TS.SCENES["h"]
@@ -152,7 +154,6 @@ def test_ws_bytes_rejects(dims):
     assert L.load().smap_trunk_ws_bytes(*dims, 1) == -1
 
 
-FAKE = 0x7F0000000000            # never dereferenced: every call below is refused before any HIP call
 VALID = (2, 5, 7, 3, 4, 128, 64)
 
 
@@ -184,17 +185,6 @@ class Args:
             return lib.smap_trunk_backward(x, prev, self.o, self.wu, self.wc, self.g_o, self.gwu, self.gwc, self.gb, self.g_o_prev, self.gx,
                                            self.gx_stride, *dims, self.ws, ws_bytes, None)
         return lib.smap_trunk_forward(x, prev, self.wu, self.wc, self.b, self.o, *dims, self.ws, ws_bytes, None)
-
-
-def _set(name, value):
-    return lambda a: setattr(a, name, value)
-
-
-def _d(which, **kw):
-    def f(a):
-        for k, v in kw.items():
-            setattr(getattr(a, which), k, v)
-    return f
 
 
 def _dims(**kw):
@@ -269,7 +259,7 @@ def test_no_up_path_backward_rejects_up_gradients(case):
 
 
 def test_parameter_keys():
-    keys = T.trunk_parameter_keys(2)
+    keys = F.trunk_parameter_keys(2)
     assert len(keys) == 28 and len(set(keys)) == 28
     assert keys[0] == "stage2.upsample.up1.u_skip.conv.weight" and "stage2.upsample.up1.up_conv.conv.weight" not in keys
     assert "stage2.upsample.up4.up_conv.bn.bias" in keys

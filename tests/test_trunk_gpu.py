@@ -18,12 +18,11 @@ import torch
 import trunk_restate as R
 import trunk_scenes as TS
 import smap_amd.lib as L
-from smap_amd import heads as H
+from smap_amd import gemm_f32 as G
 from smap_amd import trunk as T
+from train_kit import DEV, GUARD, U, guarded, held, layouts, unfolded_held
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
-U = R.U
 _cache = {}
 
 
@@ -32,7 +31,7 @@ def dims_of(s):
 
 
 def scene(name):
-    """Device operands of a scene (fp32, folded on the device by heads.fold_bn), their float64 copies, and one forward + backward run."""
+    """Device operands of a scene (fp32, folded on the device by gemm_f32.fold_bn), their float64 copies, and one forward + backward run."""
     if name in _cache:
         return _cache[name]
     s = TS.SCENES[name]
@@ -54,16 +53,6 @@ def scene(name):
                it=R.Interp(s["hp"], s["wp"], s["h"], s["w"], fp32=True) if s["ind"] > 0 else None)
     _cache[name] = out
     return out
-
-
-def held(what, got, want, bound):
-    """got within bound of want on every element; returns the largest measured / bound ratio (0 / 0 counts as 0)."""
-    err = (got - want).abs()
-    inf, zero = torch.full_like(err, float("inf")), torch.zeros_like(err)
-    ratio = float(torch.where(bound > 0, err / bound.clamp_min(1e-300), torch.where(err > 0, inf, zero)).max())
-    print("  %-22s max err %.3e  measured / bound %.4f" % (what, float(err.max()), ratio))
-    assert ratio <= 1.0, (what, ratio)
-    return ratio
 
 
 @pytest.mark.parametrize("name", list(TS.SCENES))
@@ -121,13 +110,6 @@ def test_composed_forward_and_backward(name):
             held(k, got[g], want[k], e[k])
 
 
-def layouts(t):
-    """The same fp16-representable values in every layout smap_heads_x describes."""
-    t16 = t.half()
-    return {"f32": t16.float(), "f32 padded pixel": torch.cat([t16.float(), torch.full_like(t16, float("nan"), dtype=torch.float32)], -1)[..., :t16.shape[-1]],
-            "f16": t16, "hi|lo, lo = 0": torch.stack([t16, torch.zeros_like(t16)], dim=3)}
-
-
 def run_all(x, o_prev, c):
     o, _ = T.forward(x, o_prev, c["wu"], c["wc"], c["b"])
     gwu, gwc, gb, gprev, gx, _ = T.backward(x, o_prev, o, c["wu"], c["wc"], c["g"], want_gx=True)
@@ -152,14 +134,6 @@ def test_layouts_and_runs_give_the_same_bits(name):
     assert not torch.equal(hi.float() + lo.float(), hi.float())
 
 
-GUARD = 64           # floats, 256 bytes: the payload keeps the buffer's alignment
-
-
-def guarded(n, byte):
-    buf = torch.full((4 * (n + 2 * GUARD),), byte, dtype=torch.uint8, device=DEV)
-    return buf, buf.view(torch.float32)[GUARD:GUARD + n]
-
-
 @pytest.mark.parametrize("name", ["a", "b", "d", "f", "g", "h", "i"])
 def test_writes_stay_inside_the_described_elements(name):
     c = scene(name)
@@ -170,8 +144,8 @@ def test_writes_stay_inside_the_described_elements(name):
     P, Pl, gx_stride, tail = B * h * w, B * hp * wp, cin + 8, 4096
     fwd_bytes, bwd_bytes = T.workspace_bytes(*dims, False), T.workspace_bytes(*dims, True)
     lib, stream = L.load(), torch.cuda.current_stream().cuda_stream
-    xd = H.x_descriptor(c["x"])[0]
-    pd = C.byref(H.x_descriptor(c["o_prev"])[0]) if up else None
+    xd = G.x_descriptor(c["x"])[0]
+    pd = C.byref(G.x_descriptor(c["o_prev"])[0]) if up else None
     wc = c["wc"].data_ptr() if up else None
     results = {}
     for byte in (0xFF, 0x7B):
@@ -207,7 +181,7 @@ def test_writes_stay_inside_the_described_elements(name):
 
 @pytest.mark.parametrize("name", ["b", "d"])
 def test_unit_trunk_autograd_reaches_the_unfolded_parameters(name):
-    """UnitTrunk under torch.autograd with heads.fold_bn in front: the gradients at conv.weight, conv.bias, bn.weight, bn.bias of u_skip and
+    """UnitTrunk under torch.autograd with gemm_f32.fold_bn in front: the gradients at conv.weight, conv.bias, bn.weight, bn.bias of u_skip and
     up_conv and at O_prev against the restatement's chain rule (frozen statistics).  Bound: the folded gradients' composed bounds carried
     through the fold's Jacobian on magnitudes, plus torch's own fp32 fold arithmetic: (n + 8) * 2^-24 on the magnitudes of its terms,
     n = the terms of bn.weight's sum (the conv's fan-in + 1).  The ONE gb tensor of the call goes to both biases: bit-equal gradients."""
@@ -232,11 +206,4 @@ def test_unit_trunk_autograd_reaches_the_unfolded_parameters(name):
     want = R.backward(f["x"], f["o_prev"], f["wu"], f["wc"], f["g"], mask, it)
     e = R.backward_bounds(f["x"], f["o_prev"], f["wu"], f["wc"], f["g"], mask, it)
     for m, gw, ew in ((mods[0], want["gwu"], e["gwu"]), (mods[1], want["gwc"], e["gwc"])):
-        p = {k: params["%s.%s" % (m, k)].detach().double().cpu() for k in TS.PARAM_KINDS + TS.STATS}
-        n = p["conv.weight"][0].numel() + 1
-        ref = R.unfold_grads(p, gw, want["gb"], TS.EPS)
-        carried = R.unfold_grads(p, ew, e["gb"], TS.EPS, magnitudes=True)
-        mags = R.unfold_grads(p, gw.abs() + ew, want["gb"].abs() + e["gb"], TS.EPS, magnitudes=True)
-        for kind in TS.PARAM_KINDS:
-            held("%s.%s" % (m.rsplit(".", 1)[-1], kind), params["%s.%s" % (m, kind)].grad.double().cpu(), ref[kind],
-                 carried[kind] + (n + 8) * U * mags[kind])
+        unfolded_held(m, params, lambda k: params[k].grad, gw, want["gb"], ew, e["gb"], TS.EPS)

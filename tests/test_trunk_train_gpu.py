@@ -6,21 +6,18 @@ The x3 backbone's x4 .. x1 lie within 2e-5 of their maxima of float64's (the fig
 derived for what that does to a gradient: the 28 trunk gradients and the four gradients at x4 .. x1 are MEASURED distances against the
 float64 reference -- relative L2 per tensor, the measure the 288 head gradients are held to -- recorded in profiles/trunk_parity.json and
 asserted at 4 x, the project's margin for a recorded distance."""
-import types
-
 import numpy as np
 import pytest
 import torch
 
 import heads_scenes as HS
 import valloss_inputs as VI
-from helpers import make_cfg
-from recipe import recipe_state_dict
-from smap_amd import heads as H
+from smap_amd import finetune as F
+from smap_amd import gemm_f32 as G
 from smap_amd import trunk as T
+from train_kit import DEV, golden_distances, inputs, largest_per_kind, relative_l2, small_net, source_tensor, tuner_contract, value
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
 LOSSES = ("total_loss", "loss_2d", "loss_bone", "loss_root")
 LAST = 2
 X_TOLERANCE = 2e-5                  # of each tensor's maximum: what the x3 schedule's tensors are held to against float64
@@ -36,14 +33,7 @@ MARGIN = 4
 
 @pytest.fixture(scope="module")
 def small():
-    from smap_amd.model.smap import SMAP
-    torch.manual_seed(0)
-    net = SMAP(make_cfg((16, 24))).eval()
-    sd = recipe_state_dict(net.state_dict())
-    net.load_state_dict(sd)
-    net = net.to(DEV)
-    net.precision = "x3"
-    return net, sd
+    return small_net()
 
 
 @pytest.fixture(scope="module")
@@ -75,22 +65,6 @@ def gradients(small, x):
         inp = inputs(case)
         out[case] = net.decoder_parameter_gradients(x, inp["valids"], inp["labels"], inp["rdepth"])
     return out
-
-
-def inputs(case):
-    return {k: torch.from_numpy(v).to(DEV) for k, v in VI.inputs(case).items()}
-
-
-def value(t):
-    """fp32 values of a unit tensor in either engine layout."""
-    return t[..., 0, :].float() + t[..., 1, :].float() if t.dim() == 5 else t.float()
-
-
-def source_tensor(eng, s, out):
-    """[frames, c, h, w] view of a head source through its descriptor."""
-    base = eng.arena if eng.arena.data_ptr() <= s.ptr < eng.arena.data_ptr() + eng.arena.numel() else out.view(torch.uint8)
-    off = (s.ptr - base.data_ptr()) // 4
-    return torch.as_strided(base.view(torch.float32), (eng.B, s.c, s.h, s.w), (s.frame_stride, s.ch_stride, s.w * s.pix_stride, s.pix_stride), off)
 
 
 @pytest.mark.parametrize("precision", ["x3", "f16"])
@@ -127,7 +101,7 @@ def test_keeping_unit_in_changes_no_output(small, golden, x, precision):
         want = kept.read_tensor(kept.graph.unit_in[(s, ind)].name)[:2]
         assert torch.equal(value(t), want.float()), (s, ind)
         assert float(want.min()) >= 0 and float(want.max()) > 0                      # post-ReLU, and alive
-        H.x_descriptor(t)
+        G.x_descriptor(t)
     if precision == "x3":
         first = 2 + HS.N_PROJ
         for ind in range(4):
@@ -146,26 +120,15 @@ def test_fp32_chain_at_untrained_weights_is_the_engines_out(small, x):
     eng = net.engine(2, 64, 96, x.device, all_heads=True, keep_unit_out=True, keep_unit_in=True)
     eng.run(x, out=eng.new_output())
     outs, ins = eng.unit_out_sources(), eng.unit_in_sources()
-    leaves, frozen = H.parameter_leaves(net, T.trunk_parameter_keys(LAST))
+    leaves, frozen = F.parameter_leaves(net, F.trunk_parameter_keys(LAST))
     params = {**frozen, **{k: v.detach() for k, v in leaves.items()}}
     o = None
     for ind in range(4):
-        o = T.unit_trunk(ins[(LAST, ind)], o, params, H.unit_name(LAST, ind), ind)
+        o = T.unit_trunk(ins[(LAST, ind)], o, params, F.unit_name(LAST, ind), ind)
         want = value(outs[(LAST, ind)])
         err, top = float((o - want).abs().max()), float(want.max())
         print("up%d  max |fp32 chain - x3 out| %.3e  = %.3e of the maximum" % (ind + 1, err, err / top))
         assert tuple(o.shape) == (2, 2 << ind, 3 << ind, 256) and err <= X_TOLERANCE * top, (ind, err, top)
-
-
-def relative_l2(key, got, want_digest=None, want_whole=None):
-    """Relative L2 of a tensor against the golden file: over the whole tensor, or over the digest's seeded samples, whose sum and three
-    seeded projections are held too, relative to the sum of magnitudes (times the projection's largest weight)."""
-    if want_whole is not None:
-        return float(np.linalg.norm(got - want_whole) / np.linalg.norm(want_whole))
-    first = 2 + HS.N_PROJ
-    d, scale = HS.digest(key, got, want_digest.size - first)
-    rel = np.linalg.norm(d[first:] - want_digest[first:]) / np.linalg.norm(want_digest[first:])
-    return float(max(rel, (np.abs(d[:first] - want_digest[:first]) / scale[:first]).max()))
 
 
 @pytest.mark.parametrize("case", VI.CASES)
@@ -174,25 +137,12 @@ def test_trunk_gradients_against_the_reference(small, golden, golden_losses, gra
     relative L2 per tensor at most MARGIN * TRUNK_GRADIENT_DISTANCE; the losses within MARGIN * FORWARD_DISTANCE of the reference's."""
     net, _ = small
     losses, grads, gxs = gradients[case]
-    keys = T.trunk_parameter_keys(LAST)
-    assert len(grads) == 316 and sorted(grads) == sorted(T.decoder_parameter_keys(3)) and len(gxs) == 4
+    assert len(grads) == 316 and sorted(grads) == sorted(F.decoder_parameter_keys(3)) and len(gxs) == 4
     sd = net.state_dict()
     assert all(grads[k].shape == sd[k].shape and grads[k].dtype == torch.float32 for k in grads)
     whole, digests = golden[case + "_whole"], golden[case + "_digests"]
     assert int(golden["seed"]) == VI.SEED and digests.shape[0] == 7
-    at, row, worst = 0, 0, {}
-    for k in keys:
-        got = grads[k].double().cpu().numpy()
-        if k.endswith("conv.weight"):
-            rel = relative_l2(k, got, want_digest=digests[row])
-            row += 1
-        else:
-            rel = relative_l2(k, got, want_whole=whole[at:at + got.size].reshape(got.shape))
-            at += got.size
-        kind = ".".join(k.rsplit(".", 2)[-2:])
-        if rel > worst.get(kind, (0.0, ""))[0]:
-            worst[kind] = (rel, k)
-    assert at == whole.size and row == 7
+    worst = largest_per_kind(golden_distances(F.trunk_parameter_keys(LAST), grads, whole, digests))
     for ind, g in enumerate(gxs):
         assert tuple(g.shape) == (2, 2 << ind, 3 << ind, 2048 >> ind) and g.dtype == torch.float32
         worst["gx%d" % (4 - ind)] = (relative_l2("gx%d" % (4 - ind), g.double().cpu().numpy(), want_digest=golden[case + "_gx_digests"][ind]), "")
@@ -213,17 +163,8 @@ def test_head_gradients_still_meet_the_reference(golden_heads, gradients, case):
     figure tests/test_heads_train_gpu.py holds head_parameter_gradients to."""
     _, grads, _ = gradients[case]
     whole, digests = golden_heads[case + "_whole"], golden_heads[case + "_digests"]
-    at, row, largest = 0, 0, (0.0, "")
-    for k in H.head_parameter_keys(3):
-        got = grads[k].double().cpu().numpy()
-        if k.endswith("conv.weight"):
-            rel = relative_l2(k, got, want_digest=digests[row])
-            row += 1
-        else:
-            rel = relative_l2(k, got, want_whole=whole[at:at + got.size].reshape(got.shape))
-            at += got.size
-        largest = max(largest, (rel, k))
-    assert at == whole.size and row == 72
+    assert digests.shape[0] == 72
+    largest = max([(0.0, "")] + [(rel, k) for k, rel in golden_distances(F.head_parameter_keys(3), grads, whole, digests).items()])
     print(case, "head gradients from the decoder pass, largest relative L2", largest)
     assert largest[0] <= MARGIN * HEAD_GRADIENT_DISTANCE, (case, largest)
 
@@ -233,42 +174,14 @@ def test_decoder_tuner_lowers_the_loss_and_commits_once(small, x, monkeypatch):
     before commit(); after it the model's own validation loss (the x3 all-heads schedule rebuilt from the committed weights) agrees with
     the tuner's fp32 loss at those weights within MARGIN * FORWARD_DISTANCE, relative: the recorded loss distance HeadFineTuner's commit is
     held to, although here the trunk too runs in x3 on one side and in fp32 on the other."""
-    import smap_amd.model.smap as M
-    net = M.SMAP(make_cfg((16, 24))).eval()                      # its own model: commit() changes it
-    net.load_state_dict(small[1])
-    net = net.to(DEV)
-    net.precision = "x3"
-    inp = inputs("ones")
-    built = []
-    real = M.BackboneEngine
-    monkeypatch.setattr(M, "BackboneEngine", lambda *a, **k: (built.append(k), real(*a, **k))[1])
-    cfg = make_cfg((16, 24))
-    cfg.SOLVER = types.SimpleNamespace(BASE_LR=2e-4, WEIGHT_DECAY=8e-6)             # the reference's config.py:51,54
-    assert T.DecoderFineTuner(net, cfg, num_gpu=2).optimizer.defaults["lr"] == 4e-4 and \
-        T.DecoderFineTuner(net, cfg).optimizer.defaults["weight_decay"] == 8e-6      # as make_optimizer configures it
-    with pytest.raises(ValueError, match="BASE_LR"):
-        T.DecoderFineTuner(net, make_cfg((16, 24)))
-    tuner = T.DecoderFineTuner(net, cfg, lr=1e-5)
-    assert isinstance(tuner, H.FrozenBackboneTuner) and isinstance(H.HeadFineTuner(net, cfg), H.FrozenBackboneTuner)      # one shared tuner
-    assert len(tuner.leaves) == 316 and tuner.optimizer.defaults["betas"] == (0.9, 0.999) and tuner.optimizer.defaults["eps"] == 1e-8
-    before = {k: v.detach().clone() for k, v in net.state_dict().items()}
-    seen = [float(tuner.step(x, inp["valids"], inp["labels"], inp["rdepth"])["total_loss"]) for _ in range(5)]
-    final = tuner.loss(x, inp["valids"], inp["labels"], inp["rdepth"])
-    seen.append(float(final["total_loss"]))
-    print("total_loss per step", seen)
-    assert all(b < a for a, b in zip(seen, seen[1:])), seen
-    assert len(built) == 1 and built[0].get("keep_unit_in") and built[0].get("keep_unit_out") and built[0].get("all_heads")
-    assert all(torch.equal(v, before[k]) for k, v in net.state_dict().items())      # nothing written before commit
-    trunk = T.trunk_parameter_keys(LAST)
-    assert all(not torch.equal(tuner.leaves[k].detach(), before[k]) for k in trunk)  # every trunk leaf moved
-    gen = net.weights_generation
-    tuner.commit()
-    assert net.weights_generation == gen + 1
-    keys = set(T.decoder_parameter_keys(3))
-    after = net.state_dict()
-    assert all(torch.equal(after[k], before[k]) == (k not in keys) for k in after)   # the decoder parameters moved, nothing else did
-    own = net(x, inp["valids"], inp["labels"], inp["rdepth"])
-    assert len(built) == 2 and not built[1].get("keep_unit_in")
+    def built_tuner(net, cfg, tuner):
+        assert isinstance(tuner, F.FrozenBackboneTuner) and isinstance(F.HeadFineTuner(net, cfg), F.FrozenBackboneTuner)      # one shared tuner
+        assert len(tuner.leaves) == 316 and tuner.optimizer.defaults["betas"] == (0.9, 0.999) and tuner.optimizer.defaults["eps"] == 1e-8
+
+    def before_commit(tuner, before):
+        assert all(not torch.equal(tuner.leaves[k].detach(), before[k]) for k in F.trunk_parameter_keys(LAST))  # every trunk leaf moved
+    own, final = tuner_contract(F.DecoderFineTuner, F.decoder_parameter_keys(3), ("keep_unit_in", "keep_unit_out", "all_heads"), small[1], x,
+                                monkeypatch, built_tuner, before_commit)
     for k in LOSSES:
         rel = abs(float(own[k]) - float(final[k])) / abs(float(final[k]))
         print(k, "x3 schedule", float(own[k]), "fp32 decoder", float(final[k]), "committed loss distance, relative", rel)

@@ -15,6 +15,7 @@ import loss_scenes as LS
 import valloss_inputs as VI
 from helpers import make_cfg
 from recipe import recipe_state_dict
+from train_kit import small_net, source_tensor
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -202,12 +203,7 @@ def test_forward_src_argument_errors(sources):
 # ---- the all-heads engine --------------------------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def small():
-    from smap_amd.model.smap import SMAP
-    torch.manual_seed(0)
-    net = SMAP(make_cfg((16, 24))).eval()
-    sd = recipe_state_dict(net.state_dict())
-    net.load_state_dict(sd)
-    return net.to(DEV), sd
+    return small_net(precision=None)
 
 
 @pytest.fixture(scope="module")
@@ -218,14 +214,6 @@ def golden(golden_dir):
 @pytest.fixture(scope="module")
 def x(golden_dir):
     return torch.from_numpy(np.load(f"{golden_dir}/backbone_small.npz")["x"]).to(DEV)
-
-
-def source_tensor(eng, s, out):
-    """[frames, c, h, w] view of a head source through its descriptor: what the loss reads."""
-    base = eng.arena if eng.arena.data_ptr() <= s.ptr < eng.arena.data_ptr() + eng.arena.numel() else out.view(torch.uint8)
-    off = (s.ptr - base.data_ptr()) // 4
-    flat = base.view(torch.float32)
-    return torch.as_strided(flat, (eng.B, s.c, s.h, s.w), (s.frame_stride, s.ch_stride, s.w * s.pix_stride, s.pix_stride), off)
 
 
 @pytest.mark.parametrize("taphead", ["1", "0"], ids=["tapdot_root", "plain_root"])

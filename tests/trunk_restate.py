@@ -113,13 +113,8 @@ def backward_bounds(x, o_prev, wu, wc, g, mask, it):
     return out
 
 
-def fold(p, eps=1e-5):
-    """Folded (w' [out, in], b') of one 1x1 conv_bn_relu (heads_restate.fold, the weight as a matrix)."""
-    w, b = HR.fold(p, eps)
-    return w.flatten(1), b
-
-
-unfold_grads = HR.unfold_grads          # the chain rule of the fold with frozen statistics: the same for a 1x1 trunk conv as for a head conv
+# the fold (matrix=True: the weight of a 1x1 trunk conv as [out, in]) and its chain rule with frozen statistics: the same as for a head conv
+fold, unfold_grads = HR.fold, HR.unfold_grads
 
 
 def scene_operands(name):

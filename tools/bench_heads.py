@@ -23,21 +23,23 @@ import os
 import sys
 import time
 
-import numpy as np
 import torch
 import torch.nn.functional as F
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+from bench_common import DEV, full_network_batch, read_json, reduce_positional_trace, stats, time_loop, write_merged  # noqa: E402
+from smap_amd import finetune as FT  # noqa: E402
+from smap_amd import gemm_f32 as G  # noqa: E402
 from smap_amd import heads as H  # noqa: E402
 
-DEV = "cuda:0"
 CHL, ARM_C = 256, (43, 14, 1)
 LEVELS = ((16, 26), (32, 52), (64, 104), (128, 208))
 BATCHES = (2, 8)
 GUIDE_TFLOPS = 122.0
 FORWARD_LAUNCHES = ["Z|M"] + ["Y_%d" % a for a in range(3)]
 BACKWARD_LAUNCHES = ["Z|M"] + [n % a for a in range(3) for n in ("gW2_%d part", "gW2_%d fold", "gZ_%d")] + ["gW1 part", "gW1 fold", "gX"]
+KERNELS = ("conv_gemm_kernel", "reduce_gemm_kernel", "reduce_fold_kernel")
 
 
 def launch_flops(B, h, w):
@@ -64,40 +66,18 @@ def make_unit(B, h, w, seed=0):
     return planes, w1cat, b1cat, w2, b2, gs
 
 
-def time_loop(step, iters, warmup):
-    for _ in range(warmup):
-        step()
-    torch.cuda.synchronize()
-    ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(iters)]
-    for a, b in ev:
-        a.record()
-        step()
-        b.record()
-    torch.cuda.synchronize()
-    return np.array([a.elapsed_time(b) for a, b in ev])
-
-
-def stats(ms, flops=None):
-    out = dict(device_ms_median=float(np.median(ms)), device_ms_min=float(ms.min()), device_ms_max=float(ms.max()))
-    if flops is not None:
-        out["flops"] = int(flops)
-        out["tflops"] = flops / (out["device_ms_median"] * 1e-3) / 1e12
-        out["share_of_guide_untuned_gemm"] = out["tflops"] / GUIDE_TFLOPS
-    return out
-
-
 def bench_case(B, h, w, iters, warmup, calls_only):
     print("case B %d level %d x %d" % (B, h, w), file=sys.stderr, flush=True)
     planes, w1cat, b1cat, w2, b2, gs = make_unit(B, h, w)
     ys = [torch.empty((B, c, h, w), dtype=torch.float32, device=DEV) for c in ARM_C]
-    ws_f, ws_b = H.new_workspace(B, h, w, CHL, False, DEV), H.new_workspace(B, h, w, CHL, True, DEV)
+    ws_f, ws_b = (G.new_workspace(H.workspace_bytes(B, h, w, CHL, backward), DEV) for backward in (False, True))
     ysrc, gsrc = [H.nchw_source(y) for y in ys], [H.nchw_source(g) for g in gs]
     fl = launch_flops(B, h, w)
     case = dict(B=B, level=[h, w], pixels=B * h * w)
-    fwd = time_loop(lambda: H.forward(planes, w1cat, b1cat, w2, b2, ysrc, ws=ws_f), iters, warmup)
-    bwd = time_loop(lambda: H.backward(planes, w1cat, b1cat, w2, gsrc, ws=ws_b), iters, warmup)
-    case["smap_heads_forward"] = stats(fwd, sum(fl[k] for k in FORWARD_LAUNCHES))
-    case["smap_heads_backward"] = stats(bwd, sum(fl[k] for k in BACKWARD_LAUNCHES))
+    fwd, _ = time_loop(lambda: H.forward(planes, w1cat, b1cat, w2, b2, ysrc, ws=ws_f), iters, warmup)
+    bwd, _ = time_loop(lambda: H.backward(planes, w1cat, b1cat, w2, gsrc, ws=ws_b), iters, warmup)
+    case["smap_heads_forward"] = stats(fwd, flops=sum(fl[k] for k in FORWARD_LAUNCHES), guide_tflops=GUIDE_TFLOPS)
+    case["smap_heads_backward"] = stats(bwd, flops=sum(fl[k] for k in BACKWARD_LAUNCHES), guide_tflops=GUIDE_TFLOPS)
     if calls_only:
         return case
     # the comparison path: the same unit in torch fp32, NCHW, conv2d + autograd (forward alone; forward + backward to all gradients)
@@ -117,8 +97,8 @@ def bench_case(B, h, w, iters, warmup, calls_only):
         for t in leaves:
             t.grad = None
         torch.autograd.backward(torch_forward(), gs)
-    case["torch_forward"] = stats(time_loop(torch_forward_only, iters, warmup))
-    case["torch_forward_backward"] = stats(time_loop(torch_both, iters, warmup))
+    case["torch_forward"] = stats(time_loop(torch_forward_only, iters, warmup)[0])
+    case["torch_forward_backward"] = stats(time_loop(torch_both, iters, warmup)[0])
     case["ours_forward_backward_ms"] = case["smap_heads_forward"]["device_ms_median"] + case["smap_heads_backward"]["device_ms_median"]
     got = H.backward(planes, w1cat, b1cat, w2, gsrc, ws=ws_b)
     torch_both()
@@ -138,22 +118,9 @@ def bench_case(B, h, w, iters, warmup, calls_only):
 
 def bench_step(B, iters, warmup):
     print("step B %d" % B, file=sys.stderr, flush=True)
-    from benchkit.recipe import recipe_state_dict
-    from benchkit.workload import make_cfg
-    from smap_amd.model.smap import SMAP
-    torch.manual_seed(0)
-    net = SMAP(make_cfg((128, 208))).eval()
-    net.load_state_dict(recipe_state_dict(net.state_dict()))
-    net = net.to(DEV)
-    net.precision = "x3"
-    g = torch.Generator(device=DEV).manual_seed(1)
-    imgs = torch.randn((B, 3, 512, 832), generator=g, device=DEV)
-    labels = torch.randn((B, 5, 57, 128, 208), generator=g, device=DEV)
-    valids = torch.ones((B, 57, 1), device=DEV)
-    rdepth = torch.zeros((B, 8, 3), device=DEV)
-    rdepth[:, :4] = torch.tensor([[10.5, 20.5, 2.0], [100.2, 50.7, 3.0], [64.0, 104.0, 1.5], [127.0, 207.0, 4.0]], device=DEV)
-    tuner = H.HeadFineTuner(net, make_cfg((128, 208)), lr=1e-6, weight_decay=8e-6)
-    step = lambda: tuner.step(imgs, valids, labels, rdepth)
+    net, cfg, batch = full_network_batch(B)
+    tuner = FT.HeadFineTuner(net, cfg, lr=1e-6, weight_decay=8e-6)
+    step = lambda: tuner.step(*batch)
     for _ in range(warmup):
         step()
     torch.cuda.synchronize()
@@ -167,27 +134,12 @@ def bench_step(B, iters, warmup):
 
 def reduce_trace(path, iters, warmup):
     """Per case the median duration and rate of every launch, from a kernel trace of a --calls-only run with the same --iters / --warmup."""
-    import csv
-    import re
-    rows = [r for r in csv.DictReader(open(path)) if any(k in r["Kernel_Name"] for k in ("conv_gemm_kernel", "reduce_gemm_kernel", "reduce_fold_kernel"))]
-    rows.sort(key=lambda r: int(r["Start_Timestamp"]))
-    calls, at, out = iters + warmup, 0, []
-    assert len(rows) == len(BATCHES) * len(LEVELS) * calls * (len(FORWARD_LAUNCHES) + len(BACKWARD_LAUNCHES)), len(rows)
-    for B in BATCHES:
-        for h, w in LEVELS:
-            fl, case = launch_flops(B, h, w), dict(B=B, level=[h, w])
-            for what, names in (("smap_heads_forward", FORWARD_LAUNCHES), ("smap_heads_backward", BACKWARD_LAUNCHES)):
-                block = rows[at:at + calls * len(names)]
-                at += len(block)
-                per = {}
-                for k, name in enumerate(names):
-                    ns = [int(r["End_Timestamp"]) - int(r["Start_Timestamp"]) for r in block[warmup * len(names) + k::len(names)]]
-                    med = float(np.median(ns)) / 1e3
-                    per[name] = dict(kernel=re.search(r"(conv_gemm_kernel|reduce_gemm_kernel|reduce_fold_kernel)(<[^>]*>)?", block[k]["Kernel_Name"]).group(0), median_us=med, flops=int(fl[name]),
-                                     tflops=fl[name] / (med * 1e-6) / 1e12, share_of_guide_untuned_gemm=fl[name] / (med * 1e-6) / 1e12 / GUIDE_TFLOPS)
-                case[what] = per
-            out.append(case)
-    return out
+    def case(B, h, w):
+        fl = launch_flops(B, h, w)
+        rate = lambda name, med: dict(flops=int(fl[name]), tflops=fl[name] / (med * 1e-6) / 1e12,
+                                      share_of_guide_untuned_gemm=fl[name] / (med * 1e-6) / 1e12 / GUIDE_TFLOPS)
+        return dict(B=B, level=[h, w]), [("smap_heads_forward", FORWARD_LAUNCHES, 0), ("smap_heads_backward", BACKWARD_LAUNCHES, 0)], rate
+    return reduce_positional_trace(path, KERNELS, [case(B, h, w) for B in BATCHES for h, w in LEVELS], iters + warmup, warmup)
 
 
 def main():
@@ -202,7 +154,7 @@ def main():
     default = os.path.join(ROOT, "profiles", "heads_bench.json")
     if args.reduce_trace:
         path = args.out or default
-        out = json.load(open(path)) if os.path.exists(path) else {}
+        out = read_json(path)
         out["launches"] = dict(what="rocprofv3 --kernel-trace over `tools/bench_heads.py --calls-only` (a run of its own), reduced by --reduce-trace",
                                iters=args.iters, warmup=args.warmup, cases=reduce_trace(args.reduce_trace, args.iters, args.warmup))
         json.dump(out, open(path, "w"), indent=1)
@@ -217,12 +169,7 @@ def main():
     if not args.calls_only:
         out["step"] = [bench_step(B, args.step_iters, 2) for B in BATCHES]
     if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        prev = json.load(open(args.out)) if os.path.exists(args.out) else {}
-        if "launches" in prev:
-            out["launches"] = prev["launches"]
-        with open(args.out, "w") as f:
-            json.dump(out, f, indent=1)
+        write_merged(out, args.out)
     print(json.dumps(out, indent=1))
 
 

@@ -24,13 +24,13 @@ import argparse
 import json
 import os
 import sys
-import time
 
 import numpy as np
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+from bench_common import stats, time_loop  # noqa: E402
 from benchkit.clocks import ClockSampler  # noqa: E402
 from smap_amd import loss as K  # noqa: E402
 
@@ -139,27 +139,6 @@ def make_inputs(B, seed=0):
 
 def leaves(outputs):
     return [t for key in outputs for stage in outputs[key] for t in stage]
-
-
-def time_loop(step, iters, warmup):
-    """(per-iteration device ms [iters], wall ms per iteration)."""
-    for _ in range(warmup):
-        step()
-    torch.cuda.synchronize()
-    ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(iters)]
-    t0 = time.perf_counter()
-    for a, b in ev:
-        a.record()
-        step()
-        b.record()
-    torch.cuda.synchronize()
-    wall = (time.perf_counter() - t0) * 1e3 / iters
-    return np.array([a.elapsed_time(b) for a, b in ev]), wall
-
-
-def stats(ms, wall):
-    return dict(device_ms_median=float(np.median(ms)), device_ms_min=float(ms.min()), device_ms_max=float(ms.max()),
-                device_ms_mean=float(ms.mean()), wall_ms=float(wall))
 
 
 def bench_case(B, iters, warmup, fused_only=False):

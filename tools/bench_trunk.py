@@ -23,16 +23,16 @@ import os
 import sys
 import time
 
-import numpy as np
 import torch
 import torch.nn.functional as F
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-from smap_amd import heads as H  # noqa: E402
+from bench_common import DEV, full_network_batch, read_json, reduce_positional_trace, stats, time_loop, write_merged  # noqa: E402
+from smap_amd import finetune as FT  # noqa: E402
+from smap_amd import gemm_f32 as G  # noqa: E402
 from smap_amd import trunk as T  # noqa: E402
 
-DEV = "cuda:0"
 CHL = 256
 LEVELS = ((16, 26, 2048), (32, 52, 1024), (64, 104, 512), (128, 208, 256))       # h, w, Cin of up1 .. up4
 BATCHES = (2, 8)
@@ -72,42 +72,21 @@ def make_unit(B, ind, seed=0):
     return planes, o_prev, wu, wc, b, rand(B, h, w, CHL) * 1e-6
 
 
-def time_loop(step, iters, warmup):
-    for _ in range(warmup):
-        step()
-    torch.cuda.synchronize()
-    ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(iters)]
-    for a, b in ev:
-        a.record()
-        step()
-        b.record()
-    torch.cuda.synchronize()
-    return np.array([a.elapsed_time(b) for a, b in ev])
-
-
-def stats(ms, flops=None):
-    out = dict(device_ms_median=float(np.median(ms)), device_ms_min=float(ms.min()), device_ms_max=float(ms.max()))
-    if flops is not None:
-        out["flops"] = int(flops)
-        out["tflops"] = flops / (out["device_ms_median"] * 1e-3) / 1e12
-    return out
-
-
 def bench_case(B, ind, iters, warmup, calls_only):
     h, w, cin = LEVELS[ind]
     hp, wp = (LEVELS[ind - 1][:2] if ind else (0, 0))
     print("case B %d up%d %d x %d Cin %d" % (B, ind + 1, h, w, cin), file=sys.stderr, flush=True)
     planes, o_prev, wu, wc, b, g = make_unit(B, ind)
     dims = (B, h, w, hp, wp, cin, CHL)
-    ws_f, ws_b = T.new_workspace(*dims, False, DEV), T.new_workspace(*dims, True, DEV)
+    ws_f, ws_b = (G.new_workspace(T.workspace_bytes(*dims, backward), DEV) for backward in (False, True))
     work = launch_work(B, ind)
     fwd_names, bwd_names = launches(ind)
     case = dict(B=B, unit="up%d" % (ind + 1), level=[h, w], cin=cin, pixels=B * h * w)
     o, _ = T.forward(planes, o_prev, wu, wc, b, ws=ws_f)
-    fwd = time_loop(lambda: T.forward(planes, o_prev, wu, wc, b, ws=ws_f), iters, warmup)
-    bwd = time_loop(lambda: T.backward(planes, o_prev, o, wu, wc, g, want_gx=True, ws=ws_b), iters, warmup)
-    case["smap_trunk_forward"] = stats(fwd, sum(work[k][0] for k in fwd_names))
-    case["smap_trunk_backward"] = stats(bwd, sum(work[k][0] for k in bwd_names))
+    fwd, _ = time_loop(lambda: T.forward(planes, o_prev, wu, wc, b, ws=ws_f), iters, warmup)
+    bwd, _ = time_loop(lambda: T.backward(planes, o_prev, o, wu, wc, g, want_gx=True, ws=ws_b), iters, warmup)
+    case["smap_trunk_forward"] = stats(fwd, flops=sum(work[k][0] for k in fwd_names))
+    case["smap_trunk_backward"] = stats(bwd, flops=sum(work[k][0] for k in bwd_names))
     if calls_only:
         return case
     # the comparison path: the same unit in torch fp32, NCHW, conv2d + interpolate + autograd (forward alone; forward + backward to all gradients)
@@ -131,8 +110,8 @@ def bench_case(B, ind, iters, warmup, calls_only):
         for t in leaves:
             t.grad = None
         torch.autograd.backward([torch_forward()], [gt])
-    case["torch_forward"] = stats(time_loop(torch_forward_only, iters, warmup))
-    case["torch_forward_backward"] = stats(time_loop(torch_both, iters, warmup))
+    case["torch_forward"] = stats(time_loop(torch_forward_only, iters, warmup)[0])
+    case["torch_forward_backward"] = stats(time_loop(torch_both, iters, warmup)[0])
     case["ours_forward_backward_ms"] = case["smap_trunk_forward"]["device_ms_median"] + case["smap_trunk_backward"]["device_ms_median"]
     gwu, gwc, gb, gprev, gx, _ = T.backward(planes, o_prev, o, wu, wc, g, want_gx=True, ws=ws_b)
     torch_both()
@@ -150,24 +129,11 @@ def bench_case(B, ind, iters, warmup, calls_only):
 
 def bench_step(B, iters, warmup):
     print("step B %d" % B, file=sys.stderr, flush=True)
-    from benchkit.recipe import recipe_state_dict
-    from benchkit.workload import make_cfg
-    from smap_amd.model.smap import SMAP
-    torch.manual_seed(0)
-    net = SMAP(make_cfg((128, 208))).eval()
-    net.load_state_dict(recipe_state_dict(net.state_dict()))
-    net = net.to(DEV)
-    net.precision = "x3"
-    g = torch.Generator(device=DEV).manual_seed(1)
-    imgs = torch.randn((B, 3, 512, 832), generator=g, device=DEV)
-    labels = torch.randn((B, 5, 57, 128, 208), generator=g, device=DEV)
-    valids = torch.ones((B, 57, 1), device=DEV)
-    rdepth = torch.zeros((B, 8, 3), device=DEV)
-    rdepth[:, :4] = torch.tensor([[10.5, 20.5, 2.0], [100.2, 50.7, 3.0], [64.0, 104.0, 1.5], [127.0, 207.0, 4.0]], device=DEV)
+    net, cfg, batch = full_network_batch(B)
     out = dict(B=B, images=[512, 832], iters=iters)
-    for name, cls in (("HeadFineTuner", H.HeadFineTuner), ("DecoderFineTuner", T.DecoderFineTuner)):
-        tuner = cls(net, make_cfg((128, 208)), lr=1e-6, weight_decay=8e-6)
-        step = lambda: tuner.step(imgs, valids, labels, rdepth)
+    for name, cls in (("HeadFineTuner", FT.HeadFineTuner), ("DecoderFineTuner", FT.DecoderFineTuner)):
+        tuner = cls(net, cfg, lr=1e-6, weight_decay=8e-6)
+        step = lambda: tuner.step(*batch)
         for _ in range(warmup):
             step()
         torch.cuda.synchronize()
@@ -182,33 +148,18 @@ def bench_step(B, iters, warmup):
 
 def reduce_trace(path, iters, warmup):
     """Per case the median duration of every launch, from a kernel trace of a --calls-only run with the same --iters / --warmup."""
-    import csv
-    import re
-    rows = [r for r in csv.DictReader(open(path)) if any(k in r["Kernel_Name"] for k in KERNELS)]
-    rows.sort(key=lambda r: int(r["Start_Timestamp"]))
-    calls, at, out = iters + warmup, 0, []
-    for B in BATCHES:
-        for ind, (h, w, cin) in enumerate(LEVELS):
-            work, case = launch_work(B, ind), dict(B=B, unit="up%d" % (ind + 1), level=[h, w], cin=cin)
-            fwd_names, bwd_names = launches(ind)
-            # bench_case runs one forward call before its timed loops (it makes O): that call's launches come first
-            for what, names, extra in (("smap_trunk_forward", fwd_names, 1), ("smap_trunk_backward", bwd_names, 0)):
-                block = rows[at:at + (calls + extra) * len(names)]
-                at += len(block)
-                per = {}
-                for k, name in enumerate(names):
-                    ns = [int(r["End_Timestamp"]) - int(r["Start_Timestamp"]) for r in block[(warmup + extra) * len(names) + k::len(names)]]
-                    med = float(np.median(ns)) / 1e3
-                    flops, nbytes = work[name]
-                    per[name] = dict(kernel=re.search(r"(%s)(<[^>]*>)?" % "|".join(KERNELS), block[k]["Kernel_Name"]).group(0), median_us=med)
-                    if flops:
-                        per[name].update(flops=int(flops), tflops=flops / (med * 1e-6) / 1e12)
-                    else:
-                        per[name].update(bytes=int(nbytes), gb_per_s=nbytes / (med * 1e-6) / 1e9)
-                case[what] = per
-            out.append(case)
-    assert at == len(rows), (at, len(rows))
-    return out
+    def case(B, ind):
+        h, w, cin = LEVELS[ind]
+        work = launch_work(B, ind)
+        fwd_names, bwd_names = launches(ind)
+
+        def rate(name, med):
+            flops, nbytes = work[name]
+            return dict(flops=int(flops), tflops=flops / (med * 1e-6) / 1e12) if flops else dict(bytes=int(nbytes), gb_per_s=nbytes / (med * 1e-6) / 1e9)
+        # bench_case runs one forward call before its timed loops (it makes O): that call's launches come first
+        return (dict(B=B, unit="up%d" % (ind + 1), level=[h, w], cin=cin),
+                [("smap_trunk_forward", fwd_names, 1), ("smap_trunk_backward", bwd_names, 0)], rate)
+    return reduce_positional_trace(path, KERNELS, [case(B, ind) for B in BATCHES for ind in range(4)], iters + warmup, warmup)
 
 
 def main():
@@ -223,7 +174,7 @@ def main():
     default = os.path.join(ROOT, "profiles", "trunk_bench.json")
     if args.reduce_trace:
         path = args.out or default
-        out = json.load(open(path)) if os.path.exists(path) else {}
+        out = read_json(path)
         out["launches"] = dict(what="rocprofv3 --kernel-trace over `tools/bench_trunk.py --calls-only` (a run of its own), reduced by --reduce-trace",
                                iters=args.iters, warmup=args.warmup, cases=reduce_trace(args.reduce_trace, args.iters, args.warmup))
         json.dump(out, open(path, "w"), indent=1)
@@ -238,12 +189,7 @@ def main():
     if not args.calls_only:
         out["step"] = [bench_step(B, args.step_iters, 2) for B in BATCHES]
     if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        prev = json.load(open(args.out)) if os.path.exists(args.out) else {}
-        if "launches" in prev:
-            out["launches"] = prev["launches"]
-        with open(args.out, "w") as f:
-            json.dump(out, f, indent=1)
+        write_merged(out, args.out)
     print(json.dumps(out, indent=1))
 
 
